@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — examples/sec of one DeepFM train step (BASELINE.json config 3) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what `value` needs and no more: set-up, the state preparation and W warm-up steps, the K timed
+steps, the result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`, `state`).
+`--full` adds every other leg described below to the same line: `cold_start`, the instrumented pass
+(`kernel_ms_per_step`) and the rooflines, the other id distribution and scaling mode, the extras, `configs` and
+`cpu_baseline`.  `--dump-outputs DIR` writes what the last timed step returned — the loss and the logits of its batch
+— as DIR/loss.npy and DIR/logits.npy (float32); the inputs depend on the arguments alone (seeded), so two builds
+compare output for output.
 
 A "step" is one pass of the whole hot path over one synthetic batch that is already resident in
 HBM: unique-row bookkeeping, lazy Adam catch-up, embedding gather + FM + wide linear, the
@@ -67,6 +75,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (cold start, instrumented pass and rooflines, other distribution / "
+                         "scaling, extras, configs, CPU baseline); the --no-* switches below thin out a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and logits to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-second-dist", action="store_true", help="skip the short run on the other id distribution")
     ap.add_argument("--no-extras", action="store_true", help="skip the fp32-MFMA, other-catch-up-mode and LazyAdam-semantics legs (and the configs legs)")
@@ -158,8 +171,8 @@ def merge_mode_lines(line1, line2, rc2):
 
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher.  This process has not touched the GPU and never will:
-      1. the CPU baseline, timed HERE before any rank exists (the ranks' host threads then do not compete with it), handed to
-         rank 0 as a file;
+      1. (--full) the CPU baseline, timed HERE before any rank exists (the ranks' host threads then do not compete with it),
+         handed to rank 0 as a file;
       2. a set of fresh ranks in the conservative mode — every collective of a step on ONE communicator (--route-ahead 0): its
          line is the record if nothing else works;
       3. a second set of fresh ranks with the next batch routed ahead on a second communicator (--route-ahead 1).  If it
@@ -168,7 +181,7 @@ def spawn_ranks(args):
     import tempfile
     n = args.gpus
     extra = []
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         log("cpu baseline (before the ranks start)")
         cb = cpu_baseline()
         f = tempfile.NamedTemporaryFile("w", suffix=".json", delete=False)
@@ -310,6 +323,20 @@ def cpu_baseline():
                       (B, F, E, HIDDEN, V, steps)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: name -> tensor as out_dir/<name>.npy in float32 (with N > 1 ranks, <name>_rank<r>.npy)."""
+    host = {k: t.detach().float().cpu().numpy() for k, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values()) * world
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes over the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, (k if world == 1 else "%s_rank%d" % (k, rank)) + ".npy"), a)
+
+
 ML100K_VOCAB = [2] * 19 + [1000, 2000, 50, 1000, 7, 8, 3]
 
 
@@ -379,6 +406,48 @@ def other_configs(device, sync):
     return out
 
 
+def headline(args, world, B, dt, shard, mode_catchup, presorted, final_loss, steps_before, n_prep):
+    """The part of the result line a plain run prints: the headline rate of the K timed steps and what it was measured on."""
+    return {
+        "metric": "examples/sec DeepFM batch=65536 (full train step)",
+        "value": world * B * args.steps / dt,
+        "unit": "examples/sec",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        # fp32 variables, activations, gradients, accumulation and results; the MLP's GEMM operands go to the matrix pipe
+        # as fp16 high + low parts (3 exact products per fp32 product, lo*lo dropped: ~22-bit operands, row-relative error
+        # < 1e-5) unless --gemm fp32.  The un-emulated number is config.gemm_fp32_examples_per_sec.
+        "dtype": {"f16x2": "f32 (MLP GEMM operands: fp16 hi+lo split, 3 products, fp32 accumulate)",
+                  "bf16x3": "f32 (MLP GEMM operands: bf16 x3 split, 6 products, fp32 accumulate)", "fp32": "f32"}[args.gemm],
+        "data": "synthetic (%s ids, a fresh batch every step from a pool of up to %d, random-init weights)" % (args.dist, POOL),
+        "config": {"workload": "config 3: trainers.deep_fm --embedding-size 64 --hidden-units 512 256 128 "
+                               "--batch-size 65536 --dropout 0.1, 26 fields x 1M ids (Criteo-shaped), Adam(1e-3)",
+                   "per_gpu_batch": B, "global_batch": world * B, "fields": F, "vocab_per_field": V,
+                   "embedding_size": E, "hidden_units": HIDDEN,
+                   "gemm": {"f16x2": "fp32 GEMMs via scaled fp16 high+low operand split, fp32 accumulate",
+                            "bf16x3": "fp32 GEMMs via 3-way bf16 operand split, fp32 accumulate",
+                            "fp32": "fp32-input MFMA"}[args.gemm],
+                   "parallelism": "dp%d + row-sharded embeddings (all-to-all)" % world if (world > 1 or args.force_shard) else "single GPU",
+                   "communicators": (None if shard is None else ("two: the next batch is routed ahead on a second communicator" if shard.route_ahead
+                                                                 else "one: every collective of a step in program order on one communicator")),
+                   "catchup": ("bounded-error lazy Adam replay (MI_CATCHUP_BOUNDED: every variable within 3 ulp + 2e-6 of the replayed "
+                               "movement of TF's sweep, 98.7 % within 1e-7 relative; the exact mode is the extra catchup_exact)"
+                               if mode_catchup == "bounded" else "lazy Adam replay bit-exact with TF's dense-equivalent sweep"),
+                   "input_pipeline": (("next batch's ids announced one step ahead (train_step(next_ids=...)): " +
+                                       ("their routing (sorts, count exchange, split sizes to the host) runs on a side stream "
+                                        "beside this step's sparse apply" if shard is not None else
+                                        "their sort runs on a side stream beside this step's catch-up"))
+                                      if presorted else "ids handed over step by step")},
+        "final_loss": final_loss,
+        "state": {"steps_before_timed_region": steps_before, "state_prep_steps": n_prep,
+                  "rows_with_optimizer_state": 1.0 - (1.0 - min(world * B / V, 0.999)) ** steps_before,
+                  "note": "value = steady state (>= 99 % of a field's rows have Adam state and a stamp to catch up from)"},
+    }
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -445,8 +514,9 @@ def main():
     # (256 at most: 1.7 GB of ids; a longer run cycles through them).
     # STEADY STATE: a step costs most once every row it touches has optimizer state to catch up on, so the
     # headline is timed only after a state-preparation phase of plain train steps that has given >= 99 % of
-    # the rows of a field their first update (ln(100) / -ln(1 - B_global/V) = 68 steps at B = 65536).  The
-    # same K steps timed from the freshly initialised model are reported as `cold_start` (round 1's headline).
+    # the rows of a field their first update (ln(100) / -ln(1 - B_global/V) = 68 steps at B = 65536).  With
+    # --full the same K steps timed from the freshly initialised model are reported as `cold_start` (round 1's
+    # headline) and count towards that phase.  The pool's size does not depend on --full: same batches either way.
     B_glob = B * world
     prep_total = int(math.ceil(math.log(100.0) / -math.log(1.0 - min(B_glob / V, 0.999))))
     n_cold = args.warmup + args.steps
@@ -495,25 +565,38 @@ def main():
 
     log("model and %d batches ready" % len(batches))
     run(args.warmup)
-    cold_dt, _ = timed(args.steps)
-    log("cold start: %.3f ms/step" % (cold_dt / args.steps * 1e3))
-    cold = {"value": world * B * args.steps / cold_dt, "unit": "examples/sec", "ms_per_step": cold_dt / args.steps * 1e3,
-            "note": "the same %d steps after %d warm-up steps from a freshly initialised model (few rows have optimizer "
-                    "state to catch up on yet)" % (args.steps, args.warmup)}
+    if args.full:
+        cold_dt, _ = timed(args.steps)
+        log("cold start: %.3f ms/step" % (cold_dt / args.steps * 1e3))
+        cold = {"value": world * B * args.steps / cold_dt, "unit": "examples/sec", "ms_per_step": cold_dt / args.steps * 1e3,
+                "note": "the same %d steps after %d warm-up steps from a freshly initialised model (few rows have optimizer "
+                        "state to catch up on yet)" % (args.steps, args.warmup)}
+    else:
+        n_prep = max(0, prep_total - args.warmup)        # no cold-start leg: the state preparation covers its steps
     run(n_prep)
     run(args.warmup)
-    # The timed region: only the roofline kernel (the gather) is bracketed by HIP events — an event pair costs ~10 us of
-    # stream time, and bracketing all ~50 launches of a step (as round 1 and the first builds of round 2 did) made
-    # `value` 5 % worse than the step really is (rocprofv3 kernel trace: 0.22 ms of 10-us bubbles per step).  The
+    # The timed region: (--full) only the roofline kernel (the gather) is bracketed by HIP events — an event pair costs
+    # ~10 us of stream time, and bracketing all ~50 launches of a step (as round 1 and the first builds of round 2 did)
+    # made `value` 5 % worse than the step really is (rocprofv3 kernel trace: 0.22 ms of 10-us bubbles per step).  The
     # per-entry breakdown (`kernel_ms_per_step`, `roofline_mlp`) comes from the same K steps run once more right
     # after, fully instrumented; that second pass is not part of `value`.
     roof_keys = {"mi_embed_fm_planes_fwd", "mi_embed_fm_linear_fwd"}
-    m.timers, m.k.timer_only = {}, roof_keys
-    dt, (loss, _) = timed(args.steps)
+    if args.full:
+        m.timers, m.k.timer_only = {}, roof_keys
+    dt, (loss, logits) = timed(args.steps)
     roof_timers, m.timers, m.k.timer_only = m.timers, None, None
     final_loss = float(loss.item())
     log("steady state: %.3f ms/step (host enqueue %.3f ms/step)" % (dt / args.steps * 1e3, enqueue_s[0] / args.steps * 1e3))
     steps_before = cursor[0] - args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss, "logits": logits}, rank, world)
+    if not args.full:
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(headline(args, world, B, dt, shard, m.catchup, presort[0], final_loss, steps_before, n_prep)))
+        return
     m.timers = {}
     idt, _ = timed(args.steps)
     timers, m.timers = m.timers, None
@@ -761,39 +844,8 @@ def main():
                                                     "the launch does not follow this bound — the kernel waits for rows, profiles/r05_catchup_reciprocal.md)"},
                             "traffic": tr("sparse_catchup_k") if mode_catchup == "exact" else tr("sparse_catchup_bounded_k"),
                             "traffic_note": "PMC bytes per launch of the row kernel (profiles/traffic.json)"}
-        out = {
-            "metric": "examples/sec DeepFM batch=65536 (full train step)",
-            "value": world * B * args.steps / dt,
-            "unit": "examples/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_step,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            # fp32 variables, activations, gradients, accumulation and results; the MLP's GEMM operands go to the matrix pipe
-            # as fp16 high + low parts (3 exact products per fp32 product, lo*lo dropped: ~22-bit operands, row-relative error
-            # < 1e-5) unless --gemm fp32.  The un-emulated number is config.gemm_fp32_examples_per_sec.
-            "dtype": {"f16x2": "f32 (MLP GEMM operands: fp16 hi+lo split, 3 products, fp32 accumulate)",
-                      "bf16x3": "f32 (MLP GEMM operands: bf16 x3 split, 6 products, fp32 accumulate)", "fp32": "f32"}[args.gemm],
-            "data": "synthetic (%s ids, a fresh batch every step from a pool of up to %d, random-init weights)" % (args.dist, POOL),
-            "config": {"workload": "config 3: trainers.deep_fm --embedding-size 64 --hidden-units 512 256 128 "
-                                   "--batch-size 65536 --dropout 0.1, 26 fields x 1M ids (Criteo-shaped), Adam(1e-3)",
-                       "per_gpu_batch": B, "global_batch": world * B, "fields": F, "vocab_per_field": V,
-                       "embedding_size": E, "hidden_units": HIDDEN,
-                       "gemm": {"f16x2": "fp32 GEMMs via scaled fp16 high+low operand split, fp32 accumulate",
-                                "bf16x3": "fp32 GEMMs via 3-way bf16 operand split, fp32 accumulate",
-                                "fp32": "fp32-input MFMA"}[args.gemm],
-                       "parallelism": "dp%d + row-sharded embeddings (all-to-all)" % world if (world > 1 or args.force_shard) else "single GPU",
-                       "communicators": (None if shard is None else ("two: the next batch is routed ahead on a second communicator" if shard.route_ahead
-                                                                     else "one: every collective of a step in program order on one communicator")),
-                       "catchup": ("bounded-error lazy Adam replay (MI_CATCHUP_BOUNDED: every variable within 3 ulp + 2e-6 of the replayed "
-                                   "movement of TF's sweep, 98.7 % within 1e-7 relative; the exact mode is the extra catchup_exact)"
-                                   if mode_catchup == "bounded" else "lazy Adam replay bit-exact with TF's dense-equivalent sweep"),
-                       "input_pipeline": (("next batch's ids announced one step ahead (train_step(next_ids=...)): " +
-                                           ("their routing (sorts, count exchange, split sizes to the host) runs on a side stream "
-                                            "beside this step's sparse apply" if shard is not None else
-                                            "their sort runs on a side stream beside this step's catch-up"))
-                                          if presort[0] else "ids handed over step by step")},
+        out = headline(args, world, B, dt, shard, mode_catchup, presort[0], final_loss, steps_before, n_prep)
+        out.update({
             "roofline": {"kernel": ("embed_fm_planes_fwd_k: embedding gather + FM second order, writes the input_layer concat as fp16 "
                                     "high/low planes with one exponent per example (the operand of the layer-1 GEMMs); the wide part's "
                                     "4-byte gathers run as linear_only_fwd_k on a side stream" if planes_gather else
@@ -820,12 +872,8 @@ def main():
             "kernel_ms_note": "HIP-event pairs around every launch of a second pass over %d steps right after the timed "
                               "region (%.3f ms/step with the events' ~10-us bubbles); inside the timed region only the roofline "
                               "kernel is bracketed" % (args.steps, idt / args.steps * 1e3),
-            "final_loss": final_loss,
-            "state": {"steps_before_timed_region": steps_before, "state_prep_steps": n_prep,
-                      "rows_with_optimizer_state": 1.0 - (1.0 - min(B_glob / V, 0.999)) ** steps_before,
-                      "note": "value = steady state (>= 99 % of a field's rows have Adam state and a stamp to catch up from)"},
             "cold_start": cold,
-        }
+        })
         out.update(extras)
         if other is not None:
             out["other_distribution"] = other

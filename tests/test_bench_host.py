@@ -51,6 +51,7 @@ def test_default_flags_match_the_driver_contract():
     finally:
         sys.argv = argv
     assert (a.gpus, a.steps, a.warmup) == (1, 100, 20) and a.catchup == "bounded" and a.route_ahead is None
+    assert a.full is False and a.dump_outputs is None                 # a plain run: the headline only, nothing written
     sys.path.insert(0, os.path.join(ROOT, "recommender-tensorflow_amd"))
     import inspect
     from mi355x_rec.engine import DeepFM
@@ -58,6 +59,26 @@ def test_default_flags_match_the_driver_contract():
     assert inspect.signature(DeepFM.__init__).parameters["catchup"].default == a.catchup
     opt = ("exclude_linear", "exclude_mf", "exclude_dnn", "hidden_units", "dropout")
     assert _cli.make_parser("deep_fm", opt).parse_args([]).catchup == a.catchup
+
+
+def test_dump_outputs_writes_float32_npy_files(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 whatever the tensor's dtype, a rank suffix with N > 1 ranks,
+    and a refusal (nothing written) above the 64 MB limit."""
+    import numpy as np
+    import pytest
+    import torch
+    b = _bench()
+    logits = torch.linspace(-3.0, 3.0, 7)
+    b.dump_outputs(str(tmp_path / "one"), {"loss": torch.tensor([0.5], dtype=torch.float64), "logits": logits})
+    assert sorted(os.listdir(tmp_path / "one")) == ["logits.npy", "loss.npy"]
+    got = np.load(tmp_path / "one" / "logits.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, logits.numpy())
+    assert np.load(tmp_path / "one" / "loss.npy").dtype == np.float32
+    b.dump_outputs(str(tmp_path / "two"), {"logits": logits}, rank=1, world=2)
+    assert os.listdir(tmp_path / "two") == ["logits_rank1.npy"]
+    with pytest.raises(SystemExit):
+        b.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(b.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not (tmp_path / "big").exists()
 
 
 def test_every_tool_parses():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""One line per bench.py log: ms/step, cold start, the sparse side's per-entry times, the extra legs.
-usage: python tools/bench_summary.py gpurun_out/<log> [...]"""
+"""One line per `bench.py --full` log: ms/step, cold start, the sparse side's per-entry times, the extra legs.
+usage: python tools/bench_summary.py <log> [...]"""
 import json
 import sys
 

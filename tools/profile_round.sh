@@ -7,7 +7,7 @@ set -o pipefail
 TAG=${1:-r03}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out
-B="python3 $ROOT/bench.py --warmup 5 --no-cpu-baseline --no-second-dist --no-extras"
+B="python3 $ROOT/bench.py --full --warmup 5 --no-cpu-baseline --no-second-dist --no-extras"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -o run -- $B --steps 20 > $OUT/${TAG}_stats_bench.log 2>$OUT/${TAG}_stats_bench.err && echo stats ok
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_fetch -o run -- $B --steps 6 > /dev/null 2>&1 && echo fetch ok

@@ -3,7 +3,7 @@
 end of one `sparse_apply_k` and the end of the next, with its start relative to the step's start, its duration, the
 queue it ran on and the idle time of the whole GPU before it.
 usage: step_timeline.py <kernel_trace.csv> [<memory_copy_trace.csv>] [--step K] [--mark NAME]   (K: which step, counted
-from the middle of the trace; default 0 — the timed region of bench.py, before its instrumented pass; NAME: the kernel whose
+from the middle of the trace; default 0 — the timed region of bench.py, before the instrumented pass of --full; NAME: the kernel whose
 end closes a step, default sparse_apply_k — the row-sharded step launches that one twice: --mark dense_apply_k)"""
 import csv, sys
 

@@ -2,7 +2,7 @@
 """From a rocprofv3 --kernel-trace (+ --memory-copy-trace) CSV pair: the last `nsteps` train steps' GPU timeline —
 busy time per kernel name (all kernels, ours and torch's / RCCL's), copies, and idle time between them.
 usage: trace_gaps.py <kernel_trace.csv> [<memory_copy_trace.csv>] [--window-ms 40] [--end-offset-ms 0]
-(bench.py ends with a pass that brackets every launch with HIP events — ~10 us of bubble per launch; --end-offset-ms
+(bench.py --full ends with a pass that brackets every launch with HIP events — ~10 us of bubble per launch; --end-offset-ms
 moves the window's end back past it, into the timed region.)"""
 import csv, sys, collections
 
