@@ -129,11 +129,11 @@ int32_t mi_bucketize_f32(const float* values, int64_t n, const float* boundaries
  * 2 E: ONE record [w | slot0 | slot1] per row (what the shipped host allocates: a row's weights and optimizer state are one
  * contiguous 12 E-byte run — one DRAM page visit per row and direction in the sparse apply and the catch-up instead of
  * three).  A multiple of 4, >= E.
- * The PACKED EXCHANGE of the row-sharded step (round 4): a request's row and wide weight travel as ONE record of E + 4 floats
- * [row | weight | pad x 3] (and its gradients likewise), so a chunk costs one collective per direction instead of two —
- * mi_gather_rows(out_stride = E + 4, out_lin = out_rows + E) writes such records, the forward entries read them with
- * table_stride = lin_stride = E + 4, mi_entry_grads_segsum(rows_stride, out_stride) reads and writes them,
- * mi_sparse_apply(grad_stride = E + 4, d_lin = d_rows + E) applies them.  0 everywhere = separate arrays, as before. */
+ * Row + weight records: the entries also take a gathered row and its wide weight as ONE record of S floats (a multiple
+ * of 4, >= E + 4) [row | weight | pad] per request (and its gradients likewise) — mi_gather_rows(out_stride = S, out_lin = out_rows + E)
+ * writes such records, the forward entries read them with table_stride = lin_stride = S, mi_entry_grads_segsum(rows_stride,
+ * out_stride) reads and writes them, mi_sparse_apply(grad_stride = S, d_lin = d_rows + E) applies them.  0 everywhere =
+ * separate arrays (what the row-sharded step passes). */
 int32_t mi_embed_fm_linear_fwd(const float* table, const float* lin_w, const int64_t* field_off,
                                const int32_t* ids, int64_t B, int32_t F, int32_t E,
                                float* concat, int64_t ld_concat, float* sumv, float* fm, float* lin,

@@ -270,10 +270,7 @@ __device__ __forceinline__ void store_tile_c(const GemmArgs& a, const f32x16 (&a
 }
 
 template <int LA, int LB, bool VA, bool VB, bool COLSUM, bool GATHER>
-#ifndef GEMM_LB_WAVES
-#define GEMM_LB_WAVES 2
-#endif
-__global__ __launch_bounds__(kThreads, GEMM_LB_WAVES) void gemm_f32_k(const GemmArgs a) {
+__global__ __launch_bounds__(kThreads, 2) void gemm_f32_k(const GemmArgs a) {
   __shared__ __attribute__((aligned(16))) float smem[2][2][TILE_FLOATS];
 
   // XCD-aware bijective remap: the 8 XCDs receive blocks round-robin; give each XCD a contiguous
@@ -333,13 +330,8 @@ __global__ __launch_bounds__(kThreads, GEMM_LB_WAVES) void gemm_f32_k(const Gemm
 
   // Per k-tile: the next tile's global loads are issued first and land in registers under the
   // MFMAs; the staged registers go to the other LDS buffer (idle since the previous barrier)
-  // at GEMM_STORE_POS; one barrier per tile.
-#ifndef GEMM_STORE_POS
-#define GEMM_STORE_POS 2   /* after k-group n of 4 (4 = end of tile); A/B in tools/gemm_bench.py */
-#endif
-#ifndef GEMM_FRAG_DB
-#define GEMM_FRAG_DB 1
-#endif
+  // after the second of the tile's four k-groups; one barrier per tile.  The fragments of k-group s + 1 are read
+  // from LDS while k-group s runs its MFMAs.
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
     const bool more = kt + 1 < nk;
@@ -366,16 +358,13 @@ __global__ __launch_bounds__(kThreads, GEMM_LB_WAVES) void gemm_f32_k(const Gemm
         }
       }
     };
-#if GEMM_FRAG_DB
     float fa[2][2][4], fb[2][2][4];
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) read_frag<LA>(As, arow + mi * 32, 0, h, fa[0][mi]);
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) read_frag<LB>(Bs, brow + ni * 32, 0, h, fb[0][ni]);
-#endif
 #pragma unroll
     for (int s = 0; s < BK / 8; ++s) {
-#if GEMM_FRAG_DB
       const int c = s & 1;
       if (s + 1 < BK / 8) {
 #pragma unroll
@@ -383,27 +372,14 @@ __global__ __launch_bounds__(kThreads, GEMM_LB_WAVES) void gemm_f32_k(const Gemm
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) read_frag<LB>(Bs, brow + ni * 32, s + 1, h, fb[c ^ 1][ni]);
       }
-#define FA(mi, j) fa[c][mi][j]
-#define FB(ni, j) fb[c][ni][j]
-#else
-      float fa[2][4], fb[2][4];
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) read_frag<LA>(As, arow + mi * 32, s, h, fa[mi]);
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) read_frag<LB>(Bs, brow + ni * 32, s, h, fb[ni]);
-#define FA(mi, j) fa[mi][j]
-#define FB(ni, j) fb[ni][j]
-#endif
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
           for (int ni = 0; ni < 2; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(FA(mi, j), FB(ni, j), acc[mi][ni], 0, 0, 0);
-#undef FA
-#undef FB
-      if (s + 1 == GEMM_STORE_POS) stage();
+            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][mi][j], fb[c][ni][j], acc[mi][ni], 0, 0, 0);
+      if (s == 1) stage();
     }
     __syncthreads();
   }

@@ -138,8 +138,8 @@ struct ApplyArgs {
   // 12 E bytes (one DRAM page visit per row and direction instead of three)
   int64_t ts;
   // floats between consecutive entries of d_rows / of d_lin (E and 1: two arrays; one value for both: the gradients arrive
-  // as ONE record [row gradient | weight gradient | pad] per request, d_lin = d_rows + E — the packed exchange of the
-  // row-sharded step), and the same for out_rows / out_lin of the STORE form
+  // as ONE record [row gradient | weight gradient | pad] per request, d_lin = d_rows + E), and the same for out_rows /
+  // out_lin of the STORE form
   int64_t gs, gls, os, ols;
 };
 
@@ -577,7 +577,7 @@ __device__ __forceinline__ RowIn load_row_in(const float* __restrict__ table, co
   return q;
 }
 
-template <int LPR, bool DEEP>
+template <int LPR>
 __global__ __launch_bounds__(kBlock) void sparse_catchup_bounded_k(
     float* __restrict__ table, float* __restrict__ tm, float* __restrict__ tv,
     int32_t* __restrict__ last_step, const int32_t* __restrict__ uniq_rows,
@@ -688,7 +688,6 @@ __global__ __launch_bounds__(kBlock) void sparse_catchup_bounded_k(
     // (every lane of the group read the stamp above before lane 0 overwrites it: same wave, program order)
     if (l == 0 && !defer_slots && !keep_stamps && ls < step_to) last_step[cur.r * st] = step_to;
   };
-  if constexpr (!DEEP) {
   int64_t u0 = row_at(0);
   RowIn nxt = u0 < count ? load_row_in(table, tm, tv, last_step, row_id(u0), ts, l, lane_on, st) : none;
   int64_t u1 = J > 1 ? row_at(1) : count;
@@ -703,49 +702,6 @@ __global__ __launch_bounds__(kBlock) void sparse_catchup_bounded_k(
       if (u1 < count) id_pref = row_id(u1);
     }
     replay(cur);
-  }
-  } else {
-  // Two rounds' state in flight: twice the bytes per wave on the wire for the same number of resident waves.
-  //  * Every load is UNCONDITIONAL — a lane group past the end of the list, or a lane past the row's end, loads a valid
-  //    address it does not use (position count - 1 / the row's first floats; without a row list the stamps stand in for
-  //    it): with loads under branches hipcc's wait-count bookkeeping gives up and drains the pipeline (s_waitcnt vmcnt(0))
-  //    every round.
-  //  * The three buffers ROTATE through an unrolled loop — a register copy of a state still in flight would wait for it.
-  //  * The ID of round j + 3's row is loaded BEFORE round j + 2's state, so that waiting for it a round later does not
-  //    wait for that state: vmcnt counts in order.
-  const int64_t last_pos = count - 1;                        // (count >= 1 here: J > 0)
-  const int col = lane_on ? 4 * l : 0;
-  const int32_t* id_list = uniq_rows ? uniq_rows : last_step;
-  const bool has_list = uniq_rows != nullptr;
-  auto id_at = [&](int64_t jj) -> int32_t {                  // row of round jj (clamped into the list)
-    const int64_t u = row_at(jj < J ? jj : J - 1);
-    const int64_t pos = u < count ? u : last_pos;
-    const int32_t v = id_list[pos];
-    return has_list ? v : static_cast<int32_t>(pos);
-  };
-  auto on_at = [&](int64_t jj) -> bool { return jj < J && row_at(jj) < count; };
-  auto state_of = [&](int32_t id, bool on) -> RowIn {
-    RowIn q;
-    q.r = id;
-    const int stamp = last_step[static_cast<int64_t>(id) * st];
-    const int64_t o = static_cast<int64_t>(id) * ts + col;
-    q.w = ld4(table + o); q.m = ld4_nt(tm + o); q.v = ld4_nt(tv + o);
-    q.ls = on ? stamp : INT32_MAX;
-    return q;
-  };
-  RowIn sa = state_of(id_at(0), on_at(0)), sb = state_of(id_at(1), on_at(1)), sc;
-  int32_t id_next = id_at(2);
-  auto round = [&](const RowIn& x, RowIn& z, int64_t j) {    // consume round j's state x, fill z with round j + 2's
-    const int32_t id_a = id_next;
-    id_next = id_at(j + 3);
-    z = state_of(id_a, on_at(j + 2));
-    replay(x);
-  };
-  for (int64_t j = 0; j < J; j += 3) {                       // (rounds past J - 1 are off: they load and do nothing)
-    round(sa, sc, j);
-    round(sb, sa, j + 1);
-    round(sc, sb, j + 2);
-  }
   }
 }
 
@@ -1071,19 +1027,9 @@ int32_t mi_sparse_catchup(float* table, float* t_m, float* t_v, float* lin_w, fl
     // a pipelined grid: a few resident workgroups per CU, every lane group walks its share of the rows
     int64_t pb = mi::env_int("MI_CATCHUP_BLOCKS", 1024);          // 4 workgroups per CU resident: half the wave slots stay free for the side streams' small kernels (A/B on one box, 3 x alternating: 2.864 vs 2.881 ms per step at 2048)
     while (pb > 1 && pb > blocks) pb >>= 1;                       // (a power of two: the kernel's wave -> chunk map)
-    // MI_CATCHUP_DEPTH=2: two rounds' row state in flight per lane group instead of one (see the kernel).  Alone on the
-    // GPU it is the faster kernel (tools/catchup_bench.py: 0.450 -> 0.411 ms at 1,024 workgroups, 0.398 at 2,048); inside
-    // the step it is not (A/B on one box, three alternating runs: 2.82-2.96 vs 2.84-2.95 ms) — it finishes earlier against
-    // the next batch's sort on the side stream, more of which then lands on the gather (189-216 -> 247-269 us).  Default 1.
-    if (mi::env_int("MI_CATCHUP_DEPTH", 1) >= 2) {
-      MI_DISPATCH_LPR(lpr, (sparse_catchup_bounded_k<L, true><<<dim3((unsigned)pb), dim3(kBlock), 0, mi::as_stream(stream)>>>(
-                               table, t_m, t_v, last_step, uniq_rows, num_uniq, n_max, E, step_to, lr_table, beta1, beta2,
-                               epsilon, defer, lin_stride, mi::step_state(), keep_stamps, ts)));
-    } else {
-      MI_DISPATCH_LPR(lpr, (sparse_catchup_bounded_k<L, false><<<dim3((unsigned)pb), dim3(kBlock), 0, mi::as_stream(stream)>>>(
-                               table, t_m, t_v, last_step, uniq_rows, num_uniq, n_max, E, step_to, lr_table, beta1, beta2,
-                               epsilon, defer, lin_stride, mi::step_state(), keep_stamps, ts)));
-    }
+    MI_DISPATCH_LPR(lpr, (sparse_catchup_bounded_k<L><<<dim3((unsigned)pb), dim3(kBlock), 0, mi::as_stream(stream)>>>(
+                             table, t_m, t_v, last_step, uniq_rows, num_uniq, n_max, E, step_to, lr_table, beta1, beta2,
+                             epsilon, defer, lin_stride, mi::step_state(), keep_stamps, ts)));
   } else {
     MI_DISPATCH_LPR(lpr, (sparse_catchup_k<L><<<dim3((unsigned)blocks), dim3(kBlock), 0, mi::as_stream(stream)>>>(
                              table, t_m, t_v, last_step, uniq_rows, num_uniq, n_max, E, step_to, lr_table, beta1, beta2,

@@ -306,17 +306,13 @@ namespace mi {
 
 bool wgrad_pl_plan(int64_t M, int N, int K, WgradPlPlan* p) {
   if (M <= 0 || M % 16 != 0 || (N != 128 && N != 256 && N != 512) || K <= 0 || K % 16 != 0) return false;
+  // one tile of all N columns x 128 features.  (A/B runs of the alternatives: at N = 256, 256 x 128 tiles halve the slab
+  // bytes of 256 x 256 ones, 103 -> 90 us at 65536 x 512 x 256; at N = 512, two 256-column tiles x 256 features move
+  // 32 KB of operands per k-step instead of 40 KB for the same MFMAs and were measured slower, 469 vs 451 us on the
+  // layer-1 shape: the loop is not bound by operand bytes.)
   p->tn = N / 128;
+  p->tm = 2;
   p->tiles_n = 1;
-  p->tm = p->tn == 2 ? env_int("MI_WGRAD_TM_N256", 2) : 2;      // (N = 256: 256 x 128 tiles — half the slab bytes of 256 x 256: 103 -> 90 us at 65536 x 512 x 256)
-  p->nbuf = p->tn == 1 ? env_int("MI_WGRAD_NBUF_N128", 3) : 4;
-  // N = 512: one 512-column tile x 128 features.  MI_WGRAD_TILE=256 (A/B runs): two 256-column tiles x 256 features
-  // (32 KB of operands per k-step instead of 40 KB for the same MFMAs, a half-empty last feature tile at K = 1664) —
-  // measured slower, 469 vs 451 us on the layer-1 shape: the loop is not bound by operand bytes.
-  if (p->tn == 4) {
-    if (env_int("MI_WGRAD_TILE", 512) == 256) { p->tn = 2; p->tm = 4; p->tiles_n = 2; }      // (the tools' build only)
-  }
-  if (p->tn == 2 && env_int("MI_WGRAD_N256_AS_128", 0)) { p->tn = 1; p->tm = 2; p->tiles_n = 2; p->nbuf = env_int("MI_WGRAD_NBUF_N128", 3); }   // (the tools' build only)
   if (K % 128 != 0) return false;
   p->tiles_k = static_cast<int>(ceil_div(K, 64 * p->tm));      // (the last tile may be half empty)
   // one round of resident workgroups (one per CU; the 128-column tile fits two), at least 32 k-steps per split
@@ -346,10 +342,7 @@ int32_t wgrad_pl_launch(const WgradPlPlan& p, const mi_planes_t* X, const mi_pla
   a.slab = slab; a.cpart = cpart;
   const dim3 g(static_cast<unsigned>(p.tiles_k * p.tiles_n * p.splits)), b(WG_THREADS);
   if (p.tn == 4 && p.tm == 2) wgrad_pl_k<4, 2><<<g, b, 0, st>>>(a, sx4, sy4, sc4, kflag);
-  else if (p.tn == 2 && p.tm == 4) wgrad_pl_k<2, 4><<<g, b, 0, st>>>(a, sx4, sy4, sc4, kflag);
   else if (p.tn == 2 && p.tm == 2) wgrad_pl_k<2, 2><<<g, b, 0, st>>>(a, sx4, sy4, sc4, kflag);
-  else if (p.tn == 1 && p.tm == 4) wgrad_pl_k<1, 4><<<g, b, 0, st>>>(a, sx4, sy4, sc4, kflag);
-  else if (p.tn == 1 && p.tm == 2 && p.nbuf == 6) wgrad_pl_k<1, 2, 6><<<g, b, 0, st>>>(a, sx4, sy4, sc4, kflag);
   else if (p.tn == 1 && p.tm == 2) wgrad_pl_k<1, 2><<<g, b, 0, st>>>(a, sx4, sy4, sc4, kflag);
   else {
     set_error("wgrad_pl_launch: no kernel for tile %d x %d", p.tn, p.tm);

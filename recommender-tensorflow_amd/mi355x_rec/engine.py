@@ -365,19 +365,15 @@ class DeepFM:
         if self.use_emb and self.F:
             a, b = self.opt.slot_init
             nsl = (a is not None) + (b is not None)
-            if self.ROW_RECORDS:
-                self.ts = (1 + nsl) * self.E
-                self.t_rec = torch.zeros(self.R_local, self.ts, **f32)
-                self.table = self.t_rec[:, :self.E]
-                if a is not None:
-                    self.t_s0 = self.t_rec[:, self.E:2 * self.E]
-                    self.t_s0.fill_(a)
-                if b is not None:
-                    self.t_s1 = self.t_rec[:, 2 * self.E:3 * self.E]
-                    self.t_s1.fill_(b)
-            else:                                            # (A/B runs: three [R, E] arrays, the layout of rounds 1-3)
-                self.table = torch.zeros(self.R_local, self.E, **f32)
-                self.t_s0, self.t_s1 = self._slots(self.table, self.opt)
+            self.ts = (1 + nsl) * self.E
+            self.t_rec = torch.zeros(self.R_local, self.ts, **f32)
+            self.table = self.t_rec[:, :self.E]
+            if a is not None:
+                self.t_s0 = self.t_rec[:, self.E:2 * self.E]
+                self.t_s0.fill_(a)
+            if b is not None:
+                self.t_s1 = self.t_rec[:, 2 * self.E:3 * self.E]
+                self.t_s1.fill_(b)
         t_adam = self.opt.name == "Adam" and self.table is not None
         l_adam = sparse_lin_opt.name == "Adam" and self.use_linear and self.F > 0
         self.adam_rows = t_adam or l_adam
@@ -741,7 +737,7 @@ class DeepFM:
         variables only (final since the previous step's apply), while the step's first half — sort, catch-up, gather —
         does not touch the MLP.  Two small latency-bound launches (abs-max, split: ~40 us at config 3) leave the critical
         path; the first GEMM waits for their event (in _split_weights)."""
-        if not self.planes or self.device.type != "cuda" or getattr(self, "_capturing", False) or not self.WSPLIT_AHEAD:
+        if not self.planes or self.device.type != "cuda" or getattr(self, "_capturing", False):
             return
         side = self._ws.get("wsplit_stream")
         if side is None:
@@ -791,8 +787,8 @@ class DeepFM:
         B = ids.shape[0]
         self._last_B = B
         c = {"B": B}
-        # (rows received from their owners: src also carries the receive buffer's row / weight strides — E and 1 for plain
-        # arrays, E + 4 for the packed exchange's records; the model's own rows: one [w | slots] record apart)
+        # (rows received from their owners: src also carries the receive buffer's row / weight strides, E and 1; the model's
+        # own rows: one [w | slots] record apart)
         table, lin_w, field_off, rid, tst, ls = src if src is not None else (self.table, self.lin_w, self.field_off, ids, self.ts, self.ls)
         # the wide part's view of the batch: all columns, or (wide_fields) the wide columns' ids and field offsets
         w_off, w_ids, Fw = field_off, rid, self.F
@@ -945,7 +941,7 @@ class DeepFM:
     def _tail_fusable(self):
         """the logits layer + head of a train step as ONE launch (mi_logits_head_fused): planes path, a hidden layer of 64 /
         128 / 256 units below a one-unit logits layer"""
-        if not self.TAIL_FUSED or not self.planes or len(self.layers) < 2 or not hasattr(self.k, "mi_logits_head_fused"):
+        if not self.planes or len(self.layers) < 2 or not hasattr(self.k, "mi_logits_head_fused"):
             return False
         _, _, fan, h = self.layers[-1]
         return h == 1 and fan in (64, 128, 256)
@@ -954,7 +950,7 @@ class DeepFM:
         """the last hidden layer runs inside the fused logits + head launch too (mi_hidden_logits_head_fused): a 128-unit layer
         below the one-unit logits layer whose weight gradient reads planes, a batch that fills the chip, and nobody about to
         look at the layer's output (summaries_next: the Estimator says so before a step whose layer_summary it records)"""
-        if not (self.TOP_FUSED and self._tail_fusable() and hasattr(self.k, "mi_hidden_logits_head_fused")):
+        if not (self._tail_fusable() and hasattr(self.k, "mi_hidden_logits_head_fused")):
             return False
         nh = len(self.layers) - 1
         if nh < 1 or B < self.TOP_FUSED_MIN_BATCH or getattr(self, "summaries_next", False):
@@ -1083,23 +1079,10 @@ class DeepFM:
         self._final_step = self.step
 
     GAP_SORT_MIN = 16384      # entries from which sorting the touched rows by staleness pays for itself
-    # Scheduling choices of the single-GPU step, as class attributes (no environment switches in the product; bench.py
-    # --engine-opt NAME=0/1 flips one for an A/B run; every combination gives the same bits):
-    WSPLIT_AHEAD = True       # weight planes of the step made on a side stream at its head (_split_weights_ahead)
-    LIN_SIDE = True           # the wide part's catch-up on the wide part's stream, beside the row kernel (_catchup)
-    BYGAP_AHEAD = True        # the next batch's staleness order made a step ahead (_by_gap_ahead)
-    ROW_RECORDS = True        # a table row and its optimizer slots as one [w | slot0 | slot1] record (__init__)
-    TAIL_FUSED = True         # logits layer + head + the layer's backward as one launch (_head: mi_logits_head_fused)
-    WGRAD_BATCH = True        # the planes weight gradients of a backward pass as one batch after the data gradients (_backward_dense)
-    TOP_FUSED = True          # ... and the last hidden layer with them, in its GEMM's epilogue (_head: mi_hidden_logits_head_fused)
-    TOP_FUSED_MIN_BATCH = 4096
+    TOP_FUSED_MIN_BATCH = 4096  # examples from which the last hidden layer joins the fused logits + head launch (_top_fusable)
     GRAPH_SHAPES_MAX = 4      # captured steps kept at a time, one per batch shape (graph_train_step)
-    TEST_SIDE_STREAMS = True  # side streams are tested to run beside the step's stream and each other (_new_side_stream)
-    SIDE_PRIORITY = 0         # -1: side streams are created with high priority.  HIP serves every stream priority from its own pool
-                              # of hardware queues, so a high-priority stream can never share a queue with the step's (normal-priority)
-                              # stream; normal-priority streams share 4 queues by reference count and may (parallel._side_stream)
 
-    def _new_side_stream(self, priority=None):
+    def _new_side_stream(self, priority=0):
         """A stream whose kernels really run BESIDE the step's stream and beside the side streams handed out before it.
         torch.cuda.Stream() deals the streams of a pool of 32 per priority in turn and HIP spreads them over a few hardware
         queues (4 per priority by default); two streams on one queue run one after the other.  Which pool stream the engine
@@ -1107,13 +1090,12 @@ class DeepFM:
         stream from the same pool) — tools/stream_alias_probe.py, one GPU: with 3 streams taken before, the single-GPU step
         2.74 -> 2.92 ms; with 4, the row-sharded step 4.41 -> 8.26 ms.  So a candidate is TESTED (a long and a short spin
         kernel, three events: do they overlap?) against the current stream and the earlier side streams, and the next
-        pool stream is tried if it does not.  The k-th side stream is found once per process, device and priority."""
-        prio = self.SIDE_PRIORITY if priority is None else priority
-        if not self.TEST_SIDE_STREAMS:                          # (bench.py --engine-opt TEST_SIDE_STREAMS=0: the next pool stream, as before)
-            return torch.cuda.Stream(device=self.device, priority=prio)
+        pool stream is tried if it does not.  The k-th side stream is found once per process, device and priority.
+        priority -1: a stream of the high-priority pool.  HIP serves every stream priority from its own pool of hardware
+        queues, so such a stream never shares a queue with the step's (normal-priority) stream (parallel._sim_exchange)."""
         n = self.__dict__.setdefault("_n_side", {})
-        k = n[prio] = n.get(prio, -1) + 1                       # (this engine's k-th side stream of that priority)
-        return _tested_side_stream(self.device, prio, k)
+        k = n[priority] = n.get(priority, -1) + 1               # (this engine's k-th side stream of that priority)
+        return _tested_side_stream(self.device, priority, k)
 
     def _catchup(self, uniq, num_uniq, n_max, defer=False, by_gap=None):
         """defer: the rows are about to be applied in this same step by ONE mi_sparse_apply call, which
@@ -1140,7 +1122,7 @@ class DeepFM:
             assert not defer
             parts = [(None, l_sched, 4), (t_sched, None, 0)]          # (4 = MI_CATCHUP_KEEP_STAMPS)
         elif (defer and t_sched is not None and l_sched is not None and self.shard is None and self.device.type == "cuda"
-              and self._wide_on_side_stream(n_max // max(self.F, 1)) and self.LIN_SIDE):
+              and self._wide_on_side_stream(n_max // max(self.F, 1))):
             # deferred: neither call writes a stamp or touches the other's state — the wide part's 16-byte records
             # (scattered, latency-bound: 0.08 ms) are replayed on the stream that will run the wide part's forward,
             # beside the row kernel; the head joins that stream before anything else reads them
@@ -1245,7 +1227,7 @@ class DeepFM:
         which most of the chip idles — it costs nothing; right after the sort it ran beside the gather (HBM-bound: 176 ->
         231 us) and the layer-1 forward GEMM (310 -> 374 us: kernel timelines, tools/step_timeline.py)."""
         ps = self._presorted
-        if ps is None or not self.adam_rows or not self.BYGAP_AHEAD:
+        if ps is None or not self.adam_rows:
             return
         n = ps["ids"].shape[0] * self.F
         if n < self.GAP_SORT_MIN:
@@ -1372,7 +1354,7 @@ class DeepFM:
             # launch for every layer's slab fold — at config 3 five launches instead of nine, ~40 us of small launches and
             # the gaps around them off the step).  A data gradient needs only the dY of the layer above; the factors need
             # the finished dY planes and their abs-max, which is why they could not move earlier one by one.
-            batch = [] if (self.WGRAD_BATCH and hasattr(k, "mi_dense_bwd_weight_planes_batch")) else None
+            batch = [] if hasattr(k, "mi_dense_bwd_weight_planes_batch") else None
             for i in range(nh, -1, -1):
                 _, _, fan, h = self.layers[i]
                 if i == nh and c.get("tail_done"):        # (the fused logits + head launch made dW, db and the planes of dX)
@@ -1470,10 +1452,10 @@ class DeepFM:
                                    self.d_grad[self.lin_num_off:] if self.use_linear else None, ws, ws.numel())
         return d_concat
 
-    def _apply(self, uniq, seg, sorted_entry, num_uniq, n_max, d_rows, d_lin, fused=None, d_stride=0):
+    def _apply(self, uniq, seg, sorted_entry, num_uniq, n_max, d_rows, d_lin, fused=None):
         """apply_gradients: dense Apply*, sparse apply on the unique rows, step += 1.
         fused = (d_concat, sumv, dlogit): single-GPU form, entry gradients rebuilt in the kernel.
-        d_stride: d_rows / d_lin are views of ONE record buffer, d_stride floats per entry (the packed exchange); 0: two arrays."""
+        d_rows [n, E] and d_lin [n]: the entry gradients as two arrays (mi_sparse_apply's grad_stride 0)."""
         k = self.k
         step = self.step + 1
         lr_t = self.sched.lr_t(step) if self.sched else 0.0
@@ -1511,7 +1493,7 @@ class DeepFM:
                 else:
                     k.mi_sparse_apply(*slots, self.last_step, uniq, seg, sorted_entry, num_uniq, n_max,
                                       d_rows if tb is not None else None, d_lin if lw is not None else None, self.E,
-                                      step, h, self.ls, self.ts, d_stride)
+                                      step, h, self.ls, self.ts, 0)
         self.step = step
 
     # ------------------------------------------------------------------ replayable step (hipGraph)

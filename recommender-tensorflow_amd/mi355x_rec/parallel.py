@@ -70,16 +70,12 @@ class RowShard:
         sim_links: see below (tools/sim_ranks.py only)."""
         if not (0 <= rank < world):
             raise ValueError("rank %d not in [0, %d)" % (rank, world))
+        if packed:
+            raise ValueError("the packed exchange was removed; see DESIGN.md")
         self.rank, self.world, self.group = int(rank), int(world), group
         self.chunks = chunks
         self.chunk_compute = True if chunk_compute is None else bool(chunk_compute)
         self.route_ahead = True if route_ahead is None else bool(route_ahead)
-        # packed: rows and wide weights (and their gradients) travel as one record of E + 4 floats per request — one
-        # collective per chunk and direction instead of two (_sharded_step).  OFF by default: measured with one rank
-        # (bench.py --force-shard, profiles/r04_sharded_one_rank.md) the 272-byte records cost every kernel that walks them
-        # a third cache line per row — gather_rows +0.04, the planes gather +0.05, the segment sum +0.05, the sparse apply
-        # +0.13 ms per step — more than two small RCCL launches per chunk can give back.
-        self.packed = bool(packed)
         # sim_links (tools/sim_ranks.py ONLY, a one-rank group): {"world": N, "gbs": aggregate GB/s per direction, "latency_us": per
         # collective} — every exchange of the step is followed, on a stream of its own (as RCCL's is), by a spin kernel as long as
         # the N-rank exchange of the same requests would keep the links busy: (N - 1) / N of the bytes at `gbs` + the latency.  The
@@ -530,7 +526,7 @@ def _sharded_step(m, ids, labels, x_num, train, next_ids=None):
     if book is not None and m.adam_rows and m.step > 0:
         # (the staleness order is made here, on the step's stream, and the wide records are replayed by the same call: made a
         # step ahead / on a side stream beside the row kernel, as in the single-GPU step, each costs the one-rank step 0.05 ms —
-        # same-box A/B, tools/shard_opt_ab.sh: whatever runs beside the catch-up stretches it by as much)
+        # same-box A/B, profiles/r05_sharded_one_rank.md: whatever runs beside the catch-up stretches it by as much)
         m._catchup(book[1], book[3], nr, defer=True)
     if announce:
         _route_ahead(m, next_ids, C, after=head_ev)        # (RowShard(route_ahead=False): its local work only)
@@ -541,30 +537,20 @@ def _sharded_step(m, ids, labels, x_num, train, next_ids=None):
     # device-wide synchronisation between kernels other ranks are waiting on).  Only a batch more than twice as
     # concentrated on this owner as a uniform one grows them again.
     cap_u, cap_r = max(n, 1), max(2 * n, nr, 1)
-    # PACKED exchange (a model with both an embedding and a wide part): a request's row and its wide weight travel as ONE
-    # record of E + 4 floats [row | weight | pad x 3] — and their gradients likewise — so a chunk costs one collective
-    # per direction instead of two (xGMI collectives are latency-bound at these sizes: 4 -> 2 launches per chunk).  The
-    # kernels take the record stride (include/mi355x_rec.h: out_stride / table_stride / rows_stride / grad_stride); the
-    # *_rows / *_lin names below are then strided views of the record buffers.
-    packed = bool(m.use_emb and m.use_linear and m.shard.packed)
     sim = m.shard.sim_links if (comm.world == 1 and m.device.type == "cuda") else None       # (tools/sim_ranks.py)
-    EP = E + 4
-    xs = EP if packed else 0                                     # the exchange buffers' record stride as the entries take it
 
-    def rec(name, cap, cnt, need_rows, need_lin):
-        """(record buffer or None, rows view, weight view) of `cnt` requests"""
-        if packed:
-            r = m._buf(name + "_rec", (cap, EP))[:cnt]
-            return r, r[:, :E], r[:, E]
-        return (None, m._buf(name + "_rows", (cap, E))[:cnt] if need_rows else None,
-                m._buf(name + "_lin", (cap,))[:cnt] if need_lin else None)
-    own_rec, own_rows, own_lin = rec("own", cap_r, nr, m.use_emb, m.use_linear)
-    got_rec, got_rows, got_lin = rec("got", cap_u, max(U, 1), m.use_emb, m.use_linear)
+    def bufs(name, cap, cnt):
+        """(rows [cnt, E], wide weights [cnt]) of `cnt` requests — two arrays, one collective each per chunk and
+        direction; None for a part the model does not have"""
+        return (m._buf(name + "_rows", (cap, E))[:cnt] if m.use_emb else None,
+                m._buf(name + "_lin", (cap,))[:cnt] if m.use_linear else None)
+    own_rows, own_lin = bufs("own", cap_r, nr)
+    got_rows, got_lin = bufs("got", cap_u, max(U, 1))
 
     def gather(ids_, n_, rows_out, lin_out):
         if n_ > 0:
             k.mi_gather_rows(m.table if m.use_emb else None, m.lin_w if m.use_linear else None, ids_, n_, E,
-                             rows_out if m.use_emb else None, lin_out if m.use_linear else None, m.ls, m.ts, xs)
+                             rows_out if m.use_emb else None, lin_out if m.use_linear else None, m.ls, m.ts, 0)
 
     def serve(c):
         """owners gather chunk c's rows and send them back (their own requests: straight into the receive buffer);
@@ -573,22 +559,19 @@ def _sharded_step(m, ids, labels, x_num, train, next_ids=None):
         ulo, um, uhi = uoff[c], umid[c], uoff[c + 1]
         hs = []
         gather(recv_ids[lo:mid], mid - lo, own_rows[lo:mid] if m.use_emb else None, own_lin[lo:mid] if m.use_linear else None)
-        if packed:
-            hs.append(comm.all_to_all(got_rec[ulo:um], own_rec[lo:mid], sc0[c], rc0[c], True))
-        else:
-            if m.use_emb:
-                hs.append(comm.all_to_all(got_rows[ulo:um], own_rows[lo:mid], sc0[c], rc0[c], True))
-            if m.use_linear:
-                hs.append(comm.all_to_all(got_lin[ulo:um], own_lin[lo:mid], sc0[c], rc0[c], True))
+        if m.use_emb:
+            hs.append(comm.all_to_all(got_rows[ulo:um], own_rows[lo:mid], sc0[c], rc0[c], True))
+        if m.use_linear:
+            hs.append(comm.all_to_all(got_lin[ulo:um], own_lin[lo:mid], sc0[c], rc0[c], True))
         gather(recv_ids[mid:hi], hi - mid, got_rows[um:uhi] if m.use_emb else None, got_lin[um:uhi] if m.use_linear else None)
         if sim is not None:
             hs.append(_sim_exchange(m, (hi - lo) * 4 * ((E if m.use_emb else 0) + (1 if m.use_linear else 0)),
-                                    1 if (packed or not (m.use_emb and m.use_linear)) else 2))
+                                    1 if not (m.use_emb and m.use_linear) else 2))
         return hs
 
-    # gradients: one row (record) per distinct request, in send order; the owner's side receives them in request order
-    d_rec, d_rows, d_lin = rec("d", cap_u, max(U, 1), m.use_emb, m.use_linear) if train else (None, None, None)
-    r_rec, r_rows, r_lin = rec("recv_d", cap_r, nr, m.use_emb, m.use_linear) if train else (None, None, None)
+    # gradients: one row per distinct request, in send order; the owner's side receives them in request order
+    d_rows, d_lin = bufs("d", cap_u, max(U, 1)) if train else (None, None)
+    r_rows, r_lin = bufs("recv_d", cap_r, nr) if train else (None, None)
     logits_all = m._buf("logits_all", (B,)) if C > 1 else None
     loss_all = m._buf("loss_all", (1,)) if C > 1 else None
     acc = m._buf("d_grad_acc", (m.P,)) if (train and C > 1) else None
@@ -610,17 +593,14 @@ def _sharded_step(m, ids, labels, x_num, train, next_ids=None):
                 k.mi_entry_grads_segsum(got_rows if m.use_mf else None, seg, sorted_entry, u0, cnt,
                                         d_concat if m.use_emb else None, m.D, cc["sumv"] if m.use_mf else None,
                                         dlogit if m.use_mf else None, dlogit if m.use_linear else None, b0, F, E,
-                                        o_rows, o_lin, row0, xs, xs)
-        if packed:
-            grad_h.append(comm.all_to_all(r_rec[lo:mid], d_rec[ulo:um], rc0[c], sc0[c], True))
-        else:
-            if m.use_emb:
-                grad_h.append(comm.all_to_all(r_rows[lo:mid], d_rows[ulo:um], rc0[c], sc0[c], True))
-            if m.use_linear:
-                grad_h.append(comm.all_to_all(r_lin[lo:mid], d_lin[ulo:um], rc0[c], sc0[c], True))
+                                        o_rows, o_lin, row0, 0, 0)
+        if m.use_emb:
+            grad_h.append(comm.all_to_all(r_rows[lo:mid], d_rows[ulo:um], rc0[c], sc0[c], True))
+        if m.use_linear:
+            grad_h.append(comm.all_to_all(r_lin[lo:mid], d_lin[ulo:um], rc0[c], sc0[c], True))
         if sim is not None:
             grad_h.append(_sim_exchange(m, (uhi - ulo) * 4 * ((E if m.use_emb else 0) + (1 if m.use_linear else 0)),
-                                        1 if (packed or not (m.use_emb and m.use_linear)) else 2))
+                                        1 if not (m.use_emb and m.use_linear) else 2))
 
     def backward(cc, dlogit, chunks, b0):
         """MLP backward of the examples b0..; the gradients of `chunks` leave as soon as the input layer's data gradient
@@ -645,7 +625,7 @@ def _sharded_step(m, ids, labels, x_num, train, next_ids=None):
             _ahead_in_order(m, "counts")
         pieces = [(c * Bc, (c + 1) * Bc, (lambda c=c: _wait(handles[c]))) for c in range(C)]
         m._chunk = 0
-        cc = m._forward(ids, x_num, train, (got_rows, got_lin, zero_off, slot2, xs or E, xs or 1), pieces=pieces)
+        cc = m._forward(ids, x_num, train, (got_rows, got_lin, zero_off, slot2, E, 1), pieces=pieces)
         logits, loss, dlogit = m._head(cc, labels, train, global_batch=B * m.shard.world)
         if train:
             backward(cc, dlogit, range(C), 0)
@@ -661,7 +641,7 @@ def _sharded_step(m, ids, labels, x_num, train, next_ids=None):
             rows_h = nxt
             sl = slice(c * Bc, (c + 1) * Bc)
             m._chunk = c
-            cc = m._forward(ids[sl], None if x_num is None else x_num[sl], train, (got_rows, got_lin, zero_off, slot2[sl], xs or E, xs or 1))
+            cc = m._forward(ids[sl], None if x_num is None else x_num[sl], train, (got_rows, got_lin, zero_off, slot2[sl], E, 1))
             logits, loss, dlogit = m._head(cc, None if labels is None else labels[sl], train, global_batch=B * m.shard.world)
             if C > 1:
                 logits_all[sl].copy_(logits)
@@ -696,7 +676,7 @@ def _sharded_step(m, ids, labels, x_num, train, next_ids=None):
         r["gate"].record()                                      # (the next batch's owner-side work starts here: _own_ahead)
     if book is not None:
         bs_entry, buniq, bseg, bnum = book
-        m._apply(buniq, bseg, bs_entry, bnum, nr, r_rows, r_lin, d_stride=xs)
+        m._apply(buniq, bseg, bs_entry, bnum, nr, r_rows, r_lin)
     else:
         m._apply(None, None, None, None, 0, None, None)
     _own_ahead(m)

@@ -54,7 +54,7 @@ def _worker(rank, world, port, cfg, out_q, device="cpu", backend="gloo"):
         lin_opt = OptimizerSpec(*extra["lin_opt"]) if "lin_opt" in extra else None
         m = DeepFM(vocab, n_numeric=nn, embedding_size=E, hidden_units=hidden, use_linear=flags[0], use_mf=flags[1],
                    use_dnn=flags[2], optimizer=OptimizerSpec(opt_name, lr), device=device, shard=RowShard(rank, world, chunks=chunks, chunk_compute=extra.get("chunk_compute"),
-                                                                                     route_ahead=extra.get("route_ahead"), packed=extra.get("packed", False),
+                                                                                     route_ahead=extra.get("route_ahead"),
                                                                                      sim_links=extra.get("sim_links")),
                    numeric=extra.get("numeric", "embed"), linear_optimizer=lin_opt, reduction=extra.get("reduction", "mean"),
                    _kernels=kernels, **_subsets(extra))
@@ -216,15 +216,21 @@ def test_single_communicator_step_equals_big_batch(cfg, world):
 
 
 @pytest.mark.parametrize("cfg,world", [
-    (([9, 13, 5, 6], 8, [16, 8], 32, 0, "Adam", 0.001, 3, (True, True, True), 2, dict(packed=True, announce=True)), 2),
+    (([9, 13, 5, 6], 8, [16, 8], 32, 0, "Adam", 0.001, 3, (True, True, True), 2, dict(announce=True)), 2),
     (([9, 13, 5, 6], 8, [16, 8], 16, 3, "Adagrad", 0.05, 2, (True, False, True), 2,
-      dict(numeric="raw", lin_opt=("Ftrl", 0.2), reduction="sum", chunk_compute=False, packed=True)), 2),
-    (([9, 13, 5, 6], 8, [16, 8], 16, 0, "Adam", 0.001, 3, (True, True, True), 2, dict(chunk_compute=False, packed=True)), 4)])
-def test_packed_exchange_equals_big_batch(cfg, world):
-    """RowShard(packed=True): a request's row and wide weight (and their gradients) travel as ONE record of E + 4 floats —
-    one collective per chunk and direction instead of two.  Same results; off by default (the one-rank
-    measurement: profiles/r04_sharded_one_rank.md)."""
+      dict(numeric="raw", lin_opt=("Ftrl", 0.2), reduction="sum", chunk_compute=False)), 2),
+    (([9, 13, 5, 6], 8, [16, 8], 16, 0, "Adam", 0.001, 3, (True, True, True), 2, dict(chunk_compute=False)), 4)])
+def test_rows_and_wide_weights_exchange_equals_big_batch(cfg, world):
+    """A model with an embedding and a wide part: a request's row and its wide weight (and their gradients) travel as two
+    arrays, one collective each per chunk and direction.  Same results as the big-batch step."""
     check_against_big_batch(cfg, _run(cfg, world), world)
+
+
+def test_packed_exchange_is_refused():
+    """RowShard(packed=True), the record exchange that lost its one-rank A/B (profiles/r04_sharded_one_rank.md), is gone."""
+    from mi355x_rec.parallel import RowShard
+    with pytest.raises(ValueError, match="packed exchange was removed"):
+        RowShard(0, 2, packed=True)
 
 
 def test_four_rank_pipelined_step_equals_big_batch():

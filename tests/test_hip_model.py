@@ -543,7 +543,7 @@ def test_graph_train_step_with_numeric_columns_replays_the_eager_step_bitwise(ki
 
 def test_captured_step_has_no_memset_nodes():
     """Round 2's GPU fault: a captured LINEAR step whose sorts zeroed their counters with hipMemsetAsync
-    faulted at replay ("write access to a read-only page") although — tools/graph_memset_nodes.py, round 3 — both memset
+    faulted at replay ("write access to a read-only page") although — profiles/lab_notebook_r01_r03.md, round 3 — both memset
     nodes pointed into a live torch allocation made before the capture, in bounds, and no workspace moved: the runtime's
     memset nodes are not trusted; the library zeroes with a kernel of its own.  The captured B = 1024 step (no side stream:
     a chain of nodes) must contain kernel and copy nodes only."""

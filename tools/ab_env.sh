@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of tuning-build switches (MI_* environment variables read by tools/probe/libmi355x_rec_tuning.so only):
-#   bash tools/ab_env.sh 2 "MI_SORT_FUSED=0" "MI_SORT_FUSED=1" "MI_SORT_FUSED=1 MI_CATCHUP_DEPTH=2"
+#   bash tools/ab_env.sh 2 "MI_SORT_FUSED=0" "MI_SORT_FUSED=1" "MI_SORT_FUSED=1 MI_CATCHUP_BLOCKS=2048"
 # alternates the settings ROUNDS times (boxes differ by up to 10 %: only same-box numbers compare) and prints one line each.
 ROUNDS=$1; shift
 for i in $(seq 1 $ROUNDS); do

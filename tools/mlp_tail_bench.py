@@ -161,13 +161,8 @@ def main():
             lib.mi_absmax(X.data_ptr(), X.numel(), ax.data_ptr(), st()); lib.mi_absmax(dY.data_ptr(), dY.numel(), ay.data_ptr(), st())
             ops[(N, K)] = (split(X), split(dY), ax, ay, torch.empty(K, N, device="cuda"), torch.empty(N, device="cuda"))
             del X, dY
-        for env in ({}, {"MI_WGRAD_TM_N256": "2"}, {"MI_WGRAD_NBUF_N128": "6"}, {"MI_WGRAD_MIN_KSTEPS": "16"},
-                    {"MI_WGRAD_NBUF_N128": "6", "MI_WGRAD_MIN_KSTEPS": "16"}, {"MI_WGRAD_TM_N256": "2", "MI_WGRAD_MIN_KSTEPS": "16"},
-                    {"MI_WGRAD_MIN_KSTEPS": "64"}, {"MI_WGRAD_TM_N256": "2", "MI_WGRAD_MIN_KSTEPS": "64"},
-                    {"MI_WGRAD_N256_AS_128": "1"}, {"MI_WGRAD_N256_AS_128": "1", "MI_WGRAD_MIN_KSTEPS": "64"},
-                    {"MI_WGRAD_N256_AS_128": "1", "MI_WGRAD_MIN_KSTEPS": "128"}):
-            for k_ in ("MI_WGRAD_TM_N256", "MI_WGRAD_NBUF_N128", "MI_WGRAD_MIN_KSTEPS", "MI_WGRAD_N256_AS_128"):
-                os.environ.pop(k_, None)
+        for env in ({}, {"MI_WGRAD_MIN_KSTEPS": "16"}, {"MI_WGRAD_MIN_KSTEPS": "64"}, {"MI_WGRAD_MIN_KSTEPS": "128"}):
+            os.environ.pop("MI_WGRAD_MIN_KSTEPS", None)
             os.environ.update(env)
             line = []
             for N, K in shapes:
