@@ -672,6 +672,40 @@ int32_t mi_eval_accumulate(const float* logits, const uint8_t* labels, int64_t B
                            int64_t* hist /*[2*201]*/, int64_t* counts /*[8]*/,
                            double* sums /*[4]*/, mi_stream_t stream);
 
+/* ---- top-K recommendation: fused pair scoring and selection (csrc/rank.hip) -------------------------------------
+ * For U queries and I candidates, the best k candidates of every query by the model's logit, without the [U, I] pair
+ * matrix.  The model decomposes over the two sides of a pair: with Q the query fields, C the candidate fields (a
+ * partition of the input columns), s_X = sum_{f in X} e_f and fm_X = 0.5 (|s_X|^2 - sum_{f in X} |e_f|^2),
+ *   logit(q, c) = w_q + w_c + s_q . s_c + MLP_{2..L}(act(a_q + a_c))
+ *   w_X = lin_X + fm_X (the wide part's per-side sum; the candidate side also carries the wide bias),
+ *   a_X = concat_X W1[rows of X] (layer 1 on the side's rows of kernel_0; b1 on the candidate side only).
+ * The caller computes the per-side tensors (mi_embed_fm_linear_fwd, mi_numeric_*_fwd, layer 1 with identity
+ * activation); per pair, act(a_q + a_c), layers 2..L (fp32-input MFMA; a VALU loop when every width after layer 1 is
+ * below 32), the E-wide dot and the adds run on the chip and only the selection leaves it.
+ *   a_q [U, H1], a_c [I, H1]   layer 1 per side (H1 = 0: no DNN; NULL then)
+ *   s_q [U, E],  s_c [I, E]    embedding sums per side (E = 0: no FM cross term; NULL then)
+ *   w_q [U],     w_c [I]       lin + fm per side (NULL: 0)
+ *   dense, layer_off [2 n_layers] (host), widths [n_layers + 1] (host): layers 2..L, layer i + 2 with kernel
+ *     dense[layer_off[2i]] [widths[i], widths[i+1]] and bias dense[layer_off[2i+1]] [widths[i+1]]; widths[0] = H1,
+ *     widths[n_layers] = 1.  n_layers = 0 (no hidden layer): layer 1 is the logits layer, H1 = 1.  activation: the
+ *     engine's code (0 identity, 1 relu, 2 sigmoid, 3 tanh) on every hidden layer, layer 1 included.
+ *   excl_off [U + 1], excl_idx (device, CSR): candidates excluded per query, ascending; entries outside [0, I) are
+ *     ignored.  Both NULL: nothing excluded.
+ * Outputs: top_score [U, k] fp32 logits, top_idx [U, k] int32 candidate indices.  Order: score descending, equal scores
+ * by ascending index, NaN below every number (-0 ranks as +0 and comes back as +0 in top_score, a NaN as the canonical
+ * quiet NaN).  Fewer than k eligible candidates: the tail is index -1, score -inf.  scores [U, I] (optional, NULL on the hot path): every raw pair score, excluded pairs included (int64
+ * offsets).  Deterministic: the selection is a function of the scores alone, and the scores of the split count.
+ * Accuracy: each score is an fp32 evaluation of the same function in another summation order (within 1e-5 of an fp64
+ * forward, scaled as max_err_scaled).  Limits: U, I >= 1, I < 2^31, 1 <= k <= 256, H1 <= 4096, E <= 256, at most 8
+ * layers after layer 1, widths of layers 2, 4, ... <= 256 and of layers 3, 5, ... <= 128.  workspace: mi_pair_topk_workspace_bytes(U, I, k, H1, E). */
+size_t mi_pair_topk_workspace_bytes(int64_t U, int64_t I, int32_t k, int32_t H1, int32_t E);
+int32_t mi_pair_topk(const float* a_q, const float* s_q, const float* w_q, int64_t U,
+                     const float* a_c, const float* s_c, const float* w_c, int64_t I, int32_t H1, int32_t E,
+                     const float* dense, const int64_t* layer_off, const int32_t* widths, int32_t n_layers,
+                     int32_t activation, const int64_t* excl_off, const int32_t* excl_idx, int32_t k,
+                     float* top_score, int32_t* top_idx, float* scores, void* workspace, size_t workspace_bytes,
+                     mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,573 @@
+// Top-K recommendation: every (query, candidate) pair scored by the model and the best K candidates of each query kept,
+// without the pair matrix ever reaching HBM (mi_pair_topk, include/mi355x_rec.h).
+//
+// The model splits over the two sides of a pair (Q = query fields, C = candidate fields):
+//   logit(q, c) = w_q + w_c + s_q . s_c + MLP_{2..L}(act(a_q + a_c))
+// with w = lin + fm of the side (the candidate side also carries the wide bias), s = the side's sum of embeddings and
+// a = the side's rows of layer 1 (b1 on the candidate side).  The caller computes the per-side tensors with the existing
+// entry points; what is left per pair runs here.
+//
+//   pair_score_topk_k  grid (query blocks of 32) x (candidate splits).  A wave scores ONE candidate against the
+//                      workgroup's 32 queries: h1 = act(a_q + a_c) is formed in registers as it is consumed, layers
+//                      2..L-1 run on the fp32-input MFMA in the transposed form Y^T = W^T X^T (the 32 pairs are the
+//                      MFMA's columns, so a layer's accumulators are the next layer's B operand with no LDS round trip;
+//                      the weights' k order follows the accumulator's row map), the logits layer is a dot product.
+//                      Narrow MLPs (every width after layer 1 below 32) take a VALU loop instead.  Each query keeps a
+//                      sorted top-K list in LDS; a candidate that does not beat the list's K-th key is rejected by one
+//                      64-bit compare, survivors are appended and merged into the list in batches (rank merge).
+//   topk_merge_k       one workgroup per query: the splits' partial lists merged into the final [U, K].
+//
+// Order: one 64-bit key per (score, candidate): the score's bits made monotone in the high word (NaN -> 0, below every
+// number; -0 as +0, and returned as +0), the complemented index in the low word, so "larger key" = higher score, then lower index.  Key 0 is
+// the empty slot.  Keys of one query are distinct, so every merge is a rank computation with one answer: the results do
+// not depend on the split count, the order in which waves append survivors, or timing.  No workgroup waits for another.
+#include "common.h"
+
+namespace {
+
+constexpr int kQB = 32;                 // queries per workgroup = the MFMA's N
+constexpr int kWaves = 4;
+constexpr int kThreads = kWaves * 64;
+constexpr int kSurv = 64;               // survivor slots per query between merges (one round adds at most kWaves)
+constexpr int kMaxK = 256;
+constexpr int kMaxLayers = 8;           // layers after layer 1 (hidden layers 2..L-1 and the logits layer)
+constexpr int kMaxH1 = 4096;
+constexpr int kMaxRegWidth = 256;       // widths held in registers: layers 2, 4, ... (layers 3, 5, ...: half of it)
+constexpr int kTargetBlocks = 512;      // workgroups the split count aims at (two per CU of an MI355X)
+constexpr int kMergeLds = 64 * 1024;    // the final merge's LDS image of one query's partial lists
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct Layer {
+  int64_t w_off, b_off;                 // offsets into the flat dense buffer: kernel [fan_in, fan_out], bias [fan_out]
+  int32_t fan_in, fan_out;
+};
+
+struct PairArgs {
+  const float* aqT;                     // [H1][Upad] (workspace: a_q transposed, zero columns past U)
+  const float* a_c;                     // [I][H1]
+  const float* sqT;                     // [E][Upad]
+  const float* s_c;                     // [I][E]
+  const float* w_q;                     // [U] or NULL
+  const float* w_c;                     // [I] or NULL
+  const float* dense;
+  const uint32_t* excl;                 // [U][words] bitmask or NULL
+  float* scores;                        // [U][I] or NULL
+  uint64_t* part;                       // [U][splits][K]
+  int64_t U, I, chunk;
+  const Layer* l;                       // [n_layers] (workspace; a table in the kernel arguments would be copied to
+                                        // scratch by the runtime-indexed reads)
+  int32_t Upad, H1, E, K, splits, words, act, n_layers;
+};
+
+struct LayerTable {
+  Layer l[kMaxLayers];
+};
+
+__device__ __forceinline__ float act_f(float x, int act) {
+  switch (act) {
+    case 1: return fmaxf(x, 0.f);
+    case 2: return 1.f / (1.f + expf(-x));
+    case 3: return tanhf(x);
+    default: return x;
+  }
+}
+
+__device__ __forceinline__ uint64_t rank_key(float s, uint32_t c) {
+  uint32_t u = __float_as_uint(s);
+  if (s != s) u = 0u;
+  else if (s == 0.f) u = 0x80000000u;
+  else u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return (static_cast<uint64_t>(u) << 32) | static_cast<uint32_t>(~c);
+}
+__device__ __forceinline__ float key_score(uint64_t key) {
+  const uint32_t u = static_cast<uint32_t>(key >> 32);
+  if (u == 0u) return __uint_as_float(0x7fc00000u);
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+__device__ __forceinline__ int32_t key_index(uint64_t key) { return static_cast<int32_t>(~static_cast<uint32_t>(key)); }
+
+// row of a 32x32 accumulator tile held in register r by lane half h
+__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// ---- MFMA path ------------------------------------------------------------------------------------------------------
+// y[b] (feature b*32 + acc_row(r, h), pair = lane & 31) <- act(y + bias), zero past N
+template <int NB>
+__device__ __forceinline__ void epilogue(f32x16 (&y)[NB], const float* __restrict__ bias, int N, int act, int h) {
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int n = b * 32 + acc_row(r, h);
+      y[b][r] = n < N ? act_f(y[b][r] + bias[n], act) : 0.f;
+    }
+  }
+}
+
+// layer 2: the input h1 = act(a_q + a_c) is made as it is consumed, two k per MFMA step
+template <int NB>
+__device__ __forceinline__ void layer2_mfma(const PairArgs& p, const float* __restrict__ ac, int64_t qcol, int h,
+                                            f32x16 (&y)[NB]) {
+  const int col = static_cast<int>(qcol & 31);
+  const Layer L = p.l[0];
+  const float* __restrict__ W = p.dense + L.w_off;
+  const int K = L.fan_in, N = L.fan_out;
+#pragma unroll
+  for (int b = 0; b < NB; ++b) y[b] = f32x16{};
+  for (int k0 = 0; k0 < K; k0 += 2) {
+    const int k = k0 + h;
+    float hv = 0.f;
+    if (k < K) hv = act_f(p.aqT[static_cast<int64_t>(k) * p.Upad + qcol] + ac[k], p.act);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      if (b * 32 >= N) break;
+      const int n = b * 32 + col;
+      const float w = (k < K && n < N) ? W[static_cast<int64_t>(k) * N + n] : 0.f;
+      y[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, hv, y[b], 0, 0, 0);
+    }
+  }
+  epilogue<NB>(y, p.dense + L.b_off, N, p.act, h);
+}
+
+// a hidden layer whose input x is in registers: k-step (bi, r) takes the lane's own x[bi][r] as B and the weight row
+// of that feature as A
+template <int NI, int NO>
+__device__ __forceinline__ void layer_mfma(const PairArgs& p, const Layer L, const f32x16 (&x)[NI], f32x16 (&y)[NO],
+                                           int col, int h) {
+  const float* __restrict__ W = p.dense + L.w_off;
+  const int K = L.fan_in, N = L.fan_out;
+#pragma unroll
+  for (int b = 0; b < NO; ++b) y[b] = f32x16{};
+#pragma unroll
+  for (int bi = 0; bi < NI; ++bi) {
+    if (bi * 32 < K) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int k = bi * 32 + acc_row(r, h);
+#pragma unroll
+      for (int bo = 0; bo < NO; ++bo) {
+        if (bo * 32 >= N) break;
+        const int n = bo * 32 + col;
+        const float w = (k < K && n < N) ? W[static_cast<int64_t>(k) * N + n] : 0.f;
+        y[bo] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, x[bi][r], y[bo], 0, 0, 0);
+      }
+    }
+    }
+  }
+  epilogue<NO>(y, p.dense + L.b_off, N, p.act, h);
+}
+
+template <int NB>
+__device__ __forceinline__ float logits_mfma(const PairArgs& p, const Layer L, const f32x16 (&x)[NB], int h) {
+  const float* __restrict__ W = p.dense + L.w_off;
+  float s = 0.f;
+#pragma unroll
+  for (int bi = 0; bi < NB; ++bi) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int k = bi * 32 + acc_row(r, h);
+      if (k < L.fan_in) s = fmaf(x[bi][r], W[k], s);
+    }
+  }
+  s += __shfl_xor(s, 32);
+  return s + p.dense[L.b_off];
+}
+
+// the outputs of layers 2, 4, ... live in y (NP tiles of 32 features), those of layers 3, 5, ... in x (NQ tiles)
+template <int NP, int NQ>
+__device__ __forceinline__ float dnn_mfma(const PairArgs& p, const float* __restrict__ ac, int64_t qcol, int h) {
+  const int col = static_cast<int>(qcol & 31);
+  f32x16 y[NP], x[NQ];
+  layer2_mfma<NP>(p, ac, qcol, h, y);
+  int i = 1;
+  while (true) {                       // ping-pong between the two register tiles
+    if (i == p.n_layers - 1) return logits_mfma<NP>(p, p.l[i], y, h);
+    layer_mfma<NP, NQ>(p, p.l[i], y, x, col, h);
+    ++i;
+    if (i == p.n_layers - 1) return logits_mfma<NQ>(p, p.l[i], x, h);
+    layer_mfma<NQ, NP>(p, p.l[i], x, y, col, h);
+    ++i;
+  }
+}
+
+// ---- VALU path: one lane per pair (lanes 32..63 repeat lanes 0..31); widths after layer 1 at most 32 ---------------
+constexpr int kValuW = 32;
+
+__device__ __forceinline__ void epilogue_valu(float (&y)[kValuW], const float* __restrict__ bias, int N, int act) {
+#pragma unroll
+  for (int j = 0; j < kValuW; ++j) y[j] = j < N ? act_f(y[j] + bias[j], act) : 0.f;
+}
+
+__device__ __forceinline__ void layer_valu(const PairArgs& p, const Layer L, const float (&x)[kValuW], float (&y)[kValuW]) {
+  const float* __restrict__ W = p.dense + L.w_off;
+  const int K = L.fan_in, N = L.fan_out;
+#pragma unroll
+  for (int j = 0; j < kValuW; ++j) y[j] = 0.f;
+#pragma unroll
+  for (int k = 0; k < kValuW; ++k) {
+#pragma unroll
+    for (int j = 0; j < kValuW; ++j)
+      if (k < K && j < N) y[j] = fmaf(x[k], W[k * N + j], y[j]);
+  }
+  epilogue_valu(y, p.dense + L.b_off, N, p.act);
+}
+
+__device__ __forceinline__ float logits_valu(const PairArgs& p, const Layer L, const float (&x)[kValuW]) {
+  const float* __restrict__ W = p.dense + L.w_off;
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < kValuW; ++k)
+    if (k < L.fan_in) s = fmaf(x[k], W[k], s);
+  return s + p.dense[L.b_off];
+}
+
+__device__ __forceinline__ float dnn_valu(const PairArgs& p, const float* __restrict__ ac, int64_t qcol) {
+  const int H1 = p.H1;
+  const float* __restrict__ aq = p.aqT + qcol;
+  if (p.n_layers == 0) return aq[0] + ac[0];                      // no hidden layer: layer 1 is the logits layer
+  if (p.n_layers == 1) {                                           // one hidden layer: its output meets the logits weights
+    const Layer L = p.l[0];
+    const float* __restrict__ W = p.dense + L.w_off;
+    float s = 0.f;
+    for (int k = 0; k < H1; ++k) s = fmaf(act_f(aq[static_cast<int64_t>(k) * p.Upad] + ac[k], p.act), W[k], s);
+    return s + p.dense[L.b_off];
+  }
+  float x[kValuW], y[kValuW];
+  {
+    const Layer L = p.l[0];
+    const float* __restrict__ W = p.dense + L.w_off;
+    const int N = L.fan_out;
+#pragma unroll
+    for (int j = 0; j < kValuW; ++j) y[j] = 0.f;
+    for (int k = 0; k < H1; ++k) {
+      const float hv = act_f(aq[static_cast<int64_t>(k) * p.Upad] + ac[k], p.act);
+#pragma unroll
+      for (int j = 0; j < kValuW; ++j)
+        if (j < N) y[j] = fmaf(hv, W[k * N + j], y[j]);
+    }
+    epilogue_valu(y, p.dense + L.b_off, N, p.act);
+  }
+  int i = 1;
+  while (true) {
+    if (i == p.n_layers - 1) return logits_valu(p, p.l[i], y);
+    layer_valu(p, p.l[i], y, x);
+    ++i;
+    if (i == p.n_layers - 1) return logits_valu(p, p.l[i], x);
+    layer_valu(p, p.l[i], x, y);
+    ++i;
+  }
+}
+
+// ---- selection --------------------------------------------------------------------------------------------------------
+// Merge every query's survivors into its sorted list: a list entry moves down by the survivors that beat it, a survivor
+// lands at (list entries that beat it) + (survivors that beat it).  Entries pushed to K or beyond drop out; empty slots
+// (key 0) are beaten by every survivor, so they fill the tail.  Wave w owns queries w, w + 4, ...
+__device__ __forceinline__ void merge_survivors(uint64_t* list, const uint64_t* surv, int* nsurv, int K, int wave, int lane) {
+  constexpr int kPer = kMaxK / 64;
+  for (int qq = wave; qq < kQB; qq += kWaves) {                   // the same trip count in every wave: barriers inside
+    uint64_t* L = list + qq * K;
+    const uint64_t* S = surv + qq * kSurv;
+    const int n = nsurv[qq];
+    uint64_t lv[kPer];
+    int lp[kPer];
+#pragma unroll
+    for (int t = 0; t < kPer; ++t) {
+      const int j = lane + 64 * t;
+      lv[t] = 0;
+      lp[t] = K;
+      if (j < K && n > 0) {
+        lv[t] = L[j];
+        int cnt = 0;
+        for (int u = 0; u < n; ++u) cnt += S[u] > lv[t];
+        lp[t] = j + cnt;
+      }
+    }
+    uint64_t sv = 0;
+    int sp = K;
+    if (lane < n) {
+      sv = S[lane];
+      int cnt = 0;
+      for (int u = 0; u < n; ++u) cnt += S[u] > sv;
+      int lo = 0, hi = K;                                           // list entries above sv (the list is descending)
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (L[mid] > sv) lo = mid + 1; else hi = mid;
+      }
+      sp = lo + cnt;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < kPer; ++t)
+      if (lp[t] < K) L[lp[t]] = lv[t];
+    if (sp < K) L[sp] = sv;
+    if (lane == 0) nsurv[qq] = 0;
+    __syncthreads();
+  }
+}
+
+template <bool MFMA, int NP, int NQ>
+__global__ __launch_bounds__(kThreads) void pair_score_topk_k(const PairArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int K = p.K;
+  uint64_t* list = reinterpret_cast<uint64_t*>(lds);             // [kQB][K], descending, 0 = empty
+  uint64_t* surv = list + kQB * K;                                // [kQB][kSurv]
+  int* nsurv = reinterpret_cast<int*>(surv + kQB * kSurv);        // [kQB]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31, h = lane >> 5;
+  const int64_t q0 = static_cast<int64_t>(blockIdx.x) * kQB;
+  const int split = blockIdx.y;
+  const int64_t c_begin = split * p.chunk;
+  const int64_t c_end = c_begin + p.chunk < p.I ? c_begin + p.chunk : p.I;
+  for (int i = tid; i < kQB * K; i += kThreads) list[i] = 0;
+  if (tid < kQB) nsurv[tid] = 0;
+  __syncthreads();
+  const int64_t q = q0 + col;
+  const bool q_ok = q < p.U;
+  const float wq = (p.w_q && q_ok) ? p.w_q[q] : 0.f;
+  const float* __restrict__ sq = p.sqT ? p.sqT + q0 + col : nullptr;
+  for (int64_t base = c_begin; base < c_end; base += kWaves) {
+    const int64_t c = base + wave;
+    if (c < c_end) {                                              // (wave-uniform)
+      float dnn = 0.f;
+      if (p.H1 > 0) {
+        const float* __restrict__ ac = p.a_c + c * p.H1;
+        if constexpr (MFMA) dnn = dnn_mfma<NP, NQ>(p, ac, q0 + col, h);
+        else dnn = dnn_valu(p, ac, q0 + col);
+      }
+      float dot = 0.f;
+      if (sq) {
+        const float* __restrict__ sc = p.s_c + c * p.E;
+        for (int e = 0; e < p.E; ++e) dot = fmaf(sq[static_cast<int64_t>(e) * p.Upad], sc[e], dot);
+      }
+      const float s = ((wq + (p.w_c ? p.w_c[c] : 0.f)) + dot) + dnn;
+      if (h == 0 && q_ok) {
+        if (p.scores) p.scores[q * p.I + c] = s;
+        const bool excluded = p.excl && ((p.excl[q * p.words + (c >> 5)] >> (c & 31)) & 1u);
+        if (!excluded) {
+          const uint64_t key = rank_key(s, static_cast<uint32_t>(c));
+          if (key > list[col * K + K - 1]) {
+            const int slot = atomicAdd(&nsurv[col], 1);
+            surv[col * kSurv + slot] = key;
+          }
+        }
+      }
+    }
+    // (__syncthreads_or evaluates its argument BEFORE its barrier: the counts are read only after every wave's appends of
+    // this round are in — a stale count could skip a merge the next round's appends need, and overflow the slots)
+    __syncthreads();
+    if (__syncthreads_or(tid < kQB && nsurv[tid] > kSurv - kWaves)) merge_survivors(list, surv, nsurv, K, wave, lane);
+  }
+  __syncthreads();
+  if (__syncthreads_or(tid < kQB && nsurv[tid] > 0)) merge_survivors(list, surv, nsurv, K, wave, lane);
+  for (int i = tid; i < kQB * K; i += kThreads) {
+    const int qq = i / K;
+    if (q0 + qq < p.U) p.part[((q0 + qq) * p.splits + split) * K + (i - qq * K)] = list[i];
+  }
+}
+
+// one workgroup per query: entry (s, j) of the partial lists has rank j + (entries of the other lists above it)
+__global__ __launch_bounds__(256) void topk_merge_k(const uint64_t* __restrict__ part, int splits, int K,
+                                                    float* __restrict__ top_score, int32_t* __restrict__ top_idx) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  uint64_t* m = reinterpret_cast<uint64_t*>(lds);
+  __shared__ int total;
+  const int64_t u = blockIdx.x;
+  const int n = splits * K;
+  const uint64_t* src = part + u * n;
+  for (int i = threadIdx.x; i < n; i += 256) m[i] = src[i];
+  if (threadIdx.x == 0) total = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const uint64_t x = m[i];
+    if (x == 0) continue;
+    ++mine;
+    const int s = i / K, j = i - s * K;
+    int r = j;
+    for (int s2 = 0; s2 < splits && r < K; ++s2) {
+      if (s2 == s) continue;
+      const uint64_t* L = m + s2 * K;
+      int lo = 0, hi = K;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (L[mid] > x) lo = mid + 1; else hi = mid;
+      }
+      r += lo;
+    }
+    if (r < K) {
+      top_score[u * K + r] = key_score(x);
+      top_idx[u * K + r] = key_index(x);
+    }
+  }
+  atomicAdd(&total, mine);
+  __syncthreads();
+  for (int r = total + threadIdx.x; r < K; r += 256) {
+    top_score[u * K + r] = -__builtin_huge_valf();
+    top_idx[u * K + r] = -1;
+  }
+}
+
+// dst[k][q] = src[q][k] for q < U, 0 for U <= q < Upad
+__global__ __launch_bounds__(256) void transpose_pad_k(const float* __restrict__ src, int64_t U, int W, int Upad,
+                                                       float* __restrict__ dst) {
+  const int64_t n = static_cast<int64_t>(W) * Upad;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * 256) {
+    const int64_t k = i / Upad, q = i - k * Upad;
+    dst[i] = q < U ? src[q * W + k] : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(64) void layer_table_k(const LayerTable t, int n, Layer* __restrict__ out) {
+#pragma unroll
+  for (int i = 0; i < kMaxLayers; ++i)
+    if (i < n && threadIdx.x == 0) out[i] = t.l[i];
+}
+
+__global__ __launch_bounds__(256) void zero_u32_k(uint32_t* __restrict__ p, int64_t n) {
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * 256) p[i] = 0;
+}
+
+// one workgroup per query: its excluded candidates as bits of [U][words] (entries outside [0, I) are ignored)
+__global__ __launch_bounds__(256) void excl_mask_k(const int64_t* __restrict__ off, const int32_t* __restrict__ idx,
+                                                   int64_t I, int words, uint32_t* __restrict__ mask) {
+  const int64_t u = blockIdx.x;
+  for (int64_t e = off[u] + threadIdx.x; e < off[u + 1]; e += 256) {
+    const int32_t c = idx[e];
+    if (c >= 0 && c < I) atomicOr(&mask[u * words + (c >> 5)], 1u << (c & 31));
+  }
+}
+
+struct Plan {
+  int64_t Upad, qblocks, chunk;
+  int32_t splits, words;
+  size_t off_layers, off_aq, off_sq, off_mask, off_part, total;
+};
+
+inline size_t align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
+
+Plan make_plan(int64_t U, int64_t I, int32_t k, int32_t H1, int32_t E) {
+  Plan pl;
+  pl.qblocks = mi::ceil_div(U, kQB);
+  pl.Upad = pl.qblocks * kQB;
+  int64_t s = mi::ceil_div(kTargetBlocks, pl.qblocks);
+  const int64_t s_lds = kMergeLds / (8 * static_cast<int64_t>(k));
+  const int64_t s_min_chunk = mi::ceil_div(I, 64);                 // at least 64 candidates per split
+  if (s > s_lds) s = s_lds;
+  if (s > s_min_chunk) s = s_min_chunk;
+  if (s < 1) s = 1;
+  pl.chunk = mi::ceil_div(I, s);
+  pl.splits = static_cast<int32_t>(mi::ceil_div(I, pl.chunk));
+  pl.words = static_cast<int32_t>(mi::ceil_div(I, 32));
+  size_t o = 0;
+  pl.off_layers = o; o += align256(sizeof(Layer) * kMaxLayers);
+  pl.off_aq = o; o += align256(sizeof(float) * static_cast<size_t>(H1) * pl.Upad);
+  pl.off_sq = o; o += align256(sizeof(float) * static_cast<size_t>(E) * pl.Upad);
+  pl.off_mask = o; o += align256(sizeof(uint32_t) * static_cast<size_t>(U) * pl.words);
+  pl.off_part = o; o += align256(sizeof(uint64_t) * static_cast<size_t>(U) * pl.splits * k);
+  pl.total = o;
+  return pl;
+}
+
+bool sizes_ok(int64_t U, int64_t I, int32_t k, int32_t H1, int32_t E) {
+  return U >= 1 && I >= 1 && I <= INT32_MAX && k >= 1 && k <= kMaxK && H1 >= 0 && H1 <= kMaxH1 && E >= 0 && E <= 256 &&
+         mi::ceil_div(U, kQB) <= INT32_MAX;
+}
+
+template <bool MFMA, int NP, int NQ>
+hipError_t launch_pair(const PairArgs& a, dim3 grid, size_t lds, hipStream_t st) {
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_score_topk_k<MFMA, NP, NQ>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    if (e != hipSuccess) return e;
+  }
+  pair_score_topk_k<MFMA, NP, NQ><<<grid, dim3(kThreads), lds, st>>>(a);
+  return hipSuccess;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mi_pair_topk_workspace_bytes(int64_t U, int64_t I, int32_t k, int32_t H1, int32_t E) {
+  if (!sizes_ok(U, I, k, H1, E)) return 0;
+  return make_plan(U, I, k, H1, E).total;
+}
+
+int32_t mi_pair_topk(const float* a_q, const float* s_q, const float* w_q, int64_t U,
+                     const float* a_c, const float* s_c, const float* w_c, int64_t I, int32_t H1, int32_t E,
+                     const float* dense, const int64_t* layer_off, const int32_t* widths, int32_t n_layers,
+                     int32_t activation, const int64_t* excl_off, const int32_t* excl_idx, int32_t k,
+                     float* top_score, int32_t* top_idx, float* scores, void* workspace, size_t workspace_bytes,
+                     mi_stream_t stream) {
+  MI_REQUIRE(sizes_ok(U, I, k, H1, E), "pair_topk: U=%lld I=%lld k=%d H1=%d E=%d out of range (U, I >= 1, 1 <= k <= %d, "
+             "H1 <= %d, E <= 256)", (long long)U, (long long)I, k, H1, E, kMaxK, kMaxH1);
+  MI_REQUIRE(top_score && top_idx, "pair_topk: top_score / top_idx");
+  MI_REQUIRE(activation >= 0 && activation <= 3, "pair_topk: activation %d", activation);
+  MI_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "pair_topk: %d layers after layer 1 (at most %d)", n_layers, kMaxLayers);
+  MI_REQUIRE(H1 == 0 || (a_q && a_c && dense && (n_layers == 0 || (layer_off && widths))),
+             "pair_topk: a_q / a_c / dense / layer_off / widths");
+  MI_REQUIRE(H1 > 0 || n_layers == 0, "pair_topk: layers without a layer 1");
+  MI_REQUIRE(H1 == 0 || n_layers > 0 || H1 == 1, "pair_topk: without hidden layers layer 1 is the logits layer (H1 = 1)");
+  MI_REQUIRE(E == 0 || (s_q && s_c), "pair_topk: s_q / s_c");
+  MI_REQUIRE(!excl_off == !excl_idx, "pair_topk: excl_off and excl_idx go together");
+  PairArgs a{};
+  LayerTable lt{};
+  a.n_layers = n_layers;
+  int maxw = 0, wp = 0, wq = 0;                  // widths of layers 2..L-1: all, at even / odd positions
+  for (int i = 0; i < n_layers; ++i) {
+    const int fi = widths[i], fo = widths[i + 1];
+    MI_REQUIRE(fi >= 1 && fo >= 1, "pair_topk: width %d -> %d", fi, fo);
+    MI_REQUIRE(i > 0 || fi == H1, "pair_topk: widths[0]=%d != H1=%d", fi, H1);
+    MI_REQUIRE(i + 1 < n_layers || fo == 1, "pair_topk: the last layer has %d outputs (1 expected)", fo);
+    MI_REQUIRE(layer_off[2 * i] >= 0 && layer_off[2 * i + 1] >= 0, "pair_topk: layer offsets");
+    if (i + 1 < n_layers) {
+      if (fo > maxw) maxw = fo;
+      int& w = (i & 1) ? wq : wp;
+      if (fo > w) w = fo;
+    }
+    lt.l[i] = Layer{layer_off[2 * i], layer_off[2 * i + 1], fi, fo};
+  }
+  MI_REQUIRE(wp <= kMaxRegWidth && wq <= kMaxRegWidth / 2, "pair_topk: hidden widths after layer 1: layers 2, 4, ... at most "
+             "%d (here %d), layers 3, 5, ... at most %d (here %d)", kMaxRegWidth, wp, kMaxRegWidth / 2, wq);
+  const Plan pl = make_plan(U, I, k, H1, E);
+  MI_REQUIRE(workspace && workspace_bytes >= pl.total, "pair_topk: workspace %zu < %zu bytes", workspace_bytes, pl.total);
+  hipStream_t st = mi::as_stream(stream);
+  char* ws = static_cast<char*>(workspace);
+  float* aqT = H1 ? reinterpret_cast<float*>(ws + pl.off_aq) : nullptr;
+  float* sqT = E ? reinterpret_cast<float*>(ws + pl.off_sq) : nullptr;
+  uint32_t* mask = excl_off ? reinterpret_cast<uint32_t*>(ws + pl.off_mask) : nullptr;
+  uint64_t* part = reinterpret_cast<uint64_t*>(ws + pl.off_part);
+  auto blocks = [](int64_t n) { const int64_t b = mi::ceil_div(n, 256); return static_cast<unsigned>(b < 2048 ? b : 2048); };
+  Layer* layers = reinterpret_cast<Layer*>(ws + pl.off_layers);
+  if (n_layers) layer_table_k<<<dim3(1), dim3(64), 0, st>>>(lt, n_layers, layers);
+  if (aqT) transpose_pad_k<<<dim3(blocks(static_cast<int64_t>(H1) * pl.Upad)), dim3(256), 0, st>>>(a_q, U, H1, (int)pl.Upad, aqT);
+  if (sqT) transpose_pad_k<<<dim3(blocks(static_cast<int64_t>(E) * pl.Upad)), dim3(256), 0, st>>>(s_q, U, E, (int)pl.Upad, sqT);
+  if (mask) {
+    zero_u32_k<<<dim3(blocks(U * pl.words)), dim3(256), 0, st>>>(mask, U * pl.words);
+    excl_mask_k<<<dim3(static_cast<unsigned>(U)), dim3(256), 0, st>>>(excl_off, excl_idx, I, pl.words, mask);
+  }
+  MI_CHECK_LAUNCH("pair_topk (prepare)");
+  a.aqT = aqT; a.a_c = a_c; a.sqT = sqT; a.s_c = s_c; a.w_q = w_q; a.w_c = w_c; a.dense = dense;
+  a.excl = mask; a.scores = scores; a.part = part; a.l = layers;
+  a.U = U; a.I = I; a.chunk = pl.chunk;
+  a.Upad = static_cast<int32_t>(pl.Upad); a.H1 = H1; a.E = E; a.K = k; a.splits = pl.splits; a.words = pl.words;
+  a.act = activation;
+  const size_t lds = sizeof(uint64_t) * kQB * (k + kSurv) + sizeof(int) * kQB;
+  const dim3 grid(static_cast<unsigned>(pl.qblocks), static_cast<unsigned>(pl.splits));
+  hipError_t e;
+  if (n_layers >= 2 && maxw >= 32) {
+    if (maxw <= 32) e = launch_pair<true, 1, 1>(a, grid, lds, st);
+    else if (maxw <= 64) e = launch_pair<true, 2, 2>(a, grid, lds, st);
+    else if (maxw <= 128) e = launch_pair<true, 4, 4>(a, grid, lds, st);
+    else e = launch_pair<true, 8, 4>(a, grid, lds, st);
+  } else {
+    e = launch_pair<false, 1, 1>(a, grid, lds, st);
+  }
+  MI_REQUIRE(e == hipSuccess, "pair_topk: LDS of %zu bytes: %s", lds, hipGetErrorString(e));
+  MI_CHECK_LAUNCH("pair_score_topk_k");
+  topk_merge_k<<<dim3(static_cast<unsigned>(U)), dim3(256), sizeof(uint64_t) * pl.splits * k, st>>>(part, pl.splits, k,
+                                                                                                    top_score, top_idx);
+  MI_CHECK_LAUNCH("topk_merge_k");
+  return MI_OK;
+}
+
+}  // extern "C"

@@ -141,6 +141,9 @@ SIGNATURES = {
     "mi_binary_predictions": (_i32, [_p, _p, _i64, _p, _p, _p, _p, _p]),
     "mi_layer_histogram": (_i32, [_p, _i64, _p, _i32, _p, _p, _p]),
     "mi_eval_accumulate": (_i32, [_p, _p, _i64, _p, _p, _p, _p]),
+    "mi_pair_topk_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    "mi_pair_topk": (_i32, [_p, _p, _p, _i64, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _i32, _i32, _p, _p, _i32,
+                            _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

@@ -1078,6 +1078,153 @@ class DeepFM:
         self._catchup(None, None, self.R_local)
         self._final_step = self.step
 
+    # ------------------------------------------------------------------ top-K recommendation
+    TOP_K_MAX = 256
+
+    def top_k(self, query_ids, candidate_ids, query_fields, k, query_x=None, candidate_x=None, exclude=None,
+              return_scores=False):
+        """The k best candidates of every query by logit (mi_pair_topk, include/mi355x_rec.h).
+
+        The input columns split into a query side and a candidate side: ``query_fields`` lists the query side's columns
+        by index — categorical fields 0..F-1 in plan order, numeric column j as F + j — and the other columns are the
+        candidate side.  query_ids int32 [U, Fq] / candidate_ids int32 [I, Fc] hold each side's categorical ids in
+        ascending field order, query_x / candidate_x float32 [n, .] its numeric columns (None when it has none).
+        Per side the model's existing kernels give the embedding sum s, lin + fm (candidate side: + the wide bias) and
+        layer 1 on the side's rows of kernel_0 (candidate side: + bias_0); per pair only act(a_q + a_c), layers 2..L,
+        the E-wide FM cross term and the adds run, inside the fused kernel, which keeps a running top-k per query.
+        exclude: candidates never returned for a query — a CSR pair (offsets [U+1] int64, indices int32, ascending per
+        query) or one sequence of candidate indices per query.
+        Returns (top_score [U, k] fp32 logits, top_idx [U, k] int32) — score descending, ties by lower index, index -1
+        and score -inf where fewer than k candidates are eligible — plus scores [U, I] (every pair's logit) when
+        return_scores."""
+        if self.shard is not None:
+            raise NotImplementedError("top_k runs on one GPU: a row-sharded engine has only its shard of the tables")
+        nf = self.F + self.n_numeric
+        qf = [int(f) for f in query_fields]
+        if len(set(qf)) != len(qf) or any(f < 0 or f >= nf for f in qf):
+            raise ValueError("query_fields %r must be distinct column indices in [0, %d)" % (list(query_fields), nf))
+        cf = [f for f in range(nf) if f not in set(qf)]
+        if not qf or not cf:
+            raise ValueError("query_fields must split the %d columns into two non-empty sides" % nf)
+        k = int(k)
+        if not 1 <= k <= self.TOP_K_MAX:
+            raise ValueError("k=%d outside [1, %d]" % (k, self.TOP_K_MAX))
+        sides = []
+        for name, fields, ids, x in (("query", qf, query_ids, query_x), ("candidate", cf, candidate_ids, candidate_x)):
+            cat = sorted(f for f in fields if f < self.F)
+            num = sorted(f - self.F for f in fields if f >= self.F)
+            if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[1] != len(cat) \
+                    or not ids.is_contiguous() or ids.device.type != self.device.type:
+                raise ValueError("%s_ids must be a contiguous int32 [n, %d] tensor on %s" % (name, len(cat), self.device))
+            n = ids.shape[0]
+            if n < 1:
+                raise ValueError("%s_ids: no rows" % name)
+            if num:
+                if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != (n, len(num)) \
+                        or not x.is_contiguous() or x.device.type != self.device.type:
+                    raise ValueError("%s_x must be a contiguous float32 [%d, %d] tensor on %s" % (name, n, len(num), self.device))
+            elif x is not None:
+                raise ValueError("%s_x given but the %s side has no numeric column" % (name, name))
+            sides.append((cat, num, ids, x, n))
+        U, I = sides[0][4], sides[1][4]
+        excl_off = excl_idx = None
+        if exclude is not None:
+            if isinstance(exclude, tuple) and len(exclude) == 2:
+                off = np.asarray(exclude[0].cpu() if isinstance(exclude[0], torch.Tensor) else exclude[0], np.int64)
+                idx = np.asarray(exclude[1].cpu() if isinstance(exclude[1], torch.Tensor) else exclude[1], np.int32)
+            else:
+                rows = [np.asarray(sorted(set(int(c) for c in r)), np.int32) for r in exclude]
+                if len(rows) != U:
+                    raise ValueError("exclude: %d rows for %d queries" % (len(rows), U))
+                off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+                idx = np.concatenate(rows + [np.zeros(0, np.int32)]).astype(np.int32)
+            if off.shape != (U + 1,) or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != idx.size:
+                raise ValueError("exclude: offsets must be a non-decreasing [U + 1] array from 0 to len(indices)")
+            if idx.size and (idx.min() < 0 or idx.max() >= I):
+                raise ValueError("exclude: candidate index outside [0, %d)" % I)
+            excl_off = torch.from_numpy(off).to(self.device)
+            excl_idx = torch.from_numpy(np.ascontiguousarray(idx) if idx.size else np.zeros(1, np.int32)).to(self.device)
+        self.finalize_rows()
+        k_ = self.k
+        k_.query("mi_set_gemm_mode", 0)               # (layer 1 per side on the fp32-input MFMA; every forward sets its own mode)
+        (a_q, s_q, w_q), (a_c, s_c, w_c) = [self._side_tensors(*s[:4], candidate=i == 1) for i, s in enumerate(sides)]
+        H1 = self.layers[0][3] if self.use_dnn else 0
+        rest = self.layers[1:] if self.use_dnn else []
+        layer_off = torch.tensor([o for (ko, bo, _, _) in rest for o in (ko, bo)] or [0], dtype=torch.int64)
+        widths = torch.tensor([H1] + [h for (_, _, _, h) in rest], dtype=torch.int32)
+        E = self.E if self.use_mf else 0
+        top_score = torch.empty(U, k, dtype=torch.float32, device=self.device)
+        top_idx = torch.empty(U, k, dtype=torch.int32, device=self.device)
+        scores = torch.empty(U, I, dtype=torch.float32, device=self.device) if return_scores else None
+        ws = self._bytes("topk_ws", k_.query("mi_pair_topk_workspace_bytes", U, I, k, H1, E))
+        k_.mi_pair_topk(a_q, s_q, w_q, U, a_c, s_c, w_c, I, H1, E, self.dense, layer_off, widths, len(rest), self.act,
+                        excl_off, excl_idx, k, top_score, top_idx, scores, ws, ws.numel())
+        return (top_score, top_idx, scores) if return_scores else (top_score, top_idx)
+
+    def _side_tensors(self, cat, num, ids, x, candidate):
+        """One side of top_k: (a [n, H1] or None, s [n, E] or None, w [n] or None) with the model's own kernels — the
+        gather (s, fm, lin and the side's concat), the numeric columns, layer 1 on the side's rows of kernel_0 (identity
+        activation, bias_0 on the candidate side only) and the head's sum lin + fm (+ the wide bias on the candidate
+        side).  The canned models' layouts (field_dims, wide_fields, raw numeric columns) follow from kernel_0's zero
+        rows and lin_w's unused slots exactly as in _forward."""
+        k = self.k
+        dev, E, n = self.device, self.E, ids.shape[0]
+        f32 = dict(dtype=torch.float32, device=dev)
+        Fx, nx = len(cat), len(num)
+        raw = self.raw_numeric
+        emb_num = 0 if raw else nx
+        d_emb = (Fx + emb_num) * E if self.use_emb else 0
+        D = _align(d_emb + (nx if (raw and self.use_dnn) else 0), 4)
+        concat = torch.zeros(n, max(D, 4), **f32) if (self.use_dnn or (nx and not raw and self.use_emb)) else None
+        sumv = torch.zeros(n, E, **f32) if self.use_mf else None
+        fm = torch.zeros(n, **f32) if self.use_mf else None
+        lin = torch.zeros(n, **f32) if self.use_linear else None
+        field_off = self.field_off[cat].contiguous() if Fx else None
+        if Fx and self.use_emb and (concat is not None or sumv is not None):
+            k.mi_embed_fm_linear_fwd(self.table, None, field_off, ids, n, Fx, E, concat, concat.shape[1] if concat is not None
+                                     else 0, sumv, fm, None, None, 1, self.ts)
+        if Fx and lin is not None:
+            wide = [j for j, f in enumerate(cat) if self.wide_fields is None or self.wide_fields[f]]
+            if wide:
+                w_ids = ids if len(wide) == Fx else ids[:, wide].contiguous()
+                k.mi_embed_fm_linear_fwd(None, self.lin_w, self.field_off[[cat[j] for j in wide]].contiguous(), w_ids, n,
+                                         len(wide), E, None, 0, None, None, lin, None, self.ls, 0)
+        if nx:
+            jj = torch.tensor(num, dtype=torch.int64, device=dev)
+            wn = self._seg(self.dense, self.lin_num_off, (self.n_numeric,))[jj].contiguous() if self.use_linear else None
+            if raw:
+                if concat is not None or lin is not None:
+                    k.mi_numeric_raw_fwd(x, wn, n, nx, concat if self.use_dnn else None, D, d_emb, D - d_emb, lin)
+            else:
+                V = self._seg(self.dense, self.num_emb_off, (self.n_numeric, E))[jj].contiguous()
+                k.mi_numeric_embed_fwd(x, V, wn, n, nx, E, concat, concat.shape[1], Fx * E, sumv, fm, lin)
+        a = None
+        if self.use_dnn:
+            H1 = self.layers[0][3]
+            # the side's rows of kernel_0, in the order of its concat (torch gathers them: plumbing)
+            rows = [f * E + j for f in cat for j in range(E)] if self.use_emb else []
+            if raw:
+                rows += [self.D_emb + j for j in num]
+            else:
+                rows += [self.F * E + j * E + e for j in num for e in range(E)]
+            a = torch.empty(n, H1, **f32)
+            b0 = self.bias(0) if candidate else torch.zeros(H1, **f32)
+            if rows:
+                W = torch.zeros(D, H1, **f32)
+                W[:len(rows)] = self.kernel(0)[torch.tensor(rows, dtype=torch.int64, device=dev)]
+                k.mi_dense_fwd(concat, concat.shape[1], W, b0, a, H1, n, H1, D, 0, 1.0, 0, None)
+            else:
+                a.copy_(b0.expand(n, H1))
+        w = None
+        if lin is not None or fm is not None:
+            w = torch.empty(n, **f32)
+            lb = self.dense[self.lin_bias_off:] if (candidate and self.use_linear) else None
+            hws = self._bytes("topk_head_ws", k.query("mi_head_workspace_bytes", n))
+            k.mi_sigmoid_ce_head(lin, lb, fm, None, None, n, 1.0, w, None, None, None, hws, hws.numel())
+        elif candidate and self.use_linear:
+            w = self.dense[self.lin_bias_off:self.lin_bias_off + 1].expand(n).contiguous()
+        return a, sumv, w
+
     GAP_SORT_MIN = 16384      # entries from which sorting the touched rows by staleness pays for itself
     TOP_FUSED_MIN_BATCH = 4096  # examples from which the last hidden layer joins the fused logits + head launch (_top_fusable)
     GRAPH_SHAPES_MAX = 4      # captured steps kept at a time, one per batch shape (graph_train_step)

@@ -378,6 +378,17 @@ class Estimator:
                 yield {k: v[i] for k, v in pr.items()}
 
 
+    def recommend(self, query_features, candidate_features, k, exclude=None):
+        """Top-k candidates per query (DeepFM.top_k): query_features / candidate_features are raw feature dicts like
+        predict's input, one row per query / candidate.  A column belongs to the side whose dict holds its source key
+        (a key in both dicts or in neither is an error).  exclude: per query, candidate indices never returned (a
+        sequence per query, or a CSR pair (offsets, indices)).  Returns numpy logits [U, k], probabilities [U, k]
+        (the head's logistic) and indices [U, k] (int32; -1 with logit -inf where fewer than k are eligible)."""
+        from .model import recommend_batch
+        self._first_call(query_features, None, ModeKeys.PREDICT)
+        return recommend_batch(query_features, candidate_features, k, exclude, self.params)
+
+
 def train_and_evaluate(estimator, train_spec, eval_spec):
     """Local-mode tf.estimator.train_and_evaluate: train to max_steps; after every checkpoint
     (every save_checkpoints_secs and at the end) evaluate on the whole eval input and export."""

@@ -37,6 +37,50 @@ class _EvalCounters:
         self.batch_losses = []
 
 
+def split_sides(plan, query_features, candidate_features):
+    """The plan's columns (categorical fields 0..F-1, numeric column j as F + j) on the query side: those whose source
+    key is in query_features.  A key in both dicts or in neither is an error."""
+    qf = []
+    for i, c in enumerate(list(plan.categorical) + list(plan.numeric)):
+        inq, inc = c.key in query_features, c.key in candidate_features
+        if inq == inc:
+            raise ValueError("column %r: its key %r is in %s of the two feature dicts" % (c.name, c.key, "both" if inq else "neither"))
+        if inq:
+            qf.append(i)
+    return qf
+
+
+def side_inputs(plan, fields, features, device):
+    """ids int32 [n, Fx] and numeric values float32 [n, nx] (or None) of one side's columns, ascending field order."""
+    F = len(plan.categorical)
+    cat = [plan.categorical[f] for f in fields if f < F]
+    num = [plan.numeric[f - F] for f in fields if f >= F]
+    cols = []
+    for c in cat:
+        v = np.asarray(c.transform(features))
+        if v.size and (v.min() < 0 or v.max() >= c.num_buckets):
+            raise ValueError("column %r produced an id outside [0, %d)" % (c.name, c.num_buckets))
+        cols.append(v.reshape(-1))
+    n = len(cols[0]) if cols else len(num[0].values(features))
+    ids = np.ascontiguousarray(np.stack(cols, 1) if cols else np.zeros((n, 0)), np.int32)
+    x = np.ascontiguousarray(np.stack([c.values(features) for c in num], 1), np.float32) if num else None
+    return torch.from_numpy(ids).to(device), (torch.from_numpy(x).to(device) if x is not None else None)
+
+
+def recommend_batch(query_features, candidate_features, k, exclude, params):
+    """Estimator.recommend's body: the engine's top_k on the two sides' raw features, the head's logistic on the result."""
+    store = params["_store"]
+    plan, eng = store["plan"], store["engine"]
+    qf = split_sides(plan, query_features, candidate_features)
+    cf = [f for f in range(len(plan.categorical) + len(plan.numeric)) if f not in qf]
+    q_ids, q_x = side_inputs(plan, qf, query_features, eng.device)
+    c_ids, c_x = side_inputs(plan, cf, candidate_features, eng.device)
+    score, idx = eng.top_k(q_ids, c_ids, qf, k, q_x, c_x, exclude=exclude)
+    pr = binary_predictions(score.reshape(-1).contiguous(), eng.k)
+    return {"logits": score.cpu().numpy(), "probabilities": pr["logistic"].reshape(score.shape).cpu().numpy(),
+            "indices": idx.cpu().numpy()}
+
+
 def run_batch(features, labels, mode, params, make_engine):
     """make_engine(plan, device) -> engine.DeepFM; called once, the result lives in params['_store']."""
     store = params.setdefault("_store", {})

@@ -5,10 +5,13 @@ from mi355x_rec.canned import DNNClassifier
 from trainers import _cli
 
 
+def make_estimator(args, columns, config):
+    return DNNClassifier(hidden_units=args.hidden_units, feature_columns=columns["deep"], model_dir=args.job_dir,
+                         dropout=args.dropout, config=config)
+
+
 def train_and_evaluate(args):
-    return _cli.run(args, lambda columns, config: DNNClassifier(
-        hidden_units=args.hidden_units, feature_columns=columns["deep"], model_dir=args.job_dir,
-        dropout=args.dropout, config=config))
+    return _cli.run(args, lambda columns, config: make_estimator(args, columns, config))
 
 
 if __name__ == "__main__":

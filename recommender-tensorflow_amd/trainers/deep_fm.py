@@ -35,14 +35,16 @@ def model_fn(features, labels, mode, params):
     return run_batch(features, labels, mode, params, make)
 
 
+def make_estimator(args, columns, config):
+    return Estimator(model_fn=model_fn, model_dir=args.job_dir, config=config, params={
+        "categorical_columns": columns["linear"],
+        "use_linear": not args.exclude_linear, "use_mf": not args.exclude_mf, "use_dnn": not args.exclude_dnn,
+        "embedding_size": args.embedding_size, "hidden_units": args.hidden_units, "dropout": args.dropout,
+    })
+
+
 def train_and_evaluate(args):
-    def make_estimator(columns, config):
-        return Estimator(model_fn=model_fn, model_dir=args.job_dir, config=config, params={
-            "categorical_columns": columns["linear"],
-            "use_linear": not args.exclude_linear, "use_mf": not args.exclude_mf, "use_dnn": not args.exclude_dnn,
-            "embedding_size": args.embedding_size, "hidden_units": args.hidden_units, "dropout": args.dropout,
-        })
-    return _cli.run(args, make_estimator)
+    return _cli.run(args, lambda columns, config: make_estimator(args, columns, config))
 
 
 if __name__ == "__main__":

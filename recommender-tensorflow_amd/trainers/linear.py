@@ -5,9 +5,12 @@ from mi355x_rec.canned import LinearClassifier
 from trainers import _cli
 
 
+def make_estimator(args, columns, config):
+    return LinearClassifier(feature_columns=columns["linear"], model_dir=args.job_dir, config=config)
+
+
 def train_and_evaluate(args):
-    return _cli.run(args, lambda columns, config: LinearClassifier(
-        feature_columns=columns["linear"], model_dir=args.job_dir, config=config))
+    return _cli.run(args, lambda columns, config: make_estimator(args, columns, config))
 
 
 if __name__ == "__main__":

@@ -5,10 +5,14 @@ from mi355x_rec.canned import DNNLinearCombinedClassifier
 from trainers import _cli
 
 
-def train_and_evaluate(args):
-    return _cli.run(args, lambda columns, config: DNNLinearCombinedClassifier(
+def make_estimator(args, columns, config):
+    return DNNLinearCombinedClassifier(
         model_dir=args.job_dir, linear_feature_columns=columns["linear"], dnn_feature_columns=columns["deep"],
-        dnn_hidden_units=args.hidden_units, dnn_dropout=args.dropout, config=config))
+        dnn_hidden_units=args.hidden_units, dnn_dropout=args.dropout, config=config)
+
+
+def train_and_evaluate(args):
+    return _cli.run(args, lambda columns, config: make_estimator(args, columns, config))
 
 
 if __name__ == "__main__":
