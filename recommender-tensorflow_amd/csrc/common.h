@@ -40,10 +40,21 @@ const mi_step_state_t* step_state();
 
 }  // namespace mi
 
-// Publish a workgroup's abs-max into an abs-max vector (MI_AMAX_SLOTS floats, value = largest entry).
-// Every thread of the workgroup must call it (it contains a barrier).  One atomic per workgroup at
-// most, spread over the slots, and only when the slot does not already hold a larger value: same-
-// address atomics serialise at ~0.2 us each, and a kernel's first generation of workgroups ends together.
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+
+template <int N> __device__ __forceinline__ void mi_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// A workgroup's abs-max mx (>= 0) into its slot of an abs-max vector (MI_AMAX_SLOTS floats, value = largest entry), by
+// one thread: an atomic max on the bit pattern, spread over the slots, and only when the slot does not already hold a
+// larger value — same-address atomics serialise at ~0.2 us each, and a kernel's first generation of workgroups ends together.
+__device__ __forceinline__ void mi_amax_slot_max(float* vec, float mx) {
+  unsigned int* slot = reinterpret_cast<unsigned int*>(vec) + (blockIdx.x & (MI_AMAX_SLOTS - 1));
+  const unsigned int bits = __float_as_uint(mx);
+  if (bits > *reinterpret_cast<volatile unsigned int*>(slot)) atomicMax(slot, bits);
+}
+
+// The same from every thread of the workgroup (it contains a barrier), each with its own mx.
 __device__ __forceinline__ void mi_amax_publish(float* __restrict__ vec, float mx) {
   __shared__ float part[16];
 #pragma unroll
@@ -53,9 +64,38 @@ __device__ __forceinline__ void mi_amax_publish(float* __restrict__ vec, float m
   if (threadIdx.x == 0) {
     const int nw = (blockDim.x + 63) >> 6;
     for (int w = 1; w < nw; ++w) mx = fmaxf(mx, part[w]);
-    unsigned int* slot = reinterpret_cast<unsigned int*>(vec) + (blockIdx.x & (MI_AMAX_SLOTS - 1));
-    const unsigned int bits = __float_as_uint(mx);
-    if (bits > *reinterpret_cast<volatile unsigned int*>(slot)) atomicMax(slot, bits);
+    mi_amax_slot_max(vec, mx);
+  }
+}
+
+// ---- the sigmoid cross-entropy head (binary_classification_head, deep_fm.py:118-125) ----------------------------------
+// The unfused head (head.hip) and the fused tails (tail.hip, gemm_pl.hip's PL_TOP epilogue) are tested to give the same bits.
+__device__ __forceinline__ float mi_sigmoid_stable(float x) {
+  const float e = expf(-fabsf(x));
+  return x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+}
+// the loss of logit z for label y (0 or 1), unscaled: max(z, 0) - z y + log1p(exp(-|z|))
+__device__ __forceinline__ float mi_sigmoid_ce_loss(float z, float y) { return fmaxf(z, 0.f) - z * y + log1pf(expf(-fabsf(z))); }
+// its gradient d loss / d z, scaled
+__device__ __forceinline__ float mi_sigmoid_ce_grad(float z, float y, float scale) { return (mi_sigmoid_stable(z) - y) * scale; }
+
+// ---- activation of tf.layers.dense (deep_fm.py:22,100: params["activation"], default tf.nn.relu) -----------------------
+// kind: 0 none, 1 relu, 2 sigmoid, 3 tanh; and its derivative expressed through the activation's OUTPUT y (what the forward
+// stored).  The training step, predict_logits and top-K scoring all use these.
+__device__ __forceinline__ float mi_act(int kind, float v) {
+  switch (kind) {
+    case 1: return fmaxf(v, 0.f);
+    case 2: return 1.f / (1.f + __expf(-v));
+    case 3: return tanhf(v);
+    default: return v;
+  }
+}
+__device__ __forceinline__ float mi_act_deriv_from_output(int kind, float y) {
+  switch (kind) {
+    case 1: return y > 0.f ? 1.f : 0.f;
+    case 2: return y * (1.f - y);
+    case 3: return 1.f - y * y;
+    default: return 1.f;
   }
 }
 

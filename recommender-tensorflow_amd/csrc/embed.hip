@@ -11,14 +11,12 @@
 // are in flight per lane; ids and linear weights are fetched one field per lane and handed
 // round the group with ds_bpermute.  The FM reduction over e is a butterfly inside the group.
 #include "common.h"
+#include "planes.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kRowsInFlight = 8;
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 template <int LPR>
 __device__ __forceinline__ float group_sum(float x) {
@@ -127,8 +125,6 @@ __global__ __launch_bounds__(kBlock) void embed_fm_linear_fwd_k(
 // before it writes: all F rows of the example stay in registers (FC >= F float4 per lane, all loads in
 // flight at once), then one power-of-two exponent per example, then 8-byte stores (4 k of one plane per
 // lane; the LPR lanes of a group write each field's 4E bytes of planes contiguously).  E % 16 == 0.
-typedef _Float16 e_h16x2 __attribute__((ext_vector_type(2)));
-typedef float e_f32x2 __attribute__((ext_vector_type(2)));
 template <int LPR, int FC>
 __global__ __launch_bounds__(kBlock) void embed_fm_planes_fwd_k(
     const float* __restrict__ table, const int64_t* __restrict__ field_off, const int32_t* __restrict__ ids, int64_t B,
@@ -193,9 +189,8 @@ __global__ __launch_bounds__(kBlock) void embed_fm_planes_fwd_k(
   float gmx = mx;                                  // the example's abs-max over all fields and lanes
 #pragma unroll
   for (int off = LPR / 2; off > 0; off >>= 1) gmx = fmaxf(gmx, __shfl_xor(gmx, off, LPR));
-  const int ex = static_cast<int>((__float_as_uint(gmx) >> 23) & 0xffu);
-  const int sx = max(-100, min(100, 141 - ex));
-  const float sc = __uint_as_float(static_cast<uint32_t>(127 + sx) << 23);
+  const int sx = pl_exp_for(gmx);
+  const float sc = pl_pow2(sx);
   if (valid) {
     if (sumv && lane_on) st4(sumv + b * E + eo, s);
     if (l == 0) {
@@ -204,16 +199,14 @@ __global__ __launch_bounds__(kBlock) void embed_fm_planes_fwd_k(
     }
     // 4 k of one example: 8 bytes of the high plane, 8 of the low one, in k-block (k >> 4) at planes + (k >> 4) * ldp_b
     auto store4 = [&](int k, const float4& v) {
-      const e_f32x2 u01 = {v.x * sc, v.y * sc}, u23 = {v.z * sc, v.w * sc};
-      const e_h16x2 h01 = __builtin_convertvector(u01, e_h16x2), h23 = __builtin_convertvector(u23, e_h16x2);
-      const e_f32x2 d01 = {u01[0] - static_cast<float>(h01[0]), u01[1] - static_cast<float>(h01[1])};
-      const e_f32x2 d23 = {u23[0] - static_cast<float>(h23[0]), u23[1] - static_cast<float>(h23[1])};
-      const e_h16x2 l01 = __builtin_convertvector(d01, e_h16x2), l23 = __builtin_convertvector(d23, e_h16x2);
-      char* d = planes + b * 64 + (k & 15) * 2 + (k >> 4) * ldp_b;
+      uint32_t h01, l01, h23, l23;
+      pl_split2<false>(v.x * sc, v.y * sc, h01, l01);
+      pl_split2<false>(v.z * sc, v.w * sc, h23, l23);
+      char* d = planes + b * PL_ROWB + (k & 15) * 2 + (k >> 4) * ldp_b;
       // (tried here, no gain: non-temporal stores, 0.188 vs 0.175 ms per launch; a DPP quad exchange so that every
       // lane stores a whole 16-byte piece of the block instead of two 8-byte halves, 0.168-0.176 vs 0.166-0.18)
-      *reinterpret_cast<uint2*>(d) = make_uint2(__builtin_bit_cast(uint32_t, h01), __builtin_bit_cast(uint32_t, h23));
-      *reinterpret_cast<uint2*>(d + 32) = make_uint2(__builtin_bit_cast(uint32_t, l01), __builtin_bit_cast(uint32_t, l23));
+      *reinterpret_cast<uint2*>(d) = make_uint2(h01, h23);
+      *reinterpret_cast<uint2*>(d + PL_LO) = make_uint2(l01, l23);
     };
     if (lane_on) {
 #pragma unroll
@@ -529,8 +522,8 @@ int32_t mi_embed_fm_planes_fwd(const float* table, const int64_t* field_off, con
     return MI_ERR_UNSUPPORTED;
   }
   MI_REQUIRE(table && field_off && ids && concat && concat->data && concat->row_exp, "embed_fm_planes_fwd: null buffer");
-  MI_REQUIRE(concat->blk_stride >= B * 64 && (concat->blk_stride & 63) == 0 && mi::aligned16(concat->data) && mi::aligned16(table) &&
-                 (!sumv || mi::aligned16(sumv)), "embed_fm_planes_fwd: planes block stride / alignment");
+  MI_REQUIRE(mi::planes_ok(concat, B) && mi::aligned16(table) && (!sumv || mi::aligned16(sumv)),
+             "embed_fm_planes_fwd: planes block stride / alignment");
   MI_REQUIRE(!fm || sumv, "embed_fm_planes_fwd: fm needs sumv");
   MI_REQUIRE(tail_cols >= 0 && (tail_cols & 15) == 0 && n_numeric >= 0 && n_numeric <= tail_cols && (tail_cols == 0 || x_num),
              "embed_fm_planes_fwd: %d numeric columns in a tail of %d (whole 16-k blocks, x_num given)", n_numeric, tail_cols);

@@ -16,6 +16,7 @@
 // k-values per ds_read_b128 feed four consecutive MFMAs: lane half h owns k = 8s+4h+j.
 // Workgroup ids are remapped so that the blocks sharing an A row-panel run on one XCD (shared L2).
 #include "common.h"
+#include "planes.h"
 #include "wgrad_pl.h"
 #include <algorithm>
 #include <cstdlib>
@@ -201,25 +202,6 @@ __device__ __forceinline__ void read_frag(const float* __restrict__ S, int mn, i
   }
 }
 
-// activation of tf.layers.dense (deep_fm.py:22,100: params["activation"], default tf.nn.relu): 0 none, 1 relu,
-// 2 sigmoid, 3 tanh; and its derivative expressed through the activation's OUTPUT y (what the forward stored)
-__device__ __forceinline__ float act_apply(int kind, float v) {
-  switch (kind) {
-    case 1: return fmaxf(v, 0.f);
-    case 2: return 1.f / (1.f + __expf(-v));
-    case 3: return tanhf(v);
-    default: return v;
-  }
-}
-__device__ __forceinline__ float act_deriv_from_output(int kind, float y) {
-  switch (kind) {
-    case 1: return y > 0.f ? 1.f : 0.f;
-    case 2: return y * (1.f - y);
-    case 3: return 1.f - y * y;
-    default: return 1.f;
-  }
-}
-
 // ---- epilogue shared by the fp32-MFMA and the bf16x3-split kernels --------------------------
 // C/D register map of every 32x32 MFMA (dtype independent): col = lane&31,
 // row = (r&3) + 8*(r>>2) + 4*(lane>>5).  i = lane&31, h = lane>>5.
@@ -247,7 +229,7 @@ __device__ __forceinline__ void store_tile_c(const GemmArgs& a, const f32x16 (&a
         float v = acc[mi][ni][r] * sa * sb;
         if (a.epi == EPI_BIAS_ACT) {
           v += bv;
-          v = act_apply(a.relu, v);
+          v = mi_act(a.relu, v);
           if (a.keep_prob < 1.f) v = mi_drop_keep_at(seed, row, col, thresh) ? v / a.keep_div : 0.f;
         } else if (a.epi == EPI_MASK) {
           if (a.mask_src) {
@@ -257,7 +239,7 @@ __device__ __forceinline__ void store_tile_c(const GemmArgs& a, const f32x16 (&a
             } else {
               // stored output x = act(pre) / keep or 0 (dropped; with dropout an output that is exactly 0 counts as dropped)
               const bool dropped = a.keep_div < 1.f && x == 0.f;
-              v = dropped ? 0.f : (v / a.keep_div) * act_deriv_from_output(a.relu, x * a.keep_div);
+              v = dropped ? 0.f : (v / a.keep_div) * mi_act_deriv_from_output(a.relu, x * a.keep_div);
             }
           }
         }
@@ -563,7 +545,7 @@ __global__ __launch_bounds__(kThreads) void gemv_fwd_k(const float* __restrict__
       const int64_t m = m0 + j * groups;
       if (m < M && l == 0) {
         float v = acc[j] + b0;
-        v = act_apply(relu, v);
+        v = mi_act(relu, v);
         if (keep_prob < 1.f) v = mi_drop_keep_at(seed, static_cast<uint32_t>(m), 0u, thresh) ? v / keep_div : 0.f;
         Y[m * ldy] = v;
         mx = fmaxf(mx, fabsf(v));
@@ -606,10 +588,10 @@ __global__ __launch_bounds__(kThreads) void gemv_dgrad_k(const float* __restrict
           v.z = xv[j].z > 0.f ? v.z / keep_div : 0.f; v.w = xv[j].w > 0.f ? v.w / keep_div : 0.f;
         } else {
           const bool dr = keep_div < 1.f;
-          v.x = (dr && xv[j].x == 0.f) ? 0.f : (v.x / keep_div) * act_deriv_from_output(act, xv[j].x * keep_div);
-          v.y = (dr && xv[j].y == 0.f) ? 0.f : (v.y / keep_div) * act_deriv_from_output(act, xv[j].y * keep_div);
-          v.z = (dr && xv[j].z == 0.f) ? 0.f : (v.z / keep_div) * act_deriv_from_output(act, xv[j].z * keep_div);
-          v.w = (dr && xv[j].w == 0.f) ? 0.f : (v.w / keep_div) * act_deriv_from_output(act, xv[j].w * keep_div);
+          v.x = (dr && xv[j].x == 0.f) ? 0.f : (v.x / keep_div) * mi_act_deriv_from_output(act, xv[j].x * keep_div);
+          v.y = (dr && xv[j].y == 0.f) ? 0.f : (v.y / keep_div) * mi_act_deriv_from_output(act, xv[j].y * keep_div);
+          v.z = (dr && xv[j].z == 0.f) ? 0.f : (v.z / keep_div) * mi_act_deriv_from_output(act, xv[j].z * keep_div);
+          v.w = (dr && xv[j].w == 0.f) ? 0.f : (v.w / keep_div) * mi_act_deriv_from_output(act, xv[j].w * keep_div);
         }
       }
       *reinterpret_cast<float4*>(dX + mm[j] * lddx + kk[j]) = v;
@@ -964,8 +946,7 @@ static int32_t wgrad_job_plan(const mi_planes_t* X, const mi_planes_t* dY, float
   MI_REQUIRE(M % BK == 0 && N % BN == 0 && K % BM == 0,
              "dense_bwd_weight_planes: M=%lld N=%d K=%d (examples a multiple of 32, N and K multiples of 128)", (long long)M, N, K);
   MI_REQUIRE(X && dY && X->data && dY->data && X->row_exp && dY->row_exp && dW && workspace, "dense_bwd_weight_planes: null buffer");
-  MI_REQUIRE(mi::aligned16(X->data) && mi::aligned16(dY->data) && X->blk_stride >= 64 * M && dY->blk_stride >= 64 * M &&
-                 X->blk_stride % 64 == 0 && dY->blk_stride % 64 == 0 && X->blk_stride < (1 << 28) && dY->blk_stride < (1 << 28),
+  MI_REQUIRE(mi::planes_ok(X, M) && mi::planes_ok(dY, M) && X->blk_stride < (1 << 28) && dY->blk_stride < (1 << 28),
              "dense_bwd_weight_planes: planes (16-byte aligned, 64 M <= blk_stride < 2^28, a multiple of 64)");
   MI_REQUIRE(amax && amax->a && amax->b, "dense_bwd_weight_planes: needs the abs-max vectors of X and dY");
   MI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 31u) == 0, "dense_bwd_weight_planes: workspace must be 32-byte aligned");

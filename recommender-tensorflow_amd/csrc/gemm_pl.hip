@@ -4,16 +4,11 @@
 // for every layer whose shape allows it (gemm.hip keeps the any-shape kernels; the weight gradient from planes is
 // wgrad_pl.hip).
 //
-// Operand format ("planes", mi_planes_t): a matrix [rows][K] is stored as fp16 high + fp16 low parts
-// of x * 2^s_r with ONE power-of-two exponent s_r PER ROW (row max -> [2^14, 2^15)):
-//     x * 2^s_r = hi + lo,   hi = fp16(x * 2^s_r)  (RNE),  lo = fp16(x * 2^s_r - hi)
-// so every row keeps ~22 significant bits relative to ITS OWN largest element (elements more than
-// 2^-17 below their row's maximum lose low bits gradually; the round-1 matrix-wide scale lost them for
-// whole rows, e.g. the dY rows of well-fit examples).  In memory the matrix is K-BLOCK MAJOR: for each block
-// of 16 k, all rows back to back, a row's piece being 16 x hi then 16 x lo (64 B); blocks are blk_stride
-// bytes apart.  The 16-k tile of any range of rows is therefore ONE contiguous run of full cache lines —
-// what a workgroup's LDS-DMA stage reads (measured against row-major pieces of 64 B, 6.6 KB apart: layer-1
-// forward 422 -> 339 us).
+// Operand format: planes (mi_planes_t, planes.h), fp16 high + low parts with one power-of-two exponent PER ROW, so
+// every row keeps ~22 significant bits relative to ITS OWN largest element (elements more than 2^-17 below their row's
+// maximum lose low bits gradually; the round-1 matrix-wide scale lost them for whole rows, e.g. the dY rows of well-fit
+// examples).  K-block major, the 16-k tile of any range of rows is ONE contiguous run of full cache lines — what a
+// workgroup's LDS-DMA stage reads (measured against row-major pieces of 64 B, 6.6 KB apart: layer-1 forward 422 -> 339 us).
 //
 // Both operands of these GEMMs are "k-contiguous" (NT form):
 //     forward        Y[m][n]  = sum_k X[m][k]  * Wt[n][k]      (Wt = planes of W transposed, rows = n)
@@ -34,6 +29,7 @@
 // image is dense 64-B rows with the 16-B chunk index XOR-swizzled by (row >> 2) & 3 on the SOURCE address
 // (ds_read_b128 fragment reads are then conflict-free).
 #include "common.h"
+#include "planes.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -41,13 +37,10 @@
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float fl32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int PL_THREADS = 512;
 constexpr int PL_BK = 16;
-constexpr int PL_ROWB = 64;       // bytes per tile row and stage: 16 k x (hi, lo) x 2 B
 
 enum { PL_FWD = 0, PL_DGRAD = 1, PL_TOP = 2 };
 
@@ -72,15 +65,6 @@ struct PlArgs {
   float* top_dnn; float* top_logits; float* top_dlogit; // per example (top_dnn may be NULL)
   float* top_part;                                      // [workgroups][N + 2]: the logits layer's dW partial, sum d, sum loss
 };
-
-__device__ __forceinline__ float pl_pow2(int s) { return __uint_as_float(static_cast<uint32_t>(127 + s) << 23); }
-// exponent s with amax * 2^s in [2^14, 2^15), clamped so that 2^s and 2^-s are normal numbers
-__device__ __forceinline__ int pl_exp_for(float amax) {
-  const int e = static_cast<int>((__float_as_uint(amax) >> 23) & 0xffu);
-  return max(-100, min(100, 141 - e));
-}
-
-template <int N> __device__ __forceinline__ void pl_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // -DMI_PL_STAMPS: clock64() stamps at the phase boundaries of every k-step, from lane 0 of waves 0 (group 0) and 4
 // (group 1) of the first 32 workgroups (tools/gemm_pl_stamps.py reads them back).  Not part of the product build.
@@ -247,7 +231,7 @@ __global__ __launch_bounds__(PL_THREADS, 2) void gemm_pl_k(const PlArgs a) {
   PL_MARK(0);
 #pragma unroll
   for (int s = 0; s < PL_NBUF; ++s) issue_share(min(s, nk - 1), s);
-  pl_wait_vmcnt<LPS*(PL_NBUF - 1)>();                      // own share of stage 0
+  mi_wait_vmcnt<LPS*(PL_NBUF - 1)>();                      // own share of stage 0
   __builtin_amdgcn_s_barrier();                            // barrier 0
   if (g1) __builtin_amdgcn_s_barrier();                    // the stagger
   // (sched_barrier(0): hipcc otherwise moves register-only MFMAs across s_barrier, which would put both
@@ -260,7 +244,7 @@ __global__ __launch_bounds__(PL_THREADS, 2) void gemm_pl_k(const PlArgs a) {
     PL_STAMP(1);                                           // DMA + fragment reads issued
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     PL_STAMP(2);                                           // fragments in registers
-    pl_wait_vmcnt<LPS*(DMA_IN_C ? PL_NBUF - 3 : PL_NBUF - 2)>();   // own share of stage t + 1 (issued in C(t + 2 - NBUF) / L(t + 2 - NBUF))
+    mi_wait_vmcnt<LPS*(DMA_IN_C ? PL_NBUF - 3 : PL_NBUF - 2)>();   // own share of stage t + 1 (issued in C(t + 2 - NBUF) / L(t + 2 - NBUF))
     PL_STAMP(3);                                           // own DMA share of the next stage has landed
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -289,7 +273,7 @@ __global__ __launch_bounds__(PL_THREADS, 2) void gemm_pl_k(const PlArgs a) {
   // columns go lane pair -> LDS -> the four column groups in order; sums over examples go through a 32-lane butterfly.
   if constexpr (EPI == PL_TOP) {
     static_assert(TN == 1, "PL_TOP: one 128-column tile");
-    pl_wait_vmcnt<0>();
+    mi_wait_vmcnt<0>();
     __syncthreads();
     float* e_fw = reinterpret_cast<float*>(smem);     // [128] 2^-s of the weight row
     float* e_bias = e_fw + 128;                       // [128]
@@ -374,10 +358,8 @@ __global__ __launch_bounds__(PL_THREADS, 2) void gemm_pl_k(const PlArgs a) {
       if (a.top_fm) z += a.top_fm[mc];
       z += dnn;
       const float yl = a.top_labels[mc] ? 1.f : 0.f;
-      const float loss = (fmaxf(z, 0.f) - z * yl + log1pf(expf(-fabsf(z)))) * a.top_scale;
-      const float e = expf(-fabsf(z));
-      const float sg = z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-      const float g = mok ? (sg - yl) * a.top_scale : 0.f;
+      const float loss = mi_sigmoid_ce_loss(z, yl) * a.top_scale;
+      const float g = mok ? mi_sigmoid_ce_grad(z, yl, a.top_scale) : 0.f;
       gy[y] = g;
       if (mok && wn == 0 && h == 0) {
         if (a.top_dnn) a.top_dnn[m] = dnn;
@@ -443,9 +425,7 @@ __global__ __launch_bounds__(PL_THREADS, 2) void gemm_pl_k(const PlArgs a) {
       float mx = 0.f;
 #pragma unroll
       for (int w = 0; w < 8; ++w) mx = fmaxf(mx, e_wmax[w]);
-      unsigned int* slot = reinterpret_cast<unsigned int*>(a.amax_c) + (blockIdx.x & (MI_AMAX_SLOTS - 1));
-      const unsigned int bits = __float_as_uint(mx);
-      if (bits > *reinterpret_cast<volatile unsigned int*>(slot)) atomicMax(slot, bits);
+      mi_amax_slot_max(a.amax_c, mx);
     }
     // ---- dX as planes: row exponent from the row's abs-max over the 128 columns (tail.hip's conversion: a positive value keeps
     // a positive high part)
@@ -459,19 +439,7 @@ __global__ __launch_bounds__(PL_THREADS, 2) void gemm_pl_k(const PlArgs a) {
       if (m < a.M && h == 0 && wn == 0) a.c_exp[m] = sx;
       uint32_t ph[8], pq[8];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float u0 = acc[0][y][2 * q] * sc, u1 = acc[0][y][2 * q + 1] * sc;
-        const fl32x2 uu = {u0, u1};
-        h16x2 hh = __builtin_convertvector(uu, h16x2);
-        uint32_t hb = __builtin_bit_cast(uint32_t, hh);
-        if (u0 > 0.f && (hb & 0xffffu) == 0u) hb |= 1u;
-        if (u1 > 0.f && (hb >> 16) == 0u) hb |= 0x10000u;
-        hh = __builtin_bit_cast(h16x2, hb);
-        const fl32x2 rr2 = {u0 - static_cast<float>(hh[0]), u1 - static_cast<float>(hh[1])};
-        const h16x2 ll = __builtin_convertvector(rr2, h16x2);
-        ph[q] = hb;
-        pq[q] = __builtin_bit_cast(uint32_t, ll);
-      }
+      for (int q = 0; q < 8; ++q) pl_split2<true>(acc[0][y][2 * q] * sc, acc[0][y][2 * q + 1] * sc, ph[q], pq[q]);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         auto r1 = __builtin_amdgcn_permlane32_swap(ph[q], ph[q + 4], false, false);
@@ -501,7 +469,7 @@ __global__ __launch_bounds__(PL_THREADS, 2) void gemm_pl_k(const PlArgs a) {
   }
 
   // ---------------------------------------------------------------- epilogue
-  pl_wait_vmcnt<0>();                 // the tail's re-issued loads
+  mi_wait_vmcnt<0>();                 // the tail's re-issued loads
   __syncthreads();                    // every wave is done with the stage buffers: LDS is free
   float* e_fw = reinterpret_cast<float*>(smem);     // [BNt] 2^-s of the weight row (0 outside the matrix)
   float* e_bias = e_fw + BNt;                       // [BNt]
@@ -689,9 +657,7 @@ __global__ __launch_bounds__(PL_THREADS, 2) void gemm_pl_k(const PlArgs a) {
     float mx = 0.f;
 #pragma unroll
     for (int w = 0; w < 8; ++w) mx = fmaxf(mx, e_wmax[w]);
-    unsigned int* slot = reinterpret_cast<unsigned int*>(a.amax_c) + (blockIdx.x & (MI_AMAX_SLOTS - 1));
-    const unsigned int bits = __float_as_uint(mx);
-    if (bits > *reinterpret_cast<volatile unsigned int*>(slot)) atomicMax(slot, bits);
+    mi_amax_slot_max(a.amax_c, mx);
   }
   if (!HOT && !a.Cp) {
 #ifdef MI_PL_STAMPS
@@ -715,27 +681,8 @@ __global__ __launch_bounds__(PL_THREADS, 2) void gemm_pl_k(const PlArgs a) {
     for (int x = 0; x < TN; ++x) {
       uint32_t ph[8], pq[8];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float u0 = acc[x][y][2 * q] * sc, u1 = acc[x][y][2 * q + 1] * sc;
-        const fl32x2 uu = {u0, u1};
-        h16x2 hh = __builtin_convertvector(uu, h16x2);                 // v_cvt_pk_f16_f32 (RNE)
-        uint32_t hb = __builtin_bit_cast(uint32_t, hh);
-        if constexpr (EPI == PL_FWD) {
-          // a positive value must stay positive in the high plane: the data gradient's relu/dropout mask
-          // reads "hi > 0" (only values below 2^-39 of the row maximum round to zero at all): high half =
-          // max(high half, u > 0) as ONE packed unsigned maximum — positive fp16 order like their bit patterns, and a
-          // negative half (sign bit set) is above 1 as an unsigned number, so it stays what it is.
-          const uint32_t nz = (u0 > 0.f ? 1u : 0u) | (u1 > 0.f ? 0x10000u : 0u);
-          typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-          const u16x2 mxv = __builtin_elementwise_max(__builtin_bit_cast(u16x2, hb), __builtin_bit_cast(u16x2, nz));
-          hb = __builtin_bit_cast(uint32_t, mxv);
-          hh = __builtin_bit_cast(h16x2, hb);
-        }
-        const fl32x2 rr2 = {u0 - static_cast<float>(hh[0]), u1 - static_cast<float>(hh[1])};
-        const h16x2 ll = __builtin_convertvector(rr2, h16x2);
-        ph[q] = hb;
-        pq[q] = __builtin_bit_cast(uint32_t, ll);
-      }
+      for (int q = 0; q < 8; ++q)           // (FWD: the data gradient's mask reads "hi > 0" — a positive value stays positive)
+        pl_split2<EPI == PL_FWD>(acc[x][y][2 * q] * sc, acc[x][y][2 * q + 1] * sc, ph[q], pq[q]);
       // lane h = 0 collects columns 0..15 of the 32-column tile, lane h = 1 columns 16..31
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -803,25 +750,18 @@ __global__ __launch_bounds__(256) void split_rows_k(const float* __restrict__ X,
     char* d = out + r * PL_ROWB;
     for (int k = lane; k < K16; k += 64) {
       const float x = k < K ? (transpose ? X[static_cast<int64_t>(k) * ldx + r] : X[r * ldx + k]) : 0.f;
-      const float u = x * sc;
-      _Float16 hi = static_cast<_Float16>(u);
-      if (u > 0.f && hi == static_cast<_Float16>(0.f)) hi = __builtin_bit_cast(_Float16, static_cast<unsigned short>(1));
-      const _Float16 lo = static_cast<_Float16>(u - static_cast<float>(hi));
-      _Float16* e = reinterpret_cast<_Float16*>(d + (k >> 4) * ldo_b);
-      e[k & 15] = hi;
-      e[16 + (k & 15)] = lo;
+      uint32_t hi, lo;
+      pl_split2<true>(x * sc, 0.f, hi, lo);                            // (one value: the low halves)
+      uint16_t* e = reinterpret_cast<uint16_t*>(d + (k >> 4) * ldo_b);
+      e[k & 15] = static_cast<uint16_t>(hi);
+      e[PL_LO / 2 + (k & 15)] = static_cast<uint16_t>(lo);
     }
   }
   if (amax_out) {                       // (every thread of the block reaches this)
     __shared__ float part[4];
     if (lane == 0) part[threadIdx.x >> 6] = r < rows ? mx : 0.f;
     __syncthreads();
-    if (threadIdx.x == 0) {
-      const float m4 = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
-      unsigned int* slot = reinterpret_cast<unsigned int*>(amax_out) + (blockIdx.x & (MI_AMAX_SLOTS - 1));
-      const unsigned int bits = __float_as_uint(m4);
-      if (bits > *reinterpret_cast<volatile unsigned int*>(slot)) atomicMax(slot, bits);
-    }
+    if (threadIdx.x == 0) mi_amax_slot_max(amax_out, fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3])));
   }
 }
 
@@ -861,19 +801,8 @@ __global__ __launch_bounds__(256) void split_rows_blk_k(const float* __restrict_
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float4 v = kb == l ? v0[q] : *reinterpret_cast<const float4*>(src + kb * 16 + q * 4);
-        const float u[4] = {v.x * sc, v.y * sc, v.z * sc, v.w * sc};
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const fl32x2 uu = {u[2 * e], u[2 * e + 1]};
-          h16x2 hh = __builtin_convertvector(uu, h16x2);
-          uint32_t hb = __builtin_bit_cast(uint32_t, hh);
-          if (uu[0] > 0.f && (hb & 0xffffu) == 0u) hb |= 1u;          // positive stays positive (mask reads hi > 0)
-          if (uu[1] > 0.f && (hb >> 16) == 0u) hb |= 0x10000u;
-          hh = __builtin_bit_cast(h16x2, hb);
-          const fl32x2 rr2 = {uu[0] - static_cast<float>(hh[0]), uu[1] - static_cast<float>(hh[1])};
-          ph[2 * q + e] = hb;
-          pq[2 * q + e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(rr2, h16x2));
-        }
+        pl_split2<true>(v.x * sc, v.y * sc, ph[2 * q], pq[2 * q]);
+        pl_split2<true>(v.z * sc, v.w * sc, ph[2 * q + 1], pq[2 * q + 1]);
       }
       uint4* d = reinterpret_cast<uint4*>(out + kb * ldo_b + r * PL_ROWB);
       d[0] = make_uint4(ph[0], ph[1], ph[2], ph[3]);
@@ -888,12 +817,7 @@ __global__ __launch_bounds__(256) void split_rows_blk_k(const float* __restrict_
     for (int o = 32; o >= LPR; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     if ((t & 63) == 0) part[t >> 6] = mx;
     __syncthreads();
-    if (t == 0) {
-      const float m4 = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
-      unsigned int* slot = reinterpret_cast<unsigned int*>(amax_out) + (blockIdx.x & (MI_AMAX_SLOTS - 1));
-      const unsigned int bits = __float_as_uint(m4);
-      if (bits > *reinterpret_cast<volatile unsigned int*>(slot)) atomicMax(slot, bits);
-    }
+    if (t == 0) mi_amax_slot_max(amax_out, fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3])));
   }
 }
 
@@ -956,23 +880,12 @@ __global__ __launch_bounds__(256) void vec_dgrad_planes_k(const float* __restric
       if (l == 0) row_exp[r] = s;
       for (int q = l; q < nq; q += LPR) {
         const float4 v = q == l ? v0 : value4(4 * q);
-        const float u[4] = {v.x * sc, v.y * sc, v.z * sc, v.w * sc};
         uint32_t ph[2], pq[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const fl32x2 uu = {u[2 * e], u[2 * e + 1]};
-          h16x2 hh = __builtin_convertvector(uu, h16x2);
-          uint32_t hb = __builtin_bit_cast(uint32_t, hh);
-          if (uu[0] > 0.f && (hb & 0xffffu) == 0u) hb |= 1u;          // positive stays positive (mask reads hi > 0)
-          if (uu[1] > 0.f && (hb >> 16) == 0u) hb |= 0x10000u;
-          hh = __builtin_bit_cast(h16x2, hb);
-          const fl32x2 rr2 = {uu[0] - static_cast<float>(hh[0]), uu[1] - static_cast<float>(hh[1])};
-          ph[e] = hb;
-          pq[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(rr2, h16x2));
-        }
+        pl_split2<true>(v.x * sc, v.y * sc, ph[0], pq[0]);
+        pl_split2<true>(v.z * sc, v.w * sc, ph[1], pq[1]);
         char* d = stage + ((q >> 2) * rows_per_block + rl) * PL_ROWB + (q & 3) * 8;
         *reinterpret_cast<uint2*>(d) = make_uint2(ph[0], ph[1]);
-        *reinterpret_cast<uint2*>(d + 32) = make_uint2(pq[0], pq[1]);
+        *reinterpret_cast<uint2*>(d + PL_LO) = make_uint2(pq[0], pq[1]);
       }
     }
   }
@@ -990,12 +903,7 @@ __global__ __launch_bounds__(256) void vec_dgrad_planes_k(const float* __restric
     for (int o = 32; o >= LPR; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     if ((t & 63) == 0) part[t >> 6] = mx;
     __syncthreads();
-    if (t == 0) {
-      const float m4 = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
-      unsigned int* slot = reinterpret_cast<unsigned int*>(amax_out) + (blockIdx.x & (MI_AMAX_SLOTS - 1));
-      const unsigned int bits = __float_as_uint(m4);
-      if (bits > *reinterpret_cast<volatile unsigned int*>(slot)) atomicMax(slot, bits);
-    }
+    if (t == 0) mi_amax_slot_max(amax_out, fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3])));
   }
 }
 
@@ -1040,23 +948,12 @@ __global__ __launch_bounds__(256) void split_t_k(const float* __restrict__ X, in
     if (threadIdx.x < 128 && r < rows && k0 + kb < K16) {
       uint32_t ph[8], pq[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float u0 = tile[kb + 2 * j][rl] * sc, u1 = tile[kb + 2 * j + 1][rl] * sc;
-        const fl32x2 uu = {u0, u1};
-        h16x2 hh = __builtin_convertvector(uu, h16x2);
-        uint32_t hb = __builtin_bit_cast(uint32_t, hh);
-        if (u0 > 0.f && (hb & 0xffffu) == 0u) hb |= 1u;
-        if (u1 > 0.f && (hb >> 16) == 0u) hb |= 0x10000u;
-        hh = __builtin_bit_cast(h16x2, hb);
-        const fl32x2 dd = {u0 - static_cast<float>(hh[0]), u1 - static_cast<float>(hh[1])};
-        ph[j] = hb;
-        pq[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(dd, h16x2));
-      }
+      for (int j = 0; j < 8; ++j) pl_split2<true>(tile[kb + 2 * j][rl] * sc, tile[kb + 2 * j + 1][rl] * sc, ph[j], pq[j]);
       char* d = out + ((k0 + kb) >> 4) * ldo_b + r * PL_ROWB;
       *reinterpret_cast<uint4*>(d) = make_uint4(ph[0], ph[1], ph[2], ph[3]);
       *reinterpret_cast<uint4*>(d + 16) = make_uint4(ph[4], ph[5], ph[6], ph[7]);
-      *reinterpret_cast<uint4*>(d + 32) = make_uint4(pq[0], pq[1], pq[2], pq[3]);
-      *reinterpret_cast<uint4*>(d + 48) = make_uint4(pq[4], pq[5], pq[6], pq[7]);
+      *reinterpret_cast<uint4*>(d + PL_LO) = make_uint4(pq[0], pq[1], pq[2], pq[3]);
+      *reinterpret_cast<uint4*>(d + PL_LO + 16) = make_uint4(pq[4], pq[5], pq[6], pq[7]);
     }
   }
 }
@@ -1105,16 +1002,12 @@ __global__ __launch_bounds__(256) void split_weights_k(const float* __restrict__
     for (int j = 0; j < 8; ++j) {
       const float u0 = (transposed ? tile[cb + 2 * j][rl] : tile[rl][cb + 2 * j]) * sc;
       const float u1 = (transposed ? tile[cb + 2 * j + 1][rl] : tile[rl][cb + 2 * j + 1]) * sc;
-      const fl32x2 uu = {u0, u1};
-      const h16x2 hh = __builtin_convertvector(uu, h16x2);
-      const fl32x2 dd = {u0 - static_cast<float>(hh[0]), u1 - static_cast<float>(hh[1])};
-      ph[j] = __builtin_bit_cast(uint32_t, hh);
-      pq[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(dd, h16x2));
+      pl_split2<false>(u0, u1, ph[j], pq[j]);
     }
     *reinterpret_cast<uint4*>(d) = make_uint4(ph[0], ph[1], ph[2], ph[3]);
     *reinterpret_cast<uint4*>(d + 16) = make_uint4(ph[4], ph[5], ph[6], ph[7]);
-    *reinterpret_cast<uint4*>(d + 32) = make_uint4(pq[0], pq[1], pq[2], pq[3]);
-    *reinterpret_cast<uint4*>(d + 48) = make_uint4(pq[4], pq[5], pq[6], pq[7]);
+    *reinterpret_cast<uint4*>(d + PL_LO) = make_uint4(pq[0], pq[1], pq[2], pq[3]);
+    *reinterpret_cast<uint4*>(d + PL_LO + 16) = make_uint4(pq[4], pq[5], pq[6], pq[7]);
   };
   if (jb.pw && k0 + rl < jb.K && n0 + cb < ((jb.N + 15) & ~15)) {          // rows = k, columns = n
     emit(false, jb.pw + ((n0 + cb) >> 4) * jb.bsw + static_cast<int64_t>(k0 + rl) * PL_ROWB);
@@ -1133,9 +1026,7 @@ __global__ __launch_bounds__(256) void merge_rows_k(const char* __restrict__ in,
   const int64_t r = idx / K;
   if (r >= rows) return;
   const int k = static_cast<int>(idx - r * K);
-  const _Float16* d = reinterpret_cast<const _Float16*>(in + (k >> 4) * ldi_b + r * PL_ROWB);
-  const float v = static_cast<float>(d[k & 15]) + static_cast<float>(d[16 + (k & 15)]);
-  X[r * ldx + k] = v * pl_pow2(-row_exp[r]);
+  X[r * ldx + k] = pl_decode(in + (k >> 4) * ldi_b + r * PL_ROWB, k & 15, row_exp[r]);
 }
 
 // The proof obligation of mi_div_const (common.h): the bits of x / d for every fp32 x.  One thread per bit pattern.
@@ -1180,10 +1071,6 @@ __global__ __launch_bounds__(256) void top_fold_k(const float* __restrict__ part
     else if (k == N) { if (db) db[0] = v; if (d_sum) d_sum[0] = v; }
     else if (loss) loss[0] = v;
   }
-}
-
-bool planes_ok(const mi_planes_t* p, int64_t rows, int K) {
-  return p && p->data && p->row_exp && mi::aligned16(p->data) && p->blk_stride >= rows * PL_ROWB && (p->blk_stride & 63) == 0 && rows >= 0;
 }
 
 template <int EPI>
@@ -1244,7 +1131,7 @@ int32_t mi_split_rows(const float* X, int64_t ldx, int64_t rows, int32_t K, int3
                       float* amax_out, mi_stream_t stream) {
   MI_REQUIRE(rows >= 0 && K > 0 && X, "split_rows: rows=%lld K=%d", (long long)rows, K);
   if (rows == 0) return MI_OK;
-  MI_REQUIRE(planes_ok(out, rows, K), "split_rows: output planes (16-byte aligned data, blk_stride >= 64 * rows and a multiple of 64, row_exp)");
+  MI_REQUIRE(mi::planes_ok(out, rows), "split_rows: output planes (16-byte aligned data, blk_stride >= 64 * rows and a multiple of 64, row_exp)");
   MI_REQUIRE(transpose ? ldx >= rows : ldx >= K, "split_rows: ldx=%lld", (long long)ldx);
   if (transpose) {
     const int64_t tb = mi::ceil_div(rows, 32);
@@ -1292,8 +1179,8 @@ int32_t mi_split_weights(const float* dense, const mi_weight_job_t* jobs, int32_
   for (int q = 0; q < n_jobs; ++q) {
     const mi_weight_job_t& u = jobs[q];
     MI_REQUIRE(u.K > 0 && u.N > 0 && u.offset >= 0 && (u.w.data || u.wt.data), "split_weights: job %d", q);
-    MI_REQUIRE(!u.w.data || planes_ok(&u.w, u.K, u.N), "split_weights: job %d planes of W", q);
-    MI_REQUIRE(!u.wt.data || planes_ok(&u.wt, u.N, u.K), "split_weights: job %d planes of W transposed", q);
+    MI_REQUIRE(!u.w.data || mi::planes_ok(&u.w, u.K), "split_weights: job %d planes of W", q);
+    MI_REQUIRE(!u.wt.data || mi::planes_ok(&u.wt, u.N), "split_weights: job %d planes of W transposed", q);
     WJob& j = js.j[q];
     j.off = u.offset; j.K = u.K; j.N = u.N;
     j.pw = static_cast<char*>(u.w.data); j.bsw = u.w.blk_stride; j.ew = u.w.row_exp;
@@ -1309,7 +1196,7 @@ int32_t mi_split_weights(const float* dense, const mi_weight_job_t* jobs, int32_
 int32_t mi_merge_rows(const mi_planes_t* in, int64_t rows, int32_t K, float* X, int64_t ldx, mi_stream_t stream) {
   MI_REQUIRE(rows >= 0 && K > 0 && X && ldx >= K, "merge_rows: rows=%lld K=%d", (long long)rows, K);
   if (rows == 0) return MI_OK;
-  MI_REQUIRE(planes_ok(in, rows, K), "merge_rows: input planes");
+  MI_REQUIRE(mi::planes_ok(in, rows), "merge_rows: input planes");
   const int64_t blocks = mi::ceil_div(rows * K, 256);
   MI_REQUIRE(blocks <= INT32_MAX, "merge_rows: grid too large");
   merge_rows_k<<<dim3((unsigned)blocks), dim3(256), 0, mi::as_stream(stream)>>>(static_cast<const char*>(in->data), in->blk_stride,
@@ -1325,10 +1212,10 @@ int32_t mi_dense_fwd_planes(const mi_planes_t* X, const mi_planes_t* Wt, const f
   MI_REQUIRE(!mask_bits_out || mask_ld >= (N + 31) / 32, "dense_fwd_planes: mask_ld=%lld < ceil(N / 32)", (long long)mask_ld);
   if (M == 0) return MI_OK;
   MI_REQUIRE((K & 15) == 0 && (N & 15) == 0, "dense_fwd_planes: N=%d and K=%d must be multiples of 16 (use mi_dense_fwd)", N, K);
-  MI_REQUIRE(planes_ok(X, M, K) && planes_ok(Wt, N, K), "dense_fwd_planes: operand planes");
+  MI_REQUIRE(mi::planes_ok(X, M) && mi::planes_ok(Wt, N), "dense_fwd_planes: operand planes");
   MI_REQUIRE(Y || Yp, "dense_fwd_planes: no output");
   MI_REQUIRE(!Y || (ldy >= N && (ldy & 3) == 0 && mi::aligned16(Y)), "dense_fwd_planes: Y leading dimension / alignment");
-  MI_REQUIRE(!Yp || planes_ok(Yp, M, N), "dense_fwd_planes: output planes");
+  MI_REQUIRE(!Yp || mi::planes_ok(Yp, M), "dense_fwd_planes: output planes");
   MI_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, "dense_fwd_planes: keep_prob=%f", keep_prob);
   PlArgs a{};
   a.A = static_cast<const char*>(Wt->data); a.bsa = Wt->blk_stride; a.a_exp = Wt->row_exp;
@@ -1349,12 +1236,12 @@ int32_t mi_dense_bwd_data_planes(const mi_planes_t* dY, const mi_planes_t* W, co
   MI_REQUIRE(M >= 0 && M <= INT32_MAX && N > 0 && K > 0, "dense_bwd_data_planes: M=%lld N=%d K=%d", (long long)M, N, K);
   if (M == 0) return MI_OK;
   MI_REQUIRE((K & 15) == 0 && (N & 15) == 0, "dense_bwd_data_planes: N=%d and K=%d must be multiples of 16", N, K);
-  MI_REQUIRE(planes_ok(dY, M, N) && planes_ok(W, K, N), "dense_bwd_data_planes: operand planes");
-  MI_REQUIRE(!Xact || planes_ok(Xact, M, K), "dense_bwd_data_planes: activation planes");
+  MI_REQUIRE(mi::planes_ok(dY, M) && mi::planes_ok(W, K), "dense_bwd_data_planes: operand planes");
+  MI_REQUIRE(!Xact || mi::planes_ok(Xact, M), "dense_bwd_data_planes: activation planes");
   MI_REQUIRE(!mask_bits || mask_ld >= (K + 31) / 32, "dense_bwd_data_planes: mask_ld=%lld < ceil(K / 32)", (long long)mask_ld);
   MI_REQUIRE(dX || dXp, "dense_bwd_data_planes: no output");
   MI_REQUIRE(!dX || (lddx >= K && (lddx & 3) == 0 && mi::aligned16(dX)), "dense_bwd_data_planes: dX leading dimension / alignment");
-  MI_REQUIRE(!dXp || planes_ok(dXp, M, K), "dense_bwd_data_planes: output planes");
+  MI_REQUIRE(!dXp || mi::planes_ok(dXp, M), "dense_bwd_data_planes: output planes");
   MI_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, "dense_bwd_data_planes: keep_prob=%f", keep_prob);
   PlArgs a{};
   a.A = static_cast<const char*>(W->data); a.bsa = W->blk_stride; a.a_exp = W->row_exp;
@@ -1383,9 +1270,9 @@ int32_t mi_hidden_logits_head_fused(const mi_planes_t* X, const mi_planes_t* Wt,
                                     mi_stream_t stream) {
   MI_REQUIRE(M > 0 && M <= INT32_MAX && N == 128 && K > 0 && (K & 15) == 0,
              "hidden_logits_head_fused: M=%lld N=%d (128) K=%d (a multiple of 16)", (long long)M, N, K);
-  MI_REQUIRE(planes_ok(X, M, K) && planes_ok(Wt, N, K), "hidden_logits_head_fused: operand planes");
+  MI_REQUIRE(mi::planes_ok(X, M) && mi::planes_ok(Wt, N), "hidden_logits_head_fused: operand planes");
   MI_REQUIRE(w && labels && logits && d_logit && dW && workspace && mi::aligned16(w), "hidden_logits_head_fused: null buffer / alignment");
-  MI_REQUIRE(planes_ok(dXp, M, N), "hidden_logits_head_fused: output planes");
+  MI_REQUIRE(mi::planes_ok(dXp, M), "hidden_logits_head_fused: output planes");
   MI_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, "hidden_logits_head_fused: keep_prob=%f", keep_prob);
   MI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15u) == 0, "hidden_logits_head_fused: workspace alignment");
   if (workspace_bytes < mi_hidden_logits_head_fused_workspace_bytes(M, N)) {
@@ -1420,7 +1307,7 @@ int32_t mi_dense_bwd_data_vec_planes(const float* dY, int64_t lddy, const float*
   MI_REQUIRE(dY && W && lddy >= 1 && mi::aligned16(W), "dense_bwd_data_vec_planes: dY / W");
   MI_REQUIRE(!Xact || (mi::aligned16(Xact) && ldxa >= K && (ldxa & 3) == 0), "dense_bwd_data_vec_planes: Xact leading dimension / alignment");
   MI_REQUIRE(!dX || (mi::aligned16(dX) && lddx >= K && (lddx & 3) == 0), "dense_bwd_data_vec_planes: dX leading dimension / alignment");
-  MI_REQUIRE(planes_ok(dXp, M, K), "dense_bwd_data_vec_planes: output planes");
+  MI_REQUIRE(mi::planes_ok(dXp, M), "dense_bwd_data_vec_planes: output planes");
   MI_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, "dense_bwd_data_vec_planes: keep_prob=%f", keep_prob);
   int lpr = 4;                                   // lanes per row: one per float4, 4 .. 64
   while (lpr < 64 && lpr < (K >> 2)) lpr <<= 1;

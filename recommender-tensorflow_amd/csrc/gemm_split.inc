@@ -38,8 +38,6 @@
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 s_bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 s_f16x2 __attribute__((ext_vector_type(2)));
-typedef float s_f32x2 __attribute__((ext_vector_type(2)));
 
 enum { FMT_BF16X3 = 0, FMT_F16X2 = 1 };
 template <int FMT> struct SplitFmt { static constexpr int NPL = (FMT == FMT_BF16X3) ? 3 : 2; };
@@ -47,19 +45,8 @@ template <int FMT> struct SplitFmt { static constexpr int NPL = (FMT == FMT_BF16
 constexpr int S_ROWB = 80;                 // LDS bytes per row: 32 x 16 bit + 16 B pad (ds_read_b128 conflict-free)
 constexpr int S_PLANE = BM * S_ROWB;       // 10,240 B per plane
 
-// largest entry of an abs-max vector (MI_AMAX_SLOTS floats, see store_tile_c) -> exponent s with
-// amax * 2^s in [2^14, 2^15), clamped so that 2^s and 2^-s are normal numbers
-__device__ __forceinline__ int s_scale_exp(const float* __restrict__ amax) {
-  float m = 0.f;
-#pragma unroll
-  for (int j = 0; j < MI_AMAX_SLOTS; ++j) m = fmaxf(m, amax[j]);
-  const int e = static_cast<int>((__float_as_uint(m) >> 23) & 0xffu);
-  return max(-100, min(100, 141 - e));
-}
-__device__ __forceinline__ float s_pow2(int s) { return __uint_as_float(static_cast<uint32_t>(127 + s) << 23); }
-
 __device__ __forceinline__ uint32_t s_pk(float a, float b) {
-  s_f32x2 v = {a, b};
+  f32x2 v = {a, b};
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, s_bf16x2));   // v_cvt_pk_bf16_f32, RNE
 }
 __device__ __forceinline__ float s_lo(uint32_t p) { return __builtin_bit_cast(float, p << 16); }
@@ -70,11 +57,11 @@ template <int FMT>
 __device__ __forceinline__ void s_split_store(char* __restrict__ d, float x0, float x1, float x2, float x3, float sc) {
   if constexpr (FMT == FMT_F16X2) {
     x0 *= sc; x1 *= sc; x2 *= sc; x3 *= sc;
-    const s_f32x2 v01 = {x0, x1}, v23 = {x2, x3};
-    const s_f16x2 h01 = __builtin_convertvector(v01, s_f16x2), h23 = __builtin_convertvector(v23, s_f16x2);  // v_cvt_pk_f16_f32
-    const s_f32x2 r01 = {x0 - static_cast<float>(h01[0]), x1 - static_cast<float>(h01[1])};
-    const s_f32x2 r23 = {x2 - static_cast<float>(h23[0]), x3 - static_cast<float>(h23[1])};
-    const s_f16x2 l01 = __builtin_convertvector(r01, s_f16x2), l23 = __builtin_convertvector(r23, s_f16x2);
+    const f32x2 v01 = {x0, x1}, v23 = {x2, x3};
+    const h16x2 h01 = __builtin_convertvector(v01, h16x2), h23 = __builtin_convertvector(v23, h16x2);  // v_cvt_pk_f16_f32
+    const f32x2 r01 = {x0 - static_cast<float>(h01[0]), x1 - static_cast<float>(h01[1])};
+    const f32x2 r23 = {x2 - static_cast<float>(h23[0]), x3 - static_cast<float>(h23[1])};
+    const h16x2 l01 = __builtin_convertvector(r01, h16x2), l23 = __builtin_convertvector(r23, h16x2);
     uint2 p1, p2;
     p1.x = __builtin_bit_cast(uint32_t, h01); p1.y = __builtin_bit_cast(uint32_t, h23);
     p2.x = __builtin_bit_cast(uint32_t, l01); p2.y = __builtin_bit_cast(uint32_t, l23);
@@ -271,8 +258,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_split_k(const GemmArgs a) {
   const int i = lane & 31, h = lane >> 5;
 
   int sa = 0, sb = 0;                              // f16x2: power-of-two operand scales
-  if constexpr (FMT == FMT_F16X2) { sa = s_scale_exp(a.amax_a); sb = s_scale_exp(a.amax_b); }
-  const float sca = s_pow2(sa), scb = s_pow2(sb);
+  if constexpr (FMT == FMT_F16X2) { sa = pl_scale_exp(a.amax_a); sb = pl_scale_exp(a.amax_b); }
+  const float sca = pl_pow2(sa), scb = pl_pow2(sb);
 
   f32x16 acc[2][2];
 #pragma unroll
@@ -484,5 +471,5 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_split_k(const GemmArgs a) {
       if (n0 + t < a.N) a.colsum_part[static_cast<int64_t>(split) * a.N + n0 + t] = v;
     }
   }
-  store_tile_c(a, acc, m0, n0, wm, wn, i, h, split, s_pow2(-sa), s_pow2(-sb));
+  store_tile_c(a, acc, m0, n0, wm, wn, i, h, split, pl_pow2(-sa), pl_pow2(-sb));
 }

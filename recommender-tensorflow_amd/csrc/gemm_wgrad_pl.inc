@@ -27,7 +27,6 @@ struct WgPlArgs {
   GemmArgs g;                         // C = slab, ldc, M = K (features), N, K = examples, tiles, k_per_split, colsum_part, amax_a / amax_b
 };
 
-typedef _Float16 w_h2 __attribute__((ext_vector_type(2)));
 constexpr int W_PLANE = S_PLANE + 64;
 
 __device__ __forceinline__ uint32_t w_pow2_f16_bits(int d) {      // 2^d, d <= 0: normal down to 2^-14, subnormal down to 2^-24, zero below
@@ -57,7 +56,7 @@ __device__ __forceinline__ void wgrad_scale_body(const int32_t* __restrict__ x_e
                                                  uint16_t* __restrict__ sy16, uint16_t* __restrict__ sc16,
                                                  int32_t* __restrict__ kflag, int64_t m) {
   if (m >= M) return;
-  const int SX = s_scale_exp(amax_a), SY = s_scale_exp(amax_b);
+  const int SX = pl_scale_exp(amax_a), SY = pl_scale_exp(amax_b);
   const int sy = y_exp[m];
   const int dy = min(0, SY - sy);
   const int d = min(0, SX - x_exp[m]) + dy;
@@ -79,7 +78,7 @@ __device__ __forceinline__ void wgrad_scale_body(const int32_t* __restrict__ x_e
   const int64_t slot = (m & ~int64_t(31)) + 4 * (e & 7) + (e >> 3);
   scw[slot] = bx | (bx << 16);
   scy[slot] = by | (by << 16);
-  yf[slot] = s_pow2(-sy);
+  yf[slot] = pl_pow2(-sy);
 }
 
 __global__ __launch_bounds__(kThreads) void wgrad_scale_k(const WgScaleJobs js) {
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wgrad_pl_k(const WgPlArgs wa
   const int wm = w >> 1, wn = w & 1;
   const int i = lane & 31, h = lane >> 5;
 
-  const int sa = s_scale_exp(a.amax_a), sb = s_scale_exp(a.amax_b);
+  const int sa = pl_scale_exp(a.amax_a), sb = pl_scale_exp(a.amax_b);
 
   f32x16 acc[2][2];
 #pragma unroll
@@ -162,7 +161,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wgrad_pl_k(const WgPlArgs wa
     if (COLSUM && do_colsum) rye = *reinterpret_cast<const uint4*>(wa.yf + kc + 4 * q);
   };
   auto mul2 = [](uint32_t x, uint32_t s) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(w_h2, x) * __builtin_bit_cast(w_h2, s));
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(h16x2, x) * __builtin_bit_cast(h16x2, s));
   };
   // eight features x four examples (one uint4 per example) -> per feature the four examples (8 bytes, one LDS row each)
   auto put = [&](char* d, const uint4 (&r)[4]) {
@@ -193,7 +192,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wgrad_pl_k(const WgPlArgs wa
         const uint32_t wv[4] = {rb[j].x, rb[j].y, rb[j].z, rb[j].w};
 #pragma unroll
         for (int wi = 0; wi < 4; ++wi) {
-          const w_h2 v = __builtin_bit_cast(w_h2, wv[wi]);
+          const h16x2 v = __builtin_bit_cast(h16x2, wv[wi]);
           cs[2 * wi] += static_cast<float>(v[0]) * yf[j];
           cs[2 * wi + 1] += static_cast<float>(v[1]) * yf[j];
         }
@@ -274,5 +273,5 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wgrad_pl_k(const WgPlArgs wa
       if (n0 + t < a.N) a.colsum_part[static_cast<int64_t>(split) * a.N + n0 + t] = v;
     }
   }
-  store_tile_c(a, acc, m0, n0, wm, wn, i, h, split, s_pow2(-sa), s_pow2(-sb));
+  store_tile_c(a, acc, m0, n0, wm, wn, i, h, split, pl_pow2(-sa), pl_pow2(-sb));
 }

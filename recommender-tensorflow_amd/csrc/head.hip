@@ -30,11 +30,6 @@ __device__ __forceinline__ float block_sum(float x, float* red /*[4]*/) {
   return r;
 }
 
-__device__ __forceinline__ float sigmoid_stable(float x) {
-  const float e = expf(-fabsf(x));
-  return x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-}
-
 __global__ __launch_bounds__(kBlock) void head_k(const float* __restrict__ lin,
                                                  const float* __restrict__ lin_bias,
                                                  const float* __restrict__ fm,
@@ -57,10 +52,9 @@ __global__ __launch_bounds__(kBlock) void head_k(const float* __restrict__ lin,
     if (logits) logits[b] = x;
     if (labels) {
       const float y = labels[b] ? 1.f : 0.f;
-      const float l = fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
-      acc += l * scale;
+      acc += mi_sigmoid_ce_loss(x, y) * scale;
       if (d_logit) {
-        const float d = (sigmoid_stable(x) - y) * scale;
+        const float d = mi_sigmoid_ce_grad(x, y, scale);
         d_logit[b] = d;
         dacc += d;
       }
@@ -159,7 +153,7 @@ __global__ __launch_bounds__(kBlock) void eval_accumulate_k(const float* __restr
   for (int64_t b = b0 + threadIdx.x; b < b1; b += kBlock) {
     const float x = logits[b];
     const int y = labels[b] ? 1 : 0;
-    const float p = sigmoid_stable(x);
+    const float p = mi_sigmoid_stable(x);
     int lo = 0, hi = kAucThresholds;        // k = #{j : th[j] < p}
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (th[mid] < p) lo = mid + 1; else hi = mid; }
     atomicAdd(&lh[y][lo], 1u);
@@ -312,13 +306,13 @@ __global__ __launch_bounds__(kBlock) void binary_predictions_k(const float* __re
   const int64_t b = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (b >= B) return;
   const float x = logits[b];
-  const float p = sigmoid_stable(x);
+  const float p = mi_sigmoid_stable(x);
   if (logistic) logistic[b] = p;
   if (probabilities) { probabilities[2 * b] = 1.f - p; probabilities[2 * b + 1] = p; }
   if (class_ids) class_ids[b] = p > 0.5f ? 1 : 0;
   if (unreduced_loss) {
     const float y = labels[b] ? 1.f : 0.f;
-    unreduced_loss[b] = fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
+    unreduced_loss[b] = mi_sigmoid_ce_loss(x, y);
   }
 }
 }  // namespace

@@ -84,8 +84,6 @@ __global__ __launch_bounds__(kBlock) void dense_apply_k(float* __restrict__ w, f
   }
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 // streaming forms for optimizer slots: read once and written once per step, never re-read before the
 // next step — keep them from evicting the rows the gather is about to read
 typedef float f32x4_t __attribute__((ext_vector_type(4)));

@@ -64,15 +64,6 @@ struct LayerTable {
   Layer l[kMaxLayers];
 };
 
-__device__ __forceinline__ float act_f(float x, int act) {
-  switch (act) {
-    case 1: return fmaxf(x, 0.f);
-    case 2: return 1.f / (1.f + expf(-x));
-    case 3: return tanhf(x);
-    default: return x;
-  }
-}
-
 __device__ __forceinline__ uint64_t rank_key(float s, uint32_t c) {
   uint32_t u = __float_as_uint(s);
   if (s != s) u = 0u;
@@ -99,7 +90,7 @@ __device__ __forceinline__ void epilogue(f32x16 (&y)[NB], const float* __restric
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int n = b * 32 + acc_row(r, h);
-      y[b][r] = n < N ? act_f(y[b][r] + bias[n], act) : 0.f;
+      y[b][r] = n < N ? mi_act(act, y[b][r] + bias[n]) : 0.f;
     }
   }
 }
@@ -117,7 +108,7 @@ __device__ __forceinline__ void layer2_mfma(const PairArgs& p, const float* __re
   for (int k0 = 0; k0 < K; k0 += 2) {
     const int k = k0 + h;
     float hv = 0.f;
-    if (k < K) hv = act_f(p.aqT[static_cast<int64_t>(k) * p.Upad + qcol] + ac[k], p.act);
+    if (k < K) hv = mi_act(p.act, p.aqT[static_cast<int64_t>(k) * p.Upad + qcol] + ac[k]);
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
       if (b * 32 >= N) break;
@@ -195,7 +186,7 @@ constexpr int kValuW = 32;
 
 __device__ __forceinline__ void epilogue_valu(float (&y)[kValuW], const float* __restrict__ bias, int N, int act) {
 #pragma unroll
-  for (int j = 0; j < kValuW; ++j) y[j] = j < N ? act_f(y[j] + bias[j], act) : 0.f;
+  for (int j = 0; j < kValuW; ++j) y[j] = j < N ? mi_act(act, y[j] + bias[j]) : 0.f;
 }
 
 __device__ __forceinline__ void layer_valu(const PairArgs& p, const Layer L, const float (&x)[kValuW], float (&y)[kValuW]) {
@@ -229,7 +220,7 @@ __device__ __forceinline__ float dnn_valu(const PairArgs& p, const float* __rest
     const Layer L = p.l[0];
     const float* __restrict__ W = p.dense + L.w_off;
     float s = 0.f;
-    for (int k = 0; k < H1; ++k) s = fmaf(act_f(aq[static_cast<int64_t>(k) * p.Upad] + ac[k], p.act), W[k], s);
+    for (int k = 0; k < H1; ++k) s = fmaf(mi_act(p.act, aq[static_cast<int64_t>(k) * p.Upad] + ac[k]), W[k], s);
     return s + p.dense[L.b_off];
   }
   float x[kValuW], y[kValuW];
@@ -240,7 +231,7 @@ __device__ __forceinline__ float dnn_valu(const PairArgs& p, const float* __rest
 #pragma unroll
     for (int j = 0; j < kValuW; ++j) y[j] = 0.f;
     for (int k = 0; k < H1; ++k) {
-      const float hv = act_f(aq[static_cast<int64_t>(k) * p.Upad] + ac[k], p.act);
+      const float hv = mi_act(p.act, aq[static_cast<int64_t>(k) * p.Upad] + ac[k]);
 #pragma unroll
       for (int j = 0; j < kValuW; ++j)
         if (j < N) y[j] = fmaf(hv, W[k * N + j], y[j]);

@@ -14,6 +14,7 @@
 // written per example.  Results are reproducible (fixed orders); the loss / dW sums associate differently from the
 // unfused sequence (tests hold them to 1e-6 of it), everything per-example is the unfused sequence's bits.
 #include "common.h"
+#include "planes.h"
 #include <algorithm>
 
 namespace {
@@ -21,20 +22,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kLpr = 16;                      // lanes per example
 constexpr int kGroups = kBlock / kLpr;        // examples per pass of a block
-constexpr int ROWB = 64;                      // bytes of a plane row piece: 16 hi | 16 lo
-
-typedef _Float16 t_h16x2 __attribute__((ext_vector_type(2)));
-typedef float t_f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float t_pow2(int s) { return __uint_as_float(static_cast<uint32_t>(127 + s) << 23); }
-__device__ __forceinline__ int t_exp_for(float amax) {      // gemm_pl.hip's pl_exp_for
-  const int e = static_cast<int>((__float_as_uint(amax) >> 23) & 0xffu);
-  return max(-100, min(100, 141 - e));
-}
-__device__ __forceinline__ float t_sigmoid(float x) {
-  const float e = expf(-fabsf(x));
-  return x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-}
 
 struct TailArgs {
   const float* X; int64_t ldx; const float* w; const float* b;
@@ -60,7 +47,7 @@ __global__ __launch_bounds__(kBlock) void logits_head_tail_k(const TailArgs a) {
   constexpr int K = 64 * Q, RPB = kGroups * P;
   // [K / 16][RPB][64 B] planes image of a tile; the 16-k blocks 32 bytes further apart than their rows need, so that the four
   // blocks a lane group writes at once fall on different banks
-  constexpr int BLK = RPB * ROWB + 32;
+  constexpr int BLK = RPB * PL_ROWB + 32;
   __shared__ __attribute__((aligned(16))) char stage[(K >> 4) * BLK];
   __shared__ float red[kGroups][K + 2];
   const int t = threadIdx.x, l = t & (kLpr - 1), grp = t / kLpr;
@@ -116,8 +103,8 @@ __global__ __launch_bounds__(kBlock) void logits_head_tail_k(const TailArgs a) {
       if (a.fm) z += fm_v[p];
       z += dnn;
       const float y = y_v[p];
-      const float loss = (fmaxf(z, 0.f) - z * y + log1pf(expf(-fabsf(z)))) * a.scale;
-      const float g = (t_sigmoid(z) - y) * a.scale;
+      const float loss = mi_sigmoid_ce_loss(z, y) * a.scale;
+      const float g = mi_sigmoid_ce_grad(z, y, a.scale);
       if (on && l == 0) {
         if (a.dnn) a.dnn[r] = dnn;
         a.logits[r] = z;
@@ -144,29 +131,18 @@ __global__ __launch_bounds__(kBlock) void logits_head_tail_k(const TailArgs a) {
       for (int o = kLpr / 2; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, kLpr));
       if (on) {
         bmx = fmaxf(bmx, mx);
-        const int s = t_exp_for(mx);
-        const float sc = t_pow2(s);
+        const int s = pl_exp_for(mx);
+        const float sc = pl_pow2(s);
         if (l == 0) a.row_exp[r] = s;
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-          const float u[4] = {v[q].x * sc, v[q].y * sc, v[q].z * sc, v[q].w * sc};
           uint32_t ph[2], pq[2];
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const t_f32x2 uu = {u[2 * e], u[2 * e + 1]};
-            t_h16x2 hh = __builtin_convertvector(uu, t_h16x2);
-            uint32_t hb = __builtin_bit_cast(uint32_t, hh);
-            if (uu[0] > 0.f && (hb & 0xffffu) == 0u) hb |= 1u;          // positive stays positive in the high plane
-            if (uu[1] > 0.f && (hb >> 16) == 0u) hb |= 0x10000u;
-            hh = __builtin_bit_cast(t_h16x2, hb);
-            const t_f32x2 rr2 = {uu[0] - static_cast<float>(hh[0]), uu[1] - static_cast<float>(hh[1])};
-            ph[e] = hb;
-            pq[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(rr2, t_h16x2));
-          }
+          pl_split2<true>(v[q].x * sc, v[q].y * sc, ph[0], pq[0]);
+          pl_split2<true>(v[q].z * sc, v[q].w * sc, ph[1], pq[1]);
           const int qq = l + kLpr * q;                                   // float4 index inside the row: k = 4 qq
-          char* d = stage + (qq >> 2) * BLK + rl * ROWB + (qq & 3) * 8;
+          char* d = stage + (qq >> 2) * BLK + rl * PL_ROWB + (qq & 3) * 8;
           *reinterpret_cast<uint2*>(d) = make_uint2(ph[0], ph[1]);
-          *reinterpret_cast<uint2*>(d + 32) = make_uint2(pq[0], pq[1]);
+          *reinterpret_cast<uint2*>(d + PL_LO) = make_uint2(pq[0], pq[1]);
         }
       }
     }
@@ -184,7 +160,7 @@ __global__ __launch_bounds__(kBlock) void logits_head_tail_k(const TailArgs a) {
 #pragma unroll
     for (int j = 0; j < NPC; ++j) {
       const int idx = j * kBlock + t, kb = idx / (RPB * 4), pp = idx % (RPB * 4);
-      if (pp < run16) *reinterpret_cast<uint4*>(a.out + kb * a.ldo_b + r0 * ROWB + pp * 16) = pc[j];
+      if (pp < run16) *reinterpret_cast<uint4*>(a.out + kb * a.ldo_b + r0 * PL_ROWB + pp * 16) = pc[j];
     }
     if (tile + 1 < kTiles) cur = nxt;
   }
@@ -247,8 +223,7 @@ int32_t mi_logits_head_fused(const float* X, int64_t ldx, const float* w, const 
   MI_REQUIRE(X && w && labels && logits && d_logit && dW && dXp && workspace, "logits_head_fused: null buffer");
   MI_REQUIRE(ldx >= K && (ldx & 3) == 0 && mi::aligned16(X) && mi::aligned16(w), "logits_head_fused: X / w leading dimension or alignment");
   MI_REQUIRE(!dX || (mi::aligned16(dX) && lddx >= K && (lddx & 3) == 0), "logits_head_fused: dX leading dimension / alignment");
-  MI_REQUIRE(dXp->data && dXp->row_exp && mi::aligned16(dXp->data) && dXp->blk_stride >= M * ROWB && (dXp->blk_stride & 63) == 0,
-             "logits_head_fused: output planes");
+  MI_REQUIRE(mi::planes_ok(dXp, M), "logits_head_fused: output planes");
   MI_REQUIRE(!mask_bits || mask_ld >= (K + 31) / 32, "logits_head_fused: mask_ld=%lld", (long long)mask_ld);
   MI_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, "logits_head_fused: keep_prob=%f", keep_prob);
   MI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15u) == 0, "logits_head_fused: workspace alignment");

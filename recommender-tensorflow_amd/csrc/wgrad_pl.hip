@@ -26,6 +26,7 @@
 // slab_reduce_k folds in a fixed order (bitwise reproducible).  The bias gradient (column sums of dY) rides in
 // the workgroups of the first feature tile: v_dot2_f32_f16 of the dY fragments with 2^(SY - sy[m]).
 #include "common.h"
+#include "planes.h"
 #include "wgrad_pl.h"
 #include <cstdlib>
 #include <type_traits>
@@ -34,7 +35,6 @@ namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 typedef short v4i16 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -49,16 +49,6 @@ struct WgArgs {
   float* slab;                        // [splits][K][N]
   float* cpart;                       // [splits][N] bias-gradient partials, or NULL
 };
-
-__device__ __forceinline__ float wg_pow2(int s) { return __uint_as_float(static_cast<uint32_t>(127 + s) << 23); }
-__device__ __forceinline__ int wg_scale_exp(const float* __restrict__ amax) {
-  float m = 0.f;
-#pragma unroll
-  for (int j = 0; j < MI_AMAX_SLOTS; ++j) m = fmaxf(m, amax[j]);
-  const int e = static_cast<int>((__float_as_uint(m) >> 23) & 0xffu);
-  return max(-100, min(100, 141 - e));
-}
-template <int N> __device__ __forceinline__ void wg_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // Two 4-example transposed reads (examples +0..3 and +4..7 of the lane half's eight) = one MFMA fragment.
 // Inline asm on purpose: for the ds_read_tr intrinsic hipcc cannot tell which LDS-DMA stores the read depends on
@@ -245,7 +235,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void wgrad_pl_k(const WgArgs a, cons
   // the software pipeline of gemm_pl_k (see there): waves 4-7 run one barrier behind waves 0-3
 #pragma unroll
   for (int s = 0; s < NBUF; ++s) issue_share(min(s, nk - 1), s);
-  wg_wait_vmcnt<LPS*(NBUF - 1)>();
+  mi_wait_vmcnt<LPS*(NBUF - 1)>();
   __builtin_amdgcn_s_barrier();
   if (g1w) __builtin_amdgcn_s_barrier();
   auto step = [&](int t, const Factors& cur, Factors& nxt) {
@@ -254,7 +244,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void wgrad_pl_k(const WgArgs a, cons
     __builtin_amdgcn_sched_barrier(0);                     // nothing that reads a fragment moves above the wait
     scale_and_sum(t, cur);
     fetch_factors(min(t + 1, nk - 1), nxt);
-    wg_wait_vmcnt<LPS*(DMA_IN_C ? NBUF - 3 : NBUF - 2)>();
+    mi_wait_vmcnt<LPS*(DMA_IN_C ? NBUF - 3 : NBUF - 2)>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -272,11 +262,11 @@ __global__ __launch_bounds__(WG_THREADS, 2) void wgrad_pl_k(const WgArgs a, cons
     if (t + 1 < nk) step(t + 1, f1, f0);
   }
   if (!g1w) __builtin_amdgcn_s_barrier();
-  wg_wait_vmcnt<0>();                 // the tail's re-issued loads
+  mi_wait_vmcnt<0>();                 // the tail's re-issued loads
 
   // ---------------------------------------------------------------- epilogue: the slab of this split
-  const int sx_e = wg_scale_exp(a.amax_a), sy_e = wg_scale_exp(a.amax_b);
-  const float fa = wg_pow2(-sx_e), fb = wg_pow2(-sy_e);
+  const int sx_e = pl_scale_exp(a.amax_a), sy_e = pl_scale_exp(a.amax_b);
+  const float fa = pl_pow2(-sx_e), fb = pl_pow2(-sy_e);
   float* Cb = a.slab + static_cast<int64_t>(split) * a.K * a.N;
 #pragma unroll
   for (int y = 0; y < TM; ++y) {

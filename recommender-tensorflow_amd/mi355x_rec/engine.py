@@ -100,15 +100,22 @@ class HipKernels:
 
 
 class PlaneBuf:
-    """Device memory of one mi_planes_t matrix (k-block major: [K/16 blocks][rows][64 B]) + one int32
-    exponent per row."""
+    """Device memory of one mi_planes_t matrix + one int32 exponent per row.  The library owns the layout
+    (csrc/planes.h): mi_planes_bytes(rows, K) bytes, k-block major, one block of 16 k = mi_planes_bytes(rows, 16)."""
 
-    def __init__(self, rows, K, device):
+    def __init__(self, k, rows, K, device):
+        self.k = k
         self.rows, self.K = int(rows), int(K)
-        self.blk_stride = 64 * max(self.rows, 1)
-        self.data = torch.empty(_align(self.K, 16) // 16 * self.blk_stride, dtype=torch.uint8, device=device)
-        self.exp = torch.empty(max(self.rows, 1), dtype=torch.int32, device=device)
+        n = max(self.rows, 1)
+        self.blk_stride = int(k.query("mi_planes_bytes", n, 16))
+        self.data = torch.empty(int(k.query("mi_planes_bytes", n, self.K)), dtype=torch.uint8, device=device)
+        self.exp = torch.empty(n, dtype=torch.int32, device=device)
         self.struct = _lib.Planes(self.data.data_ptr(), self.exp.data_ptr(), self.blk_stride)
+
+    def rows_from(self, b0):
+        """The mi_planes_t of rows b0.. (a block's rows are contiguous: the same blocks, b0 rows further in)."""
+        return _lib.Planes(self.data[int(self.k.query("mi_planes_bytes", b0, 16)):].data_ptr(), self.exp[b0:].data_ptr(),
+                           self.blk_stride)
 
 
 class OptimizerSpec:
@@ -678,7 +685,7 @@ class DeepFM:
     def _planes(self, name, rows, K):
         cur = self._pl.get(name)
         if cur is None or cur.rows < rows or cur.K != K:
-            cur = self._pl[name] = PlaneBuf(rows, K, self.device)
+            cur = self._pl[name] = PlaneBuf(self.k, rows, K, self.device)
             self._alloc_gen += 1
         return cur.struct
 
@@ -841,15 +848,14 @@ class DeepFM:
                                                             None, lin, None, ls, 0)
             c["lin_join"] = side
         elif pl_gather:
-            x0p = self._planes("x0p", B, ld)
+            self._planes("x0p", B, ld)
+            x0p = self._pl["x0p"]
             for b0, b1, ready in (pieces or [(0, B, None)]):
                 if ready is not None:
                     ready()
                 sl = slice(b0, b1)
-                # (rows b0.. of a k-block-major planes matrix: every block's rows are contiguous, 64 B each)
-                xp_ = x0p if (b0 == 0 and b1 == B) else _lib.Planes(x0p.data + 64 * b0, x0p.row_exp + 4 * b0, x0p.blk_stride)
                 k.mi_embed_fm_planes_fwd(table, field_off, rid[sl], b1 - b0, F, self.E, None if sumv is None else sumv[sl],
-                                         None if fm is None else fm[sl], xp_, rows_amax,
+                                         None if fm is None else fm[sl], x0p.rows_from(b0), rows_amax,
                                          None if tail[0] is None else tail[0][sl], tail[1], tail[2], tst)
                 if lin is not None:
                     k.tagged("mi_embed_fm_linear_fwd", "/wide")(None, lin_w, w_off, w_ids[sl], b1 - b0, Fw, self.E, None, 0, None, None,

@@ -64,8 +64,10 @@ def split(lib, X, transpose=False, pad=0):
     return pb
 
 
-def host_planes(X):
-    """numpy restatement of the format: per-row exponent, fp16 hi / lo (RNE), blocks of 16 k"""
+def host_planes(X, keep_positive):
+    """numpy restatement of the format: per-row exponent, fp16 hi / lo (RNE), blocks of 16 k.  keep_positive: the rule of
+    the writers whose planes a data gradient reads as a relu / dropout mask ("hi > 0"): a positive value that rounds to
+    zero in the high plane gets the smallest positive fp16 there instead"""
     rows, K = X.shape
     K16 = (K + 15) // 16 * 16
     mx = np.abs(X).max(1) if K else np.zeros(rows)
@@ -74,6 +76,8 @@ def host_planes(X):
     u = np.zeros((rows, K16), np.float32)
     u[:, :K] = X.astype(np.float32) * np.exp2(s.astype(np.float32))[:, None]
     hi = u.astype(np.float16)
+    if keep_positive:
+        hi[(u > 0) & (hi == 0)] = np.float16(2.0 ** -24)
     lo = (u - hi.astype(np.float32)).astype(np.float16)
     out = np.zeros((rows, K16 // 16, 2, 16), np.float16)
     out[:, :, 0, :] = hi.reshape(rows, -1, 16)
@@ -104,8 +108,11 @@ def test_split_rows_format_and_round_trip(lib, rows, K):
     rng = np.random.default_rng(rows + K)
     X = rows_spread(rng, rows, K)
     X[0, :] *= 0 if rows > 3 else 1                       # an all-zero row
+    if rows > 1:                                          # a row that reaches the keep-positive rule: +-1e-13 next to 1.0
+        X[-1, :] = np.where(np.arange(K) % 2 == 0, np.float32(1e-13), np.float32(-1e-13))
+        X[-1, 0] = 1.0
     pb = split(lib, X, pad=1)
-    ref_bits, ref_exp = host_planes(X)
+    ref_bits, ref_exp = host_planes(X, keep_positive=True)
     assert np.array_equal(pb.exp.cpu().numpy()[:rows], ref_exp)
     got_bits = pb.bits()
     assert float(pb.data[:, rows:, :].abs().max()) == 0 if pb.rows_alloc > rows else True     # nothing written past the rows
@@ -147,7 +154,7 @@ def test_dense_fwd_planes_exact_on_integers(lib, M, N, K):
     assert np.array_equal(got[:, :N], ref.astype(np.float32))
     assert np.all(got[:, N:] == -7.0)                        # nothing written outside [M, N]
     if yp is not None:
-        hb, he = host_planes(ref.astype(np.float32))
+        hb, he = host_planes(ref.astype(np.float32), keep_positive=True)
         assert np.array_equal(yp.exp.cpu().numpy(), he)
         assert np.array_equal(yp.bits(), hb)
 
@@ -171,7 +178,7 @@ def test_dense_fwd_planes_row_relative_error(lib, M, N, K):
     assert float(amax.max()) == float(np.abs(got).max())
     if yp is not None:
         assert row_rel_err(yp.merged(lib), ref) < 1e-5
-        hb, he = host_planes(got)                           # the planes written == split of the fp32 result
+        hb, he = host_planes(got, keep_positive=True)       # the planes written == split of the fp32 result
         assert np.array_equal(yp.exp.cpu().numpy(), he)
         assert np.array_equal(yp.bits(), hb)
 
@@ -223,7 +230,7 @@ def test_dense_bwd_data_planes(lib, M, N, K):
     assert row_rel_err(got, ref) < 1e-5
     assert np.array_equal(got == 0, ref == 0) or np.mean((got == 0) != (ref == 0)) < 1e-4
     if dxp is not None:
-        hb, he = host_planes(got)
+        hb, he = host_planes(got, keep_positive=False)
         assert np.array_equal(dxp.exp.cpu().numpy(), he)
         assert np.array_equal(dxp.bits(), hb)
     # the one-bit mask instead of the activation's planes: the same decisions, the same bits (fp32 and planes)
@@ -267,7 +274,7 @@ def test_training_variant_of_the_forward_equals_the_general_kernel_bitwise(lib, 
         out.append((yp.bits(), yp.exp.cpu().numpy(), mb.cpu().numpy(), float(am.max().item()), Y))
     (b0, e0, m0, a0, Y), (b1, e1, m1, a1, _) = out
     assert np.array_equal(b0, b1) and np.array_equal(e0, e1) and np.array_equal(m0, m1) and a0 == a1
-    hb, he = host_planes(Y.cpu().numpy())
+    hb, he = host_planes(Y.cpu().numpy(), keep_positive=True)
     assert np.array_equal(b1, hb) and np.array_equal(e1, he) and a1 == float(Y.abs().max().item())
 
 
@@ -294,7 +301,7 @@ def test_training_variant_of_the_data_gradient_equals_the_general_kernel_bitwise
     r = slice(0, 2048)                                          # (fp64 on the first rows)
     ref = (dY[r].astype(np.float64) @ W.astype(np.float64).T) * bits[r] / np.float64(np.float32(0.9))
     assert row_rel_err(got[r], ref) < 1e-5 and np.all(got[~bits] == 0)
-    hb, he = host_planes(got)
+    hb, he = host_planes(got, keep_positive=False)
     assert np.array_equal(b1, hb) and np.array_equal(e1, he)
 
 
@@ -346,7 +353,7 @@ def test_embed_fm_planes_fwd(lib, E, F, B, nd, tail):
     full = concat.cpu().numpy()
     if tail:
         full = np.concatenate([full, x, np.zeros((B, tail - nd), np.float32)], 1)
-    hb, he = host_planes(full)
+    hb, he = host_planes(full, keep_positive=False)
     assert np.array_equal(cp.exp.cpu().numpy(), he)
     assert np.array_equal(cp.bits(), hb)
     assert torch.equal(sumv, sumv2) and torch.equal(fm, fm2)
