@@ -607,7 +607,8 @@ int32_t mi_dense_bwd_weight_planes(const mi_planes_t* X, const mi_planes_t* dY, 
  * config 3 five launches instead of nine (the backward then runs all data gradients first: each needs only the layer
  * above's dY, and the factors of every layer need its finished dY planes and abs-max).  Results are those of
  * mi_dense_bwd_weight_planes per job, bit for bit.  workspace: mi_dense_bwd_weight_planes_batch_workspace_bytes, 32-byte
- * aligned; at most MI_MAX_WEIGHT_JOBS jobs. */
+ * aligned (fewer bytes than the query names are refused, as is any bad job: every job is planned before the first launch,
+ * so a refused call has written nothing); at most MI_MAX_WEIGHT_JOBS jobs. */
 typedef struct mi_wgrad_job {
   mi_planes_t X, dY;        /* the layer's input and the gradient of its output, [M] rows each */
   float* dW; float* db;     /* [K][N], [N] (db may be NULL) */

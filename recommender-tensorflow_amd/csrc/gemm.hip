@@ -1006,9 +1006,9 @@ static int32_t wgrad_job_gemm(const WgradJobPlan& p, hipStream_t st) {
   return MI_OK;
 }
 
-int32_t mi_dense_bwd_weight_planes_batch(const mi_wgrad_job_t* jobs, int32_t n_jobs, int64_t M, void* workspace, size_t workspace_bytes,
-                                         mi_stream_t stream) {
-  MI_REQUIRE(jobs && n_jobs > 0 && n_jobs <= MI_MAX_WEIGHT_JOBS, "dense_bwd_weight_planes_batch: n_jobs=%d (1..%d)", n_jobs, MI_MAX_WEIGHT_JOBS);
+// (the two public entries below check the size each of them asks for, then run this)
+static int32_t wgrad_batch_run(const mi_wgrad_job_t* jobs, int32_t n_jobs, int64_t M, void* workspace, size_t workspace_bytes,
+                               mi_stream_t stream) {
   hipStream_t st = mi::as_stream(stream);
   WgradJobPlan plans[MI_MAX_WEIGHT_JOBS];
   WgScaleJobs sj{};
@@ -1053,13 +1053,26 @@ size_t mi_dense_bwd_weight_planes_batch_workspace_bytes(const mi_wgrad_job_t* jo
   return tot + 256;
 }
 
+int32_t mi_dense_bwd_weight_planes_batch(const mi_wgrad_job_t* jobs, int32_t n_jobs, int64_t M, void* workspace, size_t workspace_bytes,
+                                         mi_stream_t stream) {
+  MI_REQUIRE(jobs && n_jobs > 0 && n_jobs <= MI_MAX_WEIGHT_JOBS, "dense_bwd_weight_planes_batch: n_jobs=%d (1..%d)", n_jobs, MI_MAX_WEIGHT_JOBS);
+  // the size the query names, not the smaller one the carving below happens to get by with: a caller that passes less
+  // than it was told to is refused whatever the last job's padding would have forgiven
+  const size_t need = mi_dense_bwd_weight_planes_batch_workspace_bytes(jobs, n_jobs, M);
+  if (workspace_bytes < need) {
+    mi::set_error("dense_bwd_weight_planes_batch: workspace %zu < %zu", workspace_bytes, need);
+    return MI_ERR_WORKSPACE;
+  }
+  return wgrad_batch_run(jobs, n_jobs, M, workspace, workspace_bytes, stream);
+}
+
 int32_t mi_dense_bwd_weight_planes(const mi_planes_t* X, const mi_planes_t* dY, float* dW, float* db, int64_t M,
                                    int32_t N, int32_t K, void* workspace, size_t workspace_bytes,
                                    const mi_gemm_amax_t* amax, mi_stream_t stream) {
   MI_REQUIRE(X && dY && amax, "dense_bwd_weight_planes: null argument");
   mi_wgrad_job_t job{};
   job.X = *X; job.dY = *dY; job.dW = dW; job.db = db; job.N = N; job.K = K; job.amax = *amax;
-  return mi_dense_bwd_weight_planes_batch(&job, 1, M, workspace, workspace_bytes, stream);
+  return wgrad_batch_run(&job, 1, M, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -13,7 +13,8 @@ import torch
 
 from oracle import deepfm as O
 from oracle import optimizers as OO
-from tests.util import dev, dropout_mask, max_err_scaled
+from tests.util import (dev, dropout_mask, exact_workspace, guarded_nan, guards_intact, max_err_scaled,
+                        workspace_surroundings_intact)
 
 pytestmark = pytest.mark.gpu
 
@@ -1125,3 +1126,104 @@ def test_layer_histogram_matches_tensorflow_bucketing(lib):
     assert abs(sums[1].item() - (x.astype(np.float64) ** 2).sum()) < 1e-6 * (x.astype(np.float64) ** 2).sum()
     pr = histogram_proto(lim, counts.cpu().numpy(), sums.cpu().numpy(), x.min(), x.max())
     assert pr["num"] == len(x) and sum(pr["bucket"]) == len(x) and len(pr["bucket"]) == len(pr["bucket_limit"]) < 400
+
+
+# ---- the numeric columns' backward kernels, as kernels ----------------------------------------------------------------------
+# (B = 255 / 256 / 257: around one block of 256 examples; 65536 with 13 columns is BASELINE config 4's call.)  Inputs are made
+# on the device and the fp64 reference is torch's, so that the largest case costs no host time.  Bar: 1e-5 of the rms of the
+# exact result; the same measure for a plain fp32 sum (torch, fp32) is printed beside it (pytest -s).
+# x and d_logit_lin are head-like rather than zero-mean — values around 0.5, (sigmoid(z) - y) / B with a quarter of the labels 1 —
+# because dw_num of ONE column is one number whose "rms" is its own magnitude: a zero-mean sum over the examples lands
+# arbitrarily near 0 and the ratio then measures the draw, not the kernel.
+NUMERIC_B = [1, 255, 256, 257, 65536]
+
+
+def _numeric_inputs(g, B, nd):
+    x = torch.randn(B, nd, device="cuda", generator=g) + 0.5
+    z = torch.randn(B, device="cuda", generator=g)
+    y = (torch.rand(B, device="cuda", generator=g) < 0.25).float()
+    return x, (torch.sigmoid(z) - y) / B
+
+
+def _rms_rel(got, ref):
+    got, ref = got.double(), ref.double()
+    rms = float(ref.pow(2).mean().sqrt())
+    err = float((got - ref).abs().max())
+    if rms == 0:
+        assert err == 0
+        return 0.0
+    return err / rms
+
+
+@pytest.mark.parametrize("nd", [1, 13])
+@pytest.mark.parametrize("B", NUMERIC_B)
+def test_numeric_raw_bwd_against_fp64(lib, B, nd):
+    """dw_num[j] = sum_b d_logit_lin[b] x[b, j]: exact workspace between guard bytes, twice the same bits (fixed order)"""
+    g = torch.Generator(device="cuda"); g.manual_seed(B * 31 + nd)
+    x, dll = _numeric_inputs(g, B, nd)
+    wbuf, ws = exact_workspace(lib.mi_numeric_raw_bwd_workspace_bytes(B, nd))
+    outs = []
+    for _ in range(2):
+        og, dw = guarded_nan(nd)
+        _chk(lib.mi_numeric_raw_bwd(x.data_ptr(), dll.data_ptr(), B, nd, dw.data_ptr(), ws.data_ptr(), ws.numel(), _st()))
+        torch.cuda.synchronize()
+        assert guards_intact(og) and workspace_surroundings_intact(wbuf, ws)
+        outs.append(dw.clone())
+    ref = (dll.double()[:, None] * x.double()).sum(0)
+    err, e32 = _rms_rel(outs[0], ref), _rms_rel((dll[:, None] * x).sum(0), ref)
+    print("NUMERIC raw   B=%-6d n_d=%-2d        dw_num %.2e (plain fp32 %.2e)" % (B, nd, err, e32))
+    assert bool(torch.isfinite(outs[0]).all()) and err < TOL
+    assert torch.equal(outs[0], outs[1])
+    assert lib.mi_numeric_raw_bwd(x.data_ptr(), dll.data_ptr(), B, nd, dw.data_ptr(), ws.data_ptr(), ws.numel() - 1, _st()) != 0
+
+
+@pytest.mark.parametrize("parts", ["all", "no-d_concat", "no-d_logit_fm", "no-d_logit_lin", "no-dw_num"])
+@pytest.mark.parametrize("E", [4, 12, 64, 128])
+@pytest.mark.parametrize("nd", [1, 13])
+@pytest.mark.parametrize("B", NUMERIC_B)
+def test_numeric_embed_bwd_against_fp64(lib, B, nd, E, parts):
+    """dV[j, e] = sum_b x[b, j] (d_concat[b, col0 + j E + e] + d_logit_fm[b] (sumv[b, e] - concat[b, col0 + j E + e])) and
+    dw_num[j] = sum_b d_logit_lin[b] x[b, j], with each optional input absent in turn; the numeric block sits behind one
+    categorical field's columns (col0 = E) in padded leading dimensions."""
+    g = torch.Generator(device="cuda"); g.manual_seed(B * 131 + nd * 17 + E)
+    col0, ld, lddc = E, (1 + nd) * E + 8, (1 + nd) * E + 4
+    r = lambda *shape: torch.randn(*shape, device="cuda", generator=g)
+    x, dlogit = _numeric_inputs(g, B, nd)
+    concat, sumv = r(B, ld), r(B, E)
+    d_concat = r(B, lddc) / B if parts != "no-d_concat" else None
+    dlf = dlogit if parts != "no-d_logit_fm" else None
+    dll = dlogit.clone() if parts != "no-d_logit_lin" else None
+    want_dw = parts != "no-dw_num"
+    wbuf, ws = exact_workspace(lib.mi_numeric_embed_bwd_workspace_bytes(B, nd, E))
+    outs = []
+    for _ in range(2):
+        vg, dV = guarded_nan(nd, E); wg, dw = guarded_nan(nd)
+        _chk(lib.mi_numeric_embed_bwd(x.data_ptr(), _p(d_concat), lddc, concat.data_ptr(), ld, col0, sumv.data_ptr(), _p(dlf),
+                                      _p(dll), B, nd, E, dV.data_ptr(), dw.data_ptr() if want_dw else None, ws.data_ptr(),
+                                      ws.numel(), _st()))
+        torch.cuda.synchronize()
+        assert guards_intact(vg) and guards_intact(wg) and workspace_surroundings_intact(wbuf, ws)
+        assert want_dw or bool(torch.isnan(dw).all())
+        outs.append((dV.clone(), dw.clone()))
+
+    def exact(dt):
+        blk = lambda t, w: t[:, col0:col0 + nd * E].to(dt).reshape(B, nd, E)
+        gv = torch.zeros(B, nd, E, dtype=dt, device="cuda")
+        if d_concat is not None:
+            gv = gv + blk(d_concat, lddc)
+        if dlf is not None:
+            gv = gv + dlf.to(dt)[:, None, None] * (sumv.to(dt)[:, None, :] - blk(concat, ld))
+        dV = (x.to(dt)[:, :, None] * gv).sum(0)
+        dw = (dll.to(dt)[:, None] * x.to(dt)).sum(0) if dll is not None else torch.zeros(nd, dtype=dt, device="cuda")
+        return dV, dw
+    (rV, rw), (fV, fw) = exact(torch.float64), exact(torch.float32)
+    eV, eV32 = _rms_rel(outs[0][0], rV), _rms_rel(fV, rV)
+    line = "NUMERIC embed B=%-6d n_d=%-2d E=%-3d %-14s dV %.2e (plain fp32 %.2e)" % (B, nd, E, parts, eV, eV32)
+    assert bool(torch.isfinite(outs[0][0]).all()) and eV < TOL, line
+    if want_dw:
+        ew, ew32 = _rms_rel(outs[0][1], rw), _rms_rel(fw, rw)
+        line += "  dw_num %.2e (plain fp32 %.2e)" % (ew, ew32)
+        assert bool(torch.isfinite(outs[0][1]).all()) and ew < TOL, line
+        assert torch.equal(outs[0][1], outs[1][1])
+    print(line)
+    assert torch.equal(outs[0][0], outs[1][0])

@@ -70,3 +70,34 @@ def max_err_scaled(a, b):
         return 0.0
     floor = np.sqrt(np.mean(b * b)) + 1e-30
     return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), floor)))
+
+
+# ---- outputs and workspaces that show a write outside what a kernel entry was given (GPU tests) ------------------------------
+GUARD = 64             # floats of NaN before and after every output (256 bytes: the output keeps its 16-byte alignment)
+WS_FILL = 0xA5
+
+
+def guarded_nan(*shape):
+    """(whole buffer, view of `shape` inside it): an output pre-filled with NaN between two NaN guard bands"""
+    n = int(np.prod(shape))
+    buf = torch.full((n + 2 * GUARD,), float("nan"), device="cuda")
+    return buf, buf[GUARD:GUARD + n].view(*shape)
+
+
+def guards_intact(buf):
+    return bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[-GUARD:]).all())
+
+
+def exact_workspace(nbytes, offset=32):
+    """(whole buffer, view of EXACTLY nbytes inside it at a 32-byte-aligned — not 64- or 256-aligned — offset); the
+    buffer is filled with a byte pattern that must survive before and after the view"""
+    buf = torch.full((int(nbytes) + 512,), WS_FILL, dtype=torch.uint8, device="cuda")
+    assert buf.data_ptr() % 256 == 0
+    ws = buf[offset:offset + int(nbytes)]
+    assert ws.data_ptr() % 256 == offset
+    return buf, ws
+
+
+def workspace_surroundings_intact(buf, ws):
+    lo = ws.data_ptr() - buf.data_ptr()
+    return bool((buf[:lo] == WS_FILL).all()) and bool((buf[lo + ws.numel():] == WS_FILL).all())
