@@ -707,6 +707,39 @@ int32_t mi_pair_topk(const float* a_q, const float* s_q, const float* w_q, int64
                      float* top_score, int32_t* top_idx, float* scores, void* workspace, size_t workspace_bytes,
                      mi_stream_t stream);
 
+/* ---- serving: the forward of a request batch as one launch (csrc/serve.hip) ---------------------------------------
+ * For B requests, what DeepFM.predict_logits followed by mi_binary_predictions computes (deep_fm.py:36-125 in PREDICT
+ * mode, model_utils.py:9-20; the requests of ml_100k.py:64-88's receiver after the columns' id transforms):
+ *   logits[b] = ((lin[b] + lin_bias) + fm[b]) + dnn[b]     (absent parts skipped; the order of mi_sigmoid_ce_head)
+ *   logistic [B], probabilities [B, 2], class_ids [B] int64: mi_binary_predictions' device functions on that logit,
+ *   bit for bit.  Any output may be NULL (not all four).
+ * Inputs are the engine's arrays, read in place:
+ *   table (rows table_stride floats apart, 0 = E), lin_w (weights lin_stride floats apart), field_off [F] (device),
+ *   ids [B, F] int32 (trusted to lie inside their field), x_num [B, n_numeric] (NULL without numeric columns);
+ *   dense, layer_off [2 n_layers] (host), widths [n_layers + 1] (host): layer i of the MLP, the logits layer included,
+ *     has kernel dense[layer_off[2i]] [widths[i], widths[i+1]] and bias dense[layer_off[2i+1]] [widths[i+1]];
+ *     widths[0] = rows of kernel_0 as stored (>= the input columns), widths[n_layers] = 1; n_layers = 0 without a DNN.
+ *     activation: the engine's code (0 identity, 1 relu, 2 sigmoid, 3 tanh) on every layer but the last;
+ *   use_linear / use_fm / use_dnn: the model's parts.  numeric_raw = 0: numeric column j enters as the row
+ *     x[b, j] * dense[num_emb_off + j E ..] (mi_numeric_embed_fwd: seen by the FM term and the MLP; linear weight
+ *     dense[lin_num_off + j]); 1: as the value itself after the embedding columns (mi_numeric_raw_fwd; no FM term);
+ *   lin_bias_off: the wide part's bias in dense;  wide_fields: bit f set = categorical field f has a linear weight.
+ *   Narrower embedding columns need nothing: their unused table columns and rows of kernel_0 are zero.
+ * Arithmetic: fp32 variables, exact fp32 products (fp32-input MFMA), fp32 accumulation; the FM term rounds each product
+ * on its own (a model with one field gives exactly 0).  Within 1e-5 of an fp64 forward, scaled as max_err_scaled.
+ * A request's outputs do not depend on the other requests of the call; two calls give the same bits.
+ * Limits, checked before anything is launched (MI_ERR_INVALID / MI_ERR_UNSUPPORTED): B >= 1, F <= 64, E a multiple of 4
+ * in [4, 256], at most 8 hidden layers, every layer width <= 512.  Enqueues one kernel on the stream; no scratch:
+ * mi_predict_fused_workspace_bytes is 0 today and workspace may be NULL (kept in the ABI for later shapes). */
+size_t mi_predict_fused_workspace_bytes(int64_t B, int32_t n_layers);
+int32_t mi_predict_fused(const float* table, int64_t table_stride, const float* lin_w, int32_t lin_stride,
+                         const int64_t* field_off, const int32_t* ids, const float* x_num, int64_t B, int32_t F, int32_t E,
+                         int32_t n_numeric, const float* dense, const int64_t* layer_off, const int32_t* widths,
+                         int32_t n_layers, int32_t activation, int32_t use_linear, int32_t use_fm, int32_t use_dnn,
+                         int32_t numeric_raw, int64_t lin_bias_off, int64_t num_emb_off, int64_t lin_num_off,
+                         uint64_t wide_fields, float* logits, float* logistic, float* probabilities, int64_t* class_ids,
+                         void* workspace, size_t workspace_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,427 @@
+// Serving: the whole forward of a request batch — DeepFM.predict_logits followed by mi_binary_predictions — as ONE
+// launch (mi_predict_fused, include/mi355x_rec.h).  Ids in, predictions out; no intermediate reaches HBM.
+//
+//   predict_fused_k   one workgroup of 4 waves per 32 requests.  The 32 requests are the columns of the fp32-input MFMA
+//                     (the transposed form Y^T = W^T X^T of rank.hip: a layer's weights are the A operand, the requests'
+//                     activations the B operand).
+//     0. rows         the requests' table rows field_off[f] + ids[b, f] into LDS ([F][32] int32): the id -> row -> table
+//                     chain of dependent loads is paid once, for all fields at a time.
+//     1. wide + FM    8 threads per request: the wide part's weights by field, the FM sums by float4 column chunk
+//                     (sum and sum of squares over the fields, each product rounded on its own: one field gives 0).
+//     2. layer 1      B operand straight from the gathered table rows: a lane holds 4 consecutive embedding columns of
+//                     its request's row (one 16-byte load) and spends them in 4 MFMA steps; the two lane halves take
+//                     neighbouring float4 chunks of the concat, so A reads kernel_0's rows in the same k order.  Numeric
+//                     columns (x V, or the raw values) follow as scalar k steps.
+//     3. layers 2..L  input from LDS as [width][32] fp32, output to the other LDS buffer, a barrier between layers.  The
+//                     four waves split a layer's 32-row output tiles (tile t -> wave t % 4, at most 4 tiles per wave:
+//                     widths up to 512).  The logits layer is the same code with one output row.
+//     4. head         logit = ((lin + bias) + fm) + dnn, then the device functions of mi_binary_predictions.
+//
+// Arithmetic: fp32 variables, exact fp32 products (v_mfma_f32_32x32x2_f32), fp32 accumulation.  At request sizes the
+// kernel waits for weights, not for the matrix pipe: no 16-bit operand split.
+#include "common.h"
+
+namespace {
+
+constexpr int kRB = 32;                 // requests per workgroup = the MFMA's N
+constexpr int kWaves = 4;
+constexpr int kThreads = kWaves * 64;
+constexpr int kParts = kThreads / kRB;  // threads per request in the wide + FM phase
+constexpr int kTPW = 4;                 // output tiles per wave
+constexpr int kMaxWidth = kTPW * kWaves * 32;   // 512
+constexpr int kMaxFields = 64;
+constexpr int kMaxLayers = 9;           // 8 hidden layers + the logits layer
+constexpr size_t kMaxLds = 160 * 1024;
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct Layer {
+  int64_t w_off, b_off;                 // offsets into the flat dense buffer: kernel [fan_in, fan_out], bias [fan_out]
+  int32_t fan_in, fan_out;
+};
+
+struct ServeArgs {
+  const float* table;                   // [R][ts] or NULL
+  const float* lin_w;                   // [R] at stride ls, or NULL
+  const int64_t* field_off;             // [F]
+  const int32_t* ids;                   // [B][F]
+  const float* x_num;                   // [B][nd] or NULL
+  const float* dense;
+  float* logits;
+  float* logistic;
+  float* probabilities;
+  int64_t* class_ids;
+  int64_t B, ts;
+  int64_t lin_bias_off, num_emb_off, lin_num_off;
+  uint64_t wide_fields;
+  int32_t F, E, nd, ls, act, n_layers;
+  int32_t use_linear, use_fm, raw;      // raw: numeric columns feed the MLP with the value itself
+  int32_t buf_a;                        // floats of the first activation buffer (the second follows it)
+  Layer l[kMaxLayers];
+};
+
+// row of a 32x32 accumulator tile held in register r by lane half h
+__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// one k step (k = the lane half's own k) of every tile this wave owns
+template <int NT>
+__device__ __forceinline__ void mfma_step(f32x16 (&acc)[NT], const float* __restrict__ W, int k, bool k_ok, int N,
+                                          int wave, int col, float hv) {
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const int n = (i * kWaves + wave) * 32 + col;
+    const float w = (k_ok && n < N) ? W[static_cast<int64_t>(k) * N + n] : 0.f;
+    acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, hv, acc[i], 0, 0, 0);
+  }
+}
+
+// The k loops run in blocks of kKB steps, two blocks alternating: the weights (and inputs) of the next block are
+// requested before the MFMAs of the current one, so a block's global-load latency hides behind the other block's
+// matrix work instead of stalling every step (the loops are bound by the weight stream, not by the matrix pipe).
+constexpr int kKB = 8;
+template <int NT>
+struct Blk {
+  float hv[kKB];                        // B operand of step j (this lane half's k), as loaded
+  uint32_t on;                          // bit j: step j lies inside the layer's k range (else its B operand counts as 0)
+  float w[kKB][NT];                     // A operand of step j, tile i
+};
+
+// Loads past the matrix are clamped into it and nothing looks at a loaded value before compute(): straight-line code, so
+// a block's loads are all in flight before its MFMAs.  A step past K is switched off through its B operand (0 times a
+// finite weight), an output row past N is computed from the clamped column and never stored (epilogue).
+template <int NT>
+__device__ __forceinline__ void load_w(Blk<NT>& b, int j, const float* __restrict__ W, int k, int K, int N, int wave, int col) {
+  const int64_t kr = static_cast<int64_t>(k < K ? k : K - 1) * N;
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const int n = (i * kWaves + wave) * 32 + col;
+    b.w[j][i] = W[kr + (n < N ? n : N - 1)];
+  }
+}
+
+template <int NT>
+__device__ __forceinline__ void compute(f32x16 (&acc)[NT], const Blk<NT>& b, int N, int wave) {
+#pragma unroll
+  for (int j = 0; j < kKB; ++j) {
+    const float hv = (b.on >> j) & 1u ? b.hv[j] : 0.f;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.w[j][i], hv, acc[i], 0, 0, 0);
+  }
+}
+
+// steps k0 .. k0 + 2 kKB of a layer whose input is in LDS
+template <int NT>
+__device__ __forceinline__ void load_hidden(Blk<NT>& b, const float* __restrict__ in, const float* __restrict__ W, int k0, int K,
+                                            int N, int wave, int col, int h) {
+  b.on = 0;
+#pragma unroll
+  for (int j = 0; j < kKB; ++j) {
+    const int k = k0 + 2 * j + h;
+    const bool on = k < K;
+    b.hv[j] = in[(on ? k : K - 1) * kRB + col];
+    b.on |= static_cast<uint32_t>(on) << j;
+    load_w<NT>(b, j, W, k, K, N, wave, col);
+  }
+}
+
+// layer 1: float4 chunks c0 + h and c0 + 2 + h of the concat (4 steps each); (f, ce) = the lane half's field and chunk
+// inside the field, moved on by the call
+template <int NT>
+__device__ __forceinline__ void load_first(Blk<NT>& b, const float* __restrict__ table, int64_t ts, const int32_t* rows,
+                                           const float* __restrict__ W, int c0, int nchunk, int cpf, int& f, int& ce, int F,
+                                           int K, int N, int wave, int col, int h) {
+  b.on = 0;
+#pragma unroll
+  for (int u = 0; u < kKB / 4; ++u) {
+    const int c = c0 + 2 * u + h;
+    const bool on = c < nchunk;
+    const float4 v = ld4(table + static_cast<int64_t>(rows[(f < F ? f : F - 1) * kRB + col]) * ts + 4 * ce);   // (ce < cpf always)
+    b.hv[4 * u] = v.x; b.hv[4 * u + 1] = v.y; b.hv[4 * u + 2] = v.z; b.hv[4 * u + 3] = v.w;
+    b.on |= (on ? 15u : 0u) << (4 * u);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) load_w<NT>(b, 4 * u + m, W, 4 * c + m, K, N, wave, col);
+    ce += 2;
+    while (ce >= cpf) { ce -= cpf; ++f; }
+  }
+}
+
+// out[n][request] = act(acc + bias[n]) for the rows n < N of this wave's tiles
+template <int NT>
+__device__ __forceinline__ void epilogue(const f32x16 (&acc)[NT], const float* __restrict__ bias, int N, int act,
+                                         float* __restrict__ out, int wave, int col, int h) {
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const int t = i * kWaves + wave;
+    if (t * 32 < N) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int n = t * 32 + acc_row(r, h);
+        if (n < N) out[n * kRB + col] = mi_act(act, acc[i][r] + bias[n]);
+      }
+    }
+  }
+}
+
+// one layer on this wave's NT tiles (tile i = output rows (i kWaves + wave) 32 ..): layer 1 from the table rows and the
+// numeric columns, a later layer from the LDS buffer `in`; the result goes to the LDS buffer `out`
+template <int NT>
+__device__ __forceinline__ void run_layer(const ServeArgs& p, const Layer ly, bool first, bool last, const int32_t* rows,
+                                          const float* __restrict__ xq, const float* __restrict__ in, float* __restrict__ out,
+                                          int wave, int col, int h) {
+  const float* __restrict__ W = p.dense + ly.w_off;
+  const int K = ly.fan_in, N = ly.fan_out;
+  const int F = p.F, E = p.E, nd = p.nd;
+  f32x16 acc[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) acc[i] = f32x16{};
+  if (first) {
+    // the concat's float4 chunks, two per step: chunk 2 i + h = columns 4 (ce) .. of field f
+    const int cpf = E / 4, nchunk = p.table ? F * cpf : 0;
+    if (nchunk) {
+      constexpr int kCB = kKB / 2;                            // chunks a block covers (both lane halves)
+      int f = h / cpf, ce = h - f * cpf;
+      Blk<NT> ba, bb;
+      load_first<NT>(ba, p.table, p.ts, rows, W, 0, nchunk, cpf, f, ce, F, K, N, wave, col, h);
+      for (int c0 = 0; c0 < nchunk; c0 += 2 * kCB) {
+        load_first<NT>(bb, p.table, p.ts, rows, W, c0 + kCB, nchunk, cpf, f, ce, F, K, N, wave, col, h);
+        compute<NT>(acc, ba, N, wave);
+        load_first<NT>(ba, p.table, p.ts, rows, W, c0 + 2 * kCB, nchunk, cpf, f, ce, F, K, N, wave, col, h);
+        if (c0 + kCB < nchunk) compute<NT>(acc, bb, N, wave);
+      }
+    }
+    // numeric columns: E columns x[b, j] V[j, :] each (numeric embeddings) or the value itself (raw)
+    const int kc = 4 * nchunk, kn = nd * (p.raw ? 1 : E);
+    const float* __restrict__ V = p.dense + p.num_emb_off;
+    for (int k0 = 0; k0 < kn; k0 += 2) {
+      const int kk = k0 + h;
+      const bool on = kk < kn;
+      float hv = 0.f;
+      if (on) hv = p.raw ? xq[kk] : __fmul_rn(xq[kk / E], V[kk]);
+      mfma_step<NT>(acc, W, kc + kk, on, N, wave, col, hv);
+    }
+  } else {
+    Blk<NT> ba, bb;
+    load_hidden<NT>(ba, in, W, 0, K, N, wave, col, h);
+    for (int k0 = 0; k0 < K; k0 += 4 * kKB) {
+      load_hidden<NT>(bb, in, W, k0 + 2 * kKB, K, N, wave, col, h);
+      compute<NT>(acc, ba, N, wave);
+      load_hidden<NT>(ba, in, W, k0 + 4 * kKB, K, N, wave, col, h);
+      if (k0 + 2 * kKB < K) compute<NT>(acc, bb, N, wave);
+    }
+  }
+  epilogue<NT>(acc, p.dense + ly.b_off, N, last ? 0 : p.act, out, wave, col, h);
+}
+
+__global__ __launch_bounds__(kThreads) void predict_fused_k(const ServeArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  __shared__ Layer layers[kMaxLayers];
+  __shared__ float red_lin[kParts][kRB], red_fm[kParts][kRB];
+  int32_t* rows = reinterpret_cast<int32_t*>(lds);                // [F][32]
+  float* buf0 = reinterpret_cast<float*>(lds) + p.F * kRB;
+  float* buf1 = buf0 + p.buf_a;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31, h = lane >> 5;
+  const int64_t b0 = static_cast<int64_t>(blockIdx.x) * kRB;
+  const int F = p.F, E = p.E, nd = p.nd;
+  // (the layer table: compile-time indices into the kernel arguments, runtime indices into LDS afterwards)
+#pragma unroll
+  for (int i = 0; i < kMaxLayers; ++i)
+    if (tid == i) layers[i] = p.l[i];
+  // 0. the requests' rows (requests past B repeat the last one: loads stay legal, stores are predicated)
+  for (int i = tid; i < F * kRB; i += kThreads) {
+    const int f = i >> 5;
+    const int64_t b = b0 + (i & 31) < p.B ? b0 + (i & 31) : p.B - 1;
+    rows[i] = static_cast<int32_t>(p.field_off[f] + p.ids[b * F + f]);
+  }
+  __syncthreads();
+  const int64_t bq = b0 + col < p.B ? b0 + col : p.B - 1;        // this lane's request
+  const float* __restrict__ xq = p.x_num ? p.x_num + bq * nd : nullptr;
+
+  // 1. wide part and FM term: part = tid / 32 of the request tid % 32
+  {
+    const int part = tid >> 5, c32 = tid & 31;
+    float lacc = 0.f, t = 0.f;
+    if (p.use_linear) {
+      float lw[kMaxFields / kParts];                              // (all of a thread's weights requested at once)
+#pragma unroll
+      for (int i = 0; i < kMaxFields / kParts; ++i) {
+        const int f = part + i * kParts;
+        lw[i] = (f < F && ((p.wide_fields >> f) & 1u)) ? p.lin_w[static_cast<int64_t>(rows[f * kRB + c32]) * p.ls] : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < kMaxFields / kParts; ++i) lacc += lw[i];
+      if (nd && !p.raw)                                           // numeric embeddings' linear weights (deep_fm.py:62-70)
+        for (int j = part; j < nd; j += kParts) lacc += __fmul_rn(xq[j], p.dense[p.lin_num_off + j]);
+    }
+    if (p.use_fm) {
+      const float* __restrict__ V = p.dense + p.num_emb_off;
+      for (int c = part; c < E / 4; c += kParts) {
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s;
+        constexpr int U = 8;                                      // rows in flight per thread
+        for (int f0 = 0; f0 < F; f0 += U) {
+          float4 r[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            r[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (f0 + u < F) r[u] = ld4(p.table + static_cast<int64_t>(rows[(f0 + u) * kRB + c32]) * p.ts + 4 * c);
+          }
+#pragma unroll
+          for (int u = 0; u < U; ++u) {                           // (a zero row adds exact zeros)
+            s.x += r[u].x; s.y += r[u].y; s.z += r[u].z; s.w += r[u].w;
+            q.x += __fmul_rn(r[u].x, r[u].x); q.y += __fmul_rn(r[u].y, r[u].y);
+            q.z += __fmul_rn(r[u].z, r[u].z); q.w += __fmul_rn(r[u].w, r[u].w);
+          }
+        }
+        for (int j = 0; j < nd; ++j) {                            // x[b, j] * V[j, :] is a row like any other
+          const float4 v = ld4(V + j * E + 4 * c);
+          const float xv = xq[j];
+          const float4 r = make_float4(__fmul_rn(xv, v.x), __fmul_rn(xv, v.y), __fmul_rn(xv, v.z), __fmul_rn(xv, v.w));
+          s.x += r.x; s.y += r.y; s.z += r.z; s.w += r.w;
+          q.x += __fmul_rn(r.x, r.x); q.y += __fmul_rn(r.y, r.y); q.z += __fmul_rn(r.z, r.z); q.w += __fmul_rn(r.w, r.w);
+        }
+        // deep_fm.py:81-87: tf.square then subtract, products rounded on their own: one field gives exactly 0
+        t += ((__fmul_rn(s.x, s.x) - q.x) + (__fmul_rn(s.y, s.y) - q.y)) +
+             ((__fmul_rn(s.z, s.z) - q.z) + (__fmul_rn(s.w, s.w) - q.w));
+      }
+    }
+    red_lin[part][c32] = lacc;
+    red_fm[part][c32] = t;
+  }
+
+  // 2., 3. the MLP
+  const int L = p.n_layers;
+  float* in = buf1;
+  float* out = buf0;
+  for (int li = 0; li < L; ++li) {
+    const Layer ly = layers[li];
+    if (wave * 32 < ly.fan_out) {                                 // (a wave without a tile only keeps the barriers)
+      const int nt = (ly.fan_out + 32 * kWaves - 1) / (32 * kWaves);
+      if (nt <= 1) run_layer<1>(p, ly, li == 0, li + 1 == L, rows, xq, in, out, wave, col, h);
+      else if (nt <= 2) run_layer<2>(p, ly, li == 0, li + 1 == L, rows, xq, in, out, wave, col, h);
+      else run_layer<kTPW>(p, ly, li == 0, li + 1 == L, rows, xq, in, out, wave, col, h);
+    }
+    __syncthreads();
+    float* sw = in; in = out; out = sw;
+  }
+  if (L == 0) __syncthreads();                                    // (red_lin / red_fm)
+
+  // 4. head: the order of mi_sigmoid_ce_head, the outputs of mi_binary_predictions
+  if (tid < kRB && b0 + tid < p.B) {
+    const int64_t b = b0 + tid;
+    float z = 0.f;
+    if (p.use_linear) {
+      float lin = 0.f;
+#pragma unroll
+      for (int i = 0; i < kParts; ++i) lin += red_lin[i][tid];
+      if (nd && p.raw)                                            // canned estimators: added in column order after the categorical sum
+        for (int j = 0; j < nd; ++j) lin = lin + __fmul_rn(xq[j], p.dense[p.lin_num_off + j]);
+      z = lin + p.dense[p.lin_bias_off];
+    }
+    if (p.use_fm) {
+      float t = 0.f;
+#pragma unroll
+      for (int i = 0; i < kParts; ++i) t += red_fm[i][tid];
+      z = z + 0.5f * t;
+    }
+    if (L) z = z + in[tid];                                       // the logits layer's one row
+    if (p.logits) p.logits[b] = z;
+    const float pr = mi_sigmoid_stable(z);
+    if (p.logistic) p.logistic[b] = pr;
+    if (p.probabilities) { p.probabilities[2 * b] = 1.f - pr; p.probabilities[2 * b + 1] = pr; }
+    if (p.class_ids) p.class_ids[b] = pr > 0.5f ? 1 : 0;
+  }
+}
+
+int32_t unsupported(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+int32_t unsupported(const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  mi::set_error("%s", buf);
+  return MI_ERR_UNSUPPORTED;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mi_predict_fused_workspace_bytes(int64_t B, int32_t n_layers) {
+  (void)B; (void)n_layers;
+  return 0;                              // everything between the ids and the predictions stays in LDS and registers
+}
+
+int32_t mi_predict_fused(const float* table, int64_t table_stride, const float* lin_w, int32_t lin_stride,
+                         const int64_t* field_off, const int32_t* ids, const float* x_num, int64_t B, int32_t F, int32_t E,
+                         int32_t n_numeric, const float* dense, const int64_t* layer_off, const int32_t* widths,
+                         int32_t n_layers, int32_t activation, int32_t use_linear, int32_t use_fm, int32_t use_dnn,
+                         int32_t numeric_raw, int64_t lin_bias_off, int64_t num_emb_off, int64_t lin_num_off,
+                         uint64_t wide_fields, float* logits, float* logistic, float* probabilities, int64_t* class_ids,
+                         void* workspace, size_t workspace_bytes, mi_stream_t stream) {
+  (void)workspace; (void)workspace_bytes;
+  MI_REQUIRE(B >= 1, "predict_fused: B=%lld (at least one request)", (long long)B);
+  MI_REQUIRE(F >= 0 && n_numeric >= 0 && F + n_numeric >= 1, "predict_fused: F=%d n_numeric=%d (at least one column)", F, n_numeric);
+  if (F > kMaxFields) return unsupported("predict_fused: F=%d categorical fields (at most %d)", F, kMaxFields);
+  MI_REQUIRE(use_linear || use_fm || use_dnn, "predict_fused: no part of the model is switched on");
+  MI_REQUIRE(logits || logistic || probabilities || class_ids, "predict_fused: no output requested");
+  MI_REQUIRE(activation >= 0 && activation <= 3, "predict_fused: activation %d", activation);
+  MI_REQUIRE(!(numeric_raw && use_fm), "predict_fused: raw numeric columns belong to the models without an FM term");
+  const bool emb = (use_fm || use_dnn) && F > 0;                  // the table is read
+  const bool num_emb = n_numeric > 0 && !numeric_raw;
+  if ((emb || num_emb) && (E < 4 || E > 256 || (E & 3)))
+    return unsupported("predict_fused: embedding size %d unsupported (multiple of 4 in [4,256])", E);
+  MI_REQUIRE(!emb || (table && mi::aligned16(table)), "predict_fused: table (16-byte aligned)");
+  MI_REQUIRE(table_stride == 0 || (table_stride >= E && (table_stride & 3) == 0),
+             "predict_fused: table_stride=%lld (0 = E, else >= E and a multiple of 4)", (long long)table_stride);
+  MI_REQUIRE(F == 0 || (field_off && ids), "predict_fused: field_off / ids");
+  MI_REQUIRE(n_numeric == 0 || x_num, "predict_fused: x_num");
+  MI_REQUIRE(!(use_linear && F > 0 && wide_fields) || (lin_w && lin_stride >= 1), "predict_fused: lin_w / lin_stride=%d", lin_stride);
+  MI_REQUIRE(!(use_linear || use_dnn || num_emb) || dense, "predict_fused: dense");
+  MI_REQUIRE(!use_linear || lin_bias_off >= 0, "predict_fused: lin_bias_off");
+  MI_REQUIRE(!(use_linear && n_numeric) || lin_num_off >= 0, "predict_fused: lin_num_off");
+  MI_REQUIRE(!num_emb || (num_emb_off >= 0 && (num_emb_off & 3) == 0 && mi::aligned16(dense)),
+             "predict_fused: num_emb_off=%lld (a multiple of 4 floats into a 16-byte aligned buffer)", (long long)num_emb_off);
+  MI_REQUIRE(!(num_emb && !use_fm && !use_dnn), "predict_fused: numeric embeddings need the FM term or the DNN");
+  MI_REQUIRE(use_dnn ? n_layers >= 1 : n_layers == 0, "predict_fused: %d layers (a DNN has at least its logits layer)", n_layers);
+  if (n_layers > kMaxLayers)
+    return unsupported("predict_fused: %d hidden layers (at most %d)", n_layers - 1, kMaxLayers - 1);
+  MI_REQUIRE(n_layers == 0 || (layer_off && widths), "predict_fused: layer_off / widths");
+  ServeArgs a{};
+  int wa = 0, wb = 0;                    // widths of the layer outputs in the first / second LDS buffer
+  for (int i = 0; i < n_layers; ++i) {
+    const int fi = widths[i], fo = widths[i + 1];
+    MI_REQUIRE(fi >= 1 && fo >= 1, "predict_fused: width %d -> %d", fi, fo);
+    MI_REQUIRE(i + 1 < n_layers || fo == 1, "predict_fused: the last layer has %d outputs (1 expected)", fo);
+    MI_REQUIRE(layer_off[2 * i] >= 0 && layer_off[2 * i + 1] >= 0, "predict_fused: layer offsets");
+    if (fo > kMaxWidth) return unsupported("predict_fused: hidden width %d (at most %d)", fo, kMaxWidth);
+    int& w = (i & 1) ? wb : wa;
+    if (fo > w) w = fo;
+    a.l[i] = Layer{layer_off[2 * i], layer_off[2 * i + 1], fi, fo};
+  }
+  if (n_layers) {
+    const int64_t d_in = (emb ? static_cast<int64_t>(F) * E : 0) + static_cast<int64_t>(n_numeric) * (numeric_raw ? 1 : E);
+    MI_REQUIRE(widths[0] >= d_in, "predict_fused: widths[0]=%d below the %lld input columns", widths[0], (long long)d_in);
+  }
+  const int64_t blocks = mi::ceil_div(B, kRB);
+  MI_REQUIRE(blocks <= INT32_MAX, "predict_fused: grid too large");
+  const size_t lds = sizeof(float) * kRB * (static_cast<size_t>(F) + wa + wb);
+  if (lds + 4096 > kMaxLds) return unsupported("predict_fused: %zu bytes of LDS for F=%d and widths %d / %d", lds, F, wa, wb);
+  a.table = emb ? table : nullptr; a.lin_w = lin_w; a.field_off = field_off; a.ids = ids; a.x_num = x_num; a.dense = dense;
+  a.logits = logits; a.logistic = logistic; a.probabilities = probabilities; a.class_ids = class_ids;
+  a.B = B; a.ts = table_stride ? table_stride : E;
+  a.lin_bias_off = lin_bias_off; a.num_emb_off = num_emb_off; a.lin_num_off = lin_num_off;
+  a.wide_fields = use_linear ? wide_fields : 0;
+  a.F = F; a.E = E; a.nd = n_numeric; a.ls = lin_stride; a.act = activation; a.n_layers = n_layers;
+  a.use_linear = use_linear != 0; a.use_fm = use_fm != 0 && (emb || num_emb); a.raw = numeric_raw != 0;
+  a.buf_a = wa * kRB;
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&predict_fused_k),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    MI_REQUIRE(e == hipSuccess, "predict_fused: LDS of %zu bytes: %s", lds, hipGetErrorString(e));
+  }
+  predict_fused_k<<<dim3(static_cast<unsigned>(blocks)), dim3(kThreads), lds, mi::as_stream(stream)>>>(a);
+  MI_CHECK_LAUNCH("predict_fused");
+  return MI_OK;
+}
+
+}  // extern "C"

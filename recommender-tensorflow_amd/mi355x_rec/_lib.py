@@ -144,6 +144,9 @@ SIGNATURES = {
     "mi_pair_topk_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
     "mi_pair_topk": (_i32, [_p, _p, _p, _i64, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _i32, _i32, _p, _p, _i32,
                             _p, _p, _p, _p, _sz, _p]),
+    "mi_predict_fused_workspace_bytes": (_sz, [_i64, _i32]),
+    "mi_predict_fused": (_i32, [_p, _i64, _p, _i32, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32,
+                                _i32, _i32, _i64, _i64, _i64, _u64, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

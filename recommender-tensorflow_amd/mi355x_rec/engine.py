@@ -1084,6 +1084,66 @@ class DeepFM:
         self._catchup(None, None, self.R_local)
         self._final_step = self.step
 
+    # ------------------------------------------------------------------ serving: the forward as one launch
+    FUSED_MAX_FIELDS = 64          # the limits of mi_predict_fused (include/mi355x_rec.h)
+    FUSED_MAX_HIDDEN_LAYERS = 8
+    FUSED_MAX_WIDTH = 512
+
+    def _fused_limit(self):
+        """The limit of mi_predict_fused this model exceeds, as text, or None when it fits."""
+        if self.F > self.FUSED_MAX_FIELDS:
+            return "%d categorical fields (at most %d)" % (self.F, self.FUSED_MAX_FIELDS)
+        if len(self.hidden) > self.FUSED_MAX_HIDDEN_LAYERS:
+            return "%d hidden layers (at most %d)" % (len(self.hidden), self.FUSED_MAX_HIDDEN_LAYERS)
+        if self.hidden and max(self.hidden) > self.FUSED_MAX_WIDTH:
+            return "a hidden layer of %d units (at most %d)" % (max(self.hidden), self.FUSED_MAX_WIDTH)
+        return None
+
+    def fused_predict_ok(self):
+        """Can predict_fused score this model?  (One GPU, within the kernel's limits.)"""
+        return self.shard is None and self._fused_limit() is None
+
+    def predict_fused(self, ids, x_num=None, out=None):
+        """PREDICT forward of a request batch as ONE launch (mi_predict_fused): ids in, the head's PREDICT dict out —
+        logits [B, 1], logistic [B, 1], probabilities [B, 2], class_ids = classes [B, 1] int64, device tensors shaped as
+        model.binary_predictions returns them.  out: a dict of such tensors to write into (a caller that keeps them per
+        batch size allocates nothing per call)."""
+        self._prep(ids, None, x_num)
+        if self.shard is not None:
+            raise NotImplementedError("predict_fused runs on one GPU: a row-sharded engine has only its shard of the tables")
+        why = self._fused_limit()
+        if why is not None:
+            raise ValueError("predict_fused: the model has %s; use predict_logits" % why)
+        B = ids.shape[0]
+        if B < 1:
+            raise ValueError("predict_fused: no rows")
+        self.finalize_rows()
+        tabs = getattr(self, "_fused_tabs", None)
+        if tabs is None:
+            layer_off = torch.tensor([o for (ko, bo, _, _) in self.layers for o in (ko, bo)] or [0], dtype=torch.int64)
+            widths = torch.tensor(([self.layers[0][2]] + [h for (_, _, _, h) in self.layers]) if self.layers else [0],
+                                  dtype=torch.int32)
+            wide = 0
+            if self.use_linear:
+                for f in range(self.F):
+                    if self.wide_fields is None or self.wide_fields[f]:
+                        wide |= 1 << f
+            tabs = self._fused_tabs = (layer_off, widths, wide)
+        layer_off, widths, wide = tabs
+        if out is None:
+            dev = self.device
+            cls = torch.empty(B, 1, dtype=torch.int64, device=dev)
+            out = {"logits": torch.empty(B, 1, dtype=torch.float32, device=dev),
+                   "logistic": torch.empty(B, 1, dtype=torch.float32, device=dev),
+                   "probabilities": torch.empty(B, 2, dtype=torch.float32, device=dev), "class_ids": cls, "classes": cls}
+        self.k.mi_predict_fused(self.table, self.ts, self.lin_w, self.ls, self.field_off, ids, x_num, B, self.F, self.E,
+                                self.n_numeric, self.dense, layer_off, widths, len(self.layers), self.act,
+                                int(self.use_linear), int(self.use_mf), int(self.use_dnn), int(self.raw_numeric),
+                                self.lin_bias_off, -1 if self.num_emb_off is None else self.num_emb_off,
+                                -1 if self.lin_num_off is None else self.lin_num_off, wide,
+                                out["logits"], out["logistic"], out["probabilities"], out["class_ids"], None, 0)
+        return out
+
     # ------------------------------------------------------------------ top-K recommendation
     TOP_K_MAX = 256
 

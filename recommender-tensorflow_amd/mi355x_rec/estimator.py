@@ -78,6 +78,21 @@ class LatestExporter:
     def __init__(self, name, serving_input_receiver_fn, exports_to_keep=5):
         self.name, self.fn, self.keep = name, serving_input_receiver_fn, exports_to_keep
 
+    @staticmethod
+    def _model(estimator):
+        """What an export must say about its model for a predictor to be built from it alone (predictor.py): the feature
+        columns in the plan's field order, the canned model kind, and the engine constructor arguments that the
+        `layout` table inside variables.pt does not carry."""
+        from .feature_column import column_to_json
+        store, eng = estimator.params["_store"], estimator._engine()
+        plan = store["plan"]
+        dims = eng.field_dims if eng.field_dims is not None else [eng.E if eng.use_emb else None] * eng.F
+        acts = {0: None, 1: "relu", 2: "sigmoid", 3: "tanh"}
+        return {"categorical_columns": [column_to_json(c, d) for c, d in zip(plan.categorical, dims)],
+                "numeric_columns": [column_to_json(c) for c in plan.numeric],
+                "tf_model": estimator.params.get("tf_model", "deep_fm"),
+                "engine": {"activation": acts[eng.act], "reduction": eng.reduction}}
+
     def export(self, estimator, export_dir):
         """Single GPU: variables.pt.  N GPUs (every rank calls this): the chief picks the directory and writes the
         signature, whose "sharding" entry says how to put the model together again — row r of the stacked tables lives
@@ -96,7 +111,7 @@ class LatestExporter:
         if estimator.is_chief:
             sig = {"receiver_tensors": {k: str(v) for k, v in recv.receiver_tensors.items()},
                    "outputs": ["logits", "logistic", "probabilities", "class_ids", "classes"],
-                   "global_step": estimator.global_step}
+                   "global_step": estimator.global_step, "model": self._model(estimator)}
             if shard is not None:
                 sig["sharding"] = {"world": shard.world, "files": ["variables.rank%d.pt" % r for r in range(shard.world)],
                                    "rule": "row r of table / lin_w / slots: file r % world, index r // world; dense replicated"}

@@ -197,6 +197,57 @@ def embedding_column(categorical_column, dimension, combiner="mean"):
     return EmbeddingColumn(categorical_column, dimension, combiner)
 
 
+# columns as plain JSON (the "model" entry of an export's signature.json; mi355x_rec/predictor.py reads it back) --------
+def _dtype_name(dtype):
+    return "string" if dtype in (str, bytes, object, None) else np.dtype(dtype).name
+
+
+def _plain(v):
+    return v.item() if hasattr(v, "item") else v
+
+
+def column_to_json(c, dimension=None):
+    """One of the five column kinds as a dict of plain JSON values.  `dimension`: the embedding dimension of the
+    embedding_column wrapped around a categorical column (None: the column is not in the deep part)."""
+    if isinstance(c, EmbeddingColumn):
+        return column_to_json(c.categorical_column, c.dimension)
+    if isinstance(c, NumericColumn):
+        return {"kind": "numeric", "key": c.key, "name": c.name, "dtype": _dtype_name(c.dtype),
+                "default": None if c.default_value is None else _plain(c.default_value)}
+    d = {"key": c.key, "name": c.name, "num_buckets": int(c.num_buckets), "embedding_dimension": dimension}
+    if isinstance(c, HashBucketColumn):
+        d.update(kind="hash_bucket", dtype=_dtype_name(c.dtype))
+    elif isinstance(c, VocabularyListColumn):
+        d.update(kind="vocabulary_list", vocabulary=[_plain(v) for v in c.vocab], default=c.default_value,
+                 num_oov_buckets=c.num_oov)
+    elif isinstance(c, IdentityColumn):
+        d.update(kind="identity", default=None if c.default_value is None else int(c.default_value))
+    elif isinstance(c, BucketizedColumn):
+        d.update(kind="bucketized", boundaries=[float(b) for b in c.boundaries], source=column_to_json(c.source))
+    else:
+        raise ValueError("not a feature column: %r" % (c,))
+    return d
+
+
+def column_from_json(d):
+    """The column column_to_json described (a categorical column comes back bare: its embedding dimension stays in
+    d["embedding_dimension"])."""
+    kind = d.get("kind")
+    if kind == "numeric":
+        return NumericColumn(d["key"], default_value=d.get("default"),
+                             dtype=str if d.get("dtype") == "string" else np.dtype(d.get("dtype", "float32")).type)
+    if kind == "hash_bucket":
+        return HashBucketColumn(d["key"], d["num_buckets"], str if d.get("dtype") == "string" else np.dtype(d["dtype"]).type)
+    if kind == "vocabulary_list":
+        return VocabularyListColumn(d["key"], d["vocabulary"], default_value=d.get("default", -1),
+                                    num_oov_buckets=d.get("num_oov_buckets", 0))
+    if kind == "identity":
+        return IdentityColumn(d["key"], d["num_buckets"], d.get("default"))
+    if kind == "bucketized":
+        return BucketizedColumn(column_from_json(d["source"]), d["boundaries"])
+    raise ValueError("unknown column kind %r" % (kind,))
+
+
 class FieldPlan:
     """Lowering of (categorical_columns, numeric_columns) to the fused-table layout.
 
