@@ -740,6 +740,40 @@ int32_t mi_predict_fused(const float* table, int64_t table_stride, const float* 
                          uint64_t wide_fields, float* logits, float* logistic, float* probabilities, int64_t* class_ids,
                          void* workspace, size_t workspace_bytes, mi_stream_t stream);
 
+/* ---- training small models: one optimizer.minimize(loss) as one launch (csrc/train_fused.hip) ------------------------
+ * What trainers/deep_fm.py:36-125 builds and model_utils.py:57-72 minimises, for one batch of a DeepFM with categorical
+ * columns only and Adam on every variable (one schedule): gather, wide part, FM term, MLP forward with dropout,
+ * sigmoid-CE head, full backward, dense Adam, and TF's dense-equivalent sparse Adam as the LITERAL all-rows sweep
+ *  — no sort, no stamps to order, no replay loop.  One kernel: block 0 does everything that depends on the
+ * loss and applies the touched rows and the dense variables; the other blocks own disjoint slices of the R rows and give
+ * every row the batch does not touch one step of the sweep (m *= beta1; v *= beta2; w -= (lr_t m) / (sqrtf(v) + eps)).
+ * No workgroup reads what another writes in the launch and none waits for another.
+ *   table / t_m / t_v (rows table_stride floats apart, 0 = E; NULL without FM term and DNN), lin_w / l_m / l_v and
+ *   last_step (elements lin_stride apart; lin_* NULL without the wide part), field_off [F] (device), R = rows in all,
+ *   ids [B, F] int32 (trusted to lie inside their field), labels [B] uint8;
+ *   dense / d_m / d_v [n_dense] with layer_off [2 n_layers] and widths [n_layers + 1] (host) as in mi_predict_fused
+ *     (widths[0] = F E); activation: 0 identity, 1 relu, 2 sigmoid, 3 tanh;  lin_bias_off: the wide part's bias;
+ *   keep_prob: 1 - dropout; hidden layer i draws the mask of mi_dense_fwd with seed + 7919 i;
+ *   scale: 1 / B (mean) or 1 (sum); step: the global step AFTER this call (>= 1); hp: Adam with lr_t of that step.
+ * PRECONDITION: every row is current (last_step == step - 1, or 0 with m = v = 0), as after mi_sparse_catchup over all rows.
+ * Results: logits [B] (before the update), loss [1]; every variable and slot updated; last_step == step for EVERY row.
+ * Entries of one row are summed in ascending entry order (mi_sparse_apply's order); the entry gradient is
+ * mi_sparse_apply_fused's.  Untouched rows get the bits of the exact one-step mi_sparse_catchup.  Results do not depend on
+ * sweep_blocks (0 = the built-in choice; a test seam) and are bitwise reproducible from equal state.
+ * Limits, checked before anything is launched (MI_ERR_UNSUPPORTED / MI_ERR_INVALID): Adam; 1 <= B <= 128; 1 <= F <= 32;
+ * E in {4, 8, 12, 16}; B F E <= 16384; at most 3 hidden layers of width <= 64; R <= 2^18; sweep_blocks <= 1024.
+ * workspace: mi_train_step_fused_workspace_bytes(B, F, E, n_dense) bytes, 16-byte aligned, touched by block 0 only
+ * (the dense gradient, and d_concat when LDS has no room for it). */
+size_t mi_train_step_fused_workspace_bytes(int64_t B, int32_t F, int32_t E, int64_t n_dense);
+int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_stride, float* lin_w, float* l_m, float* l_v,
+                            int32_t lin_stride, int32_t* last_step, const int64_t* field_off, int64_t R, const int32_t* ids,
+                            const uint8_t* labels, int64_t B, int32_t F, int32_t E, float* dense, float* d_m, float* d_v,
+                            int64_t n_dense, const int64_t* layer_off, const int32_t* widths, int32_t n_layers,
+                            int32_t activation, int32_t use_linear, int32_t use_fm, int32_t use_dnn, int64_t lin_bias_off,
+                            float keep_prob, uint64_t seed, float scale, int32_t step, const mi_opt_hparams* hp,
+                            float* logits, float* loss, int32_t sweep_blocks, void* workspace, size_t workspace_bytes,
+                            mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,62 +12,12 @@
 // (oracle/optimizers.py) bit for bit given equal gradients.  HBM-bound; per unique row the
 // algorithmic traffic is 4E (grad) + 24E (w, slot0, slot1 read+write) + 8 bytes.
 #include "common.h"
+#include "optim_rules.h"
 #include <algorithm>
 
 namespace {
 
 constexpr int kBlock = 256;
-
-struct Hp {
-  int kind;
-  float lr, beta1, beta2, eps, lr_t, decay, momentum, lr_power, l1, l2;
-};
-
-Hp make_hp(const mi_opt_hparams* h) {
-  return Hp{h->kind, h->lr, h->beta1, h->beta2, h->epsilon, h->lr_t, h->decay, h->momentum,
-            h->lr_power, h->l1, h->l2};
-}
-
-// one element of a dense variable (training_ops.cc Apply* functors)
-__device__ __forceinline__ void dense_rule(const Hp& h, float& w, float& s0, float& s1, float g) {
-  switch (h.kind) {
-    case MI_OPT_ADAM: {
-      s0 = s0 + (g - s0) * (1.f - h.beta1);
-      s1 = s1 + (g * g - s1) * (1.f - h.beta2);
-      w = w - (s0 * h.lr_t) / (sqrtf(s1) + h.eps);
-    } break;
-    case MI_OPT_ADAGRAD: {
-      s0 = s0 + g * g;
-      w = w - (g * h.lr) * (1.f / sqrtf(s0));
-    } break;
-    case MI_OPT_FTRL: {
-      const float na = s0 + g * g;
-      s1 = s1 + (g - ((sqrtf(na) - sqrtf(s0)) / h.lr) * w);
-      const float adj = fminf(fmaxf(s1, -h.l1), h.l1);
-      w = (adj - s1) / (sqrtf(na) / h.lr + 2.f * h.l2);
-      s0 = na;
-    } break;
-    case MI_OPT_RMSPROP: {
-      s0 = s0 + (g * g - s0) * (1.f - h.decay);
-      s1 = s1 * h.momentum + (g * h.lr) / sqrtf(s0 + h.eps);
-      w = w - s1;
-    } break;
-    default:
-      w = w - g * h.lr;
-  }
-}
-
-// one element of a TOUCHED row of a sparse variable.  Adam: adam.py _apply_sparse_shared
-// (m*beta1 then scatter_add); the others act on touched rows exactly like the dense rule.
-__device__ __forceinline__ void sparse_rule(const Hp& h, float& w, float& s0, float& s1, float g) {
-  if (h.kind == MI_OPT_ADAM) {
-    s0 = s0 * h.beta1 + g * (1.f - h.beta1);
-    s1 = s1 * h.beta2 + (g * g) * (1.f - h.beta2);
-    w = w - (h.lr_t * s0) / (sqrtf(s1) + h.eps);
-  } else {
-    dense_rule(h, w, s0, s1, g);
-  }
-}
 
 __global__ __launch_bounds__(kBlock) void dense_apply_k(float* __restrict__ w, float* __restrict__ s0,
                                                         float* __restrict__ s1,
@@ -332,17 +282,6 @@ __global__ __launch_bounds__(kBlock) void sparse_apply_long_k(ApplyArgs a, Hp h,
       }
       __syncthreads();
     }
-  }
-}
-
-// Lazy replay of TF Adam's whole-table decay for the steps a row sat out.
-__device__ __forceinline__ void replay(float& w, float& m, float& v, int s_from, int s_to,
-                                       const float* __restrict__ lr_table, float b1, float b2,
-                                       float eps) {
-  for (int s = s_from; s <= s_to; ++s) {
-    m = m * b1;
-    v = v * b2;
-    w = w - (lr_table[s] * m) / (sqrtf(v) + eps);
   }
 }
 

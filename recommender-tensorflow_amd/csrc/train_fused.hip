@@ -1,0 +1,532 @@
+// Training small models: one whole optimizer.minimize(loss) of a DeepFM — gather, wide part, FM term, MLP forward with
+// dropout, sigmoid-CE head, full backward, dense Adam and TF's dense-equivalent sparse Adam — as ONE launch
+// (mi_train_step_fused, include/mi355x_rec.h).  Replaces, for a model whose state fits the chip's caches, what
+// trainers/deep_fm.py:36-125 and model_utils.py:57-72 have TensorFlow execute per step.
+//
+//   train_fused_k    block 0 = the BATCH workgroup, blocks 1 .. G-1 = SWEEP workgroups.
+//     batch   everything that depends on the loss, phases separated by workgroup barriers:
+//       0. rows     field_off[f] + ids[b, f] into LDS
+//       1. forward  sumv and the FM term (products rounded one by one: a one-field model gives exactly 0), the wide sum
+//                   and layer 1 straight from the gathered table rows; then one phase per later layer, outputs
+//                   (after activation and dropout) in LDS
+//       2. head     logit = ((lin + bias) + fm) + dnn, loss, dlogit
+//       3. backward per layer, top down: the weight and bias gradient into the dense-gradient workspace, then the
+//                   data gradient IN PLACE over the layer's input (the activation's derivative is taken from the
+//                   stored output, the dropout mask from its zeros); layer 1's data gradient is d_concat
+//       4. apply    per DISTINCT touched row (the first entry of a row leads; entries of a row are summed in
+//                   ascending entry order) sparse_rule on the table record and the wide record, stamp = step;
+//                   dense_rule on every dense variable with the gradient of phase 3
+//     sweep   each workgroup owns a slice of the R rows, builds the batch's touched set itself (a bitmap of R bits in
+//             LDS, from ids) and gives every row of its slice that is NOT touched one step of TF Adam's whole-table
+//             sweep (replay_step of optim_rules.h), table record and wide record, stamp = step.
+//   Touched and untouched rows are disjoint and the dense variables belong to block 0: no workgroup reads what another
+//   writes in this launch and none waits for another — no flags, no grid barrier, no float atomics to global memory.
+//   Results do not depend on G.
+//
+// Arithmetic: fp32 throughout; compiled with -ffp-contract=off (the update rules and the FM term are written one
+// rounding per operation); the MLP's dot products use explicit fmaf.
+#include "common.h"
+#include "optim_rules.h"
+
+namespace {
+
+constexpr int kThreads = 512;
+constexpr int kMaxBatch = 128;
+constexpr int kMaxFields = 32;
+constexpr int kMaxEmb = 16;
+constexpr int kMaxHidden = 3;
+constexpr int kMaxWidth = 64;
+constexpr int kMaxLayers = kMaxHidden + 1;          // + the logits layer
+constexpr int64_t kMaxConcat = 16384;               // B F E
+constexpr int64_t kMaxRows = int64_t(1) << 18;      // a 32 KB bitmap
+constexpr int kMaxSweepBlocks = 1024;
+constexpr size_t kMaxLds = 160 * 1024 - 1024;       // (the static arrays below take the rest)
+constexpr int kRowsInFlight = 4;
+
+struct Layer {
+  int64_t w_off, b_off;                 // offsets into the flat dense buffer: kernel [fan_in, fan_out], bias [fan_out]
+  int32_t fan_in, fan_out;
+  int32_t out_off, pad;                 // the layer's output [B][fan_out] in LDS (float offset)
+};
+
+struct Args {
+  float* table; float* tm; float* tv;   // or NULL (no FM term and no DNN)
+  float* lin_w; float* lm; float* lv;   // or NULL (no wide part)
+  int32_t* last_step;
+  const int64_t* field_off;
+  const int32_t* ids;
+  const uint8_t* labels;
+  float* dense; float* dm; float* dv;
+  float* gdense;                        // workspace: the dense gradient, indexed like dense
+  float* dcat_ws;                       // workspace: d_concat [B][F E] when LDS has no room for it, else NULL
+  float* logits; float* loss;
+  int64_t ts, R, lin_bias_off;
+  uint64_t seed;
+  int32_t B, F, E, ls, act, n_layers, use_linear, use_fm, step;
+  int32_t o_sumv, o_tq, o_lin, o_dl, o_dcat;   // float offsets in LDS (the rows [B F] int32 lead)
+  float keep, scale;
+  Hp hp;
+  Layer l[kMaxLayers];
+};
+
+__device__ __forceinline__ int32_t row_of(const Args& p, int i) {
+  const int f = i % p.F;
+  int64_t r = p.field_off[f] + p.ids[i];
+  r = r < 0 ? 0 : (r >= p.R ? p.R - 1 : r);             // (ids are trusted to lie inside their field; a bad one stays inside the arrays)
+  return static_cast<int32_t>(r);
+}
+
+// ---- sweep workgroups ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void sweep_block(const Args& p, uint32_t* __restrict__ bm) {
+  const int tid = threadIdx.x;
+  const int words = static_cast<int>((p.R + 31) >> 5);
+  for (int i = tid; i < words; i += kThreads) bm[i] = 0u;
+  __syncthreads();
+  const int n = p.B * p.F;
+  for (int i = tid; i < n; i += kThreads) {
+    const int32_t r = row_of(p, i);
+    atomicOr(&bm[r >> 5], 1u << (r & 31));
+  }
+  __syncthreads();
+  const int cpf = p.table ? p.E / 4 : 1;
+  const int64_t G = static_cast<int64_t>(gridDim.x) - 1;
+  const int64_t per = (p.R + G - 1) / G;
+  const int64_t lo = (static_cast<int64_t>(blockIdx.x) - 1) * per;
+  const int64_t hi = lo + per < p.R ? lo + per : p.R;
+  const int64_t items = hi > lo ? (hi - lo) * cpf : 0;
+  const float b1 = p.hp.beta1, b2 = p.hp.beta2, eps = p.hp.eps, lr_t = p.hp.lr_t;
+  for (int64_t i0 = tid; i0 < items; i0 += static_cast<int64_t>(kThreads) * kRowsInFlight) {
+    float4 w[kRowsInFlight], m[kRowsInFlight], v[kRowsInFlight];
+    float lw[kRowsInFlight], lm[kRowsInFlight], lv[kRowsInFlight];
+    int64_t r[kRowsInFlight];
+    int c[kRowsInFlight];
+    bool on[kRowsInFlight];
+#pragma unroll
+    for (int u = 0; u < kRowsInFlight; ++u) {
+      const int64_t i = i0 + static_cast<int64_t>(u) * kThreads;
+      on[u] = i < items;
+      r[u] = lo + (on[u] ? i / cpf : 0);
+      c[u] = on[u] ? static_cast<int>(i % cpf) : 0;
+      on[u] = on[u] && !((bm[r[u] >> 5] >> (r[u] & 31)) & 1u);
+      w[u] = m[u] = v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      lw[u] = lm[u] = lv[u] = 0.f;
+      if (on[u] && p.table) {
+        const int64_t o = r[u] * p.ts + 4 * c[u];
+        w[u] = ld4(p.table + o); m[u] = ld4(p.tm + o); v[u] = ld4(p.tv + o);
+      }
+      if (on[u] && c[u] == 0 && p.lin_w) {
+        const int64_t o = r[u] * p.ls;
+        lw[u] = p.lin_w[o]; lm[u] = p.lm[o]; lv[u] = p.lv[o];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kRowsInFlight; ++u) {
+      if (!on[u]) continue;
+      if (p.table) {
+        const int64_t o = r[u] * p.ts + 4 * c[u];
+        replay_step(w[u].x, m[u].x, v[u].x, lr_t, b1, b2, eps);
+        replay_step(w[u].y, m[u].y, v[u].y, lr_t, b1, b2, eps);
+        replay_step(w[u].z, m[u].z, v[u].z, lr_t, b1, b2, eps);
+        replay_step(w[u].w, m[u].w, v[u].w, lr_t, b1, b2, eps);
+        st4(p.table + o, w[u]); st4(p.tm + o, m[u]); st4(p.tv + o, v[u]);
+      }
+      if (c[u] == 0) {
+        const int64_t o = r[u] * p.ls;
+        if (p.lin_w) {
+          replay_step(lw[u], lm[u], lv[u], lr_t, b1, b2, eps);
+          p.lin_w[o] = lw[u]; p.lm[o] = lm[u]; p.lv[o] = lv[u];
+        }
+        p.last_step[o] = p.step;
+      }
+    }
+  }
+}
+
+// ---- the batch workgroup --------------------------------------------------------------------------------------------
+// output (b, n) of a layer from its pre-activation sum: bias, activation, dropout (hidden layers only)
+__device__ __forceinline__ float finish(const Args& p, float acc, float bias, bool last, int li, int b, int n, uint32_t thresh) {
+  float v = acc + bias;
+  if (last) return v;
+  v = mi_act(p.act, v);
+  if (p.keep < 1.f)                                              // layer i's mask: seed + 7919 i (engine._layer_seed)
+    v = mi_drop_keep_at(p.seed + 7919ull * static_cast<uint64_t>(li), static_cast<uint32_t>(b), static_cast<uint32_t>(n), thresh)
+            ? v / p.keep : 0.f;
+  return v;
+}
+
+__device__ __forceinline__ void batch_block(const Args& p, char* lds, const Layer* layers, float (*red)[kThreads / 64]) {
+  const int tid = threadIdx.x;
+  const int B = p.B, F = p.F, E = p.E, L = p.n_layers, D = F * E;
+  const int64_t ts = p.ts;
+  int32_t* rows = reinterpret_cast<int32_t*>(lds);
+  float* fl = reinterpret_cast<float*>(lds);
+  float* sumv = fl + p.o_sumv;
+  float* tq = fl + p.o_tq;
+  float* zlin = fl + p.o_lin;
+  float* dl = fl + p.o_dl;
+  float* dcat = p.dcat_ws ? p.dcat_ws : fl + p.o_dcat;
+  const uint32_t thresh = mi_drop_thresh16(p.keep);
+
+  // 0. the batch's rows
+  for (int i = tid; i < B * F; i += kThreads) rows[i] = row_of(p, i);
+  __syncthreads();
+
+  // 1. forward: FM sums, the wide sum, layer 1
+  {
+    const int nE = (p.table && p.use_fm) ? B * E : 0, nL = p.use_linear ? B : 0;
+    const int w1 = L ? layers[0].fan_out : 0, n1 = B * w1;
+    for (int i = tid; i < nE + nL + n1; i += kThreads) {
+      if (i < nE) {
+        const int b = i / E, c = i - b * E;
+        float s = 0.f, q = 0.f;
+        for (int f = 0; f < F; ++f) {
+          const float v = p.table[static_cast<int64_t>(rows[b * F + f]) * ts + c];
+          s = s + v;
+          q = q + v * v;
+        }
+        sumv[i] = s;
+        tq[i] = s * s - q;                                        // deep_fm.py:81-87 (one field: exactly 0)
+      } else if (i < nE + nL) {
+        const int b = i - nE;
+        float acc = 0.f;
+        for (int f = 0; f < F; ++f) acc = acc + p.lin_w[static_cast<int64_t>(rows[b * F + f]) * p.ls];
+        zlin[b] = acc;
+      } else {
+        const int j = i - nE - nL, b = j / w1, n = j - b * w1;
+        const float* __restrict__ W = p.dense + layers[0].w_off;
+        float acc = 0.f;
+        for (int f = 0; f < F; ++f) {
+          const float* __restrict__ row = p.table + static_cast<int64_t>(rows[b * F + f]) * ts;
+          for (int c = 0; c < E; c += 4) {
+            const float4 x = ld4(row + c);
+            const float* __restrict__ wk = W + static_cast<int64_t>(f * E + c) * w1 + n;
+            acc = fmaf(x.x, wk[0], acc);
+            acc = fmaf(x.y, wk[w1], acc);
+            acc = fmaf(x.z, wk[2 * w1], acc);
+            acc = fmaf(x.w, wk[3 * w1], acc);
+          }
+        }
+        fl[layers[0].out_off + j] = finish(p, acc, p.dense[layers[0].b_off + n], L == 1, 0, b, n, thresh);
+      }
+    }
+  }
+  __syncthreads();
+  for (int li = 1; li < L; ++li) {
+    const Layer ly = layers[li];
+    const float* __restrict__ in = fl + layers[li - 1].out_off;
+    const float* __restrict__ W = p.dense + ly.w_off;
+    const int K = ly.fan_in, N = ly.fan_out;
+    for (int j = tid; j < B * N; j += kThreads) {
+      const int b = j / N, n = j - b * N;
+      float acc = 0.f;
+      for (int k = 0; k < K; ++k) acc = fmaf(in[b * K + k], W[k * N + n], acc);
+      fl[ly.out_off + j] = finish(p, acc, p.dense[ly.b_off + n], li + 1 == L, li, b, n, thresh);
+    }
+    __syncthreads();
+  }
+
+  // 2. head (the order of mi_sigmoid_ce_head); the logits layer's output becomes its gradient
+  {
+    float per = 0.f, d = 0.f;
+    if (tid < B) {
+      float z = 0.f;
+      if (p.use_linear) z = zlin[tid] + p.dense[p.lin_bias_off];
+      if (p.table && p.use_fm) {
+        float t = 0.f;
+        for (int c = 0; c < E; ++c) t = t + tq[tid * E + c];
+        z = z + 0.5f * t;
+      }
+      if (L) z = z + fl[layers[L - 1].out_off + tid];
+      const float y = static_cast<float>(p.labels[tid]);
+      per = mi_sigmoid_ce_loss(z, y) * p.scale;
+      d = mi_sigmoid_ce_grad(z, y, p.scale);
+      p.logits[tid] = z;
+      dl[tid] = d;
+      if (L) fl[layers[L - 1].out_off + tid] = d;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { per += __shfl_xor(per, o); d += __shfl_xor(d, o); }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = per; red[1][tid >> 6] = d; }
+  }
+  __syncthreads();
+  const int nw = (B + 63) >> 6;                                   // waves that hold examples (at most 2)
+  if (tid == 0) {
+    float s = red[0][0];
+    for (int w = 1; w < nw; ++w) s = s + red[0][w];
+    p.loss[0] = s;
+  }
+
+  // 3. backward through the MLP, top down
+  for (int li = L - 1; li >= 0; --li) {
+    const Layer ly = layers[li];
+    const float* __restrict__ dy = fl + ly.out_off;
+    const float* __restrict__ W = p.dense + ly.w_off;
+    const int K = ly.fan_in, N = ly.fan_out;
+    float* prev = li ? fl + layers[li - 1].out_off : nullptr;
+    // weight and bias gradient
+    for (int i = tid; i < K * N + N; i += kThreads) {
+      float acc = 0.f;
+      if (i < K * N) {
+        const int k = i / N, n = i - k * N;
+        if (li) {
+          for (int b = 0; b < B; ++b) acc = fmaf(prev[b * K + k], dy[b * N + n], acc);
+        } else {
+          const int f = k / E, c = k - f * E;
+          for (int b = 0; b < B; ++b)
+            acc = fmaf(p.table[static_cast<int64_t>(rows[b * F + f]) * ts + c], dy[b * N + n], acc);
+        }
+        p.gdense[ly.w_off + i] = acc;
+      } else {
+        const int n = i - K * N;
+        for (int b = 0; b < B; ++b) acc = acc + dy[b * N + n];
+        p.gdense[ly.b_off + n] = acc;
+      }
+    }
+    if (li) {
+      __syncthreads();                                            // (the loop above read what the loop below overwrites)
+      for (int i = tid; i < B * K; i += kThreads) {
+        const int b = i / K, k = i - b * K;
+        float g = 0.f;
+        for (int n = 0; n < N; ++n) g = fmaf(dy[b * N + n], W[k * N + n], g);
+        const float x = prev[i];                                  // the stored output: act(pre) / keep, or 0 (dropped)
+        if (p.act == 1) {
+          g = x > 0.f ? g / p.keep : 0.f;
+        } else {
+          const bool dropped = p.keep < 1.f && x == 0.f;
+          g = dropped ? 0.f : (g / p.keep) * mi_act_deriv_from_output(p.act, x * p.keep);
+        }
+        prev[i] = g;
+      }
+    } else {
+      for (int i = tid; i < B * K; i += kThreads) {               // d_concat [B][F E] (K >= F E; rows past it belong to no column)
+        const int b = i / K, k = i - b * K;
+        if (k >= D) continue;
+        float g = 0.f;
+        for (int n = 0; n < N; ++n) g = fmaf(dy[b * N + n], W[k * N + n], g);
+        dcat[b * D + k] = g;
+      }
+    }
+    __syncthreads();
+  }
+
+  // 4. apply.  Sparse: item (entry e, float4 chunk c) — the first entry of a row leads it
+  {
+    const int cpf = p.table ? E / 4 : 1;
+    for (int i = tid; i < B * F * cpf; i += kThreads) {
+      const int e = i / cpf, c = i - e * cpf, b = e / F, f = e - b * F;
+      const int32_t r = rows[e];
+      float4 w = make_float4(0.f, 0.f, 0.f, 0.f), g = w;
+      const int64_t o = static_cast<int64_t>(r) * ts + 4 * c;
+      if (p.table) w = ld4(p.table + o);
+      float gl = 0.f;
+      bool leader = true;
+      for (int b2 = 0; b2 < B; ++b2) {
+        if (rows[b2 * F + f] != r) continue;
+        if (b2 < b) { leader = false; break; }
+        const float d = dl[b2];
+        if (p.table) {
+          // d_concat[b, f, :] + dlogit[b] (sumv[b, :] - row): the entry gradient of mi_sparse_apply_fused
+          float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (L) {
+            const float* q = dcat + b2 * D + f * E + 4 * c;
+            v = make_float4(q[0], q[1], q[2], q[3]);
+          }
+          if (p.use_fm) {
+            const float* s = sumv + b2 * E + 4 * c;
+            v.x = v.x + d * (s[0] - w.x); v.y = v.y + d * (s[1] - w.y);
+            v.z = v.z + d * (s[2] - w.z); v.w = v.w + d * (s[3] - w.w);
+          }
+          g.x = g.x + v.x; g.y = g.y + v.y; g.z = g.z + v.z; g.w = g.w + v.w;
+        }
+        gl = gl + d;
+      }
+      if (!leader) continue;
+      if (p.table) {
+        float4 m = ld4(p.tm + o), v = ld4(p.tv + o);
+        sparse_rule(p.hp, w.x, m.x, v.x, g.x);
+        sparse_rule(p.hp, w.y, m.y, v.y, g.y);
+        sparse_rule(p.hp, w.z, m.z, v.z, g.z);
+        sparse_rule(p.hp, w.w, m.w, v.w, g.w);
+        st4(p.table + o, w); st4(p.tm + o, m); st4(p.tv + o, v);
+      }
+      if (c == 0) {
+        const int64_t ol = static_cast<int64_t>(r) * p.ls;
+        if (p.lin_w) {
+          float lw = p.lin_w[ol], m = p.lm[ol], v = p.lv[ol];
+          sparse_rule(p.hp, lw, m, v, gl);
+          p.lin_w[ol] = lw; p.lm[ol] = m; p.lv[ol] = v;
+        }
+        p.last_step[ol] = p.step;
+      }
+    }
+  }
+  // dense: every variable of the MLP, and the wide part's bias (its gradient is the sum of dlogit)
+  for (int li = 0; li < L; ++li) {
+    const Layer ly = layers[li];
+    const int kn = ly.fan_in * ly.fan_out;
+    for (int i = tid; i < kn + ly.fan_out; i += kThreads) {
+      const int64_t o = i < kn ? ly.w_off + i : ly.b_off + (i - kn);
+      float w = p.dense[o], m = p.dm[o], v = p.dv[o];
+      dense_rule(p.hp, w, m, v, p.gdense[o]);
+      p.dense[o] = w; p.dm[o] = m; p.dv[o] = v;
+    }
+  }
+  if (p.use_linear && tid == 0) {
+    float g = red[1][0];
+    for (int w = 1; w < nw; ++w) g = g + red[1][w];
+    const int64_t o = p.lin_bias_off;
+    float w = p.dense[o], m = p.dm[o], v = p.dv[o];
+    dense_rule(p.hp, w, m, v, g);
+    p.dense[o] = w; p.dm[o] = m; p.dv[o] = v;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void train_fused_k(const Args p) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  __shared__ Layer layers[kMaxLayers];
+  __shared__ float red[2][kThreads / 64];
+  if (blockIdx.x) {
+    sweep_block(p, reinterpret_cast<uint32_t*>(lds));
+    return;
+  }
+  // (the layer table: compile-time indices into the kernel arguments, runtime indices into LDS afterwards)
+#pragma unroll
+  for (int i = 0; i < kMaxLayers; ++i)
+    if (threadIdx.x == i) layers[i] = p.l[i];
+  __syncthreads();
+  batch_block(p, lds, layers, red);
+}
+
+int32_t unsupported(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+int32_t unsupported(const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  mi::set_error("%s", buf);
+  return MI_ERR_UNSUPPORTED;
+}
+
+int64_t align4(int64_t n) { return (n + 3) & ~int64_t(3); }
+
+// LDS of the batch workgroup without d_concat (floats)
+int64_t batch_lds_floats(int64_t B, int32_t F, int32_t E, const int32_t* widths, int32_t n_layers) {
+  int64_t n = align4(B * F) + 2 * align4(B * E) + 2 * align4(B);
+  for (int i = 0; i < n_layers; ++i) n += align4(B * widths[i + 1]);
+  return n;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mi_train_step_fused_workspace_bytes(int64_t B, int32_t F, int32_t E, int64_t n_dense) {
+  if (B < 0 || F < 0 || E < 0 || n_dense < 0) return 0;
+  return sizeof(float) * static_cast<size_t>(align4(n_dense) + align4(B * F * E));
+}
+
+int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_stride, float* lin_w, float* l_m, float* l_v,
+                            int32_t lin_stride, int32_t* last_step, const int64_t* field_off, int64_t R, const int32_t* ids,
+                            const uint8_t* labels, int64_t B, int32_t F, int32_t E, float* dense, float* d_m, float* d_v,
+                            int64_t n_dense, const int64_t* layer_off, const int32_t* widths, int32_t n_layers,
+                            int32_t activation, int32_t use_linear, int32_t use_fm, int32_t use_dnn, int64_t lin_bias_off,
+                            float keep_prob, uint64_t seed, float scale, int32_t step, const mi_opt_hparams* hp,
+                            float* logits, float* loss, int32_t sweep_blocks, void* workspace, size_t workspace_bytes,
+                            mi_stream_t stream) {
+  MI_REQUIRE(hp, "train_step_fused: hp");
+  if (hp->kind != MI_OPT_ADAM) return unsupported("train_step_fused: optimizer kind %d (Adam only)", hp->kind);
+  MI_REQUIRE(use_linear || use_fm || use_dnn, "train_step_fused: no part of the model is switched on");
+  MI_REQUIRE(activation >= 0 && activation <= 3, "train_step_fused: activation %d", activation);
+  MI_REQUIRE(step >= 1, "train_step_fused: step=%d (the global step after this call, 1-based)", step);
+  MI_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, "train_step_fused: keep_prob=%g (in (0, 1])", keep_prob);
+  if (B < 1 || B > kMaxBatch) return unsupported("train_step_fused: B=%lld (1 to %d examples)", (long long)B, kMaxBatch);
+  if (F < 1 || F > kMaxFields) return unsupported("train_step_fused: F=%d categorical fields (1 to %d)", F, kMaxFields);
+  const bool emb = use_fm || use_dnn;
+  if (emb && (E < 4 || E > kMaxEmb || (E & 3)))
+    return unsupported("train_step_fused: embedding size %d (a multiple of 4, at most %d)", E, kMaxEmb);
+  if (!emb) E = 4;
+  if (B * F * E > kMaxConcat)
+    return unsupported("train_step_fused: B F E = %lld (at most %lld)", (long long)(B * F * E), (long long)kMaxConcat);
+  if (R < 1 || R > kMaxRows) return unsupported("train_step_fused: R=%lld table rows (1 to %lld)", (long long)R, (long long)kMaxRows);
+  if (sweep_blocks < 0 || sweep_blocks > kMaxSweepBlocks)
+    return unsupported("train_step_fused: sweep_blocks=%d (0 = the built-in choice, at most %d)", sweep_blocks, kMaxSweepBlocks);
+  MI_REQUIRE(field_off && ids && labels && last_step, "train_step_fused: field_off / ids / labels / last_step");
+  MI_REQUIRE(logits && loss, "train_step_fused: logits / loss");
+  MI_REQUIRE(!emb || (table && t_m && t_v && mi::aligned16(table) && mi::aligned16(t_m) && mi::aligned16(t_v)),
+             "train_step_fused: table / t_m / t_v (16-byte aligned)");
+  MI_REQUIRE(table_stride == 0 || (table_stride >= E && (table_stride & 3) == 0),
+             "train_step_fused: table_stride=%lld (0 = E, else >= E and a multiple of 4)", (long long)table_stride);
+  MI_REQUIRE(lin_stride >= 1, "train_step_fused: lin_stride=%d", lin_stride);
+  MI_REQUIRE(!use_linear || (lin_w && l_m && l_v), "train_step_fused: lin_w / l_m / l_v");
+  MI_REQUIRE(dense && d_m && d_v && n_dense >= 1, "train_step_fused: dense / d_m / d_v / n_dense");
+  MI_REQUIRE(!use_linear || (lin_bias_off >= 0 && lin_bias_off < n_dense), "train_step_fused: lin_bias_off");
+  MI_REQUIRE(use_dnn ? n_layers >= 1 : n_layers == 0, "train_step_fused: %d layers (a DNN has at least its logits layer)", n_layers);
+  if (n_layers > kMaxLayers)
+    return unsupported("train_step_fused: %d hidden layers (at most %d)", n_layers - 1, kMaxHidden);
+  MI_REQUIRE(n_layers == 0 || (layer_off && widths), "train_step_fused: layer_off / widths");
+  Args a{};
+  for (int i = 0; i < n_layers; ++i) {
+    const int fi = widths[i], fo = widths[i + 1];
+    MI_REQUIRE(fi >= 1 && fo >= 1, "train_step_fused: width %d -> %d", fi, fo);
+    MI_REQUIRE(i + 1 < n_layers || fo == 1, "train_step_fused: the last layer has %d outputs (1 expected)", fo);
+    if (i + 1 < n_layers && fo > kMaxWidth) return unsupported("train_step_fused: hidden width %d (at most %d)", fo, kMaxWidth);
+    const int64_t wo = layer_off[2 * i], bo = layer_off[2 * i + 1];
+    MI_REQUIRE(wo >= 0 && bo >= 0 && wo + static_cast<int64_t>(fi) * fo <= n_dense && bo + fo <= n_dense,
+               "train_step_fused: layer %d lies outside the %lld dense variables", i, (long long)n_dense);
+    a.l[i].w_off = wo; a.l[i].b_off = bo; a.l[i].fan_in = fi; a.l[i].fan_out = fo;
+  }
+  MI_REQUIRE(n_layers == 0 || widths[0] == F * E, "train_step_fused: widths[0]=%d, the %d input columns expected",
+             n_layers ? widths[0] : 0, F * E);
+  const size_t need = mi_train_step_fused_workspace_bytes(B, F, E, n_dense);
+  if (workspace_bytes < need || !workspace) {
+    mi::set_error("train_step_fused: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    return MI_ERR_WORKSPACE;
+  }
+  MI_REQUIRE(mi::aligned16(workspace), "train_step_fused: workspace (16-byte aligned)");
+
+  // LDS plan of the batch workgroup
+  const int iB = static_cast<int>(B);
+  int64_t o = align4(B * F);
+  a.o_sumv = static_cast<int32_t>(o); o += align4(B * E);
+  a.o_tq = static_cast<int32_t>(o); o += align4(B * E);
+  a.o_lin = static_cast<int32_t>(o); o += align4(B);
+  a.o_dl = static_cast<int32_t>(o); o += align4(B);
+  for (int i = 0; i < n_layers; ++i) { a.l[i].out_off = static_cast<int32_t>(o); o += align4(B * widths[i + 1]); }
+  const int64_t dcat = n_layers ? align4(B * F * E) : 0;
+  a.gdense = static_cast<float*>(workspace);
+  a.dcat_ws = nullptr;
+  a.o_dcat = static_cast<int32_t>(o);
+  if (sizeof(float) * static_cast<size_t>(o + dcat) <= kMaxLds) o += dcat;
+  else a.dcat_ws = a.gdense + align4(n_dense);
+  size_t lds = sizeof(float) * static_cast<size_t>(o);
+  if (lds > kMaxLds) return unsupported("train_step_fused: %zu bytes of LDS for B=%d F=%d E=%d and these widths", lds, iB, F, E);
+  const size_t bitmap = sizeof(uint32_t) * static_cast<size_t>((R + 31) / 32);
+  if (bitmap > lds) lds = bitmap;
+
+  a.table = emb ? table : nullptr; a.tm = emb ? t_m : nullptr; a.tv = emb ? t_v : nullptr;
+  a.lin_w = use_linear ? lin_w : nullptr; a.lm = use_linear ? l_m : nullptr; a.lv = use_linear ? l_v : nullptr;
+  a.last_step = last_step; a.field_off = field_off; a.ids = ids; a.labels = labels;
+  a.dense = dense; a.dm = d_m; a.dv = d_v; a.logits = logits; a.loss = loss;
+  a.ts = table_stride ? table_stride : E; a.R = R; a.lin_bias_off = lin_bias_off; a.seed = seed;
+  a.B = iB; a.F = F; a.E = E; a.ls = lin_stride; a.act = activation; a.n_layers = n_layers;
+  a.use_linear = use_linear != 0; a.use_fm = use_fm != 0; a.step = step;
+  a.keep = keep_prob; a.scale = scale; a.hp = make_hp(hp);
+
+  int blocks = sweep_blocks;
+  if (blocks == 0) {
+    const int64_t items = R * (emb ? E / 4 : 1);
+    const int64_t want = mi::ceil_div(items, static_cast<int64_t>(kThreads) * kRowsInFlight);
+    blocks = static_cast<int>(want < 1 ? 1 : (want > 128 ? 128 : want));
+  }
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&train_fused_k),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    MI_REQUIRE(e == hipSuccess, "train_step_fused: LDS of %zu bytes: %s", lds, hipGetErrorString(e));
+  }
+  train_fused_k<<<dim3(1 + blocks), dim3(kThreads), lds, mi::as_stream(stream)>>>(a);
+  MI_CHECK_LAUNCH("train_step_fused");
+  return MI_OK;
+}
+
+}  // extern "C"

@@ -147,6 +147,10 @@ SIGNATURES = {
     "mi_predict_fused_workspace_bytes": (_sz, [_i64, _i32]),
     "mi_predict_fused": (_i32, [_p, _i64, _p, _i32, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32,
                                 _i32, _i32, _i64, _i64, _i64, _u64, _p, _p, _p, _p, _p, _sz, _p]),
+    "mi_train_step_fused_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
+    "mi_train_step_fused": (_i32, [_p, _p, _p, _i64, _p, _p, _p, _i32, _p, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _p, _i64,
+                                   _p, _p, _i32, _i32, _i32, _i32, _i32, _i64, _f32, _u64, _f32, _i32, C.POINTER(OptHparams),
+                                   _p, _p, _i32, _p, _sz, _p]),
 }
 
 _lib = None

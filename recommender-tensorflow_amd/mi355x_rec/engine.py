@@ -1144,6 +1144,107 @@ class DeepFM:
                                 out["logits"], out["logistic"], out["probabilities"], out["class_ids"], None, 0)
         return out
 
+    # ------------------------------------------------------------------ training small models: the step as one launch
+    FUSED_STEP_LIMIT_BATCH = 128     # the limits of mi_train_step_fused (include/mi355x_rec.h)
+    FUSED_STEP_LIMIT_FIELDS = 32
+    FUSED_STEP_LIMIT_EMB = 16
+    FUSED_STEP_LIMIT_HIDDEN_LAYERS = 3
+    FUSED_STEP_LIMIT_WIDTH = 64
+    FUSED_STEP_LIMIT_CONCAT = 16384  # B * F * E
+    FUSED_STEP_LIMIT_ROWS = 1 << 18
+    FUSED_STEP_SWEEP_BLOCKS = 0    # workgroups of the all-rows sweep; 0: the library's choice (tests: results do not depend on it)
+
+    def _fused_step_limit(self, B):
+        """What keeps mi_train_step_fused from running a batch of B examples on this model, as text, or None."""
+        if self.shard is not None:
+            return "row-sharded tables (the fused step runs on one GPU)"
+        if self.opt.name != "Adam" or self.lin_opt is not None:
+            return "optimizer %s%s (Adam for every variable, one schedule)" % (
+                self.opt.name, "" if self.lin_opt is None else " with linear_optimizer %s" % self.lin_opt.name)
+        if self.n_numeric:
+            return "%d numeric columns (categorical columns only)" % self.n_numeric
+        if self.field_dims is not None or self.wide_fields is not None:
+            return "field_dims / wide_fields (the canned estimators' columns)"
+        if not 1 <= self.F <= self.FUSED_STEP_LIMIT_FIELDS:
+            return "%d categorical fields (1 to %d)" % (self.F, self.FUSED_STEP_LIMIT_FIELDS)
+        if self.use_emb and self.E > self.FUSED_STEP_LIMIT_EMB:
+            return "embedding size %d (at most %d)" % (self.E, self.FUSED_STEP_LIMIT_EMB)
+        if len(self.hidden) > self.FUSED_STEP_LIMIT_HIDDEN_LAYERS:
+            return "%d hidden layers (at most %d)" % (len(self.hidden), self.FUSED_STEP_LIMIT_HIDDEN_LAYERS)
+        if self.hidden and max(self.hidden) > self.FUSED_STEP_LIMIT_WIDTH:
+            return "a hidden layer of %d units (at most %d)" % (max(self.hidden), self.FUSED_STEP_LIMIT_WIDTH)
+        if self.R > self.FUSED_STEP_LIMIT_ROWS:
+            return "%d table rows (at most %d)" % (self.R, self.FUSED_STEP_LIMIT_ROWS)
+        if not 1 <= B <= self.FUSED_STEP_LIMIT_BATCH:
+            return "a batch of %d examples (1 to %d)" % (B, self.FUSED_STEP_LIMIT_BATCH)
+        E = self.E if self.use_emb else 4
+        if B * self.F * E > self.FUSED_STEP_LIMIT_CONCAT:
+            return "B * F * E = %d (at most %d)" % (B * self.F * E, self.FUSED_STEP_LIMIT_CONCAT)
+        return None
+
+    def fused_step_ok(self, B):
+        """Can fused_train_step run a batch of B examples on this model?"""
+        return self._fused_step_limit(int(B)) is None
+
+    # params["fused_step"] = "auto" (model.run_batch): the largest measured batch, per-row optimizer state (table + wide
+    # records) and MLP parameter block at which the fused step's median lay below the hipGraph replay's 10th percentile
+    # (profiles/fused_step_latency.md: B = 32 wins and 128 loses; 16.6 MB of rows still wins; the default model's 7.9 KB
+    # of MLP parameters win and the 131 KB of E 16, [64, 64, 32] lose — the crossovers were not measured more finely)
+    FUSED_STEP_MAX_BATCH = 32
+    FUSED_STEP_MAX_STATE_BYTES = 16 << 20
+    FUSED_STEP_MAX_WEIGHT_BYTES = 8 << 10
+
+    def state_bytes(self):
+        """Bytes of per-row state the all-rows sweep of a fused step walks: table records + wide records."""
+        return self.R * (self.ts * 4 * (self.table is not None) + 16 * (self.lin_state is not None))
+
+    def fused_step_auto(self, B):
+        """Is the fused step the faster choice for this model and batch size (the measured thresholds above)?"""
+        return (self.fused_step_ok(B) and B <= self.FUSED_STEP_MAX_BATCH and self.state_bytes() <= self.FUSED_STEP_MAX_STATE_BYTES
+                and 4 * self.dnn_end <= self.FUSED_STEP_MAX_WEIGHT_BYTES)
+
+    def fused_train_step(self, ids, labels):
+        """One optimizer.minimize(loss) as ONE launch (mi_train_step_fused): returns (loss [1], logits [B]) device tensors,
+        no host sync.  The same step as train_step — same dropout masks, same Adam schedule — with TF's whole-table Adam
+        sweep done literally: after it every row is current (no catch-up is owed).  May follow and be followed by
+        train_step / graph_train_step / loss / predict_fused / top_k / state_dict in any order."""
+        B = int(ids.shape[0])
+        why = self._fused_step_limit(B)
+        if why is not None:
+            raise ValueError("fused_train_step: the model has %s; use train_step" % why)
+        if labels is None:
+            raise ValueError("fused_train_step: labels")
+        self._prep(ids, labels, None)
+        self.finalize_rows()                      # (a no-op after a fused step)
+        k = self.k
+        tabs = getattr(self, "_fused_step_tabs", None)
+        if tabs is None:
+            layer_off = torch.tensor([o for (ko, bo, _, _) in self.layers for o in (ko, bo)] or [0], dtype=torch.int64)
+            widths = torch.tensor(([self.layers[0][2]] + [h for (_, _, _, h) in self.layers]) if self.layers else [0],
+                                  dtype=torch.int32)
+            tabs = self._fused_step_tabs = (layer_off, widths, {})
+        layer_off, widths, per_b = tabs
+        bufs = per_b.get(B)
+        if bufs is None:
+            E = self.E if self.use_emb else 4
+            nbytes = int(k.query("mi_train_step_fused_workspace_bytes", B, self.F, E, self.P))
+            bufs = per_b[B] = (torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device),
+                               torch.empty(1, dtype=torch.float32, device=self.device),
+                               torch.empty(B, dtype=torch.float32, device=self.device))
+        ws, loss, logits = bufs
+        step = self.step + 1
+        hp = self.opt.hparams(self.sched.lr_t(step))
+        scale = np.float32(1.0 / B) if self.reduction == "mean" else np.float32(1.0)
+        keep = 1.0 - self.dropout if self.dropout > 0 else 1.0
+        k.mi_train_step_fused(self.table, self.t_s0, self.t_s1, self.ts, self.lin_w, self.l_s0, self.l_s1, self.ls,
+                              self.last_step, self.field_off, self.R, ids, labels, B, self.F, self.E, self.dense, self.d_s0,
+                              self.d_s1, self.P, layer_off, widths, len(self.layers), self.act, int(self.use_linear),
+                              int(self.use_mf), int(self.use_dnn), self.lin_bias_off, float(keep), self._layer_seed(0),
+                              float(scale), step, hp, logits, loss, int(self.FUSED_STEP_SWEEP_BLOCKS), ws, ws.numel())
+        self.step = step
+        self._final_step = step
+        return loss, logits
+
     # ------------------------------------------------------------------ top-K recommendation
     TOP_K_MAX = 256
 

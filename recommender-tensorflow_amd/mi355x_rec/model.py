@@ -135,6 +135,21 @@ def run_batch(features, labels, mode, params, make_engine):
         # the whole step as ONE hipGraph launch — bit for bit the eager step (tests/test_hip_model.py) — where a step is
         # launch-bound: "auto" (the default) takes it for batches of <= GRAPH_AUTO_MAX_BATCH examples on a single GPU
         # (trainers.deep_fm at the reference's defaults, B = 32: 2-2.5x the eager rate), "on" / True always, "off" never
+        # small models: the whole step as ONE kernel launch (engine.fused_train_step) — "off" (the default) never, "on"
+        # whenever the model and batch are inside the kernel's scope (outside it: an error, not a fallback), "auto" where
+        # it was measured to win.  A step whose layer summaries are recorded runs the layered path (the fused kernel
+        # keeps no activations in memory); the next fused step carries on from it.
+        fs = params.get("fused_step", "off")
+        if fs not in ("off", "on", "auto"):
+            raise ValueError("fused_step must be 'off', 'on' or 'auto'")
+        if fs != "off":
+            B = ids.shape[0]
+            ok = eng.fused_step_ok(B)
+            if fs == "on" and not ok:
+                raise ValueError("fused_step=on: the model has %s" % eng._fused_step_limit(B))
+            if ok and (fs == "on" or eng.fused_step_auto(B)) and not getattr(eng, "summaries_next", False):
+                loss, logits = eng.fused_train_step(ids, y)
+                return EstimatorSpec(mode, predictions=None, loss=rescale(loss), train_op=eng.step)
         hg = params.get("hip_graph", "auto")
         graph = hg in (True, "on") or (hg == "auto" and ids.shape[0] <= GRAPH_AUTO_MAX_BATCH)
         if getattr(eng, "summaries_next", False) and ids.shape[0] >= getattr(eng, "TOP_FUSED_MIN_BATCH", 1 << 62):

@@ -28,6 +28,10 @@ _COMMON = [
     ("--hip-graph", dict(nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                          help="replay the train step as one hipGraph launch (bit for bit the eager step): auto = for batches of at most "
                               "1,024 examples on one GPU, where a step is launch-bound (default: %(default)s)")),
+    ("--fused-step", dict(nargs="?", const="on", default="off", choices=["off", "on", "auto"],
+                          help="small DeepFM models (categorical columns, Adam, at most 128 examples, 3 hidden layers of 64 units): "
+                               "run the whole train step as ONE kernel launch — on: always (an error if the model is outside the "
+                               "kernel's scope), auto: where it was measured ahead of the hipGraph replay (default: %(default)s)")),
     ("--catchup", dict(choices=["exact", "bounded"], default="bounded",
                        help="Adam only: how the steps a table row sat out are replayed when it is next read — bounded: every variable "
                             "within 3 ulp + 2e-6 of the movement the replay covers (98.7 %% of them within 1e-7 relative of TensorFlow's "
@@ -111,6 +115,7 @@ def run(args, make_estimator):
     estimator.params["_shard"] = shard
     estimator.params["hip_graph"] = getattr(args, "hip_graph", "auto")
     estimator.params["catchup"] = getattr(args, "catchup", "bounded")
+    estimator.params["fused_step"] = getattr(args, "fused_step", "off")
     train_spec = get_train_spec(get_input_fn(args.train_csv, batch_size=args.batch_size, seed=rank if world > 1 else None),
                                 args.train_steps)
     eval_spec = get_eval_spec(get_input_fn(args.test_csv, ModeKeys.EVAL, batch_size=args.batch_size),

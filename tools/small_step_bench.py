@@ -1,22 +1,110 @@
 #!/usr/bin/env python3
-"""Step latency of the reference's default configuration (trainers.deep_fm: E=4, hidden [16,16], B=32,
-the 26 MovieLens fields) — launch-bound, not roofline-bound: reports us per train step."""
-import os, sys, time
+"""Step latency of small models — the reference's default configuration (trainers.deep_fm: E=4, hidden [16,16], B=32,
+the 26 MovieLens fields) and its neighbours — launch-bound, not roofline-bound: us per train step for the three ways
+the engine runs one step on one GPU:
+
+    eager (one launch per kernel)      DeepFM.train_step
+    hipGraph replay                    DeepFM.graph_train_step
+    fused (one launch)                 DeepFM.fused_train_step   (where the model and batch are inside its scope)
+
+Protocol: the three paths run in ONE process on three engines with identical initial state; every
+path walks the same ring of ROTATE different batches (with one repeated batch no row ever sits a step out, and the
+catch-up / sweep would have nothing to do); a block is STEPS consecutive steps of one path between two device
+synchronisations, timed on the host clock (the host's cost is part of what a user pays); blocks of the three paths
+alternate; per path the median and the 10th / 90th percentile over BLOCKS blocks are reported.
+
+    python tools/small_step_bench.py [--json FILE] [--blocks N] [--steps N]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "recommender-tensorflow_amd"))
+import numpy as np
 import torch
 from mi355x_rec.engine import DeepFM, OptimizerSpec
-VOCAB = [2] * 19 + [1000, 2000, 50, 1000, 7, 8, 3]
-for B in (32, 1024):
-    m = DeepFM(VOCAB, embedding_size=4, hidden_units=[16, 16], dropout=0.1, optimizer=OptimizerSpec("Adam", 0.001))
-    g = torch.Generator(device="cuda"); g.manual_seed(0)
-    m.init_variables(g, lin_scale=1e-3)
-    ids = torch.stack([torch.randint(0, v, (B,), device="cuda", generator=g) for v in VOCAB], 1).to(torch.int32).contiguous()
-    y = (torch.rand(B, device="cuda", generator=g) < 0.3).to(torch.uint8)
-    for name, step in (("eager (one launch per kernel)", m.train_step), ("hipGraph replay", m.graph_train_step)):
-        for _ in range(20): step(ids, y)
-        torch.cuda.synchronize(); t0 = time.perf_counter()
-        n = 300
-        for _ in range(n): step(ids, y)
-        torch.cuda.synchronize(); dt = time.perf_counter() - t0
-        print("B=%5d  %-30s %.1f us/step  (%.0f steps/s, %.0f examples/s)" % (B, name, dt / n * 1e6, n / dt, n * B / dt))
+
+ROTATE = 8
+
+
+def vocab(big=1000):
+    """the 26 MovieLens columns; `big` scales the three hash-bucket columns (user, item, zipcode: 1000 / 2000 / 1000)"""
+    return [2] * 19 + [big, 2 * big, 50, big, 7, 8, 3]
+
+
+CASES = [
+    # name, vocab, E, hidden, batch sizes
+    ("default", vocab(), 4, [16, 16], (1, 32, 128, 1024)),
+    ("top of the envelope", vocab(), 16, [64, 64, 32], (32,)),
+    ("default, 8x the rows", vocab(8000), 4, [16, 16], (32,)),
+    ("default, 32x the rows", vocab(32000), 4, [16, 16], (32,)),
+    ("default, 64x the rows", vocab(65000), 4, [16, 16], (32,)),
+]
+
+
+def engines(voc, E, hidden, n):
+    out = []
+    for _ in range(n):
+        m = DeepFM(voc, embedding_size=E, hidden_units=hidden, dropout=0.1, optimizer=OptimizerSpec("Adam", 0.001))
+        g = torch.Generator(device="cuda")
+        g.manual_seed(0)
+        m.init_variables(g, lin_scale=1e-3)
+        out.append(m)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--json", default=None, help="also write every cell to this file")
+    ap.add_argument("--blocks", type=int, default=7)
+    ap.add_argument("--steps", type=int, default=200)
+    args = ap.parse_args()
+    cells = []
+    for name, voc, E, hidden, batches in CASES:
+        for B in batches:
+            eager, graph, fused = engines(voc, E, hidden, 3)
+            g = torch.Generator(device="cuda")
+            g.manual_seed(1)
+            ring = []
+            for _ in range(ROTATE):
+                ids = torch.stack([torch.randint(0, v, (B,), device="cuda", generator=g) for v in voc], 1).to(torch.int32).contiguous()
+                ring.append((ids, (torch.rand(B, device="cuda", generator=g) < 0.3).to(torch.uint8)))
+            paths = [("eager (one launch per kernel)", eager.train_step), ("hipGraph replay", graph.graph_train_step)]
+            if fused.fused_step_ok(B):
+                paths.append(("fused (one launch)", fused.fused_train_step))
+
+            def block(step, n):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(n):
+                    step(*ring[i % ROTATE])
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / n * 1e6
+
+            for _, step in paths:                              # warm-up: every shape, the graph's capture, the ring once round
+                block(step, 3 * ROTATE)
+            times = {p: [] for p, _ in paths}
+            for _ in range(args.blocks):
+                for p, step in paths:
+                    times[p].append(block(step, args.steps))
+            state = fused.state_bytes()
+            for p, _ in paths:
+                t = np.asarray(times[p])
+                cell = {"case": name, "E": E, "hidden": hidden, "B": B, "rows": fused.R, "state_bytes": state, "path": p,
+                        "us_median": float(np.median(t)), "us_p10": float(np.percentile(t, 10)),
+                        "us_p90": float(np.percentile(t, 90)), "blocks": args.blocks, "steps_per_block": args.steps}
+                cells.append(cell)
+                print("%-22s E=%2d %-13s B=%5d rows=%6d  %-30s %7.1f us/step  (p10 %.1f, p90 %.1f; %.0f steps/s)" % (
+                    name, E, hidden, B, fused.R, p, cell["us_median"], cell["us_p10"], cell["us_p90"], 1e6 / cell["us_median"]),
+                    flush=True)
+            del eager, graph, fused
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(cells, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
