@@ -774,6 +774,69 @@ int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_
                             float* logits, float* loss, int32_t sweep_blocks, void* workspace, size_t workspace_bytes,
                             mi_stream_t stream);
 
+/* ---- training a population of small models: M steps of M models as one launch (csrc/train_fused.hip) ------------------
+ * What trainers/deep_fm.py:36-125 builds and model_utils.py:57-72 minimises, run M times (a grid of hyper-parameters, seeds,
+ * folds): M INDEPENDENT models of mi_train_step_fused's scope take one step each in ONE kernel, grid (1 + G, M) — row y of
+ * the grid is member y's batch workgroup and its G sweep workgroups, running the device code of mi_train_step_fused.
+ * Member i's results are bit for bit those of mi_train_step_fused on it alone.  A member's workgroups touch only that
+ * member's buffers; no workgroup reads what another writes in the launch and none waits for another.
+ *
+ * mi_fused_member_t: the per-model arguments of mi_train_step_fused (same meaning, same limits; layer_off / widths on the
+ *   host, read by mi_train_group_plan only; hp.lr_t is ignored) and
+ *   lr_table [lr_table_len] (device): lr_t of global step s at [s] (index 0 unused) — the member's Adam schedule;
+ *   seed_base: the dropout seed of a step is seed_base + step * 1000003 (mod 2^64), hidden layer i adds 7919 i;
+ *   workspace: mi_train_step_fused_workspace_bytes(B, F, E, n_dense) bytes of the member's own, 16-byte aligned.
+ * Members may differ in everything above; they share B, F and field_off [F] (one set of feature columns). */
+#define MI_FUSED_GROUP_MAX_MEMBERS 1024 /* the grid is at most (1 + 1024) x 1024 workgroups */
+typedef struct mi_fused_member {
+  float* table; float* t_m; float* t_v;
+  int64_t table_stride;
+  float* lin_w; float* l_m; float* l_v;
+  int32_t* last_step;
+  int64_t R;
+  float* dense; float* d_m; float* d_v;
+  int64_t n_dense;
+  const int64_t* layer_off;
+  const int32_t* widths;
+  int64_t lin_bias_off;
+  const float* lr_table;
+  int64_t lr_table_len;
+  uint64_t seed_base;
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t lin_stride, E, n_layers, activation, use_linear, use_fm, use_dnn;
+  float keep_prob, scale;
+  mi_opt_hparams hp;
+} mi_fused_member_t;
+
+/* What mi_train_group_plan leaves on the host for mi_train_group_step (caller-owned; treat as opaque). */
+typedef struct mi_fused_group_plan {
+  void* device_table;
+  uint64_t magic;
+  int32_t n_members, B, F, sweep_blocks, max_step;
+  uint32_t lds_bytes;
+} mi_fused_group_plan_t;
+
+/* mi_train_group_plan: validates every member with the checks and messages of mi_train_step_fused (prefixed
+ * "member i:"), refuses two members that share a state or workspace pointer, then writes the members' descriptions into
+ * device_table (mi_train_group_plan_bytes(n_members) bytes of device memory, 16-byte aligned; the copy has completed when
+ * the call returns) and *plan.  The plan holds the members' pointers: make a new one when a buffer, a schedule table or B
+ * changes.  n_members in [1, MI_FUSED_GROUP_MAX_MEMBERS] (MI_ERR_INVALID below, MI_ERR_UNSUPPORTED above).
+ *
+ * mi_train_group_step: one launch, no host-to-device copy, no synchronisation.  ids [B, F] / labels [B] for all members
+ * (member stride 0) or one batch per member ([M, B, F] / [M, B], member stride B F / B); step: the global step AFTER the
+ * call, the same for every member (1 <= step < every lr_table_len); member i's lr_t = lr_table[step] and its dropout seed
+ * are formed in the kernel.  Results: logits [M, B], loss [M]; each member as after mi_train_step_fused (PRECONDITION as
+ * there: every row of every member current).  Dynamic LDS is the largest member's; sweep_blocks (G; 0 = the built-in
+ * choice: the largest member's, lowered until (1 + G) M <= 65536) is one value for the launch and no result depends on it.
+ * A refused call launches nothing and writes nothing (mi_train_group_plan: neither device_table nor *plan). */
+size_t mi_train_group_plan_bytes(int32_t n_members);
+int32_t mi_train_group_plan(const mi_fused_member_t* members, int32_t n_members, int64_t B, int32_t F, const int64_t* field_off,
+                            void* device_table, size_t device_table_bytes, mi_fused_group_plan_t* plan, mi_stream_t stream);
+int32_t mi_train_group_step(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids, int64_t ids_member_stride,
+                            const uint8_t* labels, int64_t labels_member_stride, int64_t B, int32_t step, float* logits,
+                            float* loss, int32_t sweep_blocks, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

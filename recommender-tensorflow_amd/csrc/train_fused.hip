@@ -23,6 +23,13 @@
 //   writes in this launch and none waits for another — no flags, no grid barrier, no float atomics to global memory.
 //   Results do not depend on G.
 //
+//   train_fused_group_k   M independent models, one step each, in ONE launch (mi_train_group_step): grid (1 + G, M),
+//     blockIdx.y = the member, blockIdx.x == 0 its batch workgroup, the others its sweep workgroups.  A workgroup copies
+//     its member's Args from the device table mi_train_group_plan wrote, fills in what changes per step (ids, labels,
+//     outputs, step, lr_t = lr_table[step], seed = seed_base + step 1000003) and runs batch_block / sweep_block below:
+//     the arithmetic has this one definition, so a member's bits are those of train_fused_k on it alone.  A member's
+//     workgroups touch only that member's buffers.
+//
 // Arithmetic: fp32 throughout; compiled with -ffp-contract=off (the update rules and the FM term are written one
 // rounding per operation); the MLP's dot products use explicit fmaf.
 #include "common.h"
@@ -397,6 +404,51 @@ __global__ __launch_bounds__(kThreads) void train_fused_k(const Args p) {
   batch_block(p, lds, layers, red);
 }
 
+// one member of a population: its Args as mi_train_group_plan validated them (ids / labels / logits / loss / step / seed /
+// hp.lr_t are filled in by the kernel), its Adam schedule table and the step-free part of its dropout seed
+struct Member {
+  Args a;
+  const float* lr_table;                // lr_t of step s at [s], lr_len entries
+  uint64_t seed_base;
+  int64_t lr_len;
+};
+static_assert(sizeof(Args) % sizeof(uint32_t) == 0 && sizeof(Member) % 8 == 0, "Member is copied word by word");
+
+__global__ __launch_bounds__(kThreads) void train_fused_group_k(const Member* __restrict__ members, const int32_t* __restrict__ ids,
+                                                                int64_t ids_stride, const uint8_t* __restrict__ labels,
+                                                                int64_t labels_stride, float* __restrict__ logits,
+                                                                float* __restrict__ loss, int32_t step) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  __shared__ Args sp;
+  __shared__ Layer layers[kMaxLayers];
+  __shared__ float red[2][kThreads / 64];
+  const int y = blockIdx.y;
+  const Member* me = members + y;
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&me->a);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(&sp);
+    for (int i = threadIdx.x; i < static_cast<int>(sizeof(Args) / sizeof(uint32_t)); i += kThreads) dst[i] = src[i];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int64_t s = step < me->lr_len ? step : me->lr_len - 1;           // (mi_train_group_step checked it: stay inside)
+    sp.ids = ids + y * ids_stride;
+    sp.labels = labels + y * labels_stride;
+    sp.logits = logits + static_cast<int64_t>(y) * sp.B;
+    sp.loss = loss + y;
+    sp.step = step;
+    sp.hp.lr_t = me->lr_table[s];
+    sp.seed = me->seed_base + static_cast<uint64_t>(step) * 1000003ull;    // engine._layer_seed(0) of this step
+  }
+  if (threadIdx.x < kMaxLayers) layers[threadIdx.x] = sp.l[threadIdx.x];
+  __syncthreads();
+  if (blockIdx.x) {
+    sweep_block(sp, reinterpret_cast<uint32_t*>(lds));
+    return;
+  }
+  batch_block(sp, lds, layers, red);
+}
+
 int32_t unsupported(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 int32_t unsupported(const char* fmt, ...) {
   char buf[512];
@@ -417,23 +469,21 @@ int64_t batch_lds_floats(int64_t B, int32_t F, int32_t E, const int32_t* widths,
   return n;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t mi_train_step_fused_workspace_bytes(int64_t B, int32_t F, int32_t E, int64_t n_dense) {
+size_t workspace_bytes_of(int64_t B, int32_t F, int32_t E, int64_t n_dense) {
   if (B < 0 || F < 0 || E < 0 || n_dense < 0) return 0;
   return sizeof(float) * static_cast<size_t>(align4(n_dense) + align4(B * F * E));
 }
 
-int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_stride, float* lin_w, float* l_m, float* l_v,
-                            int32_t lin_stride, int32_t* last_step, const int64_t* field_off, int64_t R, const int32_t* ids,
-                            const uint8_t* labels, int64_t B, int32_t F, int32_t E, float* dense, float* d_m, float* d_v,
-                            int64_t n_dense, const int64_t* layer_off, const int32_t* widths, int32_t n_layers,
-                            int32_t activation, int32_t use_linear, int32_t use_fm, int32_t use_dnn, int64_t lin_bias_off,
-                            float keep_prob, uint64_t seed, float scale, int32_t step, const mi_opt_hparams* hp,
-                            float* logits, float* loss, int32_t sweep_blocks, void* workspace, size_t workspace_bytes,
-                            mi_stream_t stream) {
+// The checks of one model, in mi_train_step_fused's order, and its Args (everything but ids / labels / logits / loss / step /
+// seed / lr_t, which the caller fills in; have_batch / have_outputs: the caller holds those pointers — a plan has none yet),
+// the dynamic LDS of its workgroups and the built-in number of sweep workgroups.  Writes nothing but `a`.
+int32_t plan_model(float* table, float* t_m, float* t_v, int64_t table_stride, float* lin_w, float* l_m, float* l_v,
+                   int32_t lin_stride, int32_t* last_step, const int64_t* field_off, int64_t R, int64_t B, int32_t F, int32_t E,
+                   float* dense, float* d_m, float* d_v, int64_t n_dense, const int64_t* layer_off, const int32_t* widths,
+                   int32_t n_layers, int32_t activation, int32_t use_linear, int32_t use_fm, int32_t use_dnn,
+                   int64_t lin_bias_off, float keep_prob, float scale, int32_t step, const mi_opt_hparams* hp, bool have_batch,
+                   bool have_outputs, int32_t sweep_blocks, void* workspace, size_t workspace_bytes, Args& a, size_t& lds_out,
+                   int& blocks_out) {
   MI_REQUIRE(hp, "train_step_fused: hp");
   if (hp->kind != MI_OPT_ADAM) return unsupported("train_step_fused: optimizer kind %d (Adam only)", hp->kind);
   MI_REQUIRE(use_linear || use_fm || use_dnn, "train_step_fused: no part of the model is switched on");
@@ -451,8 +501,8 @@ int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_
   if (R < 1 || R > kMaxRows) return unsupported("train_step_fused: R=%lld table rows (1 to %lld)", (long long)R, (long long)kMaxRows);
   if (sweep_blocks < 0 || sweep_blocks > kMaxSweepBlocks)
     return unsupported("train_step_fused: sweep_blocks=%d (0 = the built-in choice, at most %d)", sweep_blocks, kMaxSweepBlocks);
-  MI_REQUIRE(field_off && ids && labels && last_step, "train_step_fused: field_off / ids / labels / last_step");
-  MI_REQUIRE(logits && loss, "train_step_fused: logits / loss");
+  MI_REQUIRE(field_off && have_batch && last_step, "train_step_fused: field_off / ids / labels / last_step");
+  MI_REQUIRE(have_outputs, "train_step_fused: logits / loss");
   MI_REQUIRE(!emb || (table && t_m && t_v && mi::aligned16(table) && mi::aligned16(t_m) && mi::aligned16(t_v)),
              "train_step_fused: table / t_m / t_v (16-byte aligned)");
   MI_REQUIRE(table_stride == 0 || (table_stride >= E && (table_stride & 3) == 0),
@@ -465,7 +515,7 @@ int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_
   if (n_layers > kMaxLayers)
     return unsupported("train_step_fused: %d hidden layers (at most %d)", n_layers - 1, kMaxHidden);
   MI_REQUIRE(n_layers == 0 || (layer_off && widths), "train_step_fused: layer_off / widths");
-  Args a{};
+  a = Args{};
   for (int i = 0; i < n_layers; ++i) {
     const int fi = widths[i], fo = widths[i + 1];
     MI_REQUIRE(fi >= 1 && fo >= 1, "train_step_fused: width %d -> %d", fi, fo);
@@ -478,7 +528,7 @@ int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_
   }
   MI_REQUIRE(n_layers == 0 || widths[0] == F * E, "train_step_fused: widths[0]=%d, the %d input columns expected",
              n_layers ? widths[0] : 0, F * E);
-  const size_t need = mi_train_step_fused_workspace_bytes(B, F, E, n_dense);
+  const size_t need = workspace_bytes_of(B, F, E, n_dense);
   if (workspace_bytes < need || !workspace) {
     mi::set_error("train_step_fused: workspace of %zu bytes, %zu needed", workspace_bytes, need);
     return MI_ERR_WORKSPACE;
@@ -506,26 +556,175 @@ int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_
 
   a.table = emb ? table : nullptr; a.tm = emb ? t_m : nullptr; a.tv = emb ? t_v : nullptr;
   a.lin_w = use_linear ? lin_w : nullptr; a.lm = use_linear ? l_m : nullptr; a.lv = use_linear ? l_v : nullptr;
-  a.last_step = last_step; a.field_off = field_off; a.ids = ids; a.labels = labels;
-  a.dense = dense; a.dm = d_m; a.dv = d_v; a.logits = logits; a.loss = loss;
-  a.ts = table_stride ? table_stride : E; a.R = R; a.lin_bias_off = lin_bias_off; a.seed = seed;
+  a.last_step = last_step; a.field_off = field_off;
+  a.dense = dense; a.dm = d_m; a.dv = d_v;
+  a.ts = table_stride ? table_stride : E; a.R = R; a.lin_bias_off = lin_bias_off;
   a.B = iB; a.F = F; a.E = E; a.ls = lin_stride; a.act = activation; a.n_layers = n_layers;
-  a.use_linear = use_linear != 0; a.use_fm = use_fm != 0; a.step = step;
+  a.use_linear = use_linear != 0; a.use_fm = use_fm != 0;
   a.keep = keep_prob; a.scale = scale; a.hp = make_hp(hp);
 
-  int blocks = sweep_blocks;
-  if (blocks == 0) {
-    const int64_t items = R * (emb ? E / 4 : 1);
-    const int64_t want = mi::ceil_div(items, static_cast<int64_t>(kThreads) * kRowsInFlight);
-    blocks = static_cast<int>(want < 1 ? 1 : (want > 128 ? 128 : want));
-  }
+  const int64_t items = R * (emb ? E / 4 : 1);
+  const int64_t want = mi::ceil_div(items, static_cast<int64_t>(kThreads) * kRowsInFlight);
+  blocks_out = sweep_blocks ? sweep_blocks : static_cast<int>(want < 1 ? 1 : (want > 128 ? 128 : want));
+  lds_out = lds;
+  return MI_OK;
+}
+
+template <typename K>
+int32_t raise_lds(K kernel, size_t lds, const char* what) {
   if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&train_fused_k),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    MI_REQUIRE(e == hipSuccess, "train_step_fused: LDS of %zu bytes: %s", lds, hipGetErrorString(e));
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             static_cast<int>(lds));
+    MI_REQUIRE(e == hipSuccess, "%s: LDS of %zu bytes: %s", what, lds, hipGetErrorString(e));
   }
+  return MI_OK;
+}
+
+constexpr uint64_t kPlanMagic = 0x6d695f67726f7570ull;   // "mi_group"
+constexpr int kGroupGridBlocks = 1 << 16;                // the built-in sweep_blocks keeps (1 + G) M at or below this
+
+}  // namespace
+
+extern "C" {
+
+size_t mi_train_step_fused_workspace_bytes(int64_t B, int32_t F, int32_t E, int64_t n_dense) {
+  return workspace_bytes_of(B, F, E, n_dense);
+}
+
+int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_stride, float* lin_w, float* l_m, float* l_v,
+                            int32_t lin_stride, int32_t* last_step, const int64_t* field_off, int64_t R, const int32_t* ids,
+                            const uint8_t* labels, int64_t B, int32_t F, int32_t E, float* dense, float* d_m, float* d_v,
+                            int64_t n_dense, const int64_t* layer_off, const int32_t* widths, int32_t n_layers,
+                            int32_t activation, int32_t use_linear, int32_t use_fm, int32_t use_dnn, int64_t lin_bias_off,
+                            float keep_prob, uint64_t seed, float scale, int32_t step, const mi_opt_hparams* hp,
+                            float* logits, float* loss, int32_t sweep_blocks, void* workspace, size_t workspace_bytes,
+                            mi_stream_t stream) {
+  Args a;
+  size_t lds = 0;
+  int blocks = 0;
+  const int32_t rc = plan_model(table, t_m, t_v, table_stride, lin_w, l_m, l_v, lin_stride, last_step, field_off, R, B, F, E,
+                                dense, d_m, d_v, n_dense, layer_off, widths, n_layers, activation, use_linear, use_fm, use_dnn,
+                                lin_bias_off, keep_prob, scale, step, hp, ids && labels, logits && loss, sweep_blocks, workspace,
+                                workspace_bytes, a, lds, blocks);
+  if (rc != MI_OK) return rc;
+  a.ids = ids; a.labels = labels; a.logits = logits; a.loss = loss; a.seed = seed; a.step = step;
+  const int32_t rl = raise_lds(&train_fused_k, lds, "train_step_fused");
+  if (rl != MI_OK) return rl;
   train_fused_k<<<dim3(1 + blocks), dim3(kThreads), lds, mi::as_stream(stream)>>>(a);
   MI_CHECK_LAUNCH("train_step_fused");
+  return MI_OK;
+}
+
+size_t mi_train_group_plan_bytes(int32_t n_members) {
+  return n_members < 0 ? 0 : sizeof(Member) * static_cast<size_t>(n_members);
+}
+
+int32_t mi_train_group_plan(const mi_fused_member_t* members, int32_t n_members, int64_t B, int32_t F, const int64_t* field_off,
+                            void* device_table, size_t device_table_bytes, mi_fused_group_plan_t* plan, mi_stream_t stream) {
+  MI_REQUIRE(plan, "train_group_plan: plan");
+  MI_REQUIRE(n_members >= 1, "train_group_plan: %d members (at least 1)", n_members);
+  if (n_members > MI_FUSED_GROUP_MAX_MEMBERS)
+    return unsupported("train_group_plan: %d members (at most %d in one launch)", n_members, MI_FUSED_GROUP_MAX_MEMBERS);
+  MI_REQUIRE(members, "train_group_plan: members");
+  const size_t need = mi_train_group_plan_bytes(n_members);
+  if (!device_table || device_table_bytes < need) {
+    mi::set_error("train_group_plan: device table of %zu bytes, %zu needed", device_table_bytes, need);
+    return MI_ERR_WORKSPACE;
+  }
+  MI_REQUIRE(mi::aligned16(device_table), "train_group_plan: device_table (16-byte aligned)");
+  Member* tab = static_cast<Member*>(malloc(need));
+  MI_REQUIRE(tab, "train_group_plan: out of host memory");
+  struct Owned { const void* p; int32_t member; };
+  Owned* owned = static_cast<Owned*>(malloc(sizeof(Owned) * 11 * static_cast<size_t>(n_members)));
+  if (!owned) { free(tab); mi::set_error("train_group_plan: out of host memory"); return MI_ERR_INVALID; }
+  size_t n_owned = 0, lds = 0;
+  int blocks = 1;
+  int64_t max_step = INT32_MAX;
+  int32_t rc = MI_OK;
+  for (int32_t i = 0; i < n_members && rc == MI_OK; ++i) {
+    const mi_fused_member_t& m = members[i];
+    size_t lds_i = 0;
+    int blocks_i = 0;
+    rc = plan_model(m.table, m.t_m, m.t_v, m.table_stride, m.lin_w, m.l_m, m.l_v, m.lin_stride, m.last_step, field_off, m.R, B, F,
+                    m.E, m.dense, m.d_m, m.d_v, m.n_dense, m.layer_off, m.widths, m.n_layers, m.activation, m.use_linear,
+                    m.use_fm, m.use_dnn, m.lin_bias_off, m.keep_prob, m.scale, 1, &m.hp, true, true, 0, m.workspace,
+                    m.workspace_bytes, tab[i].a, lds_i, blocks_i);
+    if (rc == MI_OK && (!m.lr_table || m.lr_table_len < 2)) {
+      mi::set_error("train_step_fused: lr_table of %lld entries (lr_t of step s at [s], s >= 1)", (long long)m.lr_table_len);
+      rc = MI_ERR_INVALID;
+    }
+    if (rc != MI_OK) {
+      char why[512];
+      snprintf(why, sizeof(why), "%s", mi_last_error());
+      mi::set_error("train_group_plan: member %d: %s", i, why);
+      break;
+    }
+    tab[i].lr_table = m.lr_table; tab[i].seed_base = m.seed_base; tab[i].lr_len = m.lr_table_len;
+    if (lds_i > lds) lds = lds_i;
+    if (blocks_i > blocks) blocks = blocks_i;
+    if (m.lr_table_len - 1 < max_step) max_step = m.lr_table_len - 1;
+    const void* own[11] = {tab[i].a.table, tab[i].a.tm, tab[i].a.tv, tab[i].a.lin_w, tab[i].a.lm, tab[i].a.lv, m.last_step,
+                           m.dense, m.d_m, m.d_v, m.workspace};
+    for (const void* p : own)
+      if (p) owned[n_owned++] = Owned{p, i};
+  }
+  if (rc == MI_OK) {
+    // two members (or two roles of one member) on the same memory: every pointer above is written by its member's workgroups
+    qsort(owned, n_owned, sizeof(Owned), [](const void* x, const void* y) {
+      const Owned* a = static_cast<const Owned*>(x);
+      const Owned* b = static_cast<const Owned*>(y);
+      return a->p < b->p ? -1 : (a->p > b->p ? 1 : (a->member < b->member ? -1 : (a->member > b->member ? 1 : 0)));
+    });
+    for (size_t j = 1; j < n_owned; ++j)
+      if (owned[j].p == owned[j - 1].p) {
+        mi::set_error("train_group_plan: member %d and member %d share a state or workspace pointer (%p): members are independent",
+                      owned[j - 1].member, owned[j].member, owned[j].p);
+        rc = MI_ERR_INVALID;
+        break;
+      }
+  }
+  if (rc == MI_OK) {
+    hipError_t e = hipMemcpyAsync(device_table, tab, need, hipMemcpyHostToDevice, mi::as_stream(stream));
+    if (e == hipSuccess) e = hipStreamSynchronize(mi::as_stream(stream));      // (tab is freed below)
+    if (e != hipSuccess) {
+      mi::set_error("train_group_plan: copying the member table: %s", hipGetErrorString(e));
+      rc = MI_ERR_LAUNCH;
+    }
+  }
+  free(owned);
+  free(tab);
+  if (rc != MI_OK) return rc;
+  while (blocks > 1 && static_cast<int64_t>(1 + blocks) * n_members > kGroupGridBlocks) --blocks;
+  plan->device_table = device_table; plan->n_members = n_members; plan->B = static_cast<int32_t>(B); plan->F = F;
+  plan->lds_bytes = static_cast<uint32_t>(lds); plan->sweep_blocks = blocks; plan->max_step = static_cast<int32_t>(max_step);
+  plan->magic = kPlanMagic;
+  return MI_OK;
+}
+
+int32_t mi_train_group_step(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids, int64_t ids_member_stride,
+                            const uint8_t* labels, int64_t labels_member_stride, int64_t B, int32_t step, float* logits,
+                            float* loss, int32_t sweep_blocks, mi_stream_t stream) {
+  MI_REQUIRE(plan && plan->magic == kPlanMagic && plan->device_table, "train_group_step: plan (not written by mi_train_group_plan)");
+  MI_REQUIRE(n_members == plan->n_members, "train_group_step: %d members, the plan has %d", n_members, plan->n_members);
+  MI_REQUIRE(B == plan->B, "train_group_step: B=%lld, the plan was made for %d", (long long)B, plan->B);
+  MI_REQUIRE(step >= 1, "train_group_step: step=%d (the global step after this call, 1-based)", step);
+  MI_REQUIRE(step <= plan->max_step, "train_group_step: step=%d, the shortest lr_table of the plan ends at %d", step, plan->max_step);
+  MI_REQUIRE(ids && labels && logits && loss, "train_group_step: ids / labels / logits / loss");
+  MI_REQUIRE(ids_member_stride == 0 || ids_member_stride == B * plan->F,
+             "train_group_step: ids_member_stride=%lld (0 = one batch for all members, or B F = %lld)",
+             (long long)ids_member_stride, (long long)(B * plan->F));
+  MI_REQUIRE(labels_member_stride == 0 || labels_member_stride == B,
+             "train_group_step: labels_member_stride=%lld (0 = one batch for all members, or B = %lld)",
+             (long long)labels_member_stride, (long long)B);
+  if (sweep_blocks < 0 || sweep_blocks > kMaxSweepBlocks)
+    return unsupported("train_group_step: sweep_blocks=%d (0 = the built-in choice, at most %d)", sweep_blocks, kMaxSweepBlocks);
+  const int blocks = sweep_blocks ? sweep_blocks : plan->sweep_blocks;
+  MI_REQUIRE(blocks >= 1 && blocks <= kMaxSweepBlocks && plan->lds_bytes <= kMaxLds, "train_group_step: plan (damaged)");
+  const int32_t rl = raise_lds(&train_fused_group_k, plan->lds_bytes, "train_group_step");
+  if (rl != MI_OK) return rl;
+  train_fused_group_k<<<dim3(1 + blocks, n_members), dim3(kThreads), plan->lds_bytes, mi::as_stream(stream)>>>(
+      static_cast<const Member*>(plan->device_table), ids, ids_member_stride, labels, labels_member_stride, logits, loss, step);
+  MI_CHECK_LAUNCH("train_group_step");
   return MI_OK;
 }
 

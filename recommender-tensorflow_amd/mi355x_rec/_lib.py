@@ -55,6 +55,27 @@ class WeightJob(C.Structure):
     _fields_ = [("offset", C.c_int64), ("K", C.c_int32), ("N", C.c_int32), ("w", Planes), ("wt", Planes)]
 
 
+FUSED_GROUP_MAX_MEMBERS = 1024  # MI_FUSED_GROUP_MAX_MEMBERS
+
+
+class FusedMember(C.Structure):
+    """mi_fused_member_t: one model of mi_train_group_plan"""
+    _fields_ = [("table", C.c_void_p), ("t_m", C.c_void_p), ("t_v", C.c_void_p), ("table_stride", C.c_int64),
+                ("lin_w", C.c_void_p), ("l_m", C.c_void_p), ("l_v", C.c_void_p), ("last_step", C.c_void_p), ("R", C.c_int64),
+                ("dense", C.c_void_p), ("d_m", C.c_void_p), ("d_v", C.c_void_p), ("n_dense", C.c_int64),
+                ("layer_off", C.c_void_p), ("widths", C.c_void_p), ("lin_bias_off", C.c_int64), ("lr_table", C.c_void_p),
+                ("lr_table_len", C.c_int64), ("seed_base", C.c_uint64), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("lin_stride", C.c_int32), ("E", C.c_int32), ("n_layers", C.c_int32),
+                ("activation", C.c_int32), ("use_linear", C.c_int32), ("use_fm", C.c_int32), ("use_dnn", C.c_int32),
+                ("keep_prob", C.c_float), ("scale", C.c_float), ("hp", OptHparams)]
+
+
+class FusedGroupPlan(C.Structure):
+    """mi_fused_group_plan_t: what mi_train_group_plan leaves on the host for mi_train_group_step"""
+    _fields_ = [("device_table", C.c_void_p), ("magic", C.c_uint64), ("n_members", C.c_int32), ("B", C.c_int32),
+                ("F", C.c_int32), ("sweep_blocks", C.c_int32), ("max_step", C.c_int32), ("lds_bytes", C.c_uint32)]
+
+
 _p = C.c_void_p
 _i32, _i64, _u32, _u64, _f32, _sz = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_size_t
 _amax = C.POINTER(GemmAmax)
@@ -151,6 +172,9 @@ SIGNATURES = {
     "mi_train_step_fused": (_i32, [_p, _p, _p, _i64, _p, _p, _p, _i32, _p, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _p, _i64,
                                    _p, _p, _i32, _i32, _i32, _i32, _i32, _i64, _f32, _u64, _f32, _i32, C.POINTER(OptHparams),
                                    _p, _p, _i32, _p, _sz, _p]),
+    "mi_train_group_plan_bytes": (_sz, [_i32]),
+    "mi_train_group_plan": (_i32, [_p, _i32, _i64, _i32, _p, _p, _sz, _p, _p]),
+    "mi_train_group_step": (_i32, [_p, _i32, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _i32, _p]),
 }
 
 _lib = None

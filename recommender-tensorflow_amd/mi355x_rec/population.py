@@ -1,0 +1,148 @@
+"""A population of small DeepFM models trained side by side: every member takes one training step in ONE launch
+(mi_train_group_step, include/mi355x_rec.h), member i's result being bit for bit what its own
+``engine.DeepFM.fused_train_step`` gives.  What the reference does for a grid of hyper-parameters, seeds or folds is M
+runs of trainers/deep_fm.py:36-125 one after the other; a model of this size leaves the chip idle, so M of them fit at once.
+
+The members are ordinary engines: after a population step each is exactly where its own fused step would have left it and
+can be used alone (loss, predict_fused, top_k, state_dict, train_step, fused_train_step) — as long as all members are at
+the same step again before the next population step."""
+import numpy as np
+import torch
+
+from . import _lib
+from .engine import DeepFM
+
+
+class FusedPopulation:
+    MAX_MEMBERS = _lib.FUSED_GROUP_MAX_MEMBERS
+    SWEEP_BLOCKS = 0     # workgroups of each member's all-rows sweep; 0: the library's choice (tests: results do not depend on it)
+
+    def __init__(self, engines):
+        engines = list(engines)
+        if not engines:
+            raise ValueError("FusedPopulation: no members")
+        if len(engines) > self.MAX_MEMBERS:
+            raise ValueError("FusedPopulation: %d members (at most %d in one launch)" % (len(engines), self.MAX_MEMBERS))
+        seen = {}
+        for i, e in enumerate(engines):
+            if not isinstance(e, DeepFM):
+                raise ValueError("FusedPopulation: member %d is %s, an engine.DeepFM is expected" % (i, type(e).__name__))
+            if id(e) in seen:
+                raise ValueError("FusedPopulation: member %d is the same engine as member %d" % (i, seen[id(e)]))
+            seen[id(e)] = i
+        first = engines[0]
+        for i, e in enumerate(engines):
+            why = e._fused_step_limit(1)
+            if why is not None:
+                raise ValueError("FusedPopulation: member %d: the model has %s; use train_step" % (i, why))
+            if e.vocab_sizes != first.vocab_sizes:
+                raise ValueError("FusedPopulation: member %d has other vocab_sizes than member 0 (%d fields against %d): the "
+                                 "members share one set of feature columns" % (i, e.F, first.F))
+            if e.device != first.device:
+                raise ValueError("FusedPopulation: member %d lives on %s, member 0 on %s" % (i, e.device, first.device))
+        self.engines = engines
+        self.M = len(engines)
+        self.F = first.F
+        self.device = first.device
+        self.k = first.k
+        self._plan = None          # (B, struct, device table, the members' schedule generations, what the struct points to)
+        self._out = {}             # B -> (loss [M], logits [M, B])
+        self._table_len = 0        # the shortest schedule table of the members (steps below it need no look at the schedules)
+
+    def __len__(self):
+        return self.M
+
+    # ------------------------------------------------------------------ the plan
+    def rebuild(self):
+        """Forget the plan: the next step makes a new one.  For a caller who REPLACED a member's tensors (load_state_dict
+        copies into them in place and needs none)."""
+        self._plan = None
+
+    def _describe(self, e, B, keep_alive):
+        """engine e as a mi_fused_member_t for batches of B (keep_alive: the tensors the struct points to and e does not hold)"""
+        layer_off = torch.tensor([o for (ko, bo, _, _) in e.layers for o in (ko, bo)] or [0], dtype=torch.int64)
+        widths = torch.tensor(([e.layers[0][2]] + [h for (_, _, _, h) in e.layers]) if e.layers else [0], dtype=torch.int32)
+        E = e.E if e.use_emb else 4
+        nbytes = int(self.k.query("mi_train_step_fused_workspace_bytes", B, e.F, E, e.P))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=e.device)
+        keep_alive += [layer_off, widths, ws, e.sched.table]
+        m = _lib.FusedMember()
+        for name, t in (("table", e.table), ("t_m", e.t_s0), ("t_v", e.t_s1), ("lin_w", e.lin_w), ("l_m", e.l_s0), ("l_v", e.l_s1),
+                        ("last_step", e.last_step), ("dense", e.dense), ("d_m", e.d_s0), ("d_v", e.d_s1),
+                        ("layer_off", layer_off), ("widths", widths), ("lr_table", e.sched.table), ("workspace", ws)):
+            setattr(m, name, _lib.ptr(t))
+        m.table_stride, m.lin_stride, m.R, m.E, m.n_dense = e.ts, e.ls, e.R, e.E, e.P
+        m.n_layers, m.activation = len(e.layers), e.act
+        m.use_linear, m.use_fm, m.use_dnn = int(e.use_linear), int(e.use_mf), int(e.use_dnn)
+        m.lin_bias_off = e.lin_bias_off
+        m.keep_prob = float(1.0 - e.dropout if e.dropout > 0 else 1.0)
+        m.scale = float(np.float32(1.0 / B)) if e.reduction == "mean" else 1.0
+        m.hp = e.opt.hparams(0.0)
+        m.lr_table_len = int(e.sched.table.numel())
+        m.seed_base = (e.seed * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)           # engine._layer_seed(0) without its step term
+        m.workspace_bytes = ws.numel()
+        return m
+
+    def _build(self, B):
+        keep_alive = []
+        members = (_lib.FusedMember * self.M)(*[self._describe(e, B, keep_alive) for e in self.engines])
+        nbytes = int(self.k.query("mi_train_group_plan_bytes", self.M))
+        table = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
+        plan = _lib.FusedGroupPlan()
+        self.k.mi_train_group_plan(members, self.M, B, self.F, self.engines[0].field_off, table, table.numel(), plan)
+        self._plan = (B, plan, table, [e.sched.gen for e in self.engines], keep_alive)
+        return self._plan
+
+    # ------------------------------------------------------------------ the step
+    def _check_batch(self, ids, labels):
+        M, F = self.M, self.F
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or not ids.is_contiguous() or ids.dim() not in (2, 3) \
+                or ids.shape[-1] != F or (ids.dim() == 3 and ids.shape[0] != M):
+            raise ValueError("FusedPopulation: ids must be a contiguous int32 [B, %d] or [%d, B, %d] tensor" % (F, M, F))
+        B = int(ids.shape[-2])
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or not labels.is_contiguous() \
+                or tuple(labels.shape) not in ((B,), (M, B)):
+            raise ValueError("FusedPopulation: labels must be a contiguous uint8 [B] or [%d, B] tensor (B = %d)" % (M, B))
+        if ids.device.type != self.device.type or labels.device.type != self.device.type:
+            raise ValueError("FusedPopulation: ids and labels must live on %s" % self.device)
+        return B
+
+    def train_step(self, ids, labels, out=None):
+        """One optimizer.minimize(loss) of EVERY member as one launch: returns (loss [M], logits [M, B]) device tensors,
+        no host sync.  ids int32 [B, F] (one batch for all members) or [M, B, F] (one per member); labels uint8 [B] or
+        [M, B].  out = (loss, logits): write there instead of into the population's own buffers."""
+        B = self._check_batch(ids, labels)
+        engines = self.engines
+        step = engines[0].step + 1
+        for i, e in enumerate(engines):
+            if e.step + 1 != step:
+                raise ValueError("FusedPopulation: member %d is at step %d, member 0 at step %d: the members of a population "
+                                 "step together (bring the others up with their own fused_train_step)" % (i, e.step, step - 1))
+        plan = self._plan
+        if plan is None or plan[0] != B:
+            for i, e in enumerate(engines):
+                why = e._fused_step_limit(B)
+                if why is not None:
+                    raise ValueError("FusedPopulation: member %d: the model has %s; use train_step" % (i, why))
+        if step >= self._table_len or any(e._final_step != e.step for e in engines):
+            for e in engines:
+                e.finalize_rows()                     # (a no-op after a fused step)
+                e.sched.lr_t(step)                    # (extends the member's table when the run outgrows it: gen changes)
+            self._table_len = min(len(e.sched.host) for e in engines)
+        if plan is None or plan[0] != B or any(e.sched.gen != g for e, g in zip(engines, plan[3])):
+            plan = self._build(B)
+        if out is None:
+            out = self._out.get(B)
+            if out is None:
+                out = self._out[B] = (torch.empty(self.M, dtype=torch.float32, device=self.device),
+                                      torch.empty(self.M, B, dtype=torch.float32, device=self.device))
+        loss, logits = out
+        if tuple(loss.shape) != (self.M,) or tuple(logits.shape) != (self.M, B) or loss.dtype != torch.float32 \
+                or logits.dtype != torch.float32 or not loss.is_contiguous() or not logits.is_contiguous():
+            raise ValueError("FusedPopulation: out = (loss float32 [%d], logits float32 [%d, %d]), contiguous" % (self.M, self.M, B))
+        self.k.mi_train_group_step(plan[1], self.M, ids, B * self.F if ids.dim() == 3 else 0, labels,
+                                   B if labels.dim() == 2 else 0, B, step, logits, loss, int(self.SWEEP_BLOCKS))
+        for e in engines:
+            e.step = step
+            e._final_step = step
+        return loss, logits

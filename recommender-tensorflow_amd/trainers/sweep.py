@@ -1,0 +1,198 @@
+"""Grid search over small DeepFM models: ``python -m trainers.sweep``.
+
+What one does with a model of trainers.deep_fm's default size is train it many times — a grid of learning rates, dropout
+rates, embedding sizes and layer specs, several seeds.  With the reference that is M runs of trainers/deep_fm.py one
+after the other; here the M members train SIDE BY SIDE: the data is read once, every batch's ids are transformed once and
+every member takes its step on it in ONE kernel launch (mi355x_rec.population.FusedPopulation), member i's variables
+being bit for bit those of a stand-alone ``trainers.deep_fm --fused-step on`` run with its hyper-parameters.
+
+Every member is an ordinary Estimator of trainers.deep_fm.model_fn with model_dir = <job-dir>/member_<i>: its
+checkpoints and export are accepted by ``trainers.deep_fm --restore``, ``trainers.predict`` and ``trainers.recommend``.
+<job-dir>/sweep.json lists the members, best first.
+
+trainers.deep_fm has no learning-rate flag (the reference has none): a member restored through ``trainers.deep_fm
+--restore`` continues at that CLI's 0.001, a member restored through ``trainers.sweep --restore`` at its own rate."""
+import itertools
+import json
+import os
+import shutil
+import time
+from argparse import ArgumentParser
+
+import numpy as np
+import torch
+
+from mi355x_rec.estimator import Estimator, ModeKeys
+from mi355x_rec.population import FusedPopulation
+from trainers import _cli, deep_fm
+from trainers.conf_utils import get_exporter
+from trainers.ml_100k import get_feature_columns, get_input_fn, serving_input_fn
+
+_KEPT = ("--train-csv", "--test-csv", "--restore", "--batch-size", "--train-steps", "--device", "--catchup", "--synthetic")
+_ASCENDING = ("loss", "average_loss")
+
+
+def make_parser():
+    p = ArgumentParser(description="Train the Cartesian product of the given hyper-parameters as one population of DeepFM "
+                                   "models, one kernel launch per step for all of them.  No step of a sweep records layer "
+                                   "summaries (the fused kernel keeps no activations).  A member restored through "
+                                   "trainers.deep_fm --restore continues at that CLI's learning rate of 0.001; through "
+                                   "trainers.sweep --restore at its own.")
+    p.add_argument("--job-dir", default="checkpoints/sweep", help="job directory; member i lives in <job-dir>/member_<i> "
+                                                                  "(default: %(default)s)")
+    for flag, kw in _cli._COMMON:
+        if flag in _KEPT:
+            p.add_argument(flag, **kw)
+    for name in ("exclude_linear", "exclude_mf", "exclude_dnn"):
+        flag, kw = _cli._OPTIONAL[name]
+        p.add_argument(flag, **kw)
+    p.add_argument("--learning-rate", type=float, nargs="+", default=[0.001], help="Adam learning rates (default: %(default)s)")
+    p.add_argument("--dropout", type=float, nargs="+", default=[0.1], help="dropout rates (default: %(default)s)")
+    p.add_argument("--embedding-size", type=int, nargs="+", default=[4], help="embedding sizes (default: %(default)s)")
+    p.add_argument("--hidden-units", type=int, nargs="+", action="append", default=None,
+                   help="a hidden layer specification; repeat the flag for several (default: 16 16)")
+    p.add_argument("--seeds", type=int, default=1, metavar="N", help="seeds 0 .. N-1 of the variable initialisers and dropout "
+                                                                     "masks (default: %(default)s)")
+    p.add_argument("--select", default="auc", choices=["auc", "accuracy", "auc_precision_recall", "loss", "average_loss"],
+                   help="the evaluation metric sweep.json is sorted by, best first (loss / average_loss: lowest first; "
+                        "default: %(default)s)")
+    return p
+
+
+def grid(args):
+    """The members' hyper-parameters: the Cartesian product of the flags, in the flags' order."""
+    specs = args.hidden_units or [[16, 16]]
+    if args.seeds < 1:
+        raise ValueError("--seeds %d (at least 1)" % args.seeds)
+    out = [dict(embedding_size=E, hidden_units=list(h), dropout=d, learning_rate=lr, seed=s)
+           for E, h, d, lr, s in itertools.product(args.embedding_size, specs, args.dropout, args.learning_rate, range(args.seeds))]
+    if len(out) > FusedPopulation.MAX_MEMBERS:
+        raise ValueError("the grid has %d members (at most %d train in one launch): split the sweep" % (
+            len(out), FusedPopulation.MAX_MEMBERS))
+    return out
+
+
+def member_flags(args, hp):
+    """The flags that rebuild a member's model with the existing CLIs (trainers.deep_fm --restore --job-dir <member dir> ...)"""
+    flags = ["--embedding-size", str(hp["embedding_size"]), "--hidden-units"] + [str(h) for h in hp["hidden_units"]] + [
+        "--dropout", repr(hp["dropout"])]
+    return flags + [f for f, on in (("--exclude-linear", args.exclude_linear), ("--exclude-mf", args.exclude_mf),
+                                    ("--exclude-dnn", args.exclude_dnn)) if on]
+
+
+def make_members(args, hps, config):
+    """One Estimator of trainers.deep_fm.model_fn per member, model_dir = <job-dir>/member_<i>, with its own params"""
+    members = []
+    for i, hp in enumerate(hps):
+        params = {"categorical_columns": get_feature_columns(embedding_size=hp["embedding_size"])["linear"],
+                  "use_linear": not args.exclude_linear, "use_mf": not args.exclude_mf, "use_dnn": not args.exclude_dnn,
+                  "catchup": getattr(args, "catchup", "bounded"), "fused_step": "on"}
+        params.update(hp)
+        members.append(Estimator(model_fn=deep_fm.model_fn, model_dir=os.path.join(args.job_dir, "member_%d" % i), config=config,
+                                 params=params))
+    return members
+
+
+def build(members, features, labels, batch_size):
+    """Every member's variables (model_fn's "_build" call: a stand-alone run's initial values for its params), its newest
+    checkpoint if its directory holds one, and the checks a population asks for — before any step."""
+    for i, est in enumerate(members):
+        est._first_call(features, labels, ModeKeys.TRAIN)
+        why = est._engine()._fused_step_limit(batch_size)
+        if why is not None:
+            hp = {k: est.params[k] for k in ("embedding_size", "hidden_units", "dropout", "learning_rate", "seed")}
+            raise ValueError("member %d (%s): the model has %s; a sweep trains models inside the fused step's scope" % (i, hp, why))
+    steps = [est.global_step for est in members]
+    if len(set(steps)) > 1:
+        raise ValueError("the members are at different steps (%s): a sweep steps its members together" % ", ".join(
+            "member %d at step %d" % (i, s) for i, s in enumerate(steps)))
+    return FusedPopulation([est._engine() for est in members])
+
+
+def train(members, input_fn, max_steps, config, job_dir=None, batch_size=None):
+    """The sweep's loop: ONE input pipeline — every batch is read and its ids are transformed once (in groups, as
+    Estimator._grouped does for small batches) — and one population step per batch.  Returns the population."""
+    lead = members[0]
+    pop = None
+    t_log = t_ckpt = time.time()
+    n_log = 0
+    log = None
+    for features, labels in lead._grouped(input_fn()):
+        if pop is None:
+            pop = build(members, features, labels, batch_size or len(labels))
+            plan, dev = lead.params["_store"]["plan"], lead._engine().device
+        step = lead.global_step
+        if step >= max_steps:
+            break
+        ahead = lead.params.get("_ahead")
+        if ahead is not None and ahead.get("features") is features:
+            g = ahead["group"]
+            if "ids" not in g:
+                g["ids"] = torch.from_numpy(plan.transform(g["features"])[0]).to(dev)
+                g["y"] = torch.from_numpy(np.ascontiguousarray(np.asarray(g["labels"]).reshape(-1)).astype(np.uint8)).to(dev)
+            lo, hi = ahead["rows"]
+            ids, y = g["ids"][lo:hi], g["y"][lo:hi]
+        else:
+            ids = torch.from_numpy(plan.transform(features)[0]).to(dev)
+            y = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1)).astype(np.uint8)).to(dev)
+        loss, _ = pop.train_step(ids, y)
+        step += 1
+        n_log += 1
+        if step % config.log_step_count_steps == 0:
+            now = time.time()
+            ls = loss.cpu().numpy()
+            print("INFO: step = %d (%.1f global_step/sec, %d members), member loss lowest = %.6f, median = %.6f, highest = %.6f" % (
+                step, n_log / max(now - t_log, 1e-9), len(members), ls.min(), float(np.median(ls)), ls.max()))
+            if job_dir is not None:
+                if log is None:
+                    os.makedirs(job_dir, exist_ok=True)
+                    log = open(os.path.join(job_dir, "sweep_log.jsonl"), "a")
+                log.write(json.dumps({"global_step": step, "loss": [float(v) for v in ls]}) + "\n")
+                log.flush()
+            t_log, n_log = now, 0
+        if config.save_checkpoints_secs and time.time() - t_ckpt >= config.save_checkpoints_secs:
+            for est in members:
+                est.save_checkpoint()
+            t_ckpt = time.time()
+    if log is not None:
+        log.close()
+    return pop
+
+
+def train_and_evaluate(args):
+    if int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("trainers.sweep runs on one GPU: its members are small models that share it")
+    if getattr(args, "synthetic", None):
+        args.train_csv, args.test_csv = "synthetic:%d:1" % args.synthetic, "synthetic:%d:2" % max(args.synthetic // 10, 1)
+    hps = grid(args)
+    if not args.restore:
+        shutil.rmtree(args.job_dir, ignore_errors=True)
+    config = _cli.get_run_config()
+    config.device = args.device
+    members = make_members(args, hps, config)
+    pop = train(members, get_input_fn(args.train_csv, batch_size=args.batch_size), args.train_steps, config, args.job_dir,
+                args.batch_size)
+    if pop is None:
+        raise ValueError("no training data in %s" % args.train_csv)
+    eval_fn = get_input_fn(args.test_csv, ModeKeys.EVAL, batch_size=args.batch_size)
+    exporter = get_exporter(serving_input_fn)
+    rows = []
+    for i, (est, hp) in enumerate(zip(members, hps)):
+        est.save_checkpoint()
+        metrics = est.evaluate(eval_fn)
+        export = exporter.export(est, os.path.join(est.model_dir, "export"))
+        rows.append({"member": i, "dir": est.model_dir, "export": export, "global_step": est.global_step, "params": hp,
+                     "flags": member_flags(args, hp), "metrics": {k: float(v) for k, v in metrics.items()}})
+    sign = 1.0 if args.select in _ASCENDING else -1.0
+    rows.sort(key=lambda r: (sign * r["metrics"][args.select], r["member"]))
+    with open(os.path.join(args.job_dir, "sweep.json"), "w") as f:
+        json.dump({"select": args.select, "members": rows}, f, indent=1)
+    best = rows[0]
+    print("INFO: best of %d members by %s: member %d (%s), %s = %.6g, in %s" % (
+        len(rows), args.select, best["member"], ", ".join("%s = %s" % kv for kv in sorted(best["params"].items())), args.select,
+        best["metrics"][args.select], best["dir"]))
+    return members
+
+
+if __name__ == "__main__":
+    train_and_evaluate(make_parser().parse_args())
