@@ -837,6 +837,33 @@ int32_t mi_train_group_step(const mi_fused_group_plan_t* plan, int32_t n_members
                             const uint8_t* labels, int64_t labels_member_stride, int64_t B, int32_t step, float* logits,
                             float* loss, int32_t sweep_blocks, mi_stream_t stream);
 
+/* ---- evaluating a population of small models: a whole evaluation set, for every member, as one launch ------------------
+ * What Estimator.evaluate does for one model (the EVAL branch of trainers/deep_fm.py:118-125 and model_utils.py:39-54) for
+ * the M members of a plan mi_train_group_plan wrote: the forward of mi_train_step_fused — the same device code — WITHOUT
+ * dropout (keep_prob = 1 whatever the member's) and without any backward, over ids [N, F] / labels [N] (one set for all
+ * members) in tiles of the plan's B examples (tile t = examples [t B, min(N, (t + 1) B)); T = ceil(N / B); the last tile may
+ * be short), and mi_eval_accumulate's counters on those logits, kept on the chip.  Grid (X, M): a workgroup walks the tiles
+ * t = x, x + X, ... of its member.  Nothing of any member (variable, slot, stamp, workspace) is written.
+ *   batch_loss [M, T] fp32: the loss of tile t alone, reduced in the head's order with the member's scale — what
+ *     mi_train_step_fused reports as loss for that batch with keep_prob = 1;
+ *   tail_scale [M] (device): member i's scale on a SHORT last tile of n = N mod B examples (the fp32 of 1 / n for a mean,
+ *     1 for a sum); may be NULL when B divides N;
+ *   logits [M, N] fp32, optional (NULL on the hot path);
+ *   hist [M, 2*201] and counts [M, 8] int64: per member exactly mi_eval_accumulate's (integer atomics into arrays the
+ *     CALLER ZEROED; order independent);
+ *   partials [M, T, 3] f64: per tile sum(loss_b), sum(sigmoid), sum(label) with mi_eval_accumulate's terms, reduced inside
+ *     the workgroup in a fixed order and written with a plain store; the host adds the tiles in ascending order.
+ * No float atomics go to global memory: two calls give the same bits, and no result depends on X.  No workgroup reads
+ * what another writes in the launch and none waits for another.  blocks: X (0 = the built-in choice from M, T and the
+ * chip's 256 compute units: about 1024 workgroups in all, at most T per member; at most 1024, and X M <= 65536; a test
+ * seam).  PRECONDITION as for the step: every row of every member current.  Refused on the host before anything is
+ * launched (MI_ERR_INVALID; blocks out of range MI_ERR_UNSUPPORTED): a plan mi_train_group_plan did not write, n_members
+ * other than the plan's, N < 1, NULL ids / labels / batch_loss / hist / counts / partials, NULL tail_scale with a short tile.
+ * One launch, no copy, no synchronisation. */
+int32_t mi_eval_group(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids, const uint8_t* labels, int64_t N,
+                      const float* tail_scale, float* logits, float* batch_loss, int64_t* hist, int64_t* counts, double* partials,
+                      int32_t blocks, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

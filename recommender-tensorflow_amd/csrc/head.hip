@@ -5,6 +5,7 @@
 // metric contract is spelled out by trainers/model_utils.py:9-54) and layer_summary
 // (model_utils.py:4-6).  Reductions are two-stage with a fixed order: bitwise reproducible.
 #include "common.h"
+#include "eval_rules.h"
 #include <cstdlib>
 #include <algorithm>
 
@@ -12,7 +13,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kMaxBlocks = 1024;
-constexpr int kAucThresholds = 200;  // tf.metrics.auc default num_thresholds
 
 __device__ __forceinline__ float wave_sum(float x) {
 #pragma unroll
@@ -134,41 +134,15 @@ __global__ __launch_bounds__(kBlock) void eval_accumulate_k(const float* __restr
                                                             unsigned long long* __restrict__ counts,
                                                             double* __restrict__ sums) {
   __shared__ float th[kAucThresholds];
-  __shared__ unsigned int lh[2][kAucThresholds + 1];
-  __shared__ unsigned int lc[8];
+  __shared__ unsigned int lh[kEvalHist];
+  __shared__ unsigned int lc[kEvalCounts];
   __shared__ double ls[4][4];
-  for (int j = threadIdx.x; j < kAucThresholds; j += kBlock) {
-    float v;
-    if (j == 0) v = static_cast<float>(0.0 - 1e-7);
-    else if (j == kAucThresholds - 1) v = static_cast<float>(1.0 + 1e-7);
-    else v = static_cast<float>(static_cast<double>(j) * 1.0 / static_cast<double>(kAucThresholds - 1));
-    th[j] = v;
-  }
-  for (int j = threadIdx.x; j < 2 * (kAucThresholds + 1); j += kBlock) (&lh[0][0])[j] = 0;
-  if (threadIdx.x < 8) lc[threadIdx.x] = 0;
+  mi_eval_init(th, lh, lc, threadIdx.x, kBlock);
   __syncthreads();
   double sl = 0, sp = 0, sy = 0;
   const int64_t per = (B + gridDim.x - 1) / gridDim.x;
   const int64_t b0 = blockIdx.x * per, b1 = min(B, b0 + per);
-  for (int64_t b = b0 + threadIdx.x; b < b1; b += kBlock) {
-    const float x = logits[b];
-    const int y = labels[b] ? 1 : 0;
-    const float p = mi_sigmoid_stable(x);
-    int lo = 0, hi = kAucThresholds;        // k = #{j : th[j] < p}
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (th[mid] < p) lo = mid + 1; else hi = mid; }
-    atomicAdd(&lh[y][lo], 1u);
-    const int cls = p > 0.5f ? 1 : 0;       // model_utils.py:12
-    atomicAdd(&lc[0], 1u);
-    if (y) atomicAdd(&lc[1], 1u);
-    if (cls) atomicAdd(&lc[2], 1u);
-    if (cls == y) atomicAdd(&lc[3], 1u);
-    if (cls && y) atomicAdd(&lc[4], 1u);
-    if (cls && !y) atomicAdd(&lc[5], 1u);
-    if (!cls && y) atomicAdd(&lc[6], 1u);
-    const double xd = x;
-    sl += fmax(xd, 0.0) - xd * y + log1p(exp(-fabs(xd)));
-    sp += p; sy += y;
-  }
+  for (int64_t b = b0 + threadIdx.x; b < b1; b += kBlock) mi_eval_count(logits[b], labels[b] ? 1 : 0, th, lh, lc, sl, sp, sy);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     sl += __shfl_xor(sl, off, 64); sp += __shfl_xor(sp, off, 64); sy += __shfl_xor(sy, off, 64);
@@ -176,11 +150,7 @@ __global__ __launch_bounds__(kBlock) void eval_accumulate_k(const float* __restr
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) { ls[w][0] = sl; ls[w][1] = sp; ls[w][2] = sy; }
   __syncthreads();
-  for (int j = threadIdx.x; j < 2 * (kAucThresholds + 1); j += kBlock) {
-    const unsigned int v = (&lh[0][0])[j];
-    if (v) atomicAdd(&hist[j], static_cast<unsigned long long>(v));
-  }
-  if (threadIdx.x < 7 && lc[threadIdx.x]) atomicAdd(&counts[threadIdx.x], static_cast<unsigned long long>(lc[threadIdx.x]));
+  mi_eval_flush(lh, lc, hist, counts, threadIdx.x, kBlock);
   if (threadIdx.x < 3) {
     const double v = (ls[0][threadIdx.x] + ls[1][threadIdx.x]) + (ls[2][threadIdx.x] + ls[3][threadIdx.x]);
     atomicAdd(&sums[threadIdx.x], v);

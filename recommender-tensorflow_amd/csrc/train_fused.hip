@@ -30,9 +30,14 @@
 //     the arithmetic has this one definition, so a member's bits are those of train_fused_k on it alone.  A member's
 //     workgroups touch only that member's buffers.
 //
+//   eval_fused_group_k    the same M models over a whole evaluation set in ONE launch (mi_eval_group): grid (X, M), a workgroup
+//     runs forward_block — phases 0-2 of batch_block, the forward's one definition — without dropout over its member's tiles
+//     and keeps mi_eval_accumulate's counters (eval_rules.h) in LDS; nothing of any model is written (see the kernel).
+//
 // Arithmetic: fp32 throughout; compiled with -ffp-contract=off (the update rules and the FM term are written one
 // rounding per operation); the MLP's dot products use explicit fmaf.
 #include "common.h"
+#include "eval_rules.h"
 #include "optim_rules.h"
 
 namespace {
@@ -161,9 +166,14 @@ __device__ __forceinline__ float finish(const Args& p, float acc, float bias, bo
   return v;
 }
 
-__device__ __forceinline__ void batch_block(const Args& p, char* lds, const Layer* layers, float (*red)[kThreads / 64]) {
+// Phases 0-2 of a batch: rows, forward, head.  The one definition of the model's forward in this file: the training step
+// (kTrain: also dlogit, into dl and over the logits layer's output, and its sum into red[1]) and the evaluation kernel
+// (no gradient, keep = 1) run it.  Returns the thread's logit (thread b < B holds example b; 0 elsewhere); p.logits may be
+// NULL; p.loss[0] = the batch loss, reduced in the head's order, is written before the return (after a barrier).
+template <bool kTrain>
+__device__ __forceinline__ float forward_block(const Args& p, char* lds, const Layer* layers, float (*red)[kThreads / 64]) {
   const int tid = threadIdx.x;
-  const int B = p.B, F = p.F, E = p.E, L = p.n_layers, D = F * E;
+  const int B = p.B, F = p.F, E = p.E, L = p.n_layers;
   const int64_t ts = p.ts;
   int32_t* rows = reinterpret_cast<int32_t*>(lds);
   float* fl = reinterpret_cast<float*>(lds);
@@ -171,7 +181,6 @@ __device__ __forceinline__ void batch_block(const Args& p, char* lds, const Laye
   float* tq = fl + p.o_tq;
   float* zlin = fl + p.o_lin;
   float* dl = fl + p.o_dl;
-  float* dcat = p.dcat_ws ? p.dcat_ws : fl + p.o_dcat;
   const uint32_t thresh = mi_drop_thresh16(p.keep);
 
   // 0. the batch's rows
@@ -233,10 +242,10 @@ __device__ __forceinline__ void batch_block(const Args& p, char* lds, const Laye
   }
 
   // 2. head (the order of mi_sigmoid_ce_head); the logits layer's output becomes its gradient
+  float z = 0.f;
   {
     float per = 0.f, d = 0.f;
     if (tid < B) {
-      float z = 0.f;
       if (p.use_linear) z = zlin[tid] + p.dense[p.lin_bias_off];
       if (p.table && p.use_fm) {
         float t = 0.f;
@@ -246,22 +255,44 @@ __device__ __forceinline__ void batch_block(const Args& p, char* lds, const Laye
       if (L) z = z + fl[layers[L - 1].out_off + tid];
       const float y = static_cast<float>(p.labels[tid]);
       per = mi_sigmoid_ce_loss(z, y) * p.scale;
-      d = mi_sigmoid_ce_grad(z, y, p.scale);
-      p.logits[tid] = z;
-      dl[tid] = d;
-      if (L) fl[layers[L - 1].out_off + tid] = d;
+      if (p.logits) p.logits[tid] = z;
+      if (kTrain) {
+        d = mi_sigmoid_ce_grad(z, y, p.scale);
+        dl[tid] = d;
+        if (L) fl[layers[L - 1].out_off + tid] = d;
+      }
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { per += __shfl_xor(per, o); d += __shfl_xor(d, o); }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = per; red[1][tid >> 6] = d; }
+    for (int o = 32; o > 0; o >>= 1) {
+      per += __shfl_xor(per, o);
+      if (kTrain) d += __shfl_xor(d, o);
+    }
+    if ((tid & 63) == 0) {
+      red[0][tid >> 6] = per;
+      if (kTrain) red[1][tid >> 6] = d;
+    }
   }
   __syncthreads();
-  const int nw = (B + 63) >> 6;                                   // waves that hold examples (at most 2)
   if (tid == 0) {
+    const int nw = (B + 63) >> 6;                                 // waves that hold examples (at most 2)
     float s = red[0][0];
     for (int w = 1; w < nw; ++w) s = s + red[0][w];
     p.loss[0] = s;
   }
+  return z;
+}
+
+__device__ __forceinline__ void batch_block(const Args& p, char* lds, const Layer* layers, float (*red)[kThreads / 64]) {
+  forward_block<true>(p, lds, layers, red);
+  const int tid = threadIdx.x;
+  const int B = p.B, F = p.F, E = p.E, L = p.n_layers, D = F * E;
+  const int64_t ts = p.ts;
+  const int32_t* rows = reinterpret_cast<const int32_t*>(lds);
+  float* fl = reinterpret_cast<float*>(lds);
+  const float* sumv = fl + p.o_sumv;
+  const float* dl = fl + p.o_dl;
+  float* dcat = p.dcat_ws ? p.dcat_ws : fl + p.o_dcat;
+  const int nw = (B + 63) >> 6;
 
   // 3. backward through the MLP, top down
   for (int li = L - 1; li >= 0; --li) {
@@ -449,6 +480,81 @@ __global__ __launch_bounds__(kThreads) void train_fused_group_k(const Member* __
   batch_block(sp, lds, layers, red);
 }
 
+// ---- evaluation of a population -----------------------------------------------------------------------------------------
+// eval_fused_group_k   grid (X, M), blockIdx.y = the member.  A workgroup runs forward_block — keep = 1 whatever the member's
+//   dropout, no gradient — over the tiles t = blockIdx.x, blockIdx.x + X, ... of its member (tile t = examples
+//   [t B, min(N, (t + 1) B)) of the evaluation set) and counts every example with eval_rules.h into LDS.  Per tile it writes
+//   batch_loss[i, t] (the head's order; the member's scale, tail_scale[i] on a short last tile), the three fp64 sums
+//   partials[i, t, :] (wave shuffle, then the waves in ascending order: one writer, a plain vector store) and, if asked, the
+//   logits.  At its end it adds its hist / counts to the member's own arrays with integer atomics.  Nothing of the model and no
+//   training workspace is written; no workgroup reads what another writes and none waits for another; no result depends on X.
+struct EvalShared {
+  Args sp;
+  Layer layers[kMaxLayers];
+  float red[2][kThreads / 64];
+  float th[kAucThresholds];
+  unsigned int lh[kEvalHist];
+  unsigned int lc[kEvalCounts];
+  double ls[kThreads / 64][4];
+};
+// what a forward needs of the dynamic LDS ends where d_concat would begin: at most this, whatever the plan asked for
+constexpr size_t kMaxForwardLds = sizeof(float) * static_cast<size_t>(kMaxConcat / 4 + 2 * (kMaxConcat / 8) + 2 * kMaxBatch +
+                                                                       kMaxHidden * kMaxBatch * kMaxWidth + kMaxBatch);
+static_assert(kMaxForwardLds + sizeof(EvalShared) + 256 <= 160 * 1024, "the evaluation kernel's LDS");
+
+__global__ __launch_bounds__(kThreads) void eval_fused_group_k(const Member* __restrict__ members, const int32_t* __restrict__ ids,
+                                                               const uint8_t* __restrict__ labels, int64_t N, int64_t T,
+                                                               const float* __restrict__ tail_scale, float* __restrict__ logits,
+                                                               float* __restrict__ batch_loss, unsigned long long* __restrict__ hist,
+                                                               unsigned long long* __restrict__ counts, double* __restrict__ partials) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  __shared__ EvalShared es;
+  const int tid = threadIdx.x;
+  const int y = blockIdx.y;
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&members[y].a);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(&es.sp);
+    for (int i = tid; i < static_cast<int>(sizeof(Args) / sizeof(uint32_t)); i += kThreads) dst[i] = src[i];
+  }
+  mi_eval_init(es.th, es.lh, es.lc, tid, kThreads);
+  __syncthreads();
+  if (tid < kMaxLayers) es.layers[tid] = es.sp.l[tid];
+  const int B = es.sp.B, F = es.sp.F;
+  const float scale = es.sp.scale;
+  __syncthreads();
+  for (int64_t t = blockIdx.x; t < T; t += gridDim.x) {
+    const int64_t b0 = t * B;
+    const int n = static_cast<int>(N - b0 < B ? N - b0 : B);
+    if (tid == 0) {
+      es.sp.ids = ids + b0 * F;
+      es.sp.labels = labels + b0;
+      es.sp.logits = logits ? logits + y * N + b0 : nullptr;
+      es.sp.loss = batch_loss + y * T + t;
+      es.sp.B = n;
+      es.sp.scale = n < B ? tail_scale[y] : scale;
+      es.sp.keep = 1.f;
+    }
+    __syncthreads();
+    const float z = forward_block<false>(es.sp, lds, es.layers, es.red);
+    double sl = 0, sp = 0, sy = 0;
+    if (tid < n) mi_eval_count(z, labels[b0 + tid] ? 1 : 0, es.th, es.lh, es.lc, sl, sp, sy);
+    if (tid < ((n + 63) & ~63)) {                                   // (wave-uniform: the waves that hold examples)
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) { sl += __shfl_xor(sl, o); sp += __shfl_xor(sp, o); sy += __shfl_xor(sy, o); }
+      if ((tid & 63) == 0) { es.ls[tid >> 6][0] = sl; es.ls[tid >> 6][1] = sp; es.ls[tid >> 6][2] = sy; }
+    }
+    __syncthreads();
+    if (tid < 3) {
+      const int nw = (n + 63) >> 6;
+      double v = es.ls[0][tid];
+      for (int w = 1; w < nw; ++w) v = v + es.ls[w][tid];
+      partials[(y * T + t) * 3 + tid] = v;
+    }
+    __syncthreads();                                                // (the next tile rewrites sp, red and ls)
+  }
+  mi_eval_flush(es.lh, es.lc, hist + static_cast<int64_t>(y) * kEvalHist, counts + static_cast<int64_t>(y) * kEvalCounts, tid, kThreads);
+}
+
 int32_t unsupported(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 int32_t unsupported(const char* fmt, ...) {
   char buf[512];
@@ -582,6 +688,7 @@ int32_t raise_lds(K kernel, size_t lds, const char* what) {
 
 constexpr uint64_t kPlanMagic = 0x6d695f67726f7570ull;   // "mi_group"
 constexpr int kGroupGridBlocks = 1 << 16;                // the built-in sweep_blocks keeps (1 + G) M at or below this
+constexpr int kEvalResident = 4 * 256;                   // workgroups of one evaluation launch (the built-in choice)
 
 }  // namespace
 
@@ -725,6 +832,41 @@ int32_t mi_train_group_step(const mi_fused_group_plan_t* plan, int32_t n_members
   train_fused_group_k<<<dim3(1 + blocks, n_members), dim3(kThreads), plan->lds_bytes, mi::as_stream(stream)>>>(
       static_cast<const Member*>(plan->device_table), ids, ids_member_stride, labels, labels_member_stride, logits, loss, step);
   MI_CHECK_LAUNCH("train_group_step");
+  return MI_OK;
+}
+
+int32_t mi_eval_group(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids, const uint8_t* labels, int64_t N,
+                      const float* tail_scale, float* logits, float* batch_loss, int64_t* hist, int64_t* counts, double* partials,
+                      int32_t blocks, mi_stream_t stream) {
+  MI_REQUIRE(plan && plan->magic == kPlanMagic && plan->device_table, "eval_group: plan (not written by mi_train_group_plan)");
+  MI_REQUIRE(n_members == plan->n_members, "eval_group: %d members, the plan has %d", n_members, plan->n_members);
+  MI_REQUIRE(N >= 1 && N <= INT32_MAX, "eval_group: N=%lld examples (1 to %d)", (long long)N, INT32_MAX);
+  MI_REQUIRE(ids && labels, "eval_group: ids / labels");
+  MI_REQUIRE(batch_loss && hist && counts && partials, "eval_group: batch_loss / hist / counts / partials");
+  MI_REQUIRE(plan->B >= 1 && plan->B <= kMaxBatch && plan->lds_bytes <= kMaxLds, "eval_group: plan (damaged)");
+  MI_REQUIRE(N % plan->B == 0 || tail_scale, "eval_group: tail_scale (the last tile has %lld of %d examples)",
+             (long long)(N % plan->B), plan->B);
+  if (blocks < 0 || blocks > kMaxSweepBlocks)
+    return unsupported("eval_group: blocks=%d (0 = the built-in choice, at most %d)", blocks, kMaxSweepBlocks);
+  const int64_t T = mi::ceil_div(N, plan->B);
+  // built-in X: kEvalResident workgroups in all (4 per compute unit of the 256, twice the 2 that 127 VGPRs let run side by
+  // side, so a workgroup that ends early is followed by another), shared out among the members, never more than a member has
+  // tiles; X M stays inside the training launch's 65536 workgroups
+  int64_t X = blocks;
+  if (!X) {
+    X = kEvalResident / n_members;
+    if (X < 1) X = 1;
+    if (X > T) X = T;
+  }
+  MI_REQUIRE(X * n_members <= kGroupGridBlocks, "eval_group: blocks=%d for %d members (at most %d workgroups in all)", blocks,
+             n_members, kGroupGridBlocks);
+  const size_t lds = plan->lds_bytes < kMaxForwardLds ? plan->lds_bytes : kMaxForwardLds;
+  const int32_t rl = raise_lds(&eval_fused_group_k, lds, "eval_group");
+  if (rl != MI_OK) return rl;
+  eval_fused_group_k<<<dim3(static_cast<unsigned>(X), n_members), dim3(kThreads), lds, mi::as_stream(stream)>>>(
+      static_cast<const Member*>(plan->device_table), ids, labels, N, T, tail_scale, logits, batch_loss,
+      reinterpret_cast<unsigned long long*>(hist), reinterpret_cast<unsigned long long*>(counts), partials);
+  MI_CHECK_LAUNCH("eval_group");
   return MI_OK;
 }
 

@@ -175,6 +175,7 @@ SIGNATURES = {
     "mi_train_group_plan_bytes": (_sz, [_i32]),
     "mi_train_group_plan": (_i32, [_p, _i32, _i64, _i32, _p, _p, _sz, _p, _p]),
     "mi_train_group_step": (_i32, [_p, _i32, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _i32, _p]),
+    "mi_eval_group": (_i32, [_p, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _i32, _p]),
 }
 
 _lib = None

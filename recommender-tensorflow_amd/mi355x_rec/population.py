@@ -11,11 +11,14 @@ import torch
 
 from . import _lib
 from .engine import DeepFM
+from .metrics import metrics_from_counters
 
 
 class FusedPopulation:
     MAX_MEMBERS = _lib.FUSED_GROUP_MAX_MEMBERS
     SWEEP_BLOCKS = 0     # workgroups of each member's all-rows sweep; 0: the library's choice (tests: results do not depend on it)
+    EVAL_BLOCKS = 0      # workgroups per member of an evaluation (mi_eval_group's X); 0: the library's choice (the same holds)
+    EVAL_BATCH = 32      # evaluate()'s tile size when neither the caller nor an earlier step names one
 
     def __init__(self, engines):
         engines = list(engines)
@@ -45,7 +48,10 @@ class FusedPopulation:
         self.F = first.F
         self.device = first.device
         self.k = first.k
-        self._plan = None          # (B, struct, device table, the members' schedule generations, what the struct points to)
+        self._plans = {}           # B -> (B, struct, device table, the members' schedule generations, what the struct points to)
+        self._last_b = None        # the batch size of the latest train_step
+        self._eval_buf = {}        # (B, N, with logits) -> evaluate()'s output buffer and its views
+        self.eval_out = None       # the latest evaluate()'s raw results on the host: hist, counts, partials, batch_loss
         self._out = {}             # B -> (loss [M], logits [M, B])
         self._table_len = 0        # the shortest schedule table of the members (steps below it need no look at the schedules)
 
@@ -56,7 +62,7 @@ class FusedPopulation:
     def rebuild(self):
         """Forget the plan: the next step makes a new one.  For a caller who REPLACED a member's tensors (load_state_dict
         copies into them in place and needs none)."""
-        self._plan = None
+        self._plans = {}
 
     def _describe(self, e, B, keep_alive):
         """engine e as a mi_fused_member_t for batches of B (keep_alive: the tensors the struct points to and e does not hold)"""
@@ -90,8 +96,24 @@ class FusedPopulation:
         table = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
         plan = _lib.FusedGroupPlan()
         self.k.mi_train_group_plan(members, self.M, B, self.F, self.engines[0].field_off, table, table.numel(), plan)
-        self._plan = (B, plan, table, [e.sched.gen for e in self.engines], keep_alive)
-        return self._plan
+        self._plans[B] = (B, plan, table, [e.sched.gen for e in self.engines], keep_alive)
+        return self._plans[B]
+
+    def _check_limits(self, B):
+        for i, e in enumerate(self.engines):
+            why = e._fused_step_limit(B)
+            if why is not None:
+                raise ValueError("FusedPopulation: member %d: the model has %s; use train_step" % (i, why))
+
+    def _plan_for(self, B):
+        """The plan for batches (tiles) of B examples: the one in hand while no member's schedule table has moved, else a new
+        one.  Plans are kept per batch size, so training and evaluating at two sizes alternate without a rebuild."""
+        plan = self._plans.get(B)
+        if plan is None:
+            self._check_limits(B)
+        if plan is None or any(e.sched.gen != g for e, g in zip(self.engines, plan[3])):
+            plan = self._build(B)
+        return plan
 
     # ------------------------------------------------------------------ the step
     def _check_batch(self, ids, labels):
@@ -118,19 +140,15 @@ class FusedPopulation:
             if e.step + 1 != step:
                 raise ValueError("FusedPopulation: member %d is at step %d, member 0 at step %d: the members of a population "
                                  "step together (bring the others up with their own fused_train_step)" % (i, e.step, step - 1))
-        plan = self._plan
-        if plan is None or plan[0] != B:
-            for i, e in enumerate(engines):
-                why = e._fused_step_limit(B)
-                if why is not None:
-                    raise ValueError("FusedPopulation: member %d: the model has %s; use train_step" % (i, why))
+        if B not in self._plans:
+            self._check_limits(B)                     # (a batch outside the kernel's scope: refused before anything is touched)
         if step >= self._table_len or any(e._final_step != e.step for e in engines):
             for e in engines:
                 e.finalize_rows()                     # (a no-op after a fused step)
                 e.sched.lr_t(step)                    # (extends the member's table when the run outgrows it: gen changes)
             self._table_len = min(len(e.sched.host) for e in engines)
-        if plan is None or plan[0] != B or any(e.sched.gen != g for e, g in zip(engines, plan[3])):
-            plan = self._build(B)
+        plan = self._plan_for(B)
+        self._last_b = B
         if out is None:
             out = self._out.get(B)
             if out is None:
@@ -146,3 +164,65 @@ class FusedPopulation:
             e.step = step
             e._final_step = step
         return loss, logits
+
+    # ------------------------------------------------------------------ evaluation
+    def evaluate(self, ids, labels, batch_size=None, return_logits=False):
+        """Every member's EVAL metrics over a whole evaluation set as ONE launch (mi_eval_group) and one device-to-host copy:
+        a list of M dicts with the keys of metrics.metrics_from_counters plus "loss", the fp64 mean over the fp32 losses of
+        the batches of batch_size examples (tf.metrics.mean over batch losses; the last batch may be short and is reduced
+        with its own 1 / n) — what Estimator.evaluate reports for the member on these batches.  ids int32 [N, F], labels uint8
+        [N], on the population's device, one set for all members.  batch_size None: that of the latest train_step, else
+        EVAL_BATCH.  No dropout; no member's variables, slots, step or schedule change.  return_logits: (metrics, logits
+        [M, N] device tensor)."""
+        M, F = self.M, self.F
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or not ids.is_contiguous() or ids.dim() != 2 \
+                or ids.shape[1] != F:
+            raise ValueError("FusedPopulation: ids must be a contiguous int32 [N, %d] tensor" % F)
+        N = int(ids.shape[0])
+        if N < 1:
+            raise ValueError("FusedPopulation: no examples to evaluate")
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or not labels.is_contiguous() \
+                or tuple(labels.shape) != (N,):
+            raise ValueError("FusedPopulation: labels must be a contiguous uint8 [N] tensor (N = %d)" % N)
+        if ids.device.type != self.device.type or labels.device.type != self.device.type:
+            raise ValueError("FusedPopulation: ids and labels must live on %s" % self.device)
+        B = int(batch_size) if batch_size is not None else (self._last_b or self.EVAL_BATCH)
+        if B < 1:
+            raise ValueError("FusedPopulation: batch_size=%d (at least 1)" % B)
+        for e in self.engines:
+            e.finalize_rows()                         # (a no-op after a fused step)
+        plan = self._plan_for(B)
+        T, n_tail = -(-N // B), N % B
+        key = (B, N, bool(return_logits))
+        buf = self._eval_buf.get(key)
+        if buf is None:
+            # one allocation, so that one copy brings everything home: [hist | counts] int64, partials f64, batch losses f32
+            n_int, n_par, n_loss = M * (2 * 201 + 8), M * T * 3, M * T
+            raw = torch.empty(8 * (n_int + n_par) + 4 * n_loss, dtype=torch.uint8, device=self.device)
+            ints = raw[:8 * n_int].view(torch.int64)
+            tail = torch.tensor([float(np.float32(1.0 / n_tail)) if (n_tail and e.reduction == "mean") else 1.0
+                                 for e in self.engines], dtype=torch.float32).to(self.device)
+            buf = self._eval_buf[key] = dict(
+                raw=raw, ints=ints, hist=ints[:M * 402].view(M, 2, 201), counts=ints[M * 402:].view(M, 8),
+                partials=raw[8 * n_int:8 * (n_int + n_par)].view(torch.float64).view(M, T, 3),
+                loss=raw[8 * (n_int + n_par):].view(torch.float32).view(M, T), tail=tail,
+                logits=torch.empty(M, N, dtype=torch.float32, device=self.device) if return_logits else None)
+            if len(self._eval_buf) > 4:
+                self._eval_buf.pop(next(iter(self._eval_buf)))
+        buf["ints"].zero_()
+        self.k.mi_eval_group(plan[1], M, ids, labels, N, buf["tail"], buf["logits"], buf["loss"], buf["hist"], buf["counts"],
+                             buf["partials"], int(self.EVAL_BLOCKS))
+        host = buf["raw"].cpu().numpy()
+        n_int, n_par = M * 410, M * T * 3
+        ints = host[:8 * n_int].view(np.int64)
+        hist, counts = ints[:M * 402].reshape(M, 2, 201), ints[M * 402:].reshape(M, 8)
+        partials = host[8 * n_int:8 * (n_int + n_par)].view(np.float64).reshape(M, T, 3)
+        losses = host[8 * (n_int + n_par):].view(np.float32).reshape(M, T)
+        sums = np.cumsum(partials, axis=1)[:, -1, :]          # (the tiles in ascending order, one addition after the other)
+        self.eval_out = dict(hist=hist, counts=counts, partials=partials, batch_loss=losses)     # (the latest evaluation, raw)
+        out = []
+        for i in range(M):
+            m = metrics_from_counters(hist[i], counts[i], sums[i])
+            m["loss"] = float(np.cumsum(losses[i].astype(np.float64))[-1] / T)
+            out.append(m)
+        return (out, buf["logits"]) if return_logits else out

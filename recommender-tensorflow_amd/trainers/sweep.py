@@ -10,6 +10,11 @@ Every member is an ordinary Estimator of trainers.deep_fm.model_fn with model_di
 checkpoints and export are accepted by ``trainers.deep_fm --restore``, ``trainers.predict`` and ``trainers.recommend``.
 <job-dir>/sweep.json lists the members, best first.
 
+--eval-every N: the held-out set is read and transformed once, kept on the device, and every N steps (and at the last) ALL
+members are evaluated on all of it in one launch (FusedPopulation.evaluate): <job-dir>/sweep_eval.jsonl holds one line per
+evaluation — the members' learning curves — and sweep.json names every member's best point.  --final-eval fused takes the
+end-of-sweep metrics from that evaluation too, instead of one Estimator.evaluate per member.
+
 trainers.deep_fm has no learning-rate flag (the reference has none): a member restored through ``trainers.deep_fm
 --restore`` continues at that CLI's 0.001, a member restored through ``trainers.sweep --restore`` at its own rate."""
 import itertools
@@ -56,6 +61,13 @@ def make_parser():
     p.add_argument("--select", default="auc", choices=["auc", "accuracy", "auc_precision_recall", "loss", "average_loss"],
                    help="the evaluation metric sweep.json is sorted by, best first (loss / average_loss: lowest first; "
                         "default: %(default)s)")
+    p.add_argument("--eval-every", type=int, default=0, metavar="N",
+                   help="evaluate every member on the whole test set every N steps and at the last step, in one launch for all "
+                        "of them; one line per evaluation goes to <job-dir>/sweep_eval.jsonl and sweep.json gains best_step / "
+                        "best_value by --select (default: 0 = off)")
+    p.add_argument("--final-eval", default="layered", choices=["layered", "fused"],
+                   help="where the end-of-sweep metrics come from: one Estimator.evaluate per member (layered) or the one-launch "
+                        "population evaluation (fused) (default: %(default)s)")
     return p
 
 
@@ -109,9 +121,58 @@ def build(members, features, labels, batch_size):
     return FusedPopulation([est._engine() for est in members])
 
 
-def train(members, input_fn, max_steps, config, job_dir=None, batch_size=None):
+class PopulationEval:
+    """The held-out set on the device and the members' curves on it: every run() is one FusedPopulation.evaluate (one launch
+    for all members), one line of <job-dir>/sweep_eval.jsonl and one log line."""
+
+    def __init__(self, test_csv, batch_size, select, job_dir, every=0):
+        self.test_csv, self.batch_size, self.select, self.job_dir, self.every = test_csv, batch_size, select, job_dir, int(every)
+        self.path = os.path.join(job_dir, "sweep_eval.jsonl")
+        self.data = None
+        self.curve = []            # (global_step, [the members' metrics]), in step order
+        if os.path.exists(self.path):                                   # (--restore: the curves carry on)
+            with open(self.path) as f:
+                self.curve = [(rec["global_step"], rec["members"]) for rec in map(json.loads, f)]
+
+    def load(self, plan, dev):
+        """the test set, read and transformed ONCE: ids int32 [N, F] and labels uint8 [N] on the device"""
+        ids, ys = [], []
+        for features, labels in get_input_fn(self.test_csv, ModeKeys.EVAL, batch_size=4096)():
+            ids.append(plan.transform(features)[0])
+            ys.append(np.asarray(labels).reshape(-1).astype(np.uint8))
+        if not ids:
+            raise ValueError("no evaluation data in %s" % self.test_csv)
+        self.data = (torch.from_numpy(np.ascontiguousarray(np.concatenate(ids))).to(dev),
+                     torch.from_numpy(np.ascontiguousarray(np.concatenate(ys))).to(dev))
+
+    def run(self, pop, step, lead):
+        """All members on the whole test set at global step `step`; returns their metrics (at most once per step)"""
+        if self.curve and self.curve[-1][0] == step:
+            return self.curve[-1][1]
+        if self.data is None:
+            self.load(lead.params["_store"]["plan"], lead._engine().device)
+        metrics = [{k: float(v) for k, v in m.items()} for m in pop.evaluate(self.data[0], self.data[1], batch_size=self.batch_size)]
+        self.curve.append((step, metrics))
+        os.makedirs(self.job_dir, exist_ok=True)
+        with open(self.path, "a") as f:
+            f.write(json.dumps({"global_step": step, "members": metrics}) + "\n")
+        vals = np.asarray([m[self.select] for m in metrics])
+        best, worst = (vals.min(), vals.max()) if self.select in _ASCENDING else (vals.max(), vals.min())
+        print("INFO: evaluation at step %d (%d members, %d examples): %s best = %.6f, median = %.6f, worst = %.6f" % (
+            step, len(metrics), self.data[1].numel(), self.select, best, float(np.median(vals)), worst))
+        return metrics
+
+    def best(self, i):
+        """(best_step, best_value) of member i's curve by the select metric; the earliest step among equals"""
+        sign = 1.0 if self.select in _ASCENDING else -1.0
+        step, ms = min(self.curve, key=lambda rec: (sign * rec[1][i][self.select], rec[0]))
+        return step, ms[i][self.select]
+
+
+def train(members, input_fn, max_steps, config, job_dir=None, batch_size=None, evaluator=None):
     """The sweep's loop: ONE input pipeline — every batch is read and its ids are transformed once (in groups, as
-    Estimator._grouped does for small batches) — and one population step per batch.  Returns the population."""
+    Estimator._grouped does for small batches) — and one population step per batch.  evaluator: a PopulationEval whose
+    run() is due every evaluator.every steps.  Returns the population."""
     lead = members[0]
     pop = None
     t_log = t_ckpt = time.time()
@@ -150,6 +211,8 @@ def train(members, input_fn, max_steps, config, job_dir=None, batch_size=None):
                 log.write(json.dumps({"global_step": step, "loss": [float(v) for v in ls]}) + "\n")
                 log.flush()
             t_log, n_log = now, 0
+        if evaluator is not None and evaluator.every > 0 and step % evaluator.every == 0:
+            evaluator.run(pop, step, lead)
         if config.save_checkpoints_secs and time.time() - t_ckpt >= config.save_checkpoints_secs:
             for est in members:
                 est.save_checkpoint()
@@ -170,19 +233,34 @@ def train_and_evaluate(args):
     config = _cli.get_run_config()
     config.device = args.device
     members = make_members(args, hps, config)
+    eval_every = int(getattr(args, "eval_every", 0) or 0)
+    final_eval = getattr(args, "final_eval", "layered")
+    if eval_every < 0:
+        raise ValueError("--eval-every %d (0 = off, or a number of steps)" % eval_every)
+    evaluator = None
+    if eval_every or final_eval == "fused":
+        evaluator = PopulationEval(args.test_csv, args.batch_size, args.select, args.job_dir, eval_every)
     pop = train(members, get_input_fn(args.train_csv, batch_size=args.batch_size), args.train_steps, config, args.job_dir,
-                args.batch_size)
+                args.batch_size, evaluator)
     if pop is None:
         raise ValueError("no training data in %s" % args.train_csv)
+    fused = None
+    if evaluator is not None:
+        fused = evaluator.run(pop, members[0].global_step, members[0])      # (the last step, unless it was just evaluated)
     eval_fn = get_input_fn(args.test_csv, ModeKeys.EVAL, batch_size=args.batch_size)
     exporter = get_exporter(serving_input_fn)
     rows = []
     for i, (est, hp) in enumerate(zip(members, hps)):
         est.save_checkpoint()
-        metrics = est.evaluate(eval_fn)
+        if final_eval == "fused":
+            metrics = dict(fused[i], global_step=est.global_step)
+        else:
+            metrics = est.evaluate(eval_fn)
         export = exporter.export(est, os.path.join(est.model_dir, "export"))
         rows.append({"member": i, "dir": est.model_dir, "export": export, "global_step": est.global_step, "params": hp,
                      "flags": member_flags(args, hp), "metrics": {k: float(v) for k, v in metrics.items()}})
+        if eval_every:
+            rows[-1]["best_step"], rows[-1]["best_value"] = evaluator.best(i)
     sign = 1.0 if args.select in _ASCENDING else -1.0
     rows.sort(key=lambda r: (sign * r["metrics"][args.select], r["member"]))
     with open(os.path.join(args.job_dir, "sweep.json"), "w") as f:
