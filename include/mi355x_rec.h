@@ -864,6 +864,62 @@ int32_t mi_eval_group(const mi_fused_group_plan_t* plan, int32_t n_members, cons
                       const float* tail_scale, float* logits, float* batch_loss, int64_t* hist, int64_t* counts, double* partials,
                       int32_t blocks, mi_stream_t stream);
 
+/* ---- serving an ensemble: M models over one request batch, averaged, as one launch (csrc/serve.hip) --------------------
+ * The payoff of a sweep (trainers/sweep.py): its best M members scored and averaged as ONE model.  Grid (ceil(B / 32), M):
+ * row y of the grid runs the device code of mi_predict_fused on member y (member_logits[y, b] holds the bits of
+ * mi_predict_fused on that member alone), and the members of a tile of 32 requests are combined inside the launch by the
+ * workgroup that arrives last at the tile's ticket (an integer fetch_add; agent-scope release before it, acquire after it):
+ *   logits[b] = (((z_0 + z_1) + z_2) + ... + z_{M-1}) / (float)M     fp32, ascending member order, one rounding per
+ *   operation, IEEE division; logistic / probabilities / class_ids: mi_binary_predictions' device functions on that logit.
+ * No workgroup waits for another (no spin, no grid barrier, no float atomics): the launch cannot hang, and the bits depend on
+ * neither dispatch order nor placement.  M = 1 takes the same path (z_0 / 1.0f).
+ *
+ * mi_serve_member_t: the per-model arguments of mi_predict_fused (same meaning, same limits; layer_off / widths on the
+ *   host, read by mi_predict_group_plan only).  Members may differ in all of them; they share F, n_numeric and
+ *   field_off [F] (one set of feature columns). */
+#define MI_PREDICT_GROUP_MAX_MEMBERS 256
+typedef struct mi_serve_member {
+  const float* table;
+  int64_t table_stride;
+  const float* lin_w;
+  const float* dense;
+  const int64_t* layer_off;
+  const int32_t* widths;
+  int64_t lin_bias_off, num_emb_off, lin_num_off;
+  uint64_t wide_fields;
+  int32_t lin_stride, E, n_layers, activation, use_linear, use_fm, use_dnn, numeric_raw;
+} mi_serve_member_t;
+
+/* What mi_predict_group_plan leaves on the host for mi_predict_group (caller-owned; treat as opaque). */
+typedef struct mi_serve_group_plan {
+  void* device_table;
+  uint64_t magic;
+  int32_t n_members, F, n_numeric;
+  uint32_t lds_bytes;
+} mi_serve_group_plan_t;
+
+/* mi_predict_group_plan: validates every member with the checks and messages of mi_predict_fused (prefixed "member i:"),
+ * then writes the members' descriptions into device_table (mi_predict_group_plan_bytes(n_members) bytes of device memory,
+ * 16-byte aligned; the copy has completed when the call returns) and *plan.  The plan holds the members' pointers: make a
+ * new one when a buffer changes.  n_members in [1, MI_PREDICT_GROUP_MAX_MEMBERS] (MI_ERR_INVALID below,
+ * MI_ERR_UNSUPPORTED above).  A refused plan writes neither device_table nor *plan.
+ *
+ * mi_predict_group: one launch, no host-to-device copy, no synchronisation, no workspace.
+ *   ids [B, F] int32, x_num [B, n_numeric] (NULL without numeric columns): one request batch for all members;
+ *   member_logits [M, B] fp32, required: every member's own logit, and where the members meet;
+ *   tickets int32 [ceil(B / 32)], caller-owned: ZERO on entry, zero again when the call has completed (the reducer of a
+ *     tile resets it), so one buffer serves call after call on a stream;
+ *   logits [B], logistic [B], probabilities [B, 2], class_ids [B] int64: any may be NULL (not all four).
+ * Dynamic LDS is the largest member's.  Refused on the host before anything is launched (MI_ERR_INVALID): a plan
+ * mi_predict_group_plan did not write, n_members other than the plan's, B < 1, NULL ids / member_logits / tickets, NULL
+ * x_num with numeric columns, no output. */
+size_t mi_predict_group_plan_bytes(int32_t n_members);
+int32_t mi_predict_group_plan(const mi_serve_member_t* members, int32_t n_members, int32_t F, int32_t n_numeric,
+                              const int64_t* field_off, void* device_table, mi_serve_group_plan_t* plan, mi_stream_t stream);
+int32_t mi_predict_group(const mi_serve_group_plan_t* plan, int32_t n_members, const int32_t* ids, const float* x_num, int64_t B,
+                         float* member_logits, int32_t* tickets, float* logits, float* logistic, float* probabilities,
+                         int64_t* class_ids, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

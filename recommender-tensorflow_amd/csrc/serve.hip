@@ -17,6 +17,31 @@
 //                     widths up to 512).  The logits layer is the same code with one output row.
 //     4. head         logit = ((lin + bias) + fm) + dnn, then the device functions of mi_binary_predictions.
 //
+//   serve_block       steps 0 to 3 and the sum of the head, as one __device__ function: the ONE definition of a request's
+//                     logit, run by both kernels of this file.
+//
+//   predict_group_k   an ensemble of M models over one request batch in ONE launch (mi_predict_group): grid
+//                     (ceil(B / 32), M), blockIdx.y = the member, blockIdx.x = the tile of 32 requests.  A workgroup copies
+//                     its member's ServeArgs from the device table mi_predict_group_plan wrote into LDS, thread 0 fills in
+//                     what changes per call (ids, x_num, B), and serve_block runs on it: member_logits[y, b] holds the bits
+//                     of mi_predict_fused on that member alone.  The members of a tile are then combined inside the launch:
+//       ticket        after its logits are stored and published (every wave drains its stores, a barrier, lane 0 issues an
+//                     agent-scope release fence and waits again), lane 0 draws a ticket from tickets[tile] with a relaxed
+//                     agent-scope fetch_add.  The workgroup that draws M - 1 is the tile's reducer — whichever member it is;
+//                     the others are done.  "I am last" reaches the workgroup through red_lin (no further LDS object).
+//       reduce        the reducer's lane 0 issues an agent-scope acquire fence, then a barrier; its first 32 threads read the
+//                     M logits of their request with plain loads, z = (((z_0 + z_1) + z_2) + ...) / (float)M in ascending
+//                     member order, one rounding per operation (this file is compiled -ffp-contract=off), and write the
+//                     four outputs with the head of predict_fused_k.  It then stores 0 back to tickets[tile]: the array is
+//                     zero again when the launch has completed.
+//                     THIS IS THE FIRST KERNEL OF THE PROJECT IN WHICH A WORKGROUP READS WHAT ANOTHER WROTE IN THE SAME
+//                     LAUNCH.  The invariant that still holds: NO WORKGROUP WAITS FOR ANOTHER — no spin, no grid barrier, no
+//                     cooperative launch, no float atomics.  Every workgroup runs to its end whatever the others do, so the
+//                     kernel cannot hang, and since the reducer is defined by the count alone and adds in member order,
+//                     the result depends on neither the dispatch order nor the placement of the grid.  A workgroup-scope
+//                     fence or a plain flag would not publish the logits to a workgroup on another XCD; the agent-scope
+//                     pair does.  M = 1 takes the same path: the only arriver is the reducer and z_0 / 1.0f is z_0.
+//
 // Arithmetic: fp32 variables, exact fp32 products (v_mfma_f32_32x32x2_f32), fp32 accumulation.  At request sizes the
 // kernel waits for weights, not for the matrix pipe: no 16-bit operand split.
 #include "common.h"
@@ -212,20 +237,15 @@ __device__ __forceinline__ void run_layer(const ServeArgs& p, const Layer ly, bo
   epilogue<NT>(acc, p.dense + ly.b_off, N, last ? 0 : p.act, out, wave, col, h);
 }
 
-__global__ __launch_bounds__(kThreads) void predict_fused_k(const ServeArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  __shared__ Layer layers[kMaxLayers];
-  __shared__ float red_lin[kParts][kRB], red_fm[kParts][kRB];
+// Steps 0 to 3 for the 32 requests b0 .. of p and the sum of the head: the logit of request b0 + tid in the threads
+// tid < 32 whose request exists (0 elsewhere).  layers: the caller's LDS copy of p.l; lds: F 32 ints + the two buffers.
+__device__ __forceinline__ float serve_block(const ServeArgs& p, char* lds, const Layer* layers, float (*red_lin)[kRB],
+                                             float (*red_fm)[kRB], int64_t b0) {
   int32_t* rows = reinterpret_cast<int32_t*>(lds);                // [F][32]
   float* buf0 = reinterpret_cast<float*>(lds) + p.F * kRB;
   float* buf1 = buf0 + p.buf_a;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31, h = lane >> 5;
-  const int64_t b0 = static_cast<int64_t>(blockIdx.x) * kRB;
   const int F = p.F, E = p.E, nd = p.nd;
-  // (the layer table: compile-time indices into the kernel arguments, runtime indices into LDS afterwards)
-#pragma unroll
-  for (int i = 0; i < kMaxLayers; ++i)
-    if (tid == i) layers[i] = p.l[i];
   // 0. the requests' rows (requests past B repeat the last one: loads stay legal, stores are predicated)
   for (int i = tid; i < F * kRB; i += kThreads) {
     const int f = i >> 5;
@@ -304,10 +324,9 @@ __global__ __launch_bounds__(kThreads) void predict_fused_k(const ServeArgs p) {
   }
   if (L == 0) __syncthreads();                                    // (red_lin / red_fm)
 
-  // 4. head: the order of mi_sigmoid_ce_head, the outputs of mi_binary_predictions
+  // 4. the head's sum: the order of mi_sigmoid_ce_head
+  float z = 0.f;
   if (tid < kRB && b0 + tid < p.B) {
-    const int64_t b = b0 + tid;
-    float z = 0.f;
     if (p.use_linear) {
       float lin = 0.f;
 #pragma unroll
@@ -323,12 +342,84 @@ __global__ __launch_bounds__(kThreads) void predict_fused_k(const ServeArgs p) {
       z = z + 0.5f * t;
     }
     if (L) z = z + in[tid];                                       // the logits layer's one row
-    if (p.logits) p.logits[b] = z;
-    const float pr = mi_sigmoid_stable(z);
-    if (p.logistic) p.logistic[b] = pr;
-    if (p.probabilities) { p.probabilities[2 * b] = 1.f - pr; p.probabilities[2 * b + 1] = pr; }
-    if (p.class_ids) p.class_ids[b] = pr > 0.5f ? 1 : 0;
   }
+  return z;
+}
+
+// the outputs of mi_binary_predictions for request b with logit z (any pointer may be NULL)
+__device__ __forceinline__ void write_head(float z, int64_t b, float* logits, float* logistic, float* probabilities,
+                                           int64_t* class_ids) {
+  if (logits) logits[b] = z;
+  const float pr = mi_sigmoid_stable(z);
+  if (logistic) logistic[b] = pr;
+  if (probabilities) { probabilities[2 * b] = 1.f - pr; probabilities[2 * b + 1] = pr; }
+  if (class_ids) class_ids[b] = pr > 0.5f ? 1 : 0;
+}
+
+__global__ __launch_bounds__(kThreads) void predict_fused_k(const ServeArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  __shared__ Layer layers[kMaxLayers];
+  __shared__ float red_lin[kParts][kRB], red_fm[kParts][kRB];
+  const int tid = threadIdx.x;
+  const int64_t b0 = static_cast<int64_t>(blockIdx.x) * kRB;
+  // (the layer table: compile-time indices into the kernel arguments, runtime indices into LDS afterwards)
+#pragma unroll
+  for (int i = 0; i < kMaxLayers; ++i)
+    if (tid == i) layers[i] = p.l[i];
+  const float z = serve_block(p, lds, layers, red_lin, red_fm, b0);
+  if (tid < kRB && b0 + tid < p.B) write_head(z, b0 + tid, p.logits, p.logistic, p.probabilities, p.class_ids);
+}
+
+static_assert(sizeof(ServeArgs) % sizeof(uint32_t) == 0, "ServeArgs is copied word by word");
+
+__global__ __launch_bounds__(kThreads) void predict_group_k(const ServeArgs* __restrict__ members, int32_t M,
+                                                            const int32_t* __restrict__ ids, const float* __restrict__ x_num,
+                                                            int64_t B, float* member_logits, int32_t* tickets,
+                                                            float* logits, float* logistic, float* probabilities,
+                                                            int64_t* class_ids) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  __shared__ ServeArgs sp;
+  __shared__ Layer layers[kMaxLayers];
+  __shared__ float red_lin[kParts][kRB], red_fm[kParts][kRB];
+  const int tid = threadIdx.x, y = blockIdx.y;
+  const int64_t b0 = static_cast<int64_t>(blockIdx.x) * kRB;
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(members + y);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(&sp);
+    for (int i = tid; i < static_cast<int>(sizeof(ServeArgs) / sizeof(uint32_t)); i += kThreads) dst[i] = src[i];
+  }
+  __syncthreads();
+  if (tid == 0) { sp.ids = ids; sp.x_num = x_num; sp.B = B; }
+  if (tid < kMaxLayers) layers[tid] = sp.l[tid];
+  __syncthreads();
+  const float z = serve_block(sp, lds, layers, red_lin, red_fm, b0);
+  if (tid < kRB && b0 + tid < B) member_logits[static_cast<int64_t>(y) * B + b0 + tid] = z;
+
+  // publish, then draw the ticket: every wave drains its stores, a barrier, lane 0 releases at agent scope and waits
+  // again (the fence before the fetch_add, always), relaxed agent-scope fetch_add.  The last of the M arrivers reduces.
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();                                                // (also: every read of red_lin by the head's sum is over)
+  int32_t* last = reinterpret_cast<int32_t*>(&red_lin[0][0]);
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int32_t t = __hip_atomic_fetch_add(&tickets[blockIdx.x], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool am_last = t == M - 1;
+    if (am_last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    *last = am_last ? 1 : 0;
+  }
+  __syncthreads();
+  if (!*last) return;                                             // nobody waits: the other M - 1 workgroups are done
+  if (tid < kRB && b0 + tid < B) {
+    const int64_t b = b0 + tid;
+    float acc = member_logits[b];
+    for (int m = 1; m < M; ++m) acc = acc + member_logits[static_cast<int64_t>(m) * B + b];
+    write_head(acc / static_cast<float>(M), b, logits, logistic, probabilities, class_ids);
+  }
+  if (tid == 0) __hip_atomic_store(&tickets[blockIdx.x], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 int32_t unsupported(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
@@ -340,6 +431,80 @@ int32_t unsupported(const char* fmt, ...) {
   va_end(ap);
   mi::set_error("%s", buf);
   return MI_ERR_UNSUPPORTED;
+}
+
+constexpr uint64_t kGroupMagic = 0x6d69707265646772ull;         // "mipredgr"
+
+// The model-side checks of mi_predict_fused and the ServeArgs they describe (ids, x_num, B and the outputs are left to the
+// caller); lds: the dynamic LDS of a workgroup.  have_ids / have_x / have_out: whether the call brought them.  One function
+// for mi_predict_fused and for every member of mi_predict_group_plan: the same checks, the same messages.
+int32_t plan_serve(const float* table, int64_t table_stride, const float* lin_w, int32_t lin_stride, const int64_t* field_off,
+                   int32_t F, int32_t E, int32_t n_numeric, const float* dense, const int64_t* layer_off, const int32_t* widths,
+                   int32_t n_layers, int32_t activation, int32_t use_linear, int32_t use_fm, int32_t use_dnn,
+                   int32_t numeric_raw, int64_t lin_bias_off, int64_t num_emb_off, int64_t lin_num_off, uint64_t wide_fields,
+                   bool have_ids, bool have_x, bool have_out, ServeArgs& a, size_t& lds) {
+  MI_REQUIRE(F >= 0 && n_numeric >= 0 && F + n_numeric >= 1, "predict_fused: F=%d n_numeric=%d (at least one column)", F, n_numeric);
+  if (F > kMaxFields) return unsupported("predict_fused: F=%d categorical fields (at most %d)", F, kMaxFields);
+  MI_REQUIRE(use_linear || use_fm || use_dnn, "predict_fused: no part of the model is switched on");
+  MI_REQUIRE(have_out, "predict_fused: no output requested");
+  MI_REQUIRE(activation >= 0 && activation <= 3, "predict_fused: activation %d", activation);
+  MI_REQUIRE(!(numeric_raw && use_fm), "predict_fused: raw numeric columns belong to the models without an FM term");
+  const bool emb = (use_fm || use_dnn) && F > 0;                  // the table is read
+  const bool num_emb = n_numeric > 0 && !numeric_raw;
+  if ((emb || num_emb) && (E < 4 || E > 256 || (E & 3)))
+    return unsupported("predict_fused: embedding size %d unsupported (multiple of 4 in [4,256])", E);
+  MI_REQUIRE(!emb || (table && mi::aligned16(table)), "predict_fused: table (16-byte aligned)");
+  MI_REQUIRE(table_stride == 0 || (table_stride >= E && (table_stride & 3) == 0),
+             "predict_fused: table_stride=%lld (0 = E, else >= E and a multiple of 4)", (long long)table_stride);
+  MI_REQUIRE(F == 0 || (field_off && have_ids), "predict_fused: field_off / ids");
+  MI_REQUIRE(n_numeric == 0 || have_x, "predict_fused: x_num");
+  MI_REQUIRE(!(use_linear && F > 0 && wide_fields) || (lin_w && lin_stride >= 1), "predict_fused: lin_w / lin_stride=%d", lin_stride);
+  MI_REQUIRE(!(use_linear || use_dnn || num_emb) || dense, "predict_fused: dense");
+  MI_REQUIRE(!use_linear || lin_bias_off >= 0, "predict_fused: lin_bias_off");
+  MI_REQUIRE(!(use_linear && n_numeric) || lin_num_off >= 0, "predict_fused: lin_num_off");
+  MI_REQUIRE(!num_emb || (num_emb_off >= 0 && (num_emb_off & 3) == 0 && mi::aligned16(dense)),
+             "predict_fused: num_emb_off=%lld (a multiple of 4 floats into a 16-byte aligned buffer)", (long long)num_emb_off);
+  MI_REQUIRE(!(num_emb && !use_fm && !use_dnn), "predict_fused: numeric embeddings need the FM term or the DNN");
+  MI_REQUIRE(use_dnn ? n_layers >= 1 : n_layers == 0, "predict_fused: %d layers (a DNN has at least its logits layer)", n_layers);
+  if (n_layers > kMaxLayers)
+    return unsupported("predict_fused: %d hidden layers (at most %d)", n_layers - 1, kMaxLayers - 1);
+  MI_REQUIRE(n_layers == 0 || (layer_off && widths), "predict_fused: layer_off / widths");
+  int wa = 0, wb = 0;                    // widths of the layer outputs in the first / second LDS buffer
+  for (int i = 0; i < n_layers; ++i) {
+    const int fi = widths[i], fo = widths[i + 1];
+    MI_REQUIRE(fi >= 1 && fo >= 1, "predict_fused: width %d -> %d", fi, fo);
+    MI_REQUIRE(i + 1 < n_layers || fo == 1, "predict_fused: the last layer has %d outputs (1 expected)", fo);
+    MI_REQUIRE(layer_off[2 * i] >= 0 && layer_off[2 * i + 1] >= 0, "predict_fused: layer offsets");
+    if (fo > kMaxWidth) return unsupported("predict_fused: hidden width %d (at most %d)", fo, kMaxWidth);
+    int& w = (i & 1) ? wb : wa;
+    if (fo > w) w = fo;
+    a.l[i] = Layer{layer_off[2 * i], layer_off[2 * i + 1], fi, fo};
+  }
+  if (n_layers) {
+    const int64_t d_in = (emb ? static_cast<int64_t>(F) * E : 0) + static_cast<int64_t>(n_numeric) * (numeric_raw ? 1 : E);
+    MI_REQUIRE(widths[0] >= d_in, "predict_fused: widths[0]=%d below the %lld input columns", widths[0], (long long)d_in);
+  }
+  lds = sizeof(float) * kRB * (static_cast<size_t>(F) + wa + wb);
+  if (lds + 4096 > kMaxLds) return unsupported("predict_fused: %zu bytes of LDS for F=%d and widths %d / %d", lds, F, wa, wb);
+  a.table = emb ? table : nullptr; a.lin_w = lin_w; a.field_off = field_off; a.dense = dense;
+  a.ts = table_stride ? table_stride : E;
+  a.lin_bias_off = lin_bias_off; a.num_emb_off = num_emb_off; a.lin_num_off = lin_num_off;
+  a.wide_fields = use_linear ? wide_fields : 0;
+  a.F = F; a.E = E; a.nd = n_numeric; a.ls = lin_stride; a.act = activation; a.n_layers = n_layers;
+  a.use_linear = use_linear != 0; a.use_fm = use_fm != 0 && (emb || num_emb); a.raw = numeric_raw != 0;
+  a.buf_a = wa * kRB;
+  return MI_OK;
+}
+
+// dynamic LDS above 64 KB has to be asked for, per kernel
+template <typename K>
+int32_t raise_lds(K* kernel, size_t lds, const char* who) {
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             static_cast<int>(lds));
+    MI_REQUIRE(e == hipSuccess, "%s: LDS of %zu bytes: %s", who, lds, hipGetErrorString(e));
+  }
+  return MI_OK;
 }
 
 }  // namespace
@@ -360,67 +525,94 @@ int32_t mi_predict_fused(const float* table, int64_t table_stride, const float* 
                          void* workspace, size_t workspace_bytes, mi_stream_t stream) {
   (void)workspace; (void)workspace_bytes;
   MI_REQUIRE(B >= 1, "predict_fused: B=%lld (at least one request)", (long long)B);
-  MI_REQUIRE(F >= 0 && n_numeric >= 0 && F + n_numeric >= 1, "predict_fused: F=%d n_numeric=%d (at least one column)", F, n_numeric);
-  if (F > kMaxFields) return unsupported("predict_fused: F=%d categorical fields (at most %d)", F, kMaxFields);
-  MI_REQUIRE(use_linear || use_fm || use_dnn, "predict_fused: no part of the model is switched on");
-  MI_REQUIRE(logits || logistic || probabilities || class_ids, "predict_fused: no output requested");
-  MI_REQUIRE(activation >= 0 && activation <= 3, "predict_fused: activation %d", activation);
-  MI_REQUIRE(!(numeric_raw && use_fm), "predict_fused: raw numeric columns belong to the models without an FM term");
-  const bool emb = (use_fm || use_dnn) && F > 0;                  // the table is read
-  const bool num_emb = n_numeric > 0 && !numeric_raw;
-  if ((emb || num_emb) && (E < 4 || E > 256 || (E & 3)))
-    return unsupported("predict_fused: embedding size %d unsupported (multiple of 4 in [4,256])", E);
-  MI_REQUIRE(!emb || (table && mi::aligned16(table)), "predict_fused: table (16-byte aligned)");
-  MI_REQUIRE(table_stride == 0 || (table_stride >= E && (table_stride & 3) == 0),
-             "predict_fused: table_stride=%lld (0 = E, else >= E and a multiple of 4)", (long long)table_stride);
-  MI_REQUIRE(F == 0 || (field_off && ids), "predict_fused: field_off / ids");
-  MI_REQUIRE(n_numeric == 0 || x_num, "predict_fused: x_num");
-  MI_REQUIRE(!(use_linear && F > 0 && wide_fields) || (lin_w && lin_stride >= 1), "predict_fused: lin_w / lin_stride=%d", lin_stride);
-  MI_REQUIRE(!(use_linear || use_dnn || num_emb) || dense, "predict_fused: dense");
-  MI_REQUIRE(!use_linear || lin_bias_off >= 0, "predict_fused: lin_bias_off");
-  MI_REQUIRE(!(use_linear && n_numeric) || lin_num_off >= 0, "predict_fused: lin_num_off");
-  MI_REQUIRE(!num_emb || (num_emb_off >= 0 && (num_emb_off & 3) == 0 && mi::aligned16(dense)),
-             "predict_fused: num_emb_off=%lld (a multiple of 4 floats into a 16-byte aligned buffer)", (long long)num_emb_off);
-  MI_REQUIRE(!(num_emb && !use_fm && !use_dnn), "predict_fused: numeric embeddings need the FM term or the DNN");
-  MI_REQUIRE(use_dnn ? n_layers >= 1 : n_layers == 0, "predict_fused: %d layers (a DNN has at least its logits layer)", n_layers);
-  if (n_layers > kMaxLayers)
-    return unsupported("predict_fused: %d hidden layers (at most %d)", n_layers - 1, kMaxLayers - 1);
-  MI_REQUIRE(n_layers == 0 || (layer_off && widths), "predict_fused: layer_off / widths");
   ServeArgs a{};
-  int wa = 0, wb = 0;                    // widths of the layer outputs in the first / second LDS buffer
-  for (int i = 0; i < n_layers; ++i) {
-    const int fi = widths[i], fo = widths[i + 1];
-    MI_REQUIRE(fi >= 1 && fo >= 1, "predict_fused: width %d -> %d", fi, fo);
-    MI_REQUIRE(i + 1 < n_layers || fo == 1, "predict_fused: the last layer has %d outputs (1 expected)", fo);
-    MI_REQUIRE(layer_off[2 * i] >= 0 && layer_off[2 * i + 1] >= 0, "predict_fused: layer offsets");
-    if (fo > kMaxWidth) return unsupported("predict_fused: hidden width %d (at most %d)", fo, kMaxWidth);
-    int& w = (i & 1) ? wb : wa;
-    if (fo > w) w = fo;
-    a.l[i] = Layer{layer_off[2 * i], layer_off[2 * i + 1], fi, fo};
-  }
-  if (n_layers) {
-    const int64_t d_in = (emb ? static_cast<int64_t>(F) * E : 0) + static_cast<int64_t>(n_numeric) * (numeric_raw ? 1 : E);
-    MI_REQUIRE(widths[0] >= d_in, "predict_fused: widths[0]=%d below the %lld input columns", widths[0], (long long)d_in);
-  }
+  size_t lds = 0;
+  const int32_t rc = plan_serve(table, table_stride, lin_w, lin_stride, field_off, F, E, n_numeric, dense, layer_off, widths,
+                                n_layers, activation, use_linear, use_fm, use_dnn, numeric_raw, lin_bias_off, num_emb_off,
+                                lin_num_off, wide_fields, ids != nullptr, x_num != nullptr,
+                                logits || logistic || probabilities || class_ids, a, lds);
+  if (rc != MI_OK) return rc;
   const int64_t blocks = mi::ceil_div(B, kRB);
   MI_REQUIRE(blocks <= INT32_MAX, "predict_fused: grid too large");
-  const size_t lds = sizeof(float) * kRB * (static_cast<size_t>(F) + wa + wb);
-  if (lds + 4096 > kMaxLds) return unsupported("predict_fused: %zu bytes of LDS for F=%d and widths %d / %d", lds, F, wa, wb);
-  a.table = emb ? table : nullptr; a.lin_w = lin_w; a.field_off = field_off; a.ids = ids; a.x_num = x_num; a.dense = dense;
+  a.ids = ids; a.x_num = x_num; a.B = B;
   a.logits = logits; a.logistic = logistic; a.probabilities = probabilities; a.class_ids = class_ids;
-  a.B = B; a.ts = table_stride ? table_stride : E;
-  a.lin_bias_off = lin_bias_off; a.num_emb_off = num_emb_off; a.lin_num_off = lin_num_off;
-  a.wide_fields = use_linear ? wide_fields : 0;
-  a.F = F; a.E = E; a.nd = n_numeric; a.ls = lin_stride; a.act = activation; a.n_layers = n_layers;
-  a.use_linear = use_linear != 0; a.use_fm = use_fm != 0 && (emb || num_emb); a.raw = numeric_raw != 0;
-  a.buf_a = wa * kRB;
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&predict_fused_k),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    MI_REQUIRE(e == hipSuccess, "predict_fused: LDS of %zu bytes: %s", lds, hipGetErrorString(e));
-  }
+  const int32_t rl = raise_lds(&predict_fused_k, lds, "predict_fused");
+  if (rl != MI_OK) return rl;
   predict_fused_k<<<dim3(static_cast<unsigned>(blocks)), dim3(kThreads), lds, mi::as_stream(stream)>>>(a);
   MI_CHECK_LAUNCH("predict_fused");
+  return MI_OK;
+}
+
+size_t mi_predict_group_plan_bytes(int32_t n_members) {
+  return n_members < 0 ? 0 : sizeof(ServeArgs) * static_cast<size_t>(n_members);
+}
+
+int32_t mi_predict_group_plan(const mi_serve_member_t* members, int32_t n_members, int32_t F, int32_t n_numeric,
+                              const int64_t* field_off, void* device_table, mi_serve_group_plan_t* plan, mi_stream_t stream) {
+  MI_REQUIRE(plan, "predict_group_plan: plan");
+  MI_REQUIRE(n_members >= 1, "predict_group_plan: %d members (at least 1)", n_members);
+  if (n_members > MI_PREDICT_GROUP_MAX_MEMBERS)
+    return unsupported("predict_group_plan: %d members (at most %d in one launch)", n_members, MI_PREDICT_GROUP_MAX_MEMBERS);
+  MI_REQUIRE(members, "predict_group_plan: members");
+  MI_REQUIRE(device_table && mi::aligned16(device_table),
+             "predict_group_plan: device_table (mi_predict_group_plan_bytes bytes of device memory, 16-byte aligned)");
+  const size_t need = mi_predict_group_plan_bytes(n_members);
+  ServeArgs* tab = static_cast<ServeArgs*>(malloc(need));
+  MI_REQUIRE(tab, "predict_group_plan: out of host memory");
+  size_t lds = 0;
+  int32_t rc = MI_OK;
+  for (int32_t i = 0; i < n_members; ++i) {
+    const mi_serve_member_t& m = members[i];
+    size_t lds_i = 0;
+    tab[i] = ServeArgs{};
+    // (ids, x_num and the outputs belong to the call: mi_predict_group checks them)
+    rc = plan_serve(m.table, m.table_stride, m.lin_w, m.lin_stride, field_off, F, m.E, n_numeric, m.dense, m.layer_off, m.widths,
+                    m.n_layers, m.activation, m.use_linear, m.use_fm, m.use_dnn, m.numeric_raw, m.lin_bias_off, m.num_emb_off,
+                    m.lin_num_off, m.wide_fields, true, true, true, tab[i], lds_i);
+    if (rc != MI_OK) {
+      char why[512];
+      snprintf(why, sizeof(why), "%s", mi_last_error());
+      mi::set_error("predict_group_plan: member %d: %s", i, why);
+      break;
+    }
+    if (lds_i > lds) lds = lds_i;
+  }
+  if (rc == MI_OK) {
+    hipError_t e = hipMemcpyAsync(device_table, tab, need, hipMemcpyHostToDevice, mi::as_stream(stream));
+    if (e == hipSuccess) e = hipStreamSynchronize(mi::as_stream(stream));      // (tab is freed below)
+    if (e != hipSuccess) {
+      mi::set_error("predict_group_plan: copying the member table: %s", hipGetErrorString(e));
+      rc = MI_ERR_LAUNCH;
+    }
+  }
+  free(tab);
+  if (rc != MI_OK) return rc;
+  plan->device_table = device_table; plan->n_members = n_members; plan->F = F; plan->n_numeric = n_numeric;
+  plan->lds_bytes = static_cast<uint32_t>(lds); plan->magic = kGroupMagic;
+  return MI_OK;
+}
+
+int32_t mi_predict_group(const mi_serve_group_plan_t* plan, int32_t n_members, const int32_t* ids, const float* x_num, int64_t B,
+                         float* member_logits, int32_t* tickets, float* logits, float* logistic, float* probabilities,
+                         int64_t* class_ids, mi_stream_t stream) {
+  MI_REQUIRE(plan && plan->magic == kGroupMagic && plan->device_table, "predict_group: plan (not written by mi_predict_group_plan)");
+  MI_REQUIRE(n_members == plan->n_members, "predict_group: %d members, the plan has %d", n_members, plan->n_members);
+  MI_REQUIRE(n_members >= 1 && n_members <= MI_PREDICT_GROUP_MAX_MEMBERS && plan->lds_bytes + 4096 <= kMaxLds,
+             "predict_group: plan (damaged)");
+  MI_REQUIRE(B >= 1, "predict_group: B=%lld (at least one request)", (long long)B);
+  MI_REQUIRE(ids, "predict_group: ids");
+  MI_REQUIRE(plan->n_numeric == 0 || x_num, "predict_group: x_num (the plan has %d numeric columns)", plan->n_numeric);
+  MI_REQUIRE(member_logits, "predict_group: member_logits ([M, B], required: the members meet there)");
+  MI_REQUIRE(tickets, "predict_group: tickets (int32 [ceil(B / 32)], zero on entry)");
+  MI_REQUIRE(logits || logistic || probabilities || class_ids, "predict_group: no output requested");
+  const int64_t blocks = mi::ceil_div(B, kRB);
+  MI_REQUIRE(blocks <= INT32_MAX, "predict_group: grid too large");
+  const int32_t rl = raise_lds(&predict_group_k, plan->lds_bytes, "predict_group");
+  if (rl != MI_OK) return rl;
+  predict_group_k<<<dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(n_members)), dim3(kThreads), plan->lds_bytes,
+                    mi::as_stream(stream)>>>(static_cast<const ServeArgs*>(plan->device_table), n_members, ids, x_num, B,
+                                             member_logits, tickets, logits, logistic, probabilities, class_ids);
+  MI_CHECK_LAUNCH("predict_group");
   return MI_OK;
 }
 

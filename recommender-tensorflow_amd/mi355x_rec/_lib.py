@@ -76,6 +76,24 @@ class FusedGroupPlan(C.Structure):
                 ("F", C.c_int32), ("sweep_blocks", C.c_int32), ("max_step", C.c_int32), ("lds_bytes", C.c_uint32)]
 
 
+PREDICT_GROUP_MAX_MEMBERS = 256  # MI_PREDICT_GROUP_MAX_MEMBERS
+
+
+class ServeMember(C.Structure):
+    """mi_serve_member_t: one model of mi_predict_group_plan"""
+    _fields_ = [("table", C.c_void_p), ("table_stride", C.c_int64), ("lin_w", C.c_void_p), ("dense", C.c_void_p),
+                ("layer_off", C.c_void_p), ("widths", C.c_void_p), ("lin_bias_off", C.c_int64), ("num_emb_off", C.c_int64),
+                ("lin_num_off", C.c_int64), ("wide_fields", C.c_uint64), ("lin_stride", C.c_int32), ("E", C.c_int32),
+                ("n_layers", C.c_int32), ("activation", C.c_int32), ("use_linear", C.c_int32), ("use_fm", C.c_int32),
+                ("use_dnn", C.c_int32), ("numeric_raw", C.c_int32)]
+
+
+class ServeGroupPlan(C.Structure):
+    """mi_serve_group_plan_t: what mi_predict_group_plan leaves on the host for mi_predict_group"""
+    _fields_ = [("device_table", C.c_void_p), ("magic", C.c_uint64), ("n_members", C.c_int32), ("F", C.c_int32),
+                ("n_numeric", C.c_int32), ("lds_bytes", C.c_uint32)]
+
+
 _p = C.c_void_p
 _i32, _i64, _u32, _u64, _f32, _sz = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_size_t
 _amax = C.POINTER(GemmAmax)
@@ -176,6 +194,9 @@ SIGNATURES = {
     "mi_train_group_plan": (_i32, [_p, _i32, _i64, _i32, _p, _p, _sz, _p, _p]),
     "mi_train_group_step": (_i32, [_p, _i32, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _i32, _p]),
     "mi_eval_group": (_i32, [_p, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _i32, _p]),
+    "mi_predict_group_plan_bytes": (_sz, [_i32]),
+    "mi_predict_group_plan": (_i32, [_p, _i32, _i32, _i32, _p, _p, _p, _p]),
+    "mi_predict_group": (_i32, [_p, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

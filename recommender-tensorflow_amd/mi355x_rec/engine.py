@@ -1103,6 +1103,21 @@ class DeepFM:
         """Can predict_fused score this model?  (One GPU, within the kernel's limits.)"""
         return self.shard is None and self._fused_limit() is None
 
+    def _fused_tables(self):
+        """(layer_off int64 [2 L], widths int32 [L + 1], wide_fields mask): the host tables of mi_predict_fused, made once"""
+        tabs = getattr(self, "_fused_tabs", None)
+        if tabs is None:
+            layer_off = torch.tensor([o for (ko, bo, _, _) in self.layers for o in (ko, bo)] or [0], dtype=torch.int64)
+            widths = torch.tensor(([self.layers[0][2]] + [h for (_, _, _, h) in self.layers]) if self.layers else [0],
+                                  dtype=torch.int32)
+            wide = 0
+            if self.use_linear:
+                for f in range(self.F):
+                    if self.wide_fields is None or self.wide_fields[f]:
+                        wide |= 1 << f
+            tabs = self._fused_tabs = (layer_off, widths, wide)
+        return tabs
+
     def predict_fused(self, ids, x_num=None, out=None):
         """PREDICT forward of a request batch as ONE launch (mi_predict_fused): ids in, the head's PREDICT dict out —
         logits [B, 1], logistic [B, 1], probabilities [B, 2], class_ids = classes [B, 1] int64, device tensors shaped as
@@ -1118,18 +1133,7 @@ class DeepFM:
         if B < 1:
             raise ValueError("predict_fused: no rows")
         self.finalize_rows()
-        tabs = getattr(self, "_fused_tabs", None)
-        if tabs is None:
-            layer_off = torch.tensor([o for (ko, bo, _, _) in self.layers for o in (ko, bo)] or [0], dtype=torch.int64)
-            widths = torch.tensor(([self.layers[0][2]] + [h for (_, _, _, h) in self.layers]) if self.layers else [0],
-                                  dtype=torch.int32)
-            wide = 0
-            if self.use_linear:
-                for f in range(self.F):
-                    if self.wide_fields is None or self.wide_fields[f]:
-                        wide |= 1 << f
-            tabs = self._fused_tabs = (layer_off, widths, wide)
-        layer_off, widths, wide = tabs
+        layer_off, widths, wide = self._fused_tables()
         if out is None:
             dev = self.device
             cls = torch.empty(B, 1, dtype=torch.int64, device=dev)

@@ -7,7 +7,11 @@ Two paths score a batch:
   fused    ``DeepFM.predict_fused``: the whole model as one HIP launch (csrc/serve.hip), ids in, predictions out, with
            the id and output buffers kept per batch size (a call allocates nothing on the device);
   layered  ``DeepFM.predict_logits`` + ``model.binary_predictions``: the training engine's forward, one launch per stage.
-``mode="auto"`` takes the path that measured faster (profiles/serve_latency.md; the constants below)."""
+``mode="auto"`` takes the path that measured faster (profiles/serve_latency.md; the constants below).
+
+An ensemble — the best members of a ``trainers.sweep``, averaged — is served by ``EnsemblePredictor``: M exports over one
+set of feature columns, ids transformed once, and in its fused mode ONE launch for all members and their mean
+(``FusedGroup``: mi_predict_group, csrc/serve.hip)."""
 import glob
 import json
 import os
@@ -15,6 +19,7 @@ import os
 import numpy as np
 import torch
 
+from . import _lib
 from . import engine as _engine
 from .feature_column import FieldPlan, column_from_json
 from .model import binary_predictions
@@ -200,3 +205,241 @@ class Predictor:
     def __call__(self, features):
         ids, x = self.transform(features)
         return self.predict_ids(ids, x)
+
+
+# ---------------------------------------------------------------------- an ensemble of exports
+def _serve_member(eng, keep_alive):
+    """engine eng as a mi_serve_member_t (keep_alive: the host tables the struct points to)"""
+    layer_off, widths, wide = eng._fused_tables()
+    keep_alive += [layer_off, widths]
+    m = _lib.ServeMember()
+    for name, t in (("table", eng.table), ("lin_w", eng.lin_w), ("dense", eng.dense), ("layer_off", layer_off), ("widths", widths)):
+        setattr(m, name, _lib.ptr(t))
+    m.table_stride, m.lin_stride, m.E, m.n_layers, m.activation = eng.ts, eng.ls, eng.E, len(eng.layers), eng.act
+    m.use_linear, m.use_fm, m.use_dnn, m.numeric_raw = int(eng.use_linear), int(eng.use_mf), int(eng.use_dnn), int(eng.raw_numeric)
+    m.lin_bias_off = eng.lin_bias_off
+    m.num_emb_off = -1 if eng.num_emb_off is None else eng.num_emb_off
+    m.lin_num_off = -1 if eng.lin_num_off is None else eng.lin_num_off
+    m.wide_fields = wide
+    return m
+
+
+class FusedGroup:
+    """M engines over one set of feature columns, scored and averaged in ONE launch (mi_predict_group): member i's logit is
+    bit for bit its own predict_fused's, the ensemble's is (((z_0 + z_1) + ...) + z_{M-1}) / M in fp32.  The plan is made
+    once, here; it holds the engines' pointers (a caller who REPLACES a member's tensors makes a new group)."""
+
+    MAX_MEMBERS = _lib.PREDICT_GROUP_MAX_MEMBERS
+
+    def __init__(self, engines):
+        self.engines = list(engines)
+        self.M = len(self.engines)
+        if self.M < 1:
+            raise ValueError("FusedGroup: no members")
+        if self.M > self.MAX_MEMBERS:
+            raise ValueError("FusedGroup: %d members (at most %d in one launch)" % (self.M, self.MAX_MEMBERS))
+        lead = self.engines[0]
+        for i, e in enumerate(self.engines):
+            if e.device != lead.device:
+                raise ValueError("FusedGroup: member %d is on %s, member 0 on %s" % (i, e.device, lead.device))
+            if list(e.vocab_sizes) != list(lead.vocab_sizes) or e.n_numeric != lead.n_numeric:
+                raise ValueError("FusedGroup: member %d has columns (%s buckets, %d numeric), member 0 (%s, %d)" % (
+                    i, list(e.vocab_sizes), e.n_numeric, list(lead.vocab_sizes), lead.n_numeric))
+            why = "row-sharded tables" if e.shard is not None else e._fused_limit()
+            if why is not None:
+                raise ValueError("FusedGroup: member %d: the model has %s" % (i, why))
+        self.k, self.device, self.F, self.n_numeric = lead.k, lead.device, lead.F, lead.n_numeric
+        self._keep = []
+        members = (_lib.ServeMember * self.M)(*[_serve_member(e, self._keep) for e in self.engines])
+        nbytes = int(self.k.query("mi_predict_group_plan_bytes", self.M))
+        self.table = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
+        self.plan = _lib.ServeGroupPlan()
+        self.k.mi_predict_group_plan(members, self.M, self.F, self.n_numeric, lead.field_off, self.table, self.plan)
+
+    def buffers(self, B):
+        """member_logits [M, B], the tickets (zero: every call leaves them zero) and the PREDICT dict for batches of B"""
+        dev = self.device
+        cls = torch.empty(B, 1, dtype=torch.int64, device=dev)
+        return {"member_logits": torch.empty(self.M, B, dtype=torch.float32, device=dev),
+                "tickets": torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev),
+                "out": {"logits": torch.empty(B, 1, dtype=torch.float32, device=dev),
+                        "logistic": torch.empty(B, 1, dtype=torch.float32, device=dev),
+                        "probabilities": torch.empty(B, 2, dtype=torch.float32, device=dev), "class_ids": cls, "classes": cls}}
+
+    def run(self, ids, x_num=None, bufs=None):
+        """ids int32 [B, F] / x_num float32 [B, n_numeric] on the device -> bufs["out"] (device tensors, as
+        DeepFM.predict_fused returns them); bufs["member_logits"] holds the members' own logits.  bufs: buffers(B), kept by
+        the caller (None: made here)."""
+        lead = self.engines[0]
+        lead._prep(ids, None, x_num)
+        B = ids.shape[0]
+        if B < 1:
+            raise ValueError("FusedGroup: no rows")
+        for e in self.engines:
+            e.finalize_rows()
+        if bufs is None:
+            bufs = self.buffers(B)
+        out = bufs["out"]
+        self.k.mi_predict_group(self.plan, self.M, ids, x_num, B, bufs["member_logits"], bufs["tickets"], out["logits"],
+                                out["logistic"], out["probabilities"], out["class_ids"])
+        return out
+
+
+def _model_columns(sig):
+    """the columns of a signature's "model" entry as the ids see them: everything but the embedding dimension"""
+    strip = lambda c: {k: v for k, v in c.items() if k != "embedding_dimension"}
+    m = sig["model"]
+    return [strip(c) for c in m["categorical_columns"]], [strip(c) for c in m["numeric_columns"]]
+
+
+class EnsemblePredictor:
+    """``ensemble(features) -> dict``: the mean logit of M Predictors over the same feature columns and what the head makes
+    of it — the Predictor dict (logits, logistic, probabilities, class_ids, classes); ``return_members=True`` adds
+    member_logits [M, B].  The request's ids are transformed ONCE (member 0's plan: the members' columns are equal), copied
+    to the device once, and the outputs come back in one copy.
+
+    mode: "fused"   all members and their mean in one launch (FusedGroup; every member within mi_predict_fused's limits);
+          "layered" every member by its own Predictor's path, then a torch fp32 sum in member order, a division and
+                    binary_predictions;
+          "auto"    fused iff every member's own use_fused(B) says fused (the measured thresholds of profiles/
+                    serve_latency.md; profiles/ensemble_latency.md has the ensemble's own table)."""
+
+    def __init__(self, predictors, mode="auto"):
+        if mode not in ("auto", "fused", "layered"):
+            raise ValueError("mode must be 'auto', 'fused' or 'layered'")
+        self.members = list(predictors)
+        if not self.members:
+            raise ValueError("EnsemblePredictor: no members (an empty list of predictors)")
+        if len(self.members) > FusedGroup.MAX_MEMBERS:
+            raise ValueError("EnsemblePredictor: %d members (at most %d)" % (len(self.members), FusedGroup.MAX_MEMBERS))
+        lead = self.members[0]
+        cats0, nums0 = _model_columns(lead.signature)
+        for i, p in enumerate(self.members[1:], 1):
+            cats, nums = _model_columns(p.signature)
+            for what, a, b in (("categorical", cats0, cats), ("numeric", nums0, nums)):
+                if len(a) != len(b):
+                    raise ValueError("EnsemblePredictor: member %d has %d %s columns, member 0 has %d" % (i, len(b), what, len(a)))
+                for f, (ca, cb) in enumerate(zip(a, b)):
+                    if ca != cb:
+                        key = next(k for k in sorted(set(ca) | set(cb)) if ca.get(k) != cb.get(k))
+                        raise ValueError("EnsemblePredictor: member %d differs from member 0 in %s column %d (%r): %s = %r "
+                                         "against %r" % (i, what, f, ca.get("name"), key, cb.get(key), ca.get(key)))
+            ra, rb = lead.signature["receiver_tensors"], p.signature["receiver_tensors"]
+            if ra != rb:
+                key = next(k for k in sorted(set(ra) | set(rb)) if ra.get(k) != rb.get(k))
+                raise ValueError("EnsemblePredictor: member %d differs from member 0 in receiver %r: %r against %r" % (
+                    i, key, rb.get(key), ra.get(key)))
+            if p.engine.device != lead.engine.device:
+                raise ValueError("EnsemblePredictor: member %d is on device %s, member 0 on %s" % (
+                    i, p.engine.device, lead.engine.device))
+        if mode == "fused":
+            for i, p in enumerate(self.members):
+                if not p.engine.fused_predict_ok():
+                    raise ValueError("mode='fused': member %d: the model has %s" % (
+                        i, p.engine._fused_limit() or "row-sharded tables"))
+        self.mode, self.signature, self.plan, self.receivers = mode, lead.signature, lead.plan, lead.receivers
+        self.device, self.k = lead.engine.device, lead.engine.k
+        self.export_dirs = [getattr(p, "export_dir", None) for p in self.members]
+        self._group = None
+        self._bufs = {}
+
+    @classmethod
+    def from_exports(cls, export_dirs, device="cuda", mode="auto", member_mode="auto"):
+        """One Predictor.from_export per directory (member_mode: the members' own mode, which "layered" and "auto" consult)"""
+        return cls([Predictor.from_export(d, device=device, mode=member_mode) for d in export_dirs], mode=mode)
+
+    @classmethod
+    def from_sweep(cls, job_dir, top, device="cuda", mode="auto", member_mode="auto"):
+        """The first `top` rows of <job_dir>/sweep.json — trainers.sweep ranked them best first — each from its export"""
+        path = os.path.join(job_dir, "sweep.json")
+        if not os.path.exists(path):
+            raise FileNotFoundError("%s has no sweep.json: an ensemble is taken from the job directory of a trainers.sweep run" % job_dir)
+        with open(path) as f:
+            rows = json.load(f)["members"]
+        if top < 1 or top > len(rows):
+            raise ValueError("top=%d: the sweep in %s has %d members (1 <= top <= %d)" % (top, job_dir, len(rows), len(rows)))
+        dirs = []
+        for row in rows[:top]:
+            d = row["export"]
+            if not os.path.isdir(d):                    # (a sweep directory that was moved: the members lie inside it)
+                d = os.path.join(job_dir, "member_%d" % row["member"], "export", "exporter")
+            dirs.append(d)
+        ens = cls.from_exports(dirs, device=device, mode=mode, member_mode=member_mode)
+        ens.sweep_members = [row["member"] for row in rows[:top]]
+        return ens
+
+    # ------------------------------------------------------------------ requests
+    def transform(self, features):
+        return self.members[0].transform(features)
+
+    def use_fused(self, B):
+        if self.mode != "auto":
+            return self.mode == "fused"
+        return all(p.use_fused(B) for p in self.members)
+
+    def _buffers(self, B):
+        """Per batch size: ids / x on the device, the group's scratch (member logits, tickets) and ONE packed output buffer
+        [logits B | logistic B | probabilities 2 B | class_ids B int64 | member_logits M B] whose views the launch writes
+        and one copy brings to the host."""
+        b = self._bufs.get(B)
+        if b is None:
+            if len(self._bufs) >= 64:
+                self._bufs.clear()
+            dev, M = self.device, len(self.members)
+            eng = self.members[0].engine
+            pack = torch.empty(24 * B + 4 * M * B, dtype=torch.uint8, device=dev)
+            f32 = lambda lo, n, *shape: pack[lo:lo + 4 * n].view(torch.float32).view(*shape)
+            cls = pack[16 * B:24 * B].view(torch.int64).view(B, 1)
+            b = self._bufs[B] = {
+                "ids": torch.empty(B, eng.F, dtype=torch.int32, device=dev),
+                "x": torch.empty(B, eng.n_numeric, dtype=torch.float32, device=dev) if eng.n_numeric else None,
+                "pack": pack, "member_logits": f32(24 * B, M * B, M, B),
+                "tickets": torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev),
+                "out": {"logits": f32(0, B, B, 1), "logistic": f32(4 * B, B, B, 1), "probabilities": f32(8 * B, 2 * B, B, 2),
+                        "class_ids": cls, "classes": cls}}
+        return b
+
+    def predict_ids(self, ids, x=None, return_members=False):
+        """The PREDICT dict (numpy) of already transformed ids [B, F] int32 / x [B, n_numeric] float32 (numpy)."""
+        B, M = ids.shape[0], len(self.members)
+        if B == 0:
+            host = {"logits": np.zeros((0, 1), np.float32), "logistic": np.zeros((0, 1), np.float32),
+                    "probabilities": np.zeros((0, 2), np.float32), "class_ids": np.zeros((0, 1), np.int64),
+                    "classes": np.zeros((0, 1), np.int64)}
+            if return_members:
+                host["member_logits"] = np.zeros((M, 0), np.float32)
+            return host
+        b = self._buffers(B)
+        b["ids"].copy_(torch.from_numpy(ids))
+        if b["x"] is not None:
+            b["x"].copy_(torch.from_numpy(x))
+        if self.use_fused(B):
+            if self._group is None:
+                self._group = FusedGroup([p.engine for p in self.members])
+            self._group.run(b["ids"], b["x"], b)
+        else:
+            acc = None
+            for i, p in enumerate(self.members):
+                eng = p.engine
+                if p.use_fused(B):
+                    z = eng.predict_fused(b["ids"], b["x"])["logits"].reshape(-1)
+                else:
+                    z = eng.predict_logits(b["ids"], b["x"]).reshape(-1)
+                b["member_logits"][i].copy_(z)
+                acc = z.clone() if acc is None else acc + z
+            pr = binary_predictions(acc / torch.full_like(acc, float(M)), self.k)
+            for key in OUTPUTS[:4]:
+                b["out"][key].copy_(pr[key])
+        n = 24 * B + (4 * M * B if return_members else 0)
+        flat = b["pack"][:n].to("cpu", copy=True).numpy()                  # (a copy: the device buffer is reused)
+        host = {"logits": flat[:4 * B].view(np.float32).reshape(B, 1), "logistic": flat[4 * B:8 * B].view(np.float32).reshape(B, 1),
+                "probabilities": flat[8 * B:16 * B].view(np.float32).reshape(B, 2),
+                "class_ids": flat[16 * B:24 * B].view(np.int64).reshape(B, 1)}
+        host["classes"] = host["class_ids"]
+        if return_members:
+            host["member_logits"] = flat[24 * B:].view(np.float32).reshape(M, B)
+        return host
+
+    def __call__(self, features, return_members=False):
+        ids, x = self.transform(features)
+        return self.predict_ids(ids, x, return_members=return_members)

@@ -3,13 +3,16 @@
 Scores the rows of a CSV in the training files' format (or ``synthetic:N[:seed]``) from the newest export under
 ``DIR/export/exporter`` and writes ``logit,probability,class_id`` per row.  It takes no model flags: the columns, the
 model's parts and its sizes all come from the export (mi355x_rec/predictor.py).  The CSV's columns that the export's
-signature does not receive (rating, timestamp, ...) are dropped here; the predictor itself refuses unknown keys."""
+signature does not receive (rating, timestamp, ...) are dropped here; the predictor itself refuses unknown keys.
+
+``--top N`` on the job directory of a ``trainers.sweep`` run scores with the ensemble of the sweep's N best members
+(EnsemblePredictor.from_sweep: the mean logit, one launch for all members in fused mode)."""
 import csv
 import os
 import sys
 from argparse import ArgumentParser
 
-from mi355x_rec.predictor import Predictor
+from mi355x_rec.predictor import EnsemblePredictor, Predictor
 from trainers.ml_100k import _read_csv
 
 
@@ -21,6 +24,9 @@ def make_parser():
     p.add_argument("--mode", choices=["auto", "fused", "layered"], default="auto",
                    help="fused: the whole model as one launch; layered: the engine's forward; auto: the faster of the two "
                         "for the batch and the model (default: %(default)s)")
+    p.add_argument("--top", type=int, default=None, metavar="N",
+                   help="--job-dir is a trainers.sweep directory: score with the mean of its N best members (default: off, one "
+                        "export is served)")
     p.add_argument("--batch-size", type=int, default=4096, help="rows scored per call (default: %(default)s)")
     p.add_argument("--device", default="cuda", help="torch device of the MI355X to run on (default: %(default)s)")
     return p
@@ -28,7 +34,15 @@ def make_parser():
 
 def main(argv=None):
     args = make_parser().parse_args(sys.argv[1:] if argv is None else argv)
-    predictor = Predictor.from_export(os.path.join(args.job_dir, "export", "exporter"), device=args.device, mode=args.mode)
+    if args.top is not None:
+        if not os.path.exists(os.path.join(args.job_dir, "sweep.json")):
+            raise SystemExit("--top %d: %s has no sweep.json (an ensemble is taken from the job directory of a trainers.sweep run)"
+                             % (args.top, args.job_dir))
+        predictor = EnsemblePredictor.from_sweep(args.job_dir, top=args.top, device=args.device, mode=args.mode)
+        predictor.export_dir = "the %d best members of %s (%s)" % (args.top, args.job_dir, ", ".join(
+            "member %d" % m for m in predictor.sweep_members))
+    else:
+        predictor = Predictor.from_export(os.path.join(args.job_dir, "export", "exporter"), device=args.device, mode=args.mode)
     cols, n = _read_csv(args.input)
     cols = {k: v for k, v in cols.items() if k in predictor.receivers}
     out = args.output or os.path.join(args.job_dir, "predict", "predictions.csv")

@@ -15,6 +15,9 @@ members are evaluated on all of it in one launch (FusedPopulation.evaluate): <jo
 evaluation — the members' learning curves — and sweep.json names every member's best point.  --final-eval fused takes the
 end-of-sweep metrics from that evaluation too, instead of one Estimator.evaluate per member.
 
+--ensemble N: after the ranking, the N best members are served as ONE model (EnsemblePredictor: their mean logit, one launch
+for all of them) over the test set; sweep.json gains "ensemble": its members and its metrics, next to the best member's.
+
 trainers.deep_fm has no learning-rate flag (the reference has none): a member restored through ``trainers.deep_fm
 --restore`` continues at that CLI's 0.001, a member restored through ``trainers.sweep --restore`` at its own rate."""
 import itertools
@@ -28,6 +31,8 @@ import numpy as np
 import torch
 
 from mi355x_rec.estimator import Estimator, ModeKeys
+from mi355x_rec.metrics import metrics_from_counters
+from mi355x_rec.predictor import EnsemblePredictor
 from mi355x_rec.population import FusedPopulation
 from trainers import _cli, deep_fm
 from trainers.conf_utils import get_exporter
@@ -68,7 +73,33 @@ def make_parser():
     p.add_argument("--final-eval", default="layered", choices=["layered", "fused"],
                    help="where the end-of-sweep metrics come from: one Estimator.evaluate per member (layered) or the one-launch "
                         "population evaluation (fused) (default: %(default)s)")
+    p.add_argument("--ensemble", type=int, default=0, metavar="N",
+                   help="after the ranking, evaluate the mean of the N best members on the test set as one model and write it "
+                        "to sweep.json as \"ensemble\" (default: 0 = off)")
     return p
+
+
+def evaluate_ensemble(job_dir, top, test_csv, device, batch_size=4096):
+    """The EVAL metrics of the mean of the sweep's `top` best members over the test set: EnsemblePredictor.from_sweep's
+    logits through mi_eval_accumulate and metrics_from_counters, as Estimator.evaluate counts one model's.  "loss" is the
+    average loss (the whole set as one batch of a mean reduction)."""
+    ens = EnsemblePredictor.from_sweep(job_dir, top=top, device=device)
+    dev = ens.device
+    hist = torch.zeros(2 * 201, dtype=torch.int64, device=dev)
+    counts = torch.zeros(8, dtype=torch.int64, device=dev)
+    sums = torch.zeros(4, dtype=torch.float64, device=dev)
+    n = 0
+    for features, labels in get_input_fn(test_csv, ModeKeys.EVAL, batch_size=batch_size)():
+        ids, x = ens.plan.transform(features)
+        z = torch.from_numpy(np.ascontiguousarray(ens.predict_ids(ids, x)["logits"][:, 0])).to(dev)
+        y = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1)).astype(np.uint8)).to(dev)
+        ens.k.mi_eval_accumulate(z, y, z.numel(), hist, counts, sums)
+        n += z.numel()
+    if not n:
+        raise ValueError("no evaluation data in %s" % test_csv)
+    metrics = metrics_from_counters(hist.cpu().numpy(), counts.cpu().numpy(), sums.cpu().numpy())
+    metrics["loss"] = metrics["average_loss"]
+    return ens.sweep_members, {k: float(v) for k, v in metrics.items()}
 
 
 def grid(args):
@@ -263,9 +294,20 @@ def train_and_evaluate(args):
             rows[-1]["best_step"], rows[-1]["best_value"] = evaluator.best(i)
     sign = 1.0 if args.select in _ASCENDING else -1.0
     rows.sort(key=lambda r: (sign * r["metrics"][args.select], r["member"]))
+    doc = {"select": args.select, "members": rows}
     with open(os.path.join(args.job_dir, "sweep.json"), "w") as f:
-        json.dump({"select": args.select, "members": rows}, f, indent=1)
+        json.dump(doc, f, indent=1)
     best = rows[0]
+    n_ens = int(getattr(args, "ensemble", 0) or 0)
+    if n_ens:
+        if n_ens < 0 or n_ens > len(rows):
+            raise ValueError("--ensemble %d: the sweep has %d members" % (n_ens, len(rows)))
+        who, metrics = evaluate_ensemble(args.job_dir, n_ens, args.test_csv, args.device)
+        doc["ensemble"] = {"members": who, "metrics": metrics}
+        with open(os.path.join(args.job_dir, "sweep.json"), "w") as f:
+            json.dump(doc, f, indent=1)
+        print("INFO: ensemble of the %d best members (%s): %s = %.6g, the best single member (member %d) has %.6g" % (
+            n_ens, ", ".join(str(m) for m in who), args.select, metrics[args.select], best["member"], best["metrics"][args.select]))
     print("INFO: best of %d members by %s: member %d (%s), %s = %.6g, in %s" % (
         len(rows), args.select, best["member"], ", ".join("%s = %s" % kv for kv in sorted(best["params"].items())), args.select,
         best["metrics"][args.select], best["dir"]))
