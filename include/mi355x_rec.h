@@ -353,7 +353,8 @@ int32_t mi_sparse_apply_fused(float* table, float* t_slot0, float* t_slot1, floa
  * — the same fp32 op sequence as the sweep, hence the same bits.  lr_table[s] (device, f32) holds
  * lr_t of step s.  Runs on the U distinct rows about to be gathered (step_to = step-1), or on all
  * rows (uniq_rows == NULL, n_max = R) before evaluation / checkpoint.
- * flags: any of MI_CATCHUP_DEFER_SLOTS | MI_CATCHUP_BOUNDED | MI_CATCHUP_KEEP_STAMPS (0 = none).
+ * flags: any of MI_CATCHUP_DEFER_SLOTS | MI_CATCHUP_BOUNDED | MI_CATCHUP_KEEP_STAMPS (0 = none), or exactly
+ * MI_CATCHUP_LOCAL_ORDER | MI_CATCHUP_BOUNDED | MI_CATCHUP_DEFER_SLOTS.
  * MI_CATCHUP_DEFER_SLOTS (with uniq_rows): only w is written; m, v and last_step keep their old values and
  * the mi_sparse_apply[_fused] of the same step — which reads and writes m, v anyway and MUST then be
  * given last_step — decays them from the old stamp (same multiply chain, same bits).  Saves a third
@@ -370,8 +371,20 @@ int32_t mi_sparse_apply_fused(float* table, float* t_slot0, float* t_slot1, floa
  * stamps are written exactly as in the exact mode.  7 packed VALU operations per element and step (no transcendental)
  * instead of 16 + 2, and no range conditions.  Needs epsilon >= 1e-30 (otherwise the exact form runs).
  * MI_CATCHUP_KEEP_STAMPS: the rows' stamps are left as they are (m, v ARE written) — for a model whose tables and wide part
- * follow two different Adam optimizers (two lr_t tables: two calls; the first must not move the stamps the second reads). */
-enum mi_catchup_flags { MI_CATCHUP_DEFER_SLOTS = 1, MI_CATCHUP_BOUNDED = 2, MI_CATCHUP_KEEP_STAMPS = 4 };
+ * follow two different Adam optimizers (two lr_t tables: two calls; the first must not move the stamps the second reads).
+ * MI_CATCHUP_LOCAL_ORDER (only together with MI_CATCHUP_BOUNDED | MI_CATCHUP_DEFER_SLOTS, uniq_rows and table; lin_w or not;
+ * anything else: MI_ERR_INVALID before any launch): the train step's catch-up in ONE launch.  uniq_rows comes in the
+ * sort's row order, NOT ordered by staleness: every workgroup orders windows of up to mi_catchup_local_chunk_rows() of its rows
+ * by staleness in LDS (within 1-2 % of the replayed steps per wave of the global order of mi_catchup_rows_by_gap, which
+ * is then not needed), replays the wide part's scalars from the very {w, m, v, stamp} records it reads the stamps from
+ * (the wide part's own kernel is not launched) and then the rows.  The results are, bit for bit, those of
+ * mi_catchup_rows_by_gap + this entry with the wide part alone + this entry with the rows alone: the per-row code is the same. */
+enum mi_catchup_flags { MI_CATCHUP_DEFER_SLOTS = 1, MI_CATCHUP_BOUNDED = 2, MI_CATCHUP_KEEP_STAMPS = 4, MI_CATCHUP_LOCAL_ORDER = 8 };
+/* The shape of an MI_CATCHUP_LOCAL_ORDER launch (host-side queries): the largest window a workgroup orders, and for a call
+ * with n_max slots of which num_uniq hold rows plan[0..2] = {workgroups, chunks per workgroup, rows per chunk}: workgroup g
+ * takes the chunks g, g + workgroups, ... of the list; the last chunks may be short or empty. */
+int32_t mi_catchup_local_chunk_rows(void);
+int32_t mi_catchup_local_plan(int64_t n_max, int64_t num_uniq, int64_t* plan);
 /* keys[u] = how many steps row uniq_rows[u] will be replayed over by mi_sparse_catchup(step_to) (0..62,
  * clamped), 63 for the slots u >= *num_uniq.  Sorting the rows by it (mi_sort_unique_rows with
  * key_range 64, then mi_gather_u32 of uniq_rows through the permutation) groups rows of equal

@@ -378,6 +378,21 @@ __device__ __forceinline__ float bounded_step(float w, float u, float s0, float 
   return fmaf(-u, __builtin_amdgcn_rcpf(fmaf(s0, rj, eps)), w);
 }
 
+// The bounded replay of ONE wide-part scalar over the steps s_from .. s_to: returns w, leaves the exact chain's m in m and
+// rho_j in rj (1 before the first step), s0 = sqrtf(v_0).  lr_at(s) = lr_t[s] (catchup_lin_k: the global table;
+// sparse_catchup_local_k: the global table for the steps older than its LDS window, then the window).  The one
+// definition both kernels call, so the two forms of a step cannot differ in a bit.
+template <class LR>
+__device__ __forceinline__ float lin_bounded_replay(float w, float& m, float s0, float& rj, int s_from, int s_to, LR lr_at,
+                                                    const RhoSplit rho, float b1, float eps) {
+  for (int s = s_from; s <= s_to; ++s) {
+    rj = fmaf(rj, rho.lo, rj * rho.hi);
+    m = m * b1;
+    w = bounded_step(w, lr_at(s) * m, s0, rj, eps);
+  }
+  return w;
+}
+
 // The wide part: one thread per row (1/E of the work).  Its own kernel, run BEFORE the row kernel (it
 // reads the stamps the row kernel writes), so that lane 0 of a row's lane group does not drag a fifth
 // chain through a second loop of the same length.
@@ -397,14 +412,8 @@ __global__ __launch_bounds__(kBlock) void catchup_lin_k(
   if (work) { w = lin_w[r]; m = lm[r]; v = lv[r]; }
   if (bounded) {
     if (work) {
-      const RhoSplit rho = rho_split(b2);
-      const float s0 = sqrtf(v);
       float rj = 1.f;
-      for (int s = ls + 1; s <= step_to; ++s) {
-        rj = fmaf(rj, rho.lo, rj * rho.hi);
-        m = m * b1;
-        w = bounded_step(w, lr_table[s] * m, s0, rj, eps);
-      }
+      w = lin_bounded_replay(w, m, sqrtf(v), rj, ls + 1, step_to, [&](int s) { return lr_table[s]; }, rho_split(b2), b1, eps);
       if (!defer_slots)
         for (int s = ls + 1; s <= step_to; ++s) v = v * b2;
       lin_w[r] = w;
@@ -514,6 +523,89 @@ __device__ __forceinline__ RowIn load_row_in(const float* __restrict__ table, co
   return q;
 }
 
+// What the bounded replay of a row needs besides the row itself.
+struct RowReplay {
+  float* table; float* tm; float* tv; int32_t* last_step; const float* lr_table;
+  int64_t ts; int step_to, base, st, l; float b1, b2, eps; RhoSplit rho; bool lane_on, defer_slots, keep_stamps;
+};
+
+// The bounded replay of one row from registers (the state a round of a pipeline took over); lr_s: the LDS window,
+// lr_s[i] = lr_t[base + i].  The one definition sparse_catchup_bounded_k and sparse_catchup_local_k call.
+__device__ __forceinline__ void replay_row_bounded(const RowReplay& c, const float* __restrict__ lr_s, const RowIn& cur) {
+  float* const table = c.table; float* const tm = c.tm; float* const tv = c.tv; int32_t* const last_step = c.last_step;
+  const float* const lr_table = c.lr_table;
+  const int64_t ts = c.ts;
+  const int step_to = c.step_to, base = c.base, st = c.st, l = c.l;
+  const float b1 = c.b1, b2 = c.b2, eps = c.eps;
+  const RhoSplit rho = c.rho;
+  const bool lane_on = c.lane_on, defer_slots = c.defer_slots, keep_stamps = c.keep_stamps;
+  // ---- replay row u (a row that was never applied has m = v = 0: every step subtracts exactly 0)
+  const int ls = cur.ls;
+  if (ls > 0 && ls < step_to) {
+    if (lane_on) {
+      float4 w = cur.w, m = cur.m;
+      // (v_sqrt_f32: 1 ulp; a v too small for it is also far too small to matter next to eps.  An overflowed v = inf keeps a
+      // FINITE root: the sweep's update is u / inf = 0, and so is u * r with r ~ 1 / FLT_MAX — but the carried reciprocal's
+      // residual 1 - inf * 0 would be NaN)
+      const float4 s0 = make_float4(fminf(__builtin_amdgcn_sqrtf(cur.v.x), 3.4028234e38f), fminf(__builtin_amdgcn_sqrtf(cur.v.y), 3.4028234e38f),
+                                    fminf(__builtin_amdgcn_sqrtf(cur.v.z), 3.4028234e38f), fminf(__builtin_amdgcn_sqrtf(cur.v.w), 3.4028234e38f));
+      float rj = 1.f;
+      int s = ls + 1;
+      for (; s < base && s <= step_to; ++s) {                 // steps older than the LDS window (rare)
+        const float lr = lr_table[s];
+        rj = fmaf(rj, rho.lo, rj * rho.hi);
+        m.x = m.x * b1; m.y = m.y * b1; m.z = m.z * b1; m.w = m.w * b1;
+        w.x = bounded_step(w.x, lr * m.x, s0.x, rj, eps); w.y = bounded_step(w.y, lr * m.y, s0.y, rj, eps);
+        w.z = bounded_step(w.z, lr * m.z, s0.z, rj, eps); w.w = bounded_step(w.w, lr * m.w, s0.w, rj, eps);
+      }
+      // (two-element vectors: hipcc then packs the fma of the denominators too; two steps per trip of the loop)
+      // The reciprocal is CARRIED from step to step instead of taken anew (round 5): v_rcp_f32 is a transcendental
+      // instruction (half rate on gfx950, one element each: tools/probe/valu_cost_probe.hip) — four of them per lane and
+      // step next to ~13 packed / scalar ones.  Consecutive denominators differ by at most 1 - sqrt(beta2) (5e-4) relatively, d_j / d_{j-1} in [sqrt(beta2), 1], so with
+      // e = 1 - d_j r_{j-1} (one fma: the exact residual, rounded once) the second-order step r_j = r_{j-1} (1 + e + e^2)
+      // lands within e^3 <= 1.3e-10 of 1 / d_j plus ONE rounding (0.5 ulp — tighter than v_rcp_f32's 1 ulp), and since
+      // every step corrects against its own d_j nothing accumulates.  Three packed full-rate fmas per two elements in place
+      // of two v_rcp_f32: 35 instead of 29 + 8 transcendental instructions per two steps.  Measured (same box, alternating,
+      // profiles/r05_catchup_reciprocal.md): rows sorted by staleness 0.441 against 0.444 ms alone and the step 2.685
+      // against 2.69 ms — the kernel waits for rows, not for the VALU — rows NOT sorted 0.63 against 0.66 ms.
+      typedef float f32x2 __attribute__((ext_vector_type(2)));
+      const f32x2 sa = {s0.x, s0.y}, sb = {s0.z, s0.w};
+      const f32x2 ev = {eps, eps}, one = {1.f, 1.f};
+      f32x2 ra, rb;                                           // 1 / (s0 rho_j + eps) of the step before the loop's first
+      {
+        const f32x2 rv = {rj, rj};
+        const f32x2 da = __builtin_elementwise_fma(sa, rv, ev), db = __builtin_elementwise_fma(sb, rv, ev);
+        ra.x = __builtin_amdgcn_rcpf(da.x); ra.y = __builtin_amdgcn_rcpf(da.y);
+        rb.x = __builtin_amdgcn_rcpf(db.x); rb.y = __builtin_amdgcn_rcpf(db.y);
+      }
+      f32x2 ma = {m.x, m.y}, mb = {m.z, m.w}, wa = {w.x, w.y}, wb = {w.z, w.w};
+#pragma unroll 2
+      for (; s <= step_to; ++s) {
+        const float lr = lr_s[s - base];
+        rj = fmaf(rj, rho.lo, rj * rho.hi);
+        ma = ma * b1; mb = mb * b1;
+        const f32x2 rv = {rj, rj};
+        const f32x2 da = __builtin_elementwise_fma(sa, rv, ev), db = __builtin_elementwise_fma(sb, rv, ev);
+        const f32x2 ea = __builtin_elementwise_fma(-da, ra, one), eb = __builtin_elementwise_fma(-db, rb, one);
+        const f32x2 pa = __builtin_elementwise_fma(ea, ea, ea), pb = __builtin_elementwise_fma(eb, eb, eb);
+        ra = __builtin_elementwise_fma(ra, pa, ra); rb = __builtin_elementwise_fma(rb, pb, rb);
+        const f32x2 ua = lr * ma, ub = lr * mb;
+        wa = __builtin_elementwise_fma(-ua, ra, wa); wb = __builtin_elementwise_fma(-ub, rb, wb);
+      }
+      m = make_float4(ma.x, ma.y, mb.x, mb.y); w = make_float4(wa.x, wa.y, wb.x, wb.y);
+      const int64_t o = cur.r * ts + 4 * l;
+      st4(table + o, w);
+      if (!defer_slots) {
+        float4 v = cur.v;
+        for (int q = ls + 1; q <= step_to; ++q) { v.x = v.x * b2; v.y = v.y * b2; v.z = v.z * b2; v.w = v.w * b2; }
+        st4_nt(tm + o, m); st4_nt(tv + o, v);
+      }
+    }
+  }
+  // (every lane of the group read the stamp above before lane 0 overwrites it: same wave, program order)
+  if (l == 0 && !defer_slots && !keep_stamps && ls < step_to) last_step[cur.r * st] = step_to;
+}
+
 template <int LPR>
 __global__ __launch_bounds__(kBlock) void sparse_catchup_bounded_k(
     float* __restrict__ table, float* __restrict__ tm, float* __restrict__ tv,
@@ -557,74 +649,8 @@ __global__ __launch_bounds__(kBlock) void sparse_catchup_bounded_k(
   // on registers.  A lane group whose chunk lies past the end of the list carries ls = step_to: nothing to do.
   RowIn none;
   none.r = 0; none.ls = INT32_MAX; none.w = none.m = none.v = make_float4(0.f, 0.f, 0.f, 0.f);
-  // the replay of one row from registers (the state a round took over)
-  auto replay = [&](const RowIn& cur) {
-    // ---- replay row u (a row that was never applied has m = v = 0: every step subtracts exactly 0)
-    const int ls = cur.ls;
-    if (ls > 0 && ls < step_to) {
-      if (lane_on) {
-        float4 w = cur.w, m = cur.m;
-        // (v_sqrt_f32: 1 ulp; a v too small for it is also far too small to matter next to eps.  An overflowed v = inf keeps a
-        // FINITE root: the sweep's update is u / inf = 0, and so is u * r with r ~ 1 / FLT_MAX — but the carried reciprocal's
-        // residual 1 - inf * 0 would be NaN)
-        const float4 s0 = make_float4(fminf(__builtin_amdgcn_sqrtf(cur.v.x), 3.4028234e38f), fminf(__builtin_amdgcn_sqrtf(cur.v.y), 3.4028234e38f),
-                                      fminf(__builtin_amdgcn_sqrtf(cur.v.z), 3.4028234e38f), fminf(__builtin_amdgcn_sqrtf(cur.v.w), 3.4028234e38f));
-        float rj = 1.f;
-        int s = ls + 1;
-        for (; s < base && s <= step_to; ++s) {                 // steps older than the LDS window (rare)
-          const float lr = lr_table[s];
-          rj = fmaf(rj, rho.lo, rj * rho.hi);
-          m.x = m.x * b1; m.y = m.y * b1; m.z = m.z * b1; m.w = m.w * b1;
-          w.x = bounded_step(w.x, lr * m.x, s0.x, rj, eps); w.y = bounded_step(w.y, lr * m.y, s0.y, rj, eps);
-          w.z = bounded_step(w.z, lr * m.z, s0.z, rj, eps); w.w = bounded_step(w.w, lr * m.w, s0.w, rj, eps);
-        }
-        // (two-element vectors: hipcc then packs the fma of the denominators too; two steps per trip of the loop)
-        // The reciprocal is CARRIED from step to step instead of taken anew (round 5): v_rcp_f32 is a transcendental
-        // instruction (half rate on gfx950, one element each: tools/probe/valu_cost_probe.hip) — four of them per lane and
-        // step next to ~13 packed / scalar ones.  Consecutive denominators differ by at most 1 - sqrt(beta2) (5e-4) relatively, d_j / d_{j-1} in [sqrt(beta2), 1], so with
-        // e = 1 - d_j r_{j-1} (one fma: the exact residual, rounded once) the second-order step r_j = r_{j-1} (1 + e + e^2)
-        // lands within e^3 <= 1.3e-10 of 1 / d_j plus ONE rounding (0.5 ulp — tighter than v_rcp_f32's 1 ulp), and since
-        // every step corrects against its own d_j nothing accumulates.  Three packed full-rate fmas per two elements in place
-        // of two v_rcp_f32: 35 instead of 29 + 8 transcendental instructions per two steps.  Measured (same box, alternating,
-        // profiles/r05_catchup_reciprocal.md): rows sorted by staleness 0.441 against 0.444 ms alone and the step 2.685
-        // against 2.69 ms — the kernel waits for rows, not for the VALU — rows NOT sorted 0.63 against 0.66 ms.
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        const f32x2 sa = {s0.x, s0.y}, sb = {s0.z, s0.w};
-        const f32x2 ev = {eps, eps}, one = {1.f, 1.f};
-        f32x2 ra, rb;                                           // 1 / (s0 rho_j + eps) of the step before the loop's first
-        {
-          const f32x2 rv = {rj, rj};
-          const f32x2 da = __builtin_elementwise_fma(sa, rv, ev), db = __builtin_elementwise_fma(sb, rv, ev);
-          ra.x = __builtin_amdgcn_rcpf(da.x); ra.y = __builtin_amdgcn_rcpf(da.y);
-          rb.x = __builtin_amdgcn_rcpf(db.x); rb.y = __builtin_amdgcn_rcpf(db.y);
-        }
-        f32x2 ma = {m.x, m.y}, mb = {m.z, m.w}, wa = {w.x, w.y}, wb = {w.z, w.w};
-#pragma unroll 2
-        for (; s <= step_to; ++s) {
-          const float lr = lr_s[s - base];
-          rj = fmaf(rj, rho.lo, rj * rho.hi);
-          ma = ma * b1; mb = mb * b1;
-          const f32x2 rv = {rj, rj};
-          const f32x2 da = __builtin_elementwise_fma(sa, rv, ev), db = __builtin_elementwise_fma(sb, rv, ev);
-          const f32x2 ea = __builtin_elementwise_fma(-da, ra, one), eb = __builtin_elementwise_fma(-db, rb, one);
-          const f32x2 pa = __builtin_elementwise_fma(ea, ea, ea), pb = __builtin_elementwise_fma(eb, eb, eb);
-          ra = __builtin_elementwise_fma(ra, pa, ra); rb = __builtin_elementwise_fma(rb, pb, rb);
-          const f32x2 ua = lr * ma, ub = lr * mb;
-          wa = __builtin_elementwise_fma(-ua, ra, wa); wb = __builtin_elementwise_fma(-ub, rb, wb);
-        }
-        m = make_float4(ma.x, ma.y, mb.x, mb.y); w = make_float4(wa.x, wa.y, wb.x, wb.y);
-        const int64_t o = cur.r * ts + 4 * l;
-        st4(table + o, w);
-        if (!defer_slots) {
-          float4 v = cur.v;
-          for (int q = ls + 1; q <= step_to; ++q) { v.x = v.x * b2; v.y = v.y * b2; v.z = v.z * b2; v.w = v.w * b2; }
-          st4_nt(tm + o, m); st4_nt(tv + o, v);
-        }
-      }
-    }
-    // (every lane of the group read the stamp above before lane 0 overwrites it: same wave, program order)
-    if (l == 0 && !defer_slots && !keep_stamps && ls < step_to) last_step[cur.r * st] = step_to;
-  };
+  const RowReplay ctx{table, tm, tv, last_step, lr_table, ts, step_to, base, st, l, b1, b2, eps, rho, lane_on, defer_slots, keep_stamps};
+  auto replay = [&](const RowIn& cur) { replay_row_bounded(ctx, lr_s, cur); };
   int64_t u0 = row_at(0);
   RowIn nxt = u0 < count ? load_row_in(table, tm, tv, last_step, row_id(u0), ts, l, lane_on, st) : none;
   int64_t u1 = J > 1 ? row_at(1) : count;
@@ -639,6 +665,203 @@ __global__ __launch_bounds__(kBlock) void sparse_catchup_bounded_k(
       if (u1 < count) id_pref = row_id(u1);
     }
     replay(cur);
+  }
+}
+
+// MI_CATCHUP_LOCAL_ORDER: the bounded, deferred catch-up of a batch's rows AND of their wide-part scalars in one launch,
+// with the staleness order made inside the kernel.  A wave's lane groups run as long as its stalest row, so rows of
+// equal staleness should share a wave — but that needs no GLOBAL order (mi_catchup_rows_by_gap: four launches and every
+// stamp's 128-byte line fetched once more): ordering windows of kLocalChunk rows leaves ~1 % more replayed steps per
+// wave than the global sort (1.012 at 1,024, 1.022 at 512, 1.040 at 256; unsorted 2.05: geometric gaps, four rows per
+// wave; measured with the 64-bin key below at config 3's chunks of 538 rows: 1.047, profiles/catchup_local_order.md), and a
+// workgroup can order a window of its own rows in LDS.  Per chunk of <= kLocalChunk consecutive positions
+// of uniq_rows (in the sort's row order), a workgroup
+//   prologue   one thread per row: row id (coalesced) -> the row's stamp — with the 16-byte {w, m, v, stamp} record of the
+//              wide part (lin_stride 4) the whole record in one load, the line catchup_lin_k fetched a second time —
+//              -> an LDS counting sort on min(gap, 63) (histogram with LDS atomics, a wave's scan, a scatter of row,
+//              stamp and w, m, v; not stable: results do not depend on the order of rows) -> the wide part's replay in
+//              the sorted order (neighbouring threads: similar gaps) with catchup_lin_k's own per-row code, w written
+//              back (m, v, stamp untouched: deferred);
+//   row phase  sparse_catchup_bounded_k's lane-group pipeline and replay code over the sorted chunk: the four lane
+//              groups of a wave take adjacent positions, row id and stamp come from LDS (so a row that needs no replay
+//              is not loaded at all), the next round's w, m, v are in flight under this round's arithmetic.
+// The chunks overlap: the ids of chunk c + 2 and the records of chunk c + 1 are loaded (into registers) before chunk c's
+// wide replay and row phase, and the first round's w, m, v before the wide replay — no stage starts with a cold
+// dependent load.  A sorted chunk runs from short replays (memory bound) to long ones (issue bound): every workgroup
+// starts its walk at a position of its own (a hash of the chunk's number), so the chip never holds one kind only.
+// The shape of a launch (local_grid, local_plan): *num_uniq is known on the device only, so the grid follows n_max and the
+// chunks are cut at run time.  A chunk has between kLocalMinChunk rows (64: the smallest window whose order still pays,
+// 1.13) and kLocalChunk; a workgroup gets three chunks where the rows allow it (so that its prologues run under its row
+// phases), more when three chunks of kLocalChunk rows do not hold its share; all chunks of a launch have the same length
+// ceil(count / (chunks per workgroup * workgroups)), the last ones may be short or empty — chunks of the full length
+// whatever the count would leave some workgroups twice the rows of others, or a small batch to a handful of workgroups.
+// LDS: lr window 4 KB + 20 bytes per row of a chunk = 24.3 KB (four workgroups per CU resident: 97 of 160 KB).
+constexpr int kLocalChunk = 1024;
+constexpr int kLocalMinChunk = 64;
+constexpr int kLocalBins = 64;
+constexpr int kLocalAim = 3;       // chunks per workgroup where the rows allow (2, 3 and 4 measure the same step: profiles/catchup_local_order.md)
+
+// workgroups for n_max rows: at most 1,024 (four resident per CU, see MI_CATCHUP_BLOCKS), and few enough that a
+// workgroup has three chunks of kLocalMinChunk rows
+int64_t local_grid(int64_t n_max) {
+  return std::min<int64_t>(1024, std::max<int64_t>(1, mi::ceil_div(n_max, 3 * kLocalMinChunk)));
+}
+
+struct LocalPlan { int64_t per_wg; int len; };          // chunks per workgroup, rows per chunk
+__host__ __device__ inline LocalPlan local_plan(int64_t count, int64_t G) {
+  int64_t k = (count + G * kLocalMinChunk - 1) / (G * kLocalMinChunk);
+  k = k < kLocalAim ? k : kLocalAim;
+  const int64_t need = (count + G * kLocalChunk - 1) / (G * kLocalChunk);
+  k = k > need ? k : need;
+  k = k > 1 ? k : 1;
+  return LocalPlan{k, static_cast<int>((count + k * G - 1) / (k * G))};
+}
+
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void sparse_catchup_local_k(
+    float* __restrict__ table, float* __restrict__ tm, float* __restrict__ tv,
+    float* __restrict__ lin_w, const float* __restrict__ lm, const float* __restrict__ lv,
+    int32_t* __restrict__ last_step, const int32_t* __restrict__ uniq_rows,
+    const int32_t* __restrict__ num_uniq, int64_t n_max, int E, int step_to,
+    const float* __restrict__ lr_table, float b1, float b2, float eps, int st,
+    const mi_step_state_t* __restrict__ ss, int64_t ts, bool rec16) {
+  constexpr int CH = kLocalChunk, RPT = CH / kBlock, RPW = 64 / LPR, WPB = kBlock / 64;
+  __shared__ float lr_s[kLrWindow];
+  __shared__ int32_t row_s[CH], stamp_s[CH];
+  __shared__ float w_s[CH], m_s[CH], v_s[CH];
+  __shared__ int bin_s[kLocalBins];
+  if (ss) step_to = ss->step - 1;
+  const int base = step_to - (kLrWindow - 1);                 // lr_s[i] = lr_t[base + i]
+  for (int i = threadIdx.x; i < kLrWindow; i += kBlock) lr_s[i] = base + i >= 1 ? lr_table[base + i] : 0.f;
+  const int t = threadIdx.x;
+  const int l = t & (LPR - 1), grp = (t & 63) / LPR, wave = t >> 6;
+  const bool lane_on = 4 * l < E;
+  const int64_t count = std::min<int64_t>(*num_uniq, n_max);
+  if (count <= 0) return;                                     // (the whole workgroup)
+  const int64_t G = gridDim.x;
+  const LocalPlan plan = local_plan(count, G);
+  const int64_t K = plan.per_wg;                              // chunks per workgroup
+  const int len = plan.len;                                   // rows per chunk, <= CH
+  const RhoSplit rho = rho_split(b2);
+  const bool wide = lin_w != nullptr;
+  // rows of chunk c of this workgroup: positions [first, first + n) of uniq_rows; n <= 0 past the end of the list
+  auto chunk_first = [&](int64_t c) { return (static_cast<int64_t>(blockIdx.x) + c * G) * len; };
+  auto chunk_rows = [&](int64_t c) {
+    return c < K ? static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(len, count - chunk_first(c)))) : 0;
+  };
+  auto load_ids = [&](int64_t c, int32_t (&id)[RPT]) {        // -1: no row
+    const int64_t first = chunk_first(c);
+    const int n = chunk_rows(c);
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) id[i] = i * kBlock + t < n ? uniq_rows[first + i * kBlock + t] : -1;
+  };
+  // rec = {w, m, v, stamp} of the wide part's scalar (w, m, v: only with a wide part)
+  auto load_recs = [&](const int32_t (&id)[RPT], float4 (&rec)[RPT]) {
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {
+      rec[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (id[i] >= 0) {
+        const int64_t r = static_cast<int64_t>(id[i]) * st;
+        if (rec16) rec[i] = ld4(lin_w + r);
+        else {
+          rec[i].w = __int_as_float(last_step[r]);
+          if (wide) { rec[i].x = lin_w[r]; rec[i].y = lm[r]; rec[i].z = lv[r]; }
+        }
+      }
+    }
+  };
+  RowIn none;
+  none.r = 0; none.ls = INT32_MAX; none.w = none.m = none.v = make_float4(0.f, 0.f, 0.f, 0.f);
+  const RowReplay ctx{table, tm, tv, last_step, lr_table, ts, step_to, base, st, l, b1, b2, eps, rho, lane_on, true, false};
+  int32_t id[RPT], id_next[RPT];
+  float4 rec[RPT];
+  load_ids(0, id);
+  load_ids(1, id_next);
+  load_recs(id, rec);
+  for (int64_t c = 0; c < K; ++c) {
+    const int n = chunk_rows(c);
+    if (n <= 0) break;                                        // (the whole workgroup; the chunks after it are empty too)
+    // ---- prologue: the counting sort of the chunk by min(gap, 63), from registers into LDS
+    if (t < kLocalBins) bin_s[t] = 0;
+    __syncthreads();                                          // (also: lr_s is filled)
+    int key[RPT];
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {
+      const int ls = __float_as_int(rec[i].w);
+      key[i] = (ls > 0 && ls < step_to) ? min(step_to - ls, kLocalBins - 1) : 0;
+      if (id[i] >= 0) atomicAdd(&bin_s[key[i]], 1);
+    }
+    __syncthreads();
+    if (t < kLocalBins) {                                     // (wave 0: an exclusive scan of the 64 counts)
+      const int cnt = bin_s[t];
+      int incl = cnt;
+#pragma unroll
+      for (int d = 1; d < kLocalBins; d <<= 1) {
+        const int up = __shfl_up(incl, d);
+        if (t >= d) incl += up;
+      }
+      bin_s[t] = incl - cnt;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < RPT; ++i)
+      if (id[i] >= 0) {
+        const int p = atomicAdd(&bin_s[key[i]], 1);           // (< n: the counts sum to n)
+        row_s[p] = id[i]; stamp_s[p] = __float_as_int(rec[i].w);
+        if (wide) { w_s[p] = rec[i].x; m_s[p] = rec[i].y; v_s[p] = rec[i].z; }
+      }
+    __syncthreads();
+    // ---- which rows this lane group replays when: the waves of the workgroup walk the chunk's quads (a wave's RPW adjacent
+    // positions) in order, from a start of the workgroup's own
+    const int n_quads = (n + RPW - 1) / RPW, n_rounds = (n_quads + WPB - 1) / WPB;
+    const int rot = static_cast<int>(((static_cast<uint32_t>(blockIdx.x) + static_cast<uint32_t>(c * G)) * 2654435761u >> 12) %
+                                     static_cast<uint32_t>(n_quads));
+    auto load_at = [&](int j) -> RowIn {                      // the row of round j: id and stamp from LDS, then w, m, v
+      const int x = j * WPB + wave;
+      int quad = x + rot;
+      if (quad >= n_quads) quad -= n_quads;
+      const int p = quad * RPW + grp;
+      if (x >= n_quads || p >= n) return none;
+      RowIn q;
+      q.r = row_s[p]; q.ls = stamp_s[p];
+      q.w = q.m = q.v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (lane_on && q.ls > 0 && q.ls < step_to) {
+        const int64_t o = q.r * ts + 4 * l;
+        q.w = ld4(table + o); q.m = ld4_nt(tm + o); q.v = ld4_nt(tv + o);
+      }
+      return q;
+    };
+    RowIn nxt = load_at(0);
+    // ---- the next chunks' loads, in flight under everything below
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) id[i] = id_next[i];
+    load_recs(id, rec);
+    load_ids(c + 2, id_next);
+    // ---- the wide part, in the sorted order
+    if (wide) {
+#pragma unroll 1
+      for (int i = 0; i < RPT; ++i) {
+        const int p = i * kBlock + t;
+        if (p < n) {
+          const int ls = stamp_s[p];
+          if (ls > 0 && ls < step_to) {
+            float m = m_s[p], rj = 1.f;
+            const float s0 = sqrtf(v_s[p]);
+            const int s_win = max(ls + 1, base);                // (steps older than the LDS window: rare)
+            float w = lin_bounded_replay(w_s[p], m, s0, rj, ls + 1, s_win - 1, [&](int s) { return lr_table[s]; }, rho, b1, eps);
+            w = lin_bounded_replay(w, m, s0, rj, s_win, step_to, [&](int s) { return lr_s[s - base]; }, rho, b1, eps);
+            lin_w[static_cast<int64_t>(row_s[p]) * st] = w;
+          }
+        }
+      }
+    }
+    // ---- the row phase
+    for (int j = 0; j < n_rounds; ++j) {
+      const RowIn cur = nxt;
+      if (j + 1 < n_rounds) nxt = load_at(j + 1);
+      replay_row_bounded(ctx, lr_s, cur);
+    }
+    __syncthreads();                                          // (row_s, stamp_s are read to the end of the row phase)
   }
 }
 
@@ -925,6 +1148,16 @@ int32_t mi_catchup_gap_keys(const int32_t* uniq_rows, const int32_t* num_uniq, c
   return MI_OK;
 }
 
+int32_t mi_catchup_local_chunk_rows(void) { return kLocalChunk; }
+
+int32_t mi_catchup_local_plan(int64_t n_max, int64_t num_uniq, int64_t* plan) {
+  MI_REQUIRE(n_max >= 0 && num_uniq >= 0 && num_uniq <= n_max && plan, "catchup_local_plan: n_max=%lld num_uniq=%lld", (long long)n_max, (long long)num_uniq);
+  const int64_t G = local_grid(n_max);
+  const LocalPlan p = local_plan(num_uniq, G);
+  plan[0] = G; plan[1] = p.per_wg; plan[2] = p.len;
+  return MI_OK;
+}
+
 int32_t mi_sparse_catchup(float* table, float* t_m, float* t_v, float* lin_w, float* l_m, float* l_v,
                           int32_t* last_step, const int32_t* uniq_rows, const int32_t* num_uniq,
                           int64_t n_max, int32_t E, int32_t step_to, const float* lr_table,
@@ -935,7 +1168,11 @@ int32_t mi_sparse_catchup(float* table, float* t_m, float* t_v, float* lin_w, fl
   MI_REQUIRE(table_stride == 0 || (table_stride >= E && (table_stride & 3) == 0), "%s: table_stride=%lld (0 = E, else >= E and a multiple of 4)", "sparse_catchup", (long long)table_stride);
   const int64_t ts = table_stride ? table_stride : E;
 
-  MI_REQUIRE((flags & ~(MI_CATCHUP_DEFER_SLOTS | MI_CATCHUP_BOUNDED | MI_CATCHUP_KEEP_STAMPS)) == 0, "sparse_catchup: flags=%d", flags);
+  MI_REQUIRE((flags & ~(MI_CATCHUP_DEFER_SLOTS | MI_CATCHUP_BOUNDED | MI_CATCHUP_KEEP_STAMPS | MI_CATCHUP_LOCAL_ORDER)) == 0, "sparse_catchup: flags=%d", flags);
+  const bool local_order = (flags & MI_CATCHUP_LOCAL_ORDER) != 0;
+  MI_REQUIRE(!local_order || (flags == (MI_CATCHUP_LOCAL_ORDER | MI_CATCHUP_BOUNDED | MI_CATCHUP_DEFER_SLOTS) && uniq_rows && num_uniq && table &&
+                              epsilon >= 1e-30f && beta2 > 0.f && beta2 <= 1.f),
+             "sparse_catchup: MI_CATCHUP_LOCAL_ORDER needs MI_CATCHUP_BOUNDED | MI_CATCHUP_DEFER_SLOTS (and no other flag), uniq_rows and a table (flags=%d)", flags);
   const bool keep_stamps = (flags & MI_CATCHUP_KEEP_STAMPS) != 0;
   const int32_t defer_slots = flags & MI_CATCHUP_DEFER_SLOTS;
   // the bounded form divides by rcp(sqrt(v) + eps): eps must keep that sum a normal number (TF's default 1e-8 does)
@@ -948,6 +1185,18 @@ int32_t mi_sparse_catchup(float* table, float* t_m, float* t_v, float* lin_w, fl
   MI_REQUIRE(!lin_w || (l_m && l_v), "sparse_catchup: lin_w needs m, v");
   MI_REQUIRE(!uniq_rows || num_uniq, "sparse_catchup: uniq_rows without num_uniq");
   const bool defer = defer_slots != 0 && uniq_rows != nullptr;
+  if (local_order) {
+    // ONE launch: the staleness order (per chunk, in LDS), the wide part's replay and the rows'
+    const int lpr = lanes_per_row(E);
+    // the wide part's {w, m, v, stamp} records: one 16-byte load each
+    const bool rec16 = lin_w && lin_stride == 4 && l_m == lin_w + 1 && l_v == lin_w + 2 &&
+                       reinterpret_cast<const float*>(last_step) == lin_w + 3 && mi::aligned16(lin_w);
+    MI_DISPATCH_LPR(lpr, (sparse_catchup_local_k<L><<<dim3((unsigned)local_grid(n_max)), dim3(kBlock), 0, mi::as_stream(stream)>>>(
+                             table, t_m, t_v, lin_w, l_m, l_v, last_step, uniq_rows, num_uniq, n_max, E, step_to, lr_table, beta1, beta2,
+                             epsilon, lin_stride, mi::step_state(), ts, rec16)));
+    MI_CHECK_LAUNCH("sparse_catchup(local order)");
+    return MI_OK;
+  }
   if (lin_w) {
     catchup_lin_k<<<dim3((unsigned)mi::ceil_div(n_max, kBlock)), dim3(kBlock), 0, mi::as_stream(stream)>>>(
         lin_w, l_m, l_v, last_step, uniq_rows, num_uniq, n_max, step_to, lr_table, beta1, beta2, epsilon, defer, lin_stride, mi::step_state(),

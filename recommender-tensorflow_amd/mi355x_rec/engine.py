@@ -1399,6 +1399,7 @@ class DeepFM:
     GAP_SORT_MIN = 16384      # entries from which sorting the touched rows by staleness pays for itself
     TOP_FUSED_MIN_BATCH = 4096  # examples from which the last hidden layer joins the fused logits + head launch (_top_fusable)
     GRAPH_SHAPES_MAX = 4      # captured steps kept at a time, one per batch shape (graph_train_step)
+    LOCAL_CATCHUP = True      # the deferred, bounded single-GPU catch-up as ONE launch that orders its rows itself (_local_catchup)
 
     def _new_side_stream(self, priority=0):
         """A stream whose kernels really run BESIDE the step's stream and beside the side streams handed out before it.
@@ -1428,11 +1429,20 @@ class DeepFM:
         for sc in (self.sched, self.lin_sched):
             if sc is not None:
                 sc.lr_t(self.step)  # make sure the table covers step
-        if uniq is not None and n_max >= self.GAP_SORT_MIN:
-            uniq = by_gap if by_gap is not None else self._rows_by_gap(uniq, num_uniq, n_max, self.step)
         flags = (1 if defer else 0) | (2 if self.catchup == "bounded" else 0)
         t_sched = self.sched if t_adam else None
         l_sched = (self.lin_sched if self.lin_opt is not None else (self.lin_sched or self.sched)) if l_adam else None
+        if self._local_catchup(defer, n_max):
+            # ONE launch on the step's stream: the kernel orders its rows by staleness itself (windows of a workgroup's rows,
+            # in LDS) and replays the wide part from the records it reads the stamps from — no _rows_by_gap, no wide-part
+            # kernel, no fork (the wide forward's stream waits for the step's stream anyway: _forward)
+            s = t_sched.spec
+            self.k.mi_sparse_catchup(self.table, self.t_s0, self.t_s1, self.lin_w, self.l_s0, self.l_s1, self.last_step, uniq,
+                                     num_uniq, n_max, self.E, self.step, t_sched.table, s.beta1, s.beta2, s.epsilon,
+                                     flags | 8, self.ls, self.ts)          # (8 = MI_CATCHUP_LOCAL_ORDER)
+            return
+        if uniq is not None and n_max >= self.GAP_SORT_MIN:
+            uniq = by_gap if by_gap is not None else self._rows_by_gap(uniq, num_uniq, n_max, self.step)
         side = None
         if t_sched is not None and l_sched is not None and t_sched is not l_sched:
             # two different Adams (tables vs wide part): one call each, with its own lr_t table and betas.  The table
@@ -1464,6 +1474,19 @@ class DeepFM:
                     call()
             else:
                 call()
+
+    def _local_catchup(self, defer, n_max):
+        """Does the catch-up of a step's n_max entries run as ONE MI_CATCHUP_LOCAL_ORDER launch?  Exactly where _catchup
+        would otherwise split the wide part's replay onto the side stream: deferred, bounded, ONE Adam for tables and wide
+        part, one GPU, on the device.  Exact mode, two Adams, no-defer calls (finalize_rows), the row-sharded step and the
+        CPU engine keep their paths."""
+        t_adam = self.opt.name == "Adam" and self.table is not None
+        l_adam = (self.lin_opt or self.opt).name == "Adam" and self.lin_w is not None
+        return bool(self.LOCAL_CATCHUP and defer and self.catchup == "bounded" and t_adam and l_adam and self.lin_opt is None
+                    and (self.lin_sched is None or self.lin_sched is self.sched)
+                    and self.opt.epsilon >= 1e-30 and 0.0 < self.opt.beta2 <= 1.0      # (where the library runs the bounded form at all)
+                    and self.shard is None and self.device.type == "cuda"
+                    and self._wide_on_side_stream(n_max // max(self.F, 1)))
 
     def _side_stream(self):
         side = self._ws.get("side_stream")
@@ -1543,12 +1566,19 @@ class DeepFM:
         """Second half of _presort, enqueued after the head: the staleness order of the next batch's rows, on the same side
         stream, behind this step's forward.  There — the logits layer, the head and the small layer-3 kernels, ~0.15 ms in
         which most of the chip idles — it costs nothing; right after the sort it ran beside the gather (HBM-bound: 176 ->
-        231 us) and the layer-1 forward GEMM (310 -> 374 us: kernel timelines, tools/step_timeline.py)."""
+        231 us) and the layer-1 forward GEMM (310 -> 374 us: kernel timelines, tools/step_timeline.py).
+        by_gap_step names the step whose order is settled.  In local-order mode (_local_catchup) "settled" means "needs
+        no pass": the catch-up kernel orders its rows itself, so by_gap_step is set and by_gap stays None."""
         ps = self._presorted
         if ps is None or not self.adam_rows:
             return
         n = ps["ids"].shape[0] * self.F
         if n < self.GAP_SORT_MIN:
+            return
+        if self._local_catchup(self.lin_opt is None, n):
+            # the next catch-up orders its rows itself: the order of step + 1 is settled here in the sense that it needs
+            # no pass — nothing is launched, by_gap stays None
+            ps["by_gap_step"] = self.step + 1
             return
         side = ps["stream"]
         side.wait_stream(torch.cuda.current_stream())

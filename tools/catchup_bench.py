@@ -2,7 +2,10 @@
 """The lazy Adam catch-up alone at config 3's size: 26 M rows x E = 64 (table + m + v = 20 GB), a batch's ~1.65 M distinct
 rows with geometric gaps (mean 15 steps), sorted by staleness as the step does (mi_catchup_rows_by_gap), then
 mi_sparse_catchup in the exact and the bounded-error form (deferred slots, as inside a train step).  HIP events.
-MI_CATCHUP_BLOCKS sets the pipelined bounded kernel's grid."""
+MI_CATCHUP_BLOCKS sets the pipelined bounded kernel's grid.
+Then the step's whole catch-up both ways: mi_catchup_rows_by_gap + the wide part's kernel + the bounded row kernel (three
+calls, timed together and apart) against the ONE MI_CATCHUP_LOCAL_ORDER launch on the rows in the sort's row order — with
+the replayed steps per wave of its windowed order (simulated on the host from the same gaps) against the ideal."""
 import os
 import sys
 
@@ -64,6 +67,59 @@ def main():
     for name, flags in (("exact", 1), ("bounded", 3)):
         best, med = run(flags, order=rows)
         print("%-8s rows kernel, rows NOT sorted by staleness: best %.3f ms, median %.3f ms" % (name, best, med), flush=True)
+    # ---- the step's whole catch-up: today's three calls against the one local-order launch
+    def timed(calls, n=6):
+        ts = []
+        for _ in range(n):
+            w.copy_(w0); rec[:, 0].copy_(lin0)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            for c in calls:
+                c()
+            b.record(); torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b))
+        return min(ts), float(np.median(ts))
+
+    lw, lm, lv = rec[:, 0], rec[:, 1], rec[:, 2]
+
+    def by_gap_call():
+        _lib.check(lib.mi_catchup_rows_by_gap(rows.data_ptr(), nu.data_ptr(), last.data_ptr(), U, step_to, 4, by_gap.data_ptr(), ws.data_ptr(), ws.numel(), st()), "by_gap")
+
+    def catchup_call(table, wide, order, flags):
+        return lambda: _lib.check(lib.mi_sparse_catchup(
+            w.data_ptr() if table else None, m.data_ptr() if table else None, v.data_ptr() if table else None,
+            lw.data_ptr() if wide else None, lm.data_ptr() if wide else None, lv.data_ptr() if wide else None, last.data_ptr(),
+            order.data_ptr(), nu.data_ptr(), U, E, step_to, lr.data_ptr(), 0.9, 0.999, 1e-8, flags, 4, 0, st()), "catchup")
+
+    legs = (("rows_by_gap", [by_gap_call]), ("wide part alone (catchup_lin_k)", [catchup_call(False, True, by_gap, 3)]),
+            ("bounded rows alone, sorted", [catchup_call(True, False, by_gap, 3)]),
+            ("the three in sequence", [by_gap_call, catchup_call(False, True, by_gap, 3), catchup_call(True, False, by_gap, 3)]),
+            ("LOCAL_ORDER, one launch (rows + wide part)", [catchup_call(True, True, rows, 3 | 8)]),
+            ("LOCAL_ORDER, rows only", [catchup_call(True, False, rows, 3 | 8)]))
+    for name, calls in legs:
+        best, med = timed(calls)
+        print("%-44s best %.3f ms, median %.3f ms" % (name, best, med), flush=True)
+    timed(legs[3][1], 1); w3, l3 = w.clone(), rec[:, 0].clone()
+    timed(legs[4][1], 1)
+    print("LOCAL_ORDER vs the three calls: table bit-identical %s, wide part bit-identical %s" %
+          (bool(torch.equal(w.view(torch.int32), w3.view(torch.int32))), bool(torch.equal(rec[:, 0].view(torch.int32), l3.view(torch.int32)))))
+    # replayed steps per wave (E = 64: four rows per wave, a wave runs as long as its stalest row) over the ideal (the mean)
+    ch, plan = int(lib.mi_catchup_local_chunk_rows()), np.zeros(3, np.int64)
+    _lib.check(lib.mi_catchup_local_plan(U, U, plan.ctypes.data), "plan")
+    G, ln = int(plan[0]), int(plan[2])
+    gp = gaps[rows.long()].cpu().numpy().astype(np.int64)
+
+    def per_wave(x):
+        pad = (-len(x)) % 4
+        return np.concatenate([x, np.zeros(pad, np.int64)]).reshape(-1, 4).max(1).sum() * 4
+
+    def keyed(x):                 # the kernel's order: a counting sort on min(gap, 63)
+        return x[np.argsort(np.minimum(x, 63), kind="stable")]
+
+    local = sum(per_wave(keyed(gp[i:i + ln])) for i in range(0, U, ln))
+    print("replayed steps per wave / ideal: unsorted %.3f, local order (%d workgroups, chunks of %d <= %d rows) %.3f, global sort %.3f" %
+          (per_wave(gp) / gp.sum(), G, ln, ch, local / gp.sum(), per_wave(np.sort(gp)) / gp.sum()), flush=True)
     we = w.clone()
     run(1, 1); wx = w.clone()
     run(3, 1); wb = w.clone()
