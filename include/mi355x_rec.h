@@ -720,6 +720,45 @@ int32_t mi_pair_topk(const float* a_q, const float* s_q, const float* w_q, int64
                      float* top_score, int32_t* top_idx, float* scores, void* workspace, size_t workspace_bytes,
                      mi_stream_t stream);
 
+/* ---- top-K recommendation with an ensemble: M models, one selection, one launch (csrc/rank.hip) ---------------------
+ * What mi_pair_topk does for one model, for the mean logit of M models (the best members of a trainers.sweep): every
+ * pair is scored by every member and
+ *   z(q, c) = (((z_0 + z_1) + z_2) + ... + z_{M-1}) / (float)M     fp32, ascending member order, one rounding per
+ *   operation, IEEE division (mi_predict_group's definition)
+ * enters the selection — the grid, the on-chip running top-k, the order (score descending, equal scores by ascending
+ * index, NaN below every number, -0 as +0), the exclusions and the -1 / -inf padding of mi_pair_topk.  z_m is bit for bit
+ * the score mi_pair_topk gives member m alone (the same device function).  M = 1 takes the same path (z_0 / 1.0f).
+ *
+ * mi_rank_member_t: the per-model arguments of mi_pair_topk (same meaning, same checks and messages, prefixed
+ *   "member i:"; layer_off / widths on the host).  Members share U, I, k and the exclusions; they may differ in H1, E,
+ *   the layers, the activation, the model's parts (NULL w_q / w_c, H1 = 0, E = 0) and dense.
+ * Scope: the VALU pair path only — a member qualifies if it has fewer than two layers after layer 1 or every hidden
+ *   width after layer 1 is below 32 (any H1 <= 4096); any other member: MI_ERR_UNSUPPORTED.
+ * Outputs: top_score / top_idx [U, k] as mi_pair_topk; optional (NULL on the hot path) scores [U, I], the mean, and
+ *   member_scores [M, U, I], every member's own score.
+ * workspace: mi_pair_topk_group_workspace_bytes(members, n_members, U, I, k) (only H1 and E of a member are read; 0 for
+ *   arguments out of range) — it holds the member table, the transposes, the exclusion mask and the partial lists.
+ * Launches: the member table (through the kernel arguments, 8 members a launch), one transpose launch for all members,
+ *   the exclusion mask, ONE pair scoring and selection launch and the final merge; no copy, no synchronisation.  No
+ *   workgroup reads what another writes in a launch and none waits for another; two calls give the same bits.
+ * Refused on the host before anything is launched: n_members < 1 (MI_ERR_INVALID) or above
+ *   MI_PAIR_TOPK_GROUP_MAX_MEMBERS (MI_ERR_UNSUPPORTED), a member outside the scope (MI_ERR_UNSUPPORTED) or failing
+ *   mi_pair_topk's checks, a short workspace, NULL top_score / top_idx, excl_off without excl_idx (MI_ERR_INVALID). */
+#define MI_PAIR_TOPK_GROUP_MAX_MEMBERS 256 /* = MI_PREDICT_GROUP_MAX_MEMBERS */
+typedef struct mi_rank_member {
+  const float* a_q; const float* s_q; const float* w_q;
+  const float* a_c; const float* s_c; const float* w_c;
+  const float* dense;
+  const int64_t* layer_off;
+  const int32_t* widths;
+  int32_t H1, E, n_layers, activation;
+} mi_rank_member_t;
+
+size_t mi_pair_topk_group_workspace_bytes(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, int32_t k);
+int32_t mi_pair_topk_group(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, const int64_t* excl_off,
+                           const int32_t* excl_idx, int32_t k, float* top_score, int32_t* top_idx, float* scores,
+                           float* member_scores, void* workspace, size_t workspace_bytes, mi_stream_t stream);
+
 /* ---- serving: the forward of a request batch as one launch (csrc/serve.hip) ---------------------------------------
  * For B requests, what DeepFM.predict_logits followed by mi_binary_predictions computes (deep_fm.py:36-125 in PREDICT
  * mode, model_utils.py:9-20; the requests of ml_100k.py:64-88's receiver after the columns' id transforms):

@@ -249,6 +249,28 @@ __device__ __forceinline__ float dnn_valu(const PairArgs& p, const float* __rest
   }
 }
 
+// ---- the score of one pair -------------------------------------------------------------------------------------------
+// logit(q, c) of the model p for candidate c and the lane's query column qcol: the DNN on act(a_q + a_c), the E-wide dot of
+// the two embedding sums, and the head's order ((w_q + w_c) + dot) + dnn.  wq / sq: the lane's w_q and its column of sqT
+// (NULL without the FM term).  Both pair kernels call this: a group member's score is its own kernel's, bit for bit
+// (every product is an explicit fmaf and no multiply feeds an add, so there is nothing for the compiler to contract).
+template <bool MFMA, int NP, int NQ>
+__device__ __forceinline__ float pair_score(const PairArgs& p, int64_t c, int64_t qcol, int h, float wq,
+                                            const float* __restrict__ sq) {
+  float dnn = 0.f;
+  if (p.H1 > 0) {
+    const float* __restrict__ ac = p.a_c + c * p.H1;
+    if constexpr (MFMA) dnn = dnn_mfma<NP, NQ>(p, ac, qcol, h);
+    else dnn = dnn_valu(p, ac, qcol);
+  }
+  float dot = 0.f;
+  if (sq) {
+    const float* __restrict__ sc = p.s_c + c * p.E;
+    for (int e = 0; e < p.E; ++e) dot = fmaf(sq[static_cast<int64_t>(e) * p.Upad], sc[e], dot);
+  }
+  return ((wq + (p.w_c ? p.w_c[c] : 0.f)) + dot) + dnn;
+}
+
 // ---- selection --------------------------------------------------------------------------------------------------------
 // Merge every query's survivors into its sorted list: a list entry moves down by the survivors that beat it, a survivor
 // lands at (list entries that beat it) + (survivors that beat it).  Entries pushed to K or beyond drop out; empty slots
@@ -318,18 +340,7 @@ __global__ __launch_bounds__(kThreads) void pair_score_topk_k(const PairArgs p) 
   for (int64_t base = c_begin; base < c_end; base += kWaves) {
     const int64_t c = base + wave;
     if (c < c_end) {                                              // (wave-uniform)
-      float dnn = 0.f;
-      if (p.H1 > 0) {
-        const float* __restrict__ ac = p.a_c + c * p.H1;
-        if constexpr (MFMA) dnn = dnn_mfma<NP, NQ>(p, ac, q0 + col, h);
-        else dnn = dnn_valu(p, ac, q0 + col);
-      }
-      float dot = 0.f;
-      if (sq) {
-        const float* __restrict__ sc = p.s_c + c * p.E;
-        for (int e = 0; e < p.E; ++e) dot = fmaf(sq[static_cast<int64_t>(e) * p.Upad], sc[e], dot);
-      }
-      const float s = ((wq + (p.w_c ? p.w_c[c] : 0.f)) + dot) + dnn;
+      const float s = pair_score<MFMA, NP, NQ>(p, c, q0 + col, h, wq, sq);
       if (h == 0 && q_ok) {
         if (p.scores) p.scores[q * p.I + c] = s;
         const bool excluded = p.excl && ((p.excl[q * p.words + (c >> 5)] >> (c & 31)) & 1u);
@@ -352,6 +363,106 @@ __global__ __launch_bounds__(kThreads) void pair_score_topk_k(const PairArgs p) 
   for (int i = tid; i < kQB * K; i += kThreads) {
     const int qq = i / K;
     if (q0 + qq < p.U) p.part[((q0 + qq) * p.splits + split) * K + (i - qq * K)] = list[i];
+  }
+}
+
+// ---- an ensemble: M models, one selection (mi_pair_topk_group) ------------------------------------------------------
+// A member of the group as the kernels see it, in device memory (workspace): the scoring arguments of its own
+// pair_score_topk_k (p.l points at l below, p.aqT / p.sqT at the member's transposes in the workspace) and the caller's
+// query-side tensors the transposes are made from.
+struct GroupMember {
+  PairArgs p;
+  const float* a_q;                     // [U][H1]
+  const float* s_q;                     // [U][E]
+  Layer l[kMaxLayers];
+};
+
+// A member's scoring arguments from the table, word by word and every word made wave-uniform (readfirstlane): the loop
+// bounds, the activation and the pointers stay in scalar registers, as pair_score_topk_k holds its kernel arguments.  A
+// pointer is put together from its two words AS A GLOBAL ONE: a pointer read from memory is a generic pointer to the
+// compiler, and it treats what a generic (flat) load returns as divergent — the layer table's widths, every loop bound.
+struct MemberWords {
+  const uint32_t* __restrict__ w;
+  __device__ __forceinline__ uint32_t u32(size_t off) const { return __builtin_amdgcn_readfirstlane(w[off / 4]); }
+  template <class T>
+  __device__ __forceinline__ const T* ptr(size_t off) const {
+    const uint64_t v = u32(off) | (static_cast<uint64_t>(u32(off + 4)) << 32);
+    return (const T*)(const __attribute__((address_space(1))) T*)v;
+  }
+};
+
+__device__ __forceinline__ PairArgs load_member(const GroupMember* __restrict__ gm) {
+  const MemberWords m{reinterpret_cast<const uint32_t*>(&gm->p)};
+  PairArgs p{};                                  // (the fields pair_score reads; the selection's are the group's)
+  p.aqT = m.ptr<float>(offsetof(PairArgs, aqT)); p.a_c = m.ptr<float>(offsetof(PairArgs, a_c));
+  p.sqT = m.ptr<float>(offsetof(PairArgs, sqT)); p.s_c = m.ptr<float>(offsetof(PairArgs, s_c));
+  p.w_q = m.ptr<float>(offsetof(PairArgs, w_q)); p.w_c = m.ptr<float>(offsetof(PairArgs, w_c));
+  p.dense = m.ptr<float>(offsetof(PairArgs, dense)); p.l = m.ptr<Layer>(offsetof(PairArgs, l));
+  p.Upad = static_cast<int32_t>(m.u32(offsetof(PairArgs, Upad))); p.H1 = static_cast<int32_t>(m.u32(offsetof(PairArgs, H1)));
+  p.E = static_cast<int32_t>(m.u32(offsetof(PairArgs, E))); p.act = static_cast<int32_t>(m.u32(offsetof(PairArgs, act)));
+  p.n_layers = static_cast<int32_t>(m.u32(offsetof(PairArgs, n_layers)));
+  return p;
+}
+
+// The grid, the LDS lists and the selection of pair_score_topk_k; what enters the selection is the mean logit
+//   z = (((z_0 + z_1) + z_2) + ... + z_{M-1}) / (float)M    ascending member order, one rounding per operation
+// (mi_predict_group's definition), z_m = pair_score on member m's arguments (the VALU path: mi_pair_topk_group refuses a
+// member whose own call would take the MFMA path).  The member table is read from device memory with wave-uniform
+// addresses; nothing of it lives in LDS.
+__global__ __launch_bounds__(kThreads) void pair_score_topk_group_k(const GroupMember* __restrict__ tab, int M,
+                                                                   const uint32_t* __restrict__ excl, float* __restrict__ scores,
+                                                                   float* __restrict__ member_scores, uint64_t* __restrict__ part,
+                                                                   int64_t U, int64_t I, int64_t chunk, int K, int splits,
+                                                                   int words) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  uint64_t* list = reinterpret_cast<uint64_t*>(lds);             // [kQB][K], descending, 0 = empty
+  uint64_t* surv = list + kQB * K;                                // [kQB][kSurv]
+  int* nsurv = reinterpret_cast<int*>(surv + kQB * kSurv);        // [kQB]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31, h = lane >> 5;
+  const int64_t q0 = static_cast<int64_t>(blockIdx.x) * kQB;
+  const int split = blockIdx.y;
+  const int64_t c_begin = split * chunk;
+  const int64_t c_end = c_begin + chunk < I ? c_begin + chunk : I;
+  for (int i = tid; i < kQB * K; i += kThreads) list[i] = 0;
+  if (tid < kQB) nsurv[tid] = 0;
+  __syncthreads();
+  const int64_t q = q0 + col;
+  const bool q_ok = q < U;
+  const float fM = static_cast<float>(M);
+  for (int64_t base = c_begin; base < c_end; base += kWaves) {
+    const int64_t c = base + wave;
+    if (c < c_end) {                                              // (wave-uniform)
+      float acc = 0.f;
+      for (int m = 0; m < M; ++m) {
+        const PairArgs p = load_member(tab + m);
+        const float wq = (p.w_q && q_ok) ? p.w_q[q] : 0.f;
+        const float* __restrict__ sq = p.sqT ? p.sqT + q0 + col : nullptr;
+        const float z = pair_score<false, 1, 1>(p, c, q0 + col, h, wq, sq);
+        if (member_scores && h == 0 && q_ok) member_scores[(static_cast<int64_t>(m) * U + q) * I + c] = z;
+        acc = m == 0 ? z : acc + z;
+      }
+      const float s = acc / fM;
+      if (h == 0 && q_ok) {
+        if (scores) scores[q * I + c] = s;
+        const bool excluded = excl && ((excl[q * words + (c >> 5)] >> (c & 31)) & 1u);
+        if (!excluded) {
+          const uint64_t key = rank_key(s, static_cast<uint32_t>(c));
+          if (key > list[col * K + K - 1]) {
+            const int slot = atomicAdd(&nsurv[col], 1);
+            surv[col * kSurv + slot] = key;
+          }
+        }
+      }
+    }
+    // (as in pair_score_topk_k: the counts are read only after every wave's appends of this round are in)
+    __syncthreads();
+    if (__syncthreads_or(tid < kQB && nsurv[tid] > kSurv - kWaves)) merge_survivors(list, surv, nsurv, K, wave, lane);
+  }
+  __syncthreads();
+  if (__syncthreads_or(tid < kQB && nsurv[tid] > 0)) merge_survivors(list, surv, nsurv, K, wave, lane);
+  for (int i = tid; i < kQB * K; i += kThreads) {
+    const int qq = i / K;
+    if (q0 + qq < U) part[((q0 + qq) * splits + split) * K + (i - qq * K)] = list[i];
   }
 }
 
@@ -427,6 +538,35 @@ __global__ __launch_bounds__(256) void excl_mask_k(const int64_t* __restrict__ o
   }
 }
 
+// The group's member table reaches the workspace through the kernel arguments, kTabChunk members a launch (compile-time
+// indices: see PairArgs::l) — no host-to-device copy, so the call neither synchronises nor needs pinned memory.
+constexpr int kTabChunk = 8;
+struct MemberChunk {
+  GroupMember m[kTabChunk];
+};
+static_assert(sizeof(MemberChunk) <= 3072, "the member chunk travels in the kernel arguments");
+
+__global__ __launch_bounds__(64) void member_table_k(const MemberChunk t, int n, GroupMember* __restrict__ out) {
+#pragma unroll
+  for (int i = 0; i < kTabChunk; ++i)
+    if (i < n && threadIdx.x == 0) out[i] = t.m[i];
+}
+
+// transpose_pad_k for every member in one launch: grid (blocks, M, 2), z = 0: a_q -> aqT, z = 1: s_q -> sqT
+__global__ __launch_bounds__(256) void transpose_pad_group_k(const GroupMember* __restrict__ tab, int64_t U) {
+  const GroupMember& gm = tab[blockIdx.y];
+  const bool a = blockIdx.z == 0;
+  const float* __restrict__ src = a ? gm.a_q : gm.s_q;
+  float* __restrict__ dst = const_cast<float*>(a ? gm.p.aqT : gm.p.sqT);
+  if (!dst) return;
+  const int W = a ? gm.p.H1 : gm.p.E, Upad = gm.p.Upad;
+  const int64_t n = static_cast<int64_t>(W) * Upad;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * 256) {
+    const int64_t k = i / Upad, q = i - k * Upad;
+    dst[i] = q < U ? src[q * W + k] : 0.f;
+  }
+}
+
 struct Plan {
   int64_t Upad, qblocks, chunk;
   int32_t splits, words;
@@ -463,6 +603,86 @@ bool sizes_ok(int64_t U, int64_t I, int32_t k, int32_t H1, int32_t E) {
          mi::ceil_div(U, kQB) <= INT32_MAX;
 }
 
+// The checks of mi_pair_topk in their order, shared with mi_pair_topk_group (which prefixes "member i:" and has checked the
+// per-call arguments — outputs, excl_paired — itself): fills the layer table and maxw, the largest hidden width after layer 1.
+int32_t check_model(int64_t U, int64_t I, int32_t k, const float* a_q, const float* s_q, const float* a_c, const float* s_c,
+                    int32_t H1, int32_t E, const float* dense, const int64_t* layer_off, const int32_t* widths,
+                    int32_t n_layers, int32_t activation, bool outputs, bool excl_paired, LayerTable& lt, int& maxw) {
+  MI_REQUIRE(sizes_ok(U, I, k, H1, E), "pair_topk: U=%lld I=%lld k=%d H1=%d E=%d out of range (U, I >= 1, 1 <= k <= %d, "
+             "H1 <= %d, E <= 256)", (long long)U, (long long)I, k, H1, E, kMaxK, kMaxH1);
+  MI_REQUIRE(outputs, "pair_topk: top_score / top_idx");
+  MI_REQUIRE(activation >= 0 && activation <= 3, "pair_topk: activation %d", activation);
+  MI_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "pair_topk: %d layers after layer 1 (at most %d)", n_layers, kMaxLayers);
+  MI_REQUIRE(H1 == 0 || (a_q && a_c && dense && (n_layers == 0 || (layer_off && widths))),
+             "pair_topk: a_q / a_c / dense / layer_off / widths");
+  MI_REQUIRE(H1 > 0 || n_layers == 0, "pair_topk: layers without a layer 1");
+  MI_REQUIRE(H1 == 0 || n_layers > 0 || H1 == 1, "pair_topk: without hidden layers layer 1 is the logits layer (H1 = 1)");
+  MI_REQUIRE(E == 0 || (s_q && s_c), "pair_topk: s_q / s_c");
+  MI_REQUIRE(excl_paired, "pair_topk: excl_off and excl_idx go together");
+  int wp = 0, wq = 0;                            // widths of layers 2..L-1 at even / odd positions
+  maxw = 0;
+  for (int i = 0; i < n_layers; ++i) {
+    const int fi = widths[i], fo = widths[i + 1];
+    MI_REQUIRE(fi >= 1 && fo >= 1, "pair_topk: width %d -> %d", fi, fo);
+    MI_REQUIRE(i > 0 || fi == H1, "pair_topk: widths[0]=%d != H1=%d", fi, H1);
+    MI_REQUIRE(i + 1 < n_layers || fo == 1, "pair_topk: the last layer has %d outputs (1 expected)", fo);
+    MI_REQUIRE(layer_off[2 * i] >= 0 && layer_off[2 * i + 1] >= 0, "pair_topk: layer offsets");
+    if (i + 1 < n_layers) {
+      if (fo > maxw) maxw = fo;
+      int& w = (i & 1) ? wq : wp;
+      if (fo > w) w = fo;
+    }
+    lt.l[i] = Layer{layer_off[2 * i], layer_off[2 * i + 1], fi, fo};
+  }
+  MI_REQUIRE(wp <= kMaxRegWidth && wq <= kMaxRegWidth / 2, "pair_topk: hidden widths after layer 1: layers 2, 4, ... at most "
+             "%d (here %d), layers 3, 5, ... at most %d (here %d)", kMaxRegWidth, wp, kMaxRegWidth / 2, wq);
+  return MI_OK;
+}
+
+// does mi_pair_topk score this model on the MFMA (launch_pair<true, ...>)?  Otherwise the VALU loop (<false, 1, 1>)
+inline bool takes_mfma(int n_layers, int maxw) { return n_layers >= 2 && maxw >= kValuW; }
+
+int32_t unsupported(const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  mi::set_error("%s", buf);
+  return MI_ERR_UNSUPPORTED;
+}
+
+// What the group shares (query blocks, splits, exclusion mask, partial lists: make_plan with no per-model tensors) and
+// where the member table and the members' transposes lie in the workspace.
+constexpr size_t kMaxGroupLds = 160 * 1024;      // the dynamic LDS a launch can be raised to on gfx950
+
+struct GroupPlan {
+  Plan pl;
+  size_t off_table, off_sides, total;
+};
+
+inline size_t side_bytes(const Plan& pl, int32_t H1, int32_t E) {
+  return align256(sizeof(float) * static_cast<size_t>(H1) * pl.Upad) + align256(sizeof(float) * static_cast<size_t>(E) * pl.Upad);
+}
+
+bool group_sizes_ok(const mi_rank_member_t* members, int32_t n, int64_t U, int64_t I, int32_t k) {
+  if (!members || n < 1 || n > MI_PAIR_TOPK_GROUP_MAX_MEMBERS) return false;
+  for (int32_t i = 0; i < n; ++i)
+    if (!sizes_ok(U, I, k, members[i].H1, members[i].E)) return false;
+  return true;
+}
+
+GroupPlan make_group_plan(const mi_rank_member_t* members, int32_t n, int64_t U, int64_t I, int32_t k) {
+  GroupPlan gp;
+  gp.pl = make_plan(U, I, k, 0, 0);
+  size_t o = gp.pl.total;
+  gp.off_table = o; o += align256(sizeof(GroupMember) * static_cast<size_t>(n));
+  gp.off_sides = o;
+  for (int32_t i = 0; i < n; ++i) o += side_bytes(gp.pl, members[i].H1, members[i].E);
+  gp.total = o;
+  return gp;
+}
+
 template <bool MFMA, int NP, int NQ>
 hipError_t launch_pair(const PairArgs& a, dim3 grid, size_t lds, hipStream_t st) {
   if (lds > 64 * 1024) {
@@ -489,36 +709,13 @@ int32_t mi_pair_topk(const float* a_q, const float* s_q, const float* w_q, int64
                      int32_t activation, const int64_t* excl_off, const int32_t* excl_idx, int32_t k,
                      float* top_score, int32_t* top_idx, float* scores, void* workspace, size_t workspace_bytes,
                      mi_stream_t stream) {
-  MI_REQUIRE(sizes_ok(U, I, k, H1, E), "pair_topk: U=%lld I=%lld k=%d H1=%d E=%d out of range (U, I >= 1, 1 <= k <= %d, "
-             "H1 <= %d, E <= 256)", (long long)U, (long long)I, k, H1, E, kMaxK, kMaxH1);
-  MI_REQUIRE(top_score && top_idx, "pair_topk: top_score / top_idx");
-  MI_REQUIRE(activation >= 0 && activation <= 3, "pair_topk: activation %d", activation);
-  MI_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "pair_topk: %d layers after layer 1 (at most %d)", n_layers, kMaxLayers);
-  MI_REQUIRE(H1 == 0 || (a_q && a_c && dense && (n_layers == 0 || (layer_off && widths))),
-             "pair_topk: a_q / a_c / dense / layer_off / widths");
-  MI_REQUIRE(H1 > 0 || n_layers == 0, "pair_topk: layers without a layer 1");
-  MI_REQUIRE(H1 == 0 || n_layers > 0 || H1 == 1, "pair_topk: without hidden layers layer 1 is the logits layer (H1 = 1)");
-  MI_REQUIRE(E == 0 || (s_q && s_c), "pair_topk: s_q / s_c");
-  MI_REQUIRE(!excl_off == !excl_idx, "pair_topk: excl_off and excl_idx go together");
   PairArgs a{};
   LayerTable lt{};
+  int maxw = 0;
+  const int32_t rc = check_model(U, I, k, a_q, s_q, a_c, s_c, H1, E, dense, layer_off, widths, n_layers, activation,
+                                 top_score && top_idx, !excl_off == !excl_idx, lt, maxw);
+  if (rc != MI_OK) return rc;
   a.n_layers = n_layers;
-  int maxw = 0, wp = 0, wq = 0;                  // widths of layers 2..L-1: all, at even / odd positions
-  for (int i = 0; i < n_layers; ++i) {
-    const int fi = widths[i], fo = widths[i + 1];
-    MI_REQUIRE(fi >= 1 && fo >= 1, "pair_topk: width %d -> %d", fi, fo);
-    MI_REQUIRE(i > 0 || fi == H1, "pair_topk: widths[0]=%d != H1=%d", fi, H1);
-    MI_REQUIRE(i + 1 < n_layers || fo == 1, "pair_topk: the last layer has %d outputs (1 expected)", fo);
-    MI_REQUIRE(layer_off[2 * i] >= 0 && layer_off[2 * i + 1] >= 0, "pair_topk: layer offsets");
-    if (i + 1 < n_layers) {
-      if (fo > maxw) maxw = fo;
-      int& w = (i & 1) ? wq : wp;
-      if (fo > w) w = fo;
-    }
-    lt.l[i] = Layer{layer_off[2 * i], layer_off[2 * i + 1], fi, fo};
-  }
-  MI_REQUIRE(wp <= kMaxRegWidth && wq <= kMaxRegWidth / 2, "pair_topk: hidden widths after layer 1: layers 2, 4, ... at most "
-             "%d (here %d), layers 3, 5, ... at most %d (here %d)", kMaxRegWidth, wp, kMaxRegWidth / 2, wq);
   const Plan pl = make_plan(U, I, k, H1, E);
   MI_REQUIRE(workspace && workspace_bytes >= pl.total, "pair_topk: workspace %zu < %zu bytes", workspace_bytes, pl.total);
   hipStream_t st = mi::as_stream(stream);
@@ -545,7 +742,7 @@ int32_t mi_pair_topk(const float* a_q, const float* s_q, const float* w_q, int64
   const size_t lds = sizeof(uint64_t) * kQB * (k + kSurv) + sizeof(int) * kQB;
   const dim3 grid(static_cast<unsigned>(pl.qblocks), static_cast<unsigned>(pl.splits));
   hipError_t e;
-  if (n_layers >= 2 && maxw >= 32) {
+  if (takes_mfma(n_layers, maxw)) {
     if (maxw <= 32) e = launch_pair<true, 1, 1>(a, grid, lds, st);
     else if (maxw <= 64) e = launch_pair<true, 2, 2>(a, grid, lds, st);
     else if (maxw <= 128) e = launch_pair<true, 4, 4>(a, grid, lds, st);
@@ -555,6 +752,97 @@ int32_t mi_pair_topk(const float* a_q, const float* s_q, const float* w_q, int64
   }
   MI_REQUIRE(e == hipSuccess, "pair_topk: LDS of %zu bytes: %s", lds, hipGetErrorString(e));
   MI_CHECK_LAUNCH("pair_score_topk_k");
+  topk_merge_k<<<dim3(static_cast<unsigned>(U)), dim3(256), sizeof(uint64_t) * pl.splits * k, st>>>(part, pl.splits, k,
+                                                                                                    top_score, top_idx);
+  MI_CHECK_LAUNCH("topk_merge_k");
+  return MI_OK;
+}
+
+size_t mi_pair_topk_group_workspace_bytes(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, int32_t k) {
+  if (!group_sizes_ok(members, n_members, U, I, k)) return 0;
+  return make_group_plan(members, n_members, U, I, k).total;
+}
+
+int32_t mi_pair_topk_group(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, const int64_t* excl_off,
+                           const int32_t* excl_idx, int32_t k, float* top_score, int32_t* top_idx, float* scores,
+                           float* member_scores, void* workspace, size_t workspace_bytes, mi_stream_t stream) {
+  MI_REQUIRE(n_members >= 1, "pair_topk_group: %d members (at least 1)", n_members);
+  if (n_members > MI_PAIR_TOPK_GROUP_MAX_MEMBERS)
+    return unsupported("pair_topk_group: %d members (at most %d in one launch)", n_members, MI_PAIR_TOPK_GROUP_MAX_MEMBERS);
+  MI_REQUIRE(members, "pair_topk_group: members");
+  MI_REQUIRE(top_score && top_idx, "pair_topk_group: top_score / top_idx");
+  MI_REQUIRE(!excl_off == !excl_idx, "pair_topk_group: excl_off and excl_idx go together");
+  // every member is checked before anything is launched
+  for (int32_t i = 0; i < n_members; ++i) {
+    const mi_rank_member_t& m = members[i];
+    LayerTable lt{};
+    int maxw = 0;
+    const int32_t rc = check_model(U, I, k, m.a_q, m.s_q, m.a_c, m.s_c, m.H1, m.E, m.dense, m.layer_off, m.widths, m.n_layers,
+                                   m.activation, true, true, lt, maxw);
+    if (rc != MI_OK) {
+      char why[512];
+      snprintf(why, sizeof(why), "%s", mi_last_error());
+      mi::set_error("pair_topk_group: member %d: %s", i, why);
+      return rc;
+    }
+    if (takes_mfma(m.n_layers, maxw))
+      return unsupported("pair_topk_group: member %d: %d layers after layer 1 with a hidden width of %d: the group kernel takes "
+                         "the VALU pair path only (fewer than two layers after layer 1, or every hidden width after layer 1 "
+                         "below %d)", i, m.n_layers, maxw, kValuW);
+  }
+  const GroupPlan gp = make_group_plan(members, n_members, U, I, k);
+  const Plan& pl = gp.pl;
+  MI_REQUIRE(workspace && workspace_bytes >= gp.total, "pair_topk_group: workspace %zu < %zu bytes", workspace_bytes, gp.total);
+  const size_t lds = sizeof(uint64_t) * kQB * (k + kSurv) + sizeof(int) * kQB;    // (the lists; no member data lives in LDS)
+  if (lds > kMaxGroupLds) return unsupported("pair_topk_group: %zu bytes of LDS for k=%d (at most %zu)", lds, k, kMaxGroupLds);
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_score_topk_group_k),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    MI_REQUIRE(e == hipSuccess, "pair_topk_group: LDS of %zu bytes: %s", lds, hipGetErrorString(e));
+  }
+  hipStream_t st = mi::as_stream(stream);
+  char* ws = static_cast<char*>(workspace);
+  GroupMember* tab = reinterpret_cast<GroupMember*>(ws + gp.off_table);
+  uint32_t* mask = excl_off ? reinterpret_cast<uint32_t*>(ws + pl.off_mask) : nullptr;
+  uint64_t* part = reinterpret_cast<uint64_t*>(ws + pl.off_part);
+  auto blocks = [](int64_t n) { const int64_t b = mi::ceil_div(n, 256); return static_cast<unsigned>(b < 2048 ? b : 2048); };
+  size_t side = gp.off_sides;
+  int maxside = 0;
+  MemberChunk ch{};
+  for (int32_t i = 0; i < n_members; ++i) {
+    const mi_rank_member_t& m = members[i];
+    GroupMember& gm = ch.m[i % kTabChunk];
+    gm = GroupMember{};
+    for (int j = 0; j < m.n_layers; ++j)
+      gm.l[j] = Layer{m.layer_off[2 * j], m.layer_off[2 * j + 1], m.widths[j], m.widths[j + 1]};
+    float* aqT = m.H1 ? reinterpret_cast<float*>(ws + side) : nullptr;
+    float* sqT = m.E ? reinterpret_cast<float*>(ws + side + align256(sizeof(float) * static_cast<size_t>(m.H1) * pl.Upad)) : nullptr;
+    side += side_bytes(pl, m.H1, m.E);
+    PairArgs& a = gm.p;
+    a.aqT = aqT; a.a_c = m.a_c; a.sqT = sqT; a.s_c = m.s_c; a.w_q = m.w_q; a.w_c = m.w_c; a.dense = m.dense;
+    a.l = tab[i].l;                              // (the address of this member's layers in the workspace)
+    a.U = U; a.I = I; a.chunk = pl.chunk;
+    a.Upad = static_cast<int32_t>(pl.Upad); a.H1 = m.H1; a.E = m.E; a.K = k; a.splits = pl.splits; a.words = pl.words;
+    a.act = m.activation; a.n_layers = m.n_layers;
+    gm.a_q = m.a_q; gm.s_q = m.s_q;
+    if (m.H1 > maxside) maxside = m.H1;
+    if (m.E > maxside) maxside = m.E;
+    if (i % kTabChunk == kTabChunk - 1 || i + 1 == n_members) {
+      const int first = i - i % kTabChunk;
+      member_table_k<<<dim3(1), dim3(64), 0, st>>>(ch, i - first + 1, tab + first);
+    }
+  }
+  if (maxside)
+    transpose_pad_group_k<<<dim3(blocks(static_cast<int64_t>(maxside) * pl.Upad), static_cast<unsigned>(n_members), 2), dim3(256), 0,
+                            st>>>(tab, U);
+  if (mask) {
+    zero_u32_k<<<dim3(blocks(U * pl.words)), dim3(256), 0, st>>>(mask, U * pl.words);
+    excl_mask_k<<<dim3(static_cast<unsigned>(U)), dim3(256), 0, st>>>(excl_off, excl_idx, I, pl.words, mask);
+  }
+  MI_CHECK_LAUNCH("pair_topk_group (prepare)");
+  pair_score_topk_group_k<<<dim3(static_cast<unsigned>(pl.qblocks), static_cast<unsigned>(pl.splits)), dim3(kThreads), lds, st>>>(
+      tab, n_members, mask, scores, member_scores, part, U, I, pl.chunk, k, pl.splits, pl.words);
+  MI_CHECK_LAUNCH("pair_score_topk_group_k");
   topk_merge_k<<<dim3(static_cast<unsigned>(U)), dim3(256), sizeof(uint64_t) * pl.splits * k, st>>>(part, pl.splits, k,
                                                                                                     top_score, top_idx);
   MI_CHECK_LAUNCH("topk_merge_k");

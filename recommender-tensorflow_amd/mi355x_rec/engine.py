@@ -1268,6 +1268,21 @@ class DeepFM:
         Returns (top_score [U, k] fp32 logits, top_idx [U, k] int32) — score descending, ties by lower index, index -1
         and score -inf where fewer than k candidates are eligible — plus scores [U, I] (every pair's logit) when
         return_scores."""
+        sides, U, I, k = self._top_k_check(query_ids, candidate_ids, query_fields, k, query_x, candidate_x)
+        excl_off, excl_idx = self._top_k_exclusions(exclude, U, I) if exclude is not None else (None, None)
+        a = self._top_k_sides(sides)
+        top_score = torch.empty(U, k, dtype=torch.float32, device=self.device)
+        top_idx = torch.empty(U, k, dtype=torch.int32, device=self.device)
+        scores = torch.empty(U, I, dtype=torch.float32, device=self.device) if return_scores else None
+        k_ = self.k
+        ws = self._bytes("topk_ws", k_.query("mi_pair_topk_workspace_bytes", U, I, k, a["H1"], a["E"]))
+        k_.mi_pair_topk(a["a_q"], a["s_q"], a["w_q"], U, a["a_c"], a["s_c"], a["w_c"], I, a["H1"], a["E"], self.dense,
+                        a["layer_off"], a["widths"], a["n_layers"], self.act, excl_off, excl_idx, k, top_score, top_idx, scores,
+                        ws, ws.numel())
+        return (top_score, top_idx, scores) if return_scores else (top_score, top_idx)
+
+    def _top_k_check(self, query_ids, candidate_ids, query_fields, k, query_x, candidate_x):
+        """top_k's argument validation: ([(cat, num, ids, x, n) of the query side, of the candidate side], U, I, k)"""
         if self.shard is not None:
             raise NotImplementedError("top_k runs on one GPU: a row-sharded engine has only its shard of the tables")
         nf = self.F + self.n_numeric
@@ -1297,40 +1312,52 @@ class DeepFM:
             elif x is not None:
                 raise ValueError("%s_x given but the %s side has no numeric column" % (name, name))
             sides.append((cat, num, ids, x, n))
-        U, I = sides[0][4], sides[1][4]
-        excl_off = excl_idx = None
-        if exclude is not None:
-            if isinstance(exclude, tuple) and len(exclude) == 2:
-                off = np.asarray(exclude[0].cpu() if isinstance(exclude[0], torch.Tensor) else exclude[0], np.int64)
-                idx = np.asarray(exclude[1].cpu() if isinstance(exclude[1], torch.Tensor) else exclude[1], np.int32)
-            else:
-                rows = [np.asarray(sorted(set(int(c) for c in r)), np.int32) for r in exclude]
-                if len(rows) != U:
-                    raise ValueError("exclude: %d rows for %d queries" % (len(rows), U))
-                off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
-                idx = np.concatenate(rows + [np.zeros(0, np.int32)]).astype(np.int32)
-            if off.shape != (U + 1,) or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != idx.size:
-                raise ValueError("exclude: offsets must be a non-decreasing [U + 1] array from 0 to len(indices)")
-            if idx.size and (idx.min() < 0 or idx.max() >= I):
-                raise ValueError("exclude: candidate index outside [0, %d)" % I)
-            excl_off = torch.from_numpy(off).to(self.device)
-            excl_idx = torch.from_numpy(np.ascontiguousarray(idx) if idx.size else np.zeros(1, np.int32)).to(self.device)
+        return sides, sides[0][4], sides[1][4], k
+
+    def _top_k_exclusions(self, exclude, U, I):
+        """top_k's exclude argument as the kernel's CSR pair on the device: (offsets int64 [U + 1], indices int32); callers
+        skip it when nothing is excluded"""
+        if isinstance(exclude, tuple) and len(exclude) == 2:
+            off = np.asarray(exclude[0].cpu() if isinstance(exclude[0], torch.Tensor) else exclude[0], np.int64)
+            idx = np.asarray(exclude[1].cpu() if isinstance(exclude[1], torch.Tensor) else exclude[1], np.int32)
+        else:
+            rows = [np.asarray(sorted(set(int(c) for c in r)), np.int32) for r in exclude]
+            if len(rows) != U:
+                raise ValueError("exclude: %d rows for %d queries" % (len(rows), U))
+            off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+            idx = np.concatenate(rows + [np.zeros(0, np.int32)]).astype(np.int32)
+        if off.shape != (U + 1,) or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != idx.size:
+            raise ValueError("exclude: offsets must be a non-decreasing [U + 1] array from 0 to len(indices)")
+        if idx.size and (idx.min() < 0 or idx.max() >= I):
+            raise ValueError("exclude: candidate index outside [0, %d)" % I)
+        excl_off = torch.from_numpy(off).to(self.device)
+        excl_idx = torch.from_numpy(np.ascontiguousarray(idx) if idx.size else np.zeros(1, np.int32)).to(self.device)
+        return excl_off, excl_idx
+
+    def _top_k_sides(self, sides):
+        """top_k's per-side precompute (every row current first): the per-model arguments of mi_pair_topk as a dict —
+        a_q, s_q, w_q, a_c, s_c, w_c (device), layer_off, widths (host), H1, E, n_layers"""
         self.finalize_rows()
-        k_ = self.k
-        k_.query("mi_set_gemm_mode", 0)               # (layer 1 per side on the fp32-input MFMA; every forward sets its own mode)
+        self.k.query("mi_set_gemm_mode", 0)           # (layer 1 per side on the fp32-input MFMA; every forward sets its own mode)
         (a_q, s_q, w_q), (a_c, s_c, w_c) = [self._side_tensors(*s[:4], candidate=i == 1) for i, s in enumerate(sides)]
         H1 = self.layers[0][3] if self.use_dnn else 0
         rest = self.layers[1:] if self.use_dnn else []
         layer_off = torch.tensor([o for (ko, bo, _, _) in rest for o in (ko, bo)] or [0], dtype=torch.int64)
         widths = torch.tensor([H1] + [h for (_, _, _, h) in rest], dtype=torch.int32)
-        E = self.E if self.use_mf else 0
-        top_score = torch.empty(U, k, dtype=torch.float32, device=self.device)
-        top_idx = torch.empty(U, k, dtype=torch.int32, device=self.device)
-        scores = torch.empty(U, I, dtype=torch.float32, device=self.device) if return_scores else None
-        ws = self._bytes("topk_ws", k_.query("mi_pair_topk_workspace_bytes", U, I, k, H1, E))
-        k_.mi_pair_topk(a_q, s_q, w_q, U, a_c, s_c, w_c, I, H1, E, self.dense, layer_off, widths, len(rest), self.act,
-                        excl_off, excl_idx, k, top_score, top_idx, scores, ws, ws.numel())
-        return (top_score, top_idx, scores) if return_scores else (top_score, top_idx)
+        return {"a_q": a_q, "s_q": s_q, "w_q": w_q, "a_c": a_c, "s_c": s_c, "w_c": w_c, "layer_off": layer_off,
+                "widths": widths, "H1": H1, "E": self.E if self.use_mf else 0, "n_layers": len(rest)}
+
+    TOP_K_GROUP_MAX_WIDTH = 32     # mi_pair_topk_group: the VALU pair path (include/mi355x_rec.h)
+
+    def _top_k_group_limit(self):
+        """What keeps mi_pair_topk_group from scoring this model as a member, as text, or None: the group kernel takes the
+        pair kernel's VALU path — fewer than two layers after layer 1, or every hidden width after layer 1 below 32."""
+        if self.shard is not None:
+            return "row-sharded tables (top_k runs on one GPU)"
+        after = list(self.hidden[1:]) if self.use_dnn else []
+        if len(after) >= 1 and max(after) >= self.TOP_K_GROUP_MAX_WIDTH:
+            return "a hidden layer of %d units after the first (below %d)" % (max(after), self.TOP_K_GROUP_MAX_WIDTH)
+        return None
 
     def _side_tensors(self, cat, num, ids, x, candidate):
         """One side of top_k: (a [n, H1] or None, s [n, E] or None, w [n] or None) with the model's own kernels — the
@@ -2079,3 +2106,53 @@ class DeepFM:
         self._final_step = self.step
         self._presorted = None           # (a sort of a batch announced before the restore: dropped)
         self.drop_graphs()               # (captured steps are re-captured against the restored state)
+
+
+# ---------------------------------------------------------------------- top-K recommendation with an ensemble
+def top_k_group(engines, query_ids, candidate_ids, query_fields, k, query_x=None, candidate_x=None, exclude=None,
+                return_scores=False, return_member_scores=False):
+    """DeepFM.top_k for the MEAN logit of several engines over one set of feature columns (mi_pair_topk_group,
+    include/mi355x_rec.h): same arguments, same returns — (top_score [U, k], top_idx [U, k]), then scores [U, I] (the mean)
+    when return_scores, then member_scores [M, U, I] when return_member_scores.  The mean is
+    (((z_0 + z_1) + ...) + z_{M-1}) / M in fp32; member m's z_m is bit for bit its own top_k score.  The arguments are
+    checked and the exclusions built once (member 0), the per-side precompute runs once per member with the member's own
+    kernels, then ONE pair scoring and selection launch.  ValueError (naming the member and the limit) for a member
+    outside the group kernel's scope."""
+    engines = list(engines)
+    M = len(engines)
+    if M < 1:
+        raise ValueError("top_k_group: no members")
+    if M > _lib.PAIR_TOPK_GROUP_MAX_MEMBERS:
+        raise ValueError("top_k_group: %d members (at most %d in one launch)" % (M, _lib.PAIR_TOPK_GROUP_MAX_MEMBERS))
+    lead = engines[0]
+    for i, e in enumerate(engines):
+        if e.device != lead.device:
+            raise ValueError("top_k_group: member %d is on %s, member 0 on %s" % (i, e.device, lead.device))
+        if list(e.vocab_sizes) != list(lead.vocab_sizes) or e.n_numeric != lead.n_numeric:
+            raise ValueError("top_k_group: member %d has columns (%s buckets, %d numeric), member 0 (%s, %d)" % (
+                i, list(e.vocab_sizes), e.n_numeric, list(lead.vocab_sizes), lead.n_numeric))
+        why = e._top_k_group_limit()
+        if why is not None:
+            raise ValueError("top_k_group: member %d: the model has %s" % (i, why))
+    sides, U, I, k = lead._top_k_check(query_ids, candidate_ids, query_fields, k, query_x, candidate_x)
+    excl_off, excl_idx = lead._top_k_exclusions(exclude, U, I) if exclude is not None else (None, None)
+    args = [e._top_k_sides(sides) for e in engines]          # (kept alive until the launch is enqueued)
+    members = (_lib.RankMember * M)()
+    for m, e, a in zip(members, engines, args):
+        for name in ("a_q", "s_q", "w_q", "a_c", "s_c", "w_c", "layer_off", "widths"):
+            setattr(m, name, ptr(a[name]))
+        m.dense = ptr(e.dense)
+        m.H1, m.E, m.n_layers, m.activation = a["H1"], a["E"], a["n_layers"], e.act
+    dev, k_ = lead.device, lead.k
+    top_score = torch.empty(U, k, dtype=torch.float32, device=dev)
+    top_idx = torch.empty(U, k, dtype=torch.int32, device=dev)
+    scores = torch.empty(U, I, dtype=torch.float32, device=dev) if return_scores else None
+    member_scores = torch.empty(M, U, I, dtype=torch.float32, device=dev) if return_member_scores else None
+    ws = lead._bytes("topk_group_ws", k_.query("mi_pair_topk_group_workspace_bytes", members, M, U, I, k))
+    k_.mi_pair_topk_group(members, M, U, I, excl_off, excl_idx, k, top_score, top_idx, scores, member_scores, ws, ws.numel())
+    out = (top_score, top_idx)
+    if return_scores:
+        out += (scores,)
+    if return_member_scores:
+        out += (member_scores,)
+    return out

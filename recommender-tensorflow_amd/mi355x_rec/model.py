@@ -67,10 +67,10 @@ def side_inputs(plan, fields, features, device):
     return torch.from_numpy(ids).to(device), (torch.from_numpy(x).to(device) if x is not None else None)
 
 
-def recommend_batch(query_features, candidate_features, k, exclude, params):
-    """Estimator.recommend's body: the engine's top_k on the two sides' raw features, the head's logistic on the result."""
-    store = params["_store"]
-    plan, eng = store["plan"], store["engine"]
+def recommend_sides(plan, eng, query_features, candidate_features, k, exclude):
+    """The engine's top_k on the two sides' raw features and the head's logistic on the result, as numpy: logits [U, k],
+    probabilities [U, k], indices [U, k].  Estimator.recommend (a checkpoint) and Predictor.recommend (an export) both
+    end here."""
     qf = split_sides(plan, query_features, candidate_features)
     cf = [f for f in range(len(plan.categorical) + len(plan.numeric)) if f not in qf]
     q_ids, q_x = side_inputs(plan, qf, query_features, eng.device)
@@ -79,6 +79,12 @@ def recommend_batch(query_features, candidate_features, k, exclude, params):
     pr = binary_predictions(score.reshape(-1).contiguous(), eng.k)
     return {"logits": score.cpu().numpy(), "probabilities": pr["logistic"].reshape(score.shape).cpu().numpy(),
             "indices": idx.cpu().numpy()}
+
+
+def recommend_batch(query_features, candidate_features, k, exclude, params):
+    """Estimator.recommend's body: recommend_sides on the estimator's plan and engine."""
+    store = params["_store"]
+    return recommend_sides(store["plan"], store["engine"], query_features, candidate_features, k, exclude)
 
 
 def run_batch(features, labels, mode, params, make_engine):

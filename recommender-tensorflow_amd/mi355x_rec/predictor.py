@@ -22,7 +22,7 @@ import torch
 from . import _lib
 from . import engine as _engine
 from .feature_column import FieldPlan, column_from_json
-from .model import binary_predictions
+from .model import binary_predictions, recommend_sides, side_inputs, split_sides
 
 # mode="auto": the fused launch for batches up to FUSED_MAX_BATCH requests, as long as the MLP's weights — which every
 # workgroup of 32 requests streams through one CU — stay below FUSED_MAX_WEIGHT_BYTES.  Both from the table in
@@ -205,6 +205,33 @@ class Predictor:
     def __call__(self, features):
         ids, x = self.transform(features)
         return self.predict_ids(ids, x)
+
+    # ------------------------------------------------------------------ top-K recommendation
+    def recommend(self, query_features, candidate_features, k, exclude=None):
+        """What Estimator.recommend does for a checkpoint, for this export: the k best candidates of every query by logit
+        (DeepFM.top_k).  The two dicts map the columns' source keys to each side's raw values (a column belongs to the side
+        whose dict holds its key; keys no column reads are ignored); exclude as DeepFM.top_k takes it.  Returns numpy
+        arrays: logits [U, k], probabilities [U, k] (the head's logistic) and indices [U, k] (-1 / -inf / 0 past the
+        eligible candidates)."""
+        return recommend_sides(self.plan, self.engine, query_features, candidate_features, k, exclude)
+
+
+def host_top_k(scores, k, excl_off=None, excl_idx=None):
+    """The selection rule of mi_pair_topk (include/mi355x_rec.h) on the host: per row of scores [U, I] the k best eligible
+    candidates — score descending, equal scores by ascending index, NaN below every number, a -0 returned as +0 — padded
+    with index -1 / score -inf.  excl_off / excl_idx: the excluded candidates per row as a CSR pair (numpy), or None."""
+    U, I = scores.shape
+    top_s = np.full((U, k), -np.inf, np.float32)
+    top_i = np.full((U, k), -1, np.int32)
+    for u in range(U):
+        ok = np.arange(I)
+        if excl_off is not None:
+            ok = np.setdiff1d(ok, np.asarray(excl_idx[excl_off[u]:excl_off[u + 1]], np.int64))
+        s = scores[u, ok]
+        order = np.lexsort((ok, np.where(np.isnan(s), np.inf, -s)))[:k]
+        top_s[u, :len(order)] = s[order] + np.float32(0.0)
+        top_i[u, :len(order)] = ok[order]
+    return top_s, top_i
 
 
 # ---------------------------------------------------------------------- an ensemble of exports
@@ -443,3 +470,60 @@ class EnsemblePredictor:
     def __call__(self, features, return_members=False):
         ids, x = self.transform(features)
         return self.predict_ids(ids, x, return_members=return_members)
+
+    # ------------------------------------------------------------------ top-K recommendation
+    def rank_fused_limit(self):
+        """(member, text) of the first member outside mi_pair_topk_group's scope, or None when the group launch can rank"""
+        for i, p in enumerate(self.members):
+            why = p.engine._top_k_group_limit()
+            if why is not None:
+                return i, why
+        return None
+
+    def recommend(self, query_features, candidate_features, k, exclude=None, mode=None, return_scores=False):
+        """Predictor.recommend for the ensemble: the k best candidates of every query by the MEAN logit of the members.
+        Both sides' ids are transformed once (member 0's plan) and the exclusions built once; the per-side precompute runs
+        once per member with the member's own kernels.
+
+        mode (None: the ensemble's own):
+          "fused"   one pair scoring and selection launch for all members (engine.top_k_group: mi_pair_topk_group);
+                    ValueError naming the member and the limit when a member is outside that kernel's scope;
+          "layered" every member's top_k(return_scores=True), a torch fp32 sum in member order, a division, and the
+                    header's selection rule on the host (host_top_k) — the fallback, not the hot path;
+          "auto"    fused iff every member is inside the kernel's scope.
+        Returns numpy arrays: logits [U, k] (the mean logit), probabilities [U, k], indices [U, k]; return_scores adds
+        scores [U, I], every pair's mean logit."""
+        mode = self.mode if mode is None else mode
+        if mode not in ("auto", "fused", "layered"):
+            raise ValueError("mode must be 'auto', 'fused' or 'layered'")
+        limit = self.rank_fused_limit()
+        if mode == "fused" and limit is not None:
+            raise ValueError("mode='fused': member %d: the model has %s" % limit)
+        fused = mode == "fused" or (mode == "auto" and limit is None)
+        plan, lead = self.plan, self.members[0].engine
+        qf = split_sides(plan, query_features, candidate_features)
+        cf = [f for f in range(len(plan.categorical) + len(plan.numeric)) if f not in qf]
+        q_ids, q_x = side_inputs(plan, qf, query_features, self.device)
+        c_ids, c_x = side_inputs(plan, cf, candidate_features, self.device)
+        engines = [p.engine for p in self.members]
+        if fused:
+            out = _engine.top_k_group(engines, q_ids, c_ids, qf, k, q_x, c_x, exclude=exclude, return_scores=return_scores)
+            score, idx = out[0], out[1]
+            scores = out[2].cpu().numpy() if return_scores else None
+        else:
+            _, U, I, k = lead._top_k_check(q_ids, c_ids, qf, k, q_x, c_x)
+            off, ix = lead._top_k_exclusions(exclude, U, I) if exclude is not None else (None, None)
+            acc = None
+            for e in engines:
+                z = e.top_k(q_ids, c_ids, qf, k, q_x, c_x, return_scores=True)[2]
+                acc = z.clone() if acc is None else acc + z
+            scores = (acc / torch.full_like(acc, float(len(engines)))).cpu().numpy()
+            top_s, top_i = host_top_k(scores, k, None if off is None else off.cpu().numpy(),
+                                      None if ix is None else ix.cpu().numpy())
+            score, idx = torch.from_numpy(top_s).to(self.device), torch.from_numpy(top_i).to(self.device)
+        pr = binary_predictions(score.reshape(-1).contiguous(), self.k)
+        host = {"logits": score.cpu().numpy(), "probabilities": pr["logistic"].reshape(score.shape).cpu().numpy(),
+                "indices": idx.cpu().numpy()}
+        if return_scores:
+            host["scores"] = scores
+        return host

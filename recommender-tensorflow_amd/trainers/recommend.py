@@ -6,7 +6,12 @@ are the query side, the item columns the candidate side) and writes ``user_id,ra
 Users are the distinct user_ids of --test-csv, items the distinct item_ids of --train-csv and --test-csv; each takes
 its features from its first row.  A user's training items are excluded unless --include-seen.  hit_rate@K, recall@K
 and ndcg@K over the test positives (rating >= 5, get_input_fn's cutoff; users with at least one positive) are printed
-and saved next to the CSV."""
+and saved next to the CSV.
+
+``--top N`` (with ``--model deep_fm``) ranks with an ensemble instead: --job-dir is then the job directory of a
+``trainers.sweep`` run, the sweep's N best members are loaded from their exports (EnsemblePredictor.from_sweep) and every
+item is ranked by the members' mean logit, in one launch where the members allow it (EnsemblePredictor.recommend).  The
+output goes to ``<job-dir>/recommend/top<K>_ensemble<N>.csv`` with the same columns and the same ``_metrics.json``."""
 import csv
 import json
 import math
@@ -34,7 +39,10 @@ def make_parser(model):
     p.add_argument("--model", choices=sorted(MODELS), required=True, help="the trainer whose checkpoint --job-dir holds")
     p.add_argument("--top-k", type=int, default=10, help="items per user (default: %(default)s)")
     p.add_argument("--include-seen", action="store_true", help="also rank the items a user rated in the training file")
-    p.add_argument("--output", default=None, help="CSV to write (default: <job-dir>/recommend/top<K>.csv)")
+    p.add_argument("--output", default=None, help="CSV to write (default: <job-dir>/recommend/top<K>.csv; with --top: "
+                                                   "<job-dir>/recommend/top<K>_ensemble<N>.csv)")
+    p.add_argument("--top", type=int, default=None, metavar="N",
+                   help="rank with the ensemble of the N best members of the trainers.sweep run in --job-dir (--model deep_fm)")
     return p
 
 
@@ -104,23 +112,43 @@ def main(argv=None):
         raise SystemExit("--top-k %d outside [1, 256]" % k)
     if getattr(args, "synthetic", None):
         args.train_csv, args.test_csv = "synthetic:%d:1" % args.synthetic, "synthetic:%d:2" % max(args.synthetic // 10, 1)
-    module = MODELS[args.model][0]
-    config = get_run_config()
-    config.device = args.device
-    est = module.make_estimator(args, get_feature_columns(embedding_size=args.embedding_size), config)
-    if est.latest_checkpoint() is None:
-        raise SystemExit("no checkpoint in %s: train the model first (python -m trainers.%s --job-dir %s ...)" % (
-            args.job_dir, args.model, args.job_dir))
+    ens = None
+    if args.top is not None:
+        from mi355x_rec.predictor import EnsemblePredictor
+        if args.model != "deep_fm":
+            raise SystemExit("--top %d: an ensemble is made of the members of a trainers.sweep run, which are deep_fm models "
+                             "(--model %s)" % (args.top, args.model))
+        if not os.path.exists(os.path.join(args.job_dir, "sweep.json")):
+            raise SystemExit("--top %d: %s has no sweep.json (an ensemble is taken from the job directory of a trainers.sweep run)"
+                             % (args.top, args.job_dir))
+        with open(os.path.join(args.job_dir, "sweep.json")) as f:
+            n_members = len(json.load(f)["members"])
+        if not 1 <= args.top <= n_members:
+            raise SystemExit("--top %d out of range: the sweep in %s has %d members (1 <= top <= %d)" % (
+                args.top, args.job_dir, n_members, n_members))
+        try:
+            ens = EnsemblePredictor.from_sweep(args.job_dir, top=args.top, device=args.device)
+        except ValueError as e:
+            raise SystemExit("--top %d: %s" % (args.top, e))
+    else:
+        module = MODELS[args.model][0]
+        config = get_run_config()
+        config.device = args.device
+        est = module.make_estimator(args, get_feature_columns(embedding_size=args.embedding_size), config)
+        if est.latest_checkpoint() is None:
+            raise SystemExit("no checkpoint in %s: train the model first (python -m trainers.%s --job-dir %s ...)" % (
+                args.job_dir, args.model, args.job_dir))
     train, _ = _read_csv(args.train_csv)
     test, _ = _read_csv(args.test_csv)
     users, qf, items, cf = tables(train, test)
     excl = None if args.include_seen else exclusion_csr(users, items, train)
     try:
-        out = est.recommend(qf, cf, k, exclude=excl)
+        out = ens.recommend(qf, cf, k, exclude=excl) if ens is not None else est.recommend(qf, cf, k, exclude=excl)
     except ValueError as e:
         raise SystemExit("recommend: %s" % e)
     logits, probs, idx = out["logits"], out["probabilities"], out["indices"]
-    path = args.output or os.path.join(args.job_dir, "recommend", "top%d.csv" % k)
+    path = args.output or os.path.join(args.job_dir, "recommend",
+                                       "top%d.csv" % k if ens is None else "top%d_ensemble%d.csv" % (k, args.top))
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     top = {}
     with open(path, "w", newline="") as f:
