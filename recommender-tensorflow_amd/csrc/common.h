@@ -14,6 +14,13 @@ namespace mi {
 constexpr int kWave = 64;
 
 void set_error(const char* fmt, ...);
+// the error text of a legal request that is not built; returns MI_ERR_UNSUPPORTED
+int32_t unsupported(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+// a group entry's refusal of its member i: the last error becomes "<entry>: member <i>: <the last error>"
+void member_error(const char* entry, int i);
+// a plan's member table from the host to the device, complete on return (who: the entry, for "<who>: copying the member
+// table: ..." and MI_ERR_LAUNCH)
+int32_t upload_table(void* device, const void* host, size_t bytes, mi_stream_t stream, const char* who);
 
 inline hipStream_t as_stream(mi_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -42,6 +49,15 @@ const mi_step_state_t* step_state();
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+
+// *from to *to, word by word, by the kThreads threads of a workgroup: a member's arguments out of a group plan's device table
+template <int kThreads, typename T>
+__device__ __forceinline__ void mi_copy_words(T* to, const T* from) {
+  static_assert(sizeof(T) % 4 == 0, "copied word by word");
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(from);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(to);
+  for (int i = threadIdx.x; i < static_cast<int>(sizeof(T) / sizeof(uint32_t)); i += kThreads) dst[i] = src[i];
+}
 
 template <int N> __device__ __forceinline__ void mi_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -168,3 +184,18 @@ __device__ __forceinline__ float mi_div_const(float x, float d, float r) {
       return MI_ERR_LAUNCH;                                                     \
     }                                                                           \
   } while (0)
+
+namespace mi {
+
+// dynamic LDS above 64 KB has to be asked for, per kernel
+template <typename K>
+int32_t raise_lds(K* kernel, size_t lds, const char* who) {
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             static_cast<int>(lds));
+    MI_REQUIRE(e == hipSuccess, "%s: LDS of %zu bytes: %s", who, lds, hipGetErrorString(e));
+  }
+  return MI_OK;
+}
+
+}  // namespace mi

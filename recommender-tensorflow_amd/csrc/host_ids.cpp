@@ -27,6 +27,28 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+int32_t unsupported(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+  return MI_ERR_UNSUPPORTED;
+}
+
+void member_error(const char* entry, int i) {
+  char why[sizeof(g_err)];
+  snprintf(why, sizeof(why), "%s", g_err);
+  set_error("%s: member %d: %s", entry, i, why);
+}
+
+int32_t upload_table(void* device, const void* host, size_t bytes, mi_stream_t stream, const char* who) {
+  hipError_t e = hipMemcpyAsync(device, host, bytes, hipMemcpyHostToDevice, as_stream(stream));
+  if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));           // (the caller frees the host table)
+  if (e == hipSuccess) return MI_OK;
+  set_error("%s: copying the member table: %s", who, hipGetErrorString(e));
+  return MI_ERR_LAUNCH;
+}
+
 namespace farm {
 
 constexpr uint64_t k0 = 0xc3a5c85c97cb3127ULL;

@@ -642,15 +642,7 @@ int32_t check_model(int64_t U, int64_t I, int32_t k, const float* a_q, const flo
 // does mi_pair_topk score this model on the MFMA (launch_pair<true, ...>)?  Otherwise the VALU loop (<false, 1, 1>)
 inline bool takes_mfma(int n_layers, int maxw) { return n_layers >= 2 && maxw >= kValuW; }
 
-int32_t unsupported(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  mi::set_error("%s", buf);
-  return MI_ERR_UNSUPPORTED;
-}
+using mi::unsupported;
 
 // What the group shares (query blocks, splits, exclusion mask, partial lists: make_plan with no per-model tensors) and
 // where the member table and the members' transposes lie in the workspace.
@@ -684,14 +676,11 @@ GroupPlan make_group_plan(const mi_rank_member_t* members, int32_t n, int64_t U,
 }
 
 template <bool MFMA, int NP, int NQ>
-hipError_t launch_pair(const PairArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_score_topk_k<MFMA, NP, NQ>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-  }
+int32_t launch_pair(const PairArgs& a, dim3 grid, size_t lds, hipStream_t st) {
+  const int32_t rl = mi::raise_lds(&pair_score_topk_k<MFMA, NP, NQ>, lds, "pair_topk");
+  if (rl != MI_OK) return rl;
   pair_score_topk_k<MFMA, NP, NQ><<<grid, dim3(kThreads), lds, st>>>(a);
-  return hipSuccess;
+  return MI_OK;
 }
 
 }  // namespace
@@ -741,16 +730,16 @@ int32_t mi_pair_topk(const float* a_q, const float* s_q, const float* w_q, int64
   a.act = activation;
   const size_t lds = sizeof(uint64_t) * kQB * (k + kSurv) + sizeof(int) * kQB;
   const dim3 grid(static_cast<unsigned>(pl.qblocks), static_cast<unsigned>(pl.splits));
-  hipError_t e;
+  int32_t rl;
   if (takes_mfma(n_layers, maxw)) {
-    if (maxw <= 32) e = launch_pair<true, 1, 1>(a, grid, lds, st);
-    else if (maxw <= 64) e = launch_pair<true, 2, 2>(a, grid, lds, st);
-    else if (maxw <= 128) e = launch_pair<true, 4, 4>(a, grid, lds, st);
-    else e = launch_pair<true, 8, 4>(a, grid, lds, st);
+    if (maxw <= 32) rl = launch_pair<true, 1, 1>(a, grid, lds, st);
+    else if (maxw <= 64) rl = launch_pair<true, 2, 2>(a, grid, lds, st);
+    else if (maxw <= 128) rl = launch_pair<true, 4, 4>(a, grid, lds, st);
+    else rl = launch_pair<true, 8, 4>(a, grid, lds, st);
   } else {
-    e = launch_pair<false, 1, 1>(a, grid, lds, st);
+    rl = launch_pair<false, 1, 1>(a, grid, lds, st);
   }
-  MI_REQUIRE(e == hipSuccess, "pair_topk: LDS of %zu bytes: %s", lds, hipGetErrorString(e));
+  if (rl != MI_OK) return rl;
   MI_CHECK_LAUNCH("pair_score_topk_k");
   topk_merge_k<<<dim3(static_cast<unsigned>(U)), dim3(256), sizeof(uint64_t) * pl.splits * k, st>>>(part, pl.splits, k,
                                                                                                     top_score, top_idx);
@@ -780,9 +769,7 @@ int32_t mi_pair_topk_group(const mi_rank_member_t* members, int32_t n_members, i
     const int32_t rc = check_model(U, I, k, m.a_q, m.s_q, m.a_c, m.s_c, m.H1, m.E, m.dense, m.layer_off, m.widths, m.n_layers,
                                    m.activation, true, true, lt, maxw);
     if (rc != MI_OK) {
-      char why[512];
-      snprintf(why, sizeof(why), "%s", mi_last_error());
-      mi::set_error("pair_topk_group: member %d: %s", i, why);
+      mi::member_error("pair_topk_group", i);
       return rc;
     }
     if (takes_mfma(m.n_layers, maxw))
@@ -795,11 +782,8 @@ int32_t mi_pair_topk_group(const mi_rank_member_t* members, int32_t n_members, i
   MI_REQUIRE(workspace && workspace_bytes >= gp.total, "pair_topk_group: workspace %zu < %zu bytes", workspace_bytes, gp.total);
   const size_t lds = sizeof(uint64_t) * kQB * (k + kSurv) + sizeof(int) * kQB;    // (the lists; no member data lives in LDS)
   if (lds > kMaxGroupLds) return unsupported("pair_topk_group: %zu bytes of LDS for k=%d (at most %zu)", lds, k, kMaxGroupLds);
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_score_topk_group_k),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    MI_REQUIRE(e == hipSuccess, "pair_topk_group: LDS of %zu bytes: %s", lds, hipGetErrorString(e));
-  }
+  const int32_t rl = mi::raise_lds(&pair_score_topk_group_k, lds, "pair_topk_group");
+  if (rl != MI_OK) return rl;
   hipStream_t st = mi::as_stream(stream);
   char* ws = static_cast<char*>(workspace);
   GroupMember* tab = reinterpret_cast<GroupMember*>(ws + gp.off_table);

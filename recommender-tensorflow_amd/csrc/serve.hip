@@ -44,6 +44,9 @@
 //
 // Arithmetic: fp32 variables, exact fp32 products (v_mfma_f32_32x32x2_f32), fp32 accumulation.  At request sizes the
 // kernel waits for weights, not for the matrix pipe: no 16-bit operand split.
+#include <memory>
+#include <new>
+
 #include "common.h"
 
 namespace {
@@ -370,8 +373,6 @@ __global__ __launch_bounds__(kThreads) void predict_fused_k(const ServeArgs p) {
   if (tid < kRB && b0 + tid < p.B) write_head(z, b0 + tid, p.logits, p.logistic, p.probabilities, p.class_ids);
 }
 
-static_assert(sizeof(ServeArgs) % sizeof(uint32_t) == 0, "ServeArgs is copied word by word");
-
 __global__ __launch_bounds__(kThreads) void predict_group_k(const ServeArgs* __restrict__ members, int32_t M,
                                                             const int32_t* __restrict__ ids, const float* __restrict__ x_num,
                                                             int64_t B, float* member_logits, int32_t* tickets,
@@ -383,11 +384,7 @@ __global__ __launch_bounds__(kThreads) void predict_group_k(const ServeArgs* __r
   __shared__ float red_lin[kParts][kRB], red_fm[kParts][kRB];
   const int tid = threadIdx.x, y = blockIdx.y;
   const int64_t b0 = static_cast<int64_t>(blockIdx.x) * kRB;
-  {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(members + y);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&sp);
-    for (int i = tid; i < static_cast<int>(sizeof(ServeArgs) / sizeof(uint32_t)); i += kThreads) dst[i] = src[i];
-  }
+  mi_copy_words<kThreads>(&sp, members + y);
   __syncthreads();
   if (tid == 0) { sp.ids = ids; sp.x_num = x_num; sp.B = B; }
   if (tid < kMaxLayers) layers[tid] = sp.l[tid];
@@ -422,88 +419,67 @@ __global__ __launch_bounds__(kThreads) void predict_group_k(const ServeArgs* __r
   if (tid == 0) __hip_atomic_store(&tickets[blockIdx.x], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-int32_t unsupported(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-int32_t unsupported(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  mi::set_error("%s", buf);
-  return MI_ERR_UNSUPPORTED;
-}
+using mi::unsupported;
 
 constexpr uint64_t kGroupMagic = 0x6d69707265646772ull;         // "mipredgr"
 
 // The model-side checks of mi_predict_fused and the ServeArgs they describe (ids, x_num, B and the outputs are left to the
 // caller); lds: the dynamic LDS of a workgroup.  have_ids / have_x / have_out: whether the call brought them.  One function
 // for mi_predict_fused and for every member of mi_predict_group_plan: the same checks, the same messages.
-int32_t plan_serve(const float* table, int64_t table_stride, const float* lin_w, int32_t lin_stride, const int64_t* field_off,
-                   int32_t F, int32_t E, int32_t n_numeric, const float* dense, const int64_t* layer_off, const int32_t* widths,
-                   int32_t n_layers, int32_t activation, int32_t use_linear, int32_t use_fm, int32_t use_dnn,
-                   int32_t numeric_raw, int64_t lin_bias_off, int64_t num_emb_off, int64_t lin_num_off, uint64_t wide_fields,
-                   bool have_ids, bool have_x, bool have_out, ServeArgs& a, size_t& lds) {
+int32_t plan_serve(const mi_serve_member_t& m, const int64_t* field_off, int32_t F, int32_t n_numeric, bool have_ids,
+                   bool have_x, bool have_out, ServeArgs& a, size_t& lds) {
+  const int32_t E = m.E, n_layers = m.n_layers;
   MI_REQUIRE(F >= 0 && n_numeric >= 0 && F + n_numeric >= 1, "predict_fused: F=%d n_numeric=%d (at least one column)", F, n_numeric);
   if (F > kMaxFields) return unsupported("predict_fused: F=%d categorical fields (at most %d)", F, kMaxFields);
-  MI_REQUIRE(use_linear || use_fm || use_dnn, "predict_fused: no part of the model is switched on");
+  MI_REQUIRE(m.use_linear || m.use_fm || m.use_dnn, "predict_fused: no part of the model is switched on");
   MI_REQUIRE(have_out, "predict_fused: no output requested");
-  MI_REQUIRE(activation >= 0 && activation <= 3, "predict_fused: activation %d", activation);
-  MI_REQUIRE(!(numeric_raw && use_fm), "predict_fused: raw numeric columns belong to the models without an FM term");
-  const bool emb = (use_fm || use_dnn) && F > 0;                  // the table is read
-  const bool num_emb = n_numeric > 0 && !numeric_raw;
+  MI_REQUIRE(m.activation >= 0 && m.activation <= 3, "predict_fused: activation %d", m.activation);
+  MI_REQUIRE(!(m.numeric_raw && m.use_fm), "predict_fused: raw numeric columns belong to the models without an FM term");
+  const bool emb = (m.use_fm || m.use_dnn) && F > 0;              // the table is read
+  const bool num_emb = n_numeric > 0 && !m.numeric_raw;
   if ((emb || num_emb) && (E < 4 || E > 256 || (E & 3)))
     return unsupported("predict_fused: embedding size %d unsupported (multiple of 4 in [4,256])", E);
-  MI_REQUIRE(!emb || (table && mi::aligned16(table)), "predict_fused: table (16-byte aligned)");
-  MI_REQUIRE(table_stride == 0 || (table_stride >= E && (table_stride & 3) == 0),
-             "predict_fused: table_stride=%lld (0 = E, else >= E and a multiple of 4)", (long long)table_stride);
+  MI_REQUIRE(!emb || (m.table && mi::aligned16(m.table)), "predict_fused: table (16-byte aligned)");
+  MI_REQUIRE(m.table_stride == 0 || (m.table_stride >= E && (m.table_stride & 3) == 0),
+             "predict_fused: table_stride=%lld (0 = E, else >= E and a multiple of 4)", (long long)m.table_stride);
   MI_REQUIRE(F == 0 || (field_off && have_ids), "predict_fused: field_off / ids");
   MI_REQUIRE(n_numeric == 0 || have_x, "predict_fused: x_num");
-  MI_REQUIRE(!(use_linear && F > 0 && wide_fields) || (lin_w && lin_stride >= 1), "predict_fused: lin_w / lin_stride=%d", lin_stride);
-  MI_REQUIRE(!(use_linear || use_dnn || num_emb) || dense, "predict_fused: dense");
-  MI_REQUIRE(!use_linear || lin_bias_off >= 0, "predict_fused: lin_bias_off");
-  MI_REQUIRE(!(use_linear && n_numeric) || lin_num_off >= 0, "predict_fused: lin_num_off");
-  MI_REQUIRE(!num_emb || (num_emb_off >= 0 && (num_emb_off & 3) == 0 && mi::aligned16(dense)),
-             "predict_fused: num_emb_off=%lld (a multiple of 4 floats into a 16-byte aligned buffer)", (long long)num_emb_off);
-  MI_REQUIRE(!(num_emb && !use_fm && !use_dnn), "predict_fused: numeric embeddings need the FM term or the DNN");
-  MI_REQUIRE(use_dnn ? n_layers >= 1 : n_layers == 0, "predict_fused: %d layers (a DNN has at least its logits layer)", n_layers);
+  MI_REQUIRE(!(m.use_linear && F > 0 && m.wide_fields) || (m.lin_w && m.lin_stride >= 1), "predict_fused: lin_w / lin_stride=%d",
+             m.lin_stride);
+  MI_REQUIRE(!(m.use_linear || m.use_dnn || num_emb) || m.dense, "predict_fused: dense");
+  MI_REQUIRE(!m.use_linear || m.lin_bias_off >= 0, "predict_fused: lin_bias_off");
+  MI_REQUIRE(!(m.use_linear && n_numeric) || m.lin_num_off >= 0, "predict_fused: lin_num_off");
+  MI_REQUIRE(!num_emb || (m.num_emb_off >= 0 && (m.num_emb_off & 3) == 0 && mi::aligned16(m.dense)),
+             "predict_fused: num_emb_off=%lld (a multiple of 4 floats into a 16-byte aligned buffer)", (long long)m.num_emb_off);
+  MI_REQUIRE(!(num_emb && !m.use_fm && !m.use_dnn), "predict_fused: numeric embeddings need the FM term or the DNN");
+  MI_REQUIRE(m.use_dnn ? n_layers >= 1 : n_layers == 0, "predict_fused: %d layers (a DNN has at least its logits layer)", n_layers);
   if (n_layers > kMaxLayers)
     return unsupported("predict_fused: %d hidden layers (at most %d)", n_layers - 1, kMaxLayers - 1);
-  MI_REQUIRE(n_layers == 0 || (layer_off && widths), "predict_fused: layer_off / widths");
+  MI_REQUIRE(n_layers == 0 || (m.layer_off && m.widths), "predict_fused: layer_off / widths");
   int wa = 0, wb = 0;                    // widths of the layer outputs in the first / second LDS buffer
   for (int i = 0; i < n_layers; ++i) {
-    const int fi = widths[i], fo = widths[i + 1];
+    const int fi = m.widths[i], fo = m.widths[i + 1];
     MI_REQUIRE(fi >= 1 && fo >= 1, "predict_fused: width %d -> %d", fi, fo);
     MI_REQUIRE(i + 1 < n_layers || fo == 1, "predict_fused: the last layer has %d outputs (1 expected)", fo);
-    MI_REQUIRE(layer_off[2 * i] >= 0 && layer_off[2 * i + 1] >= 0, "predict_fused: layer offsets");
+    MI_REQUIRE(m.layer_off[2 * i] >= 0 && m.layer_off[2 * i + 1] >= 0, "predict_fused: layer offsets");
     if (fo > kMaxWidth) return unsupported("predict_fused: hidden width %d (at most %d)", fo, kMaxWidth);
     int& w = (i & 1) ? wb : wa;
     if (fo > w) w = fo;
-    a.l[i] = Layer{layer_off[2 * i], layer_off[2 * i + 1], fi, fo};
+    a.l[i] = Layer{m.layer_off[2 * i], m.layer_off[2 * i + 1], fi, fo};
   }
   if (n_layers) {
-    const int64_t d_in = (emb ? static_cast<int64_t>(F) * E : 0) + static_cast<int64_t>(n_numeric) * (numeric_raw ? 1 : E);
-    MI_REQUIRE(widths[0] >= d_in, "predict_fused: widths[0]=%d below the %lld input columns", widths[0], (long long)d_in);
+    const int64_t d_in = (emb ? static_cast<int64_t>(F) * E : 0) + static_cast<int64_t>(n_numeric) * (m.numeric_raw ? 1 : E);
+    MI_REQUIRE(m.widths[0] >= d_in, "predict_fused: widths[0]=%d below the %lld input columns", m.widths[0], (long long)d_in);
   }
   lds = sizeof(float) * kRB * (static_cast<size_t>(F) + wa + wb);
   if (lds + 4096 > kMaxLds) return unsupported("predict_fused: %zu bytes of LDS for F=%d and widths %d / %d", lds, F, wa, wb);
-  a.table = emb ? table : nullptr; a.lin_w = lin_w; a.field_off = field_off; a.dense = dense;
-  a.ts = table_stride ? table_stride : E;
-  a.lin_bias_off = lin_bias_off; a.num_emb_off = num_emb_off; a.lin_num_off = lin_num_off;
-  a.wide_fields = use_linear ? wide_fields : 0;
-  a.F = F; a.E = E; a.nd = n_numeric; a.ls = lin_stride; a.act = activation; a.n_layers = n_layers;
-  a.use_linear = use_linear != 0; a.use_fm = use_fm != 0 && (emb || num_emb); a.raw = numeric_raw != 0;
+  a.table = emb ? m.table : nullptr; a.lin_w = m.lin_w; a.field_off = field_off; a.dense = m.dense;
+  a.ts = m.table_stride ? m.table_stride : E;
+  a.lin_bias_off = m.lin_bias_off; a.num_emb_off = m.num_emb_off; a.lin_num_off = m.lin_num_off;
+  a.wide_fields = m.use_linear ? m.wide_fields : 0;
+  a.F = F; a.E = E; a.nd = n_numeric; a.ls = m.lin_stride; a.act = m.activation; a.n_layers = n_layers;
+  a.use_linear = m.use_linear != 0; a.use_fm = m.use_fm != 0 && (emb || num_emb); a.raw = m.numeric_raw != 0;
   a.buf_a = wa * kRB;
-  return MI_OK;
-}
-
-// dynamic LDS above 64 KB has to be asked for, per kernel
-template <typename K>
-int32_t raise_lds(K* kernel, size_t lds, const char* who) {
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             static_cast<int>(lds));
-    MI_REQUIRE(e == hipSuccess, "%s: LDS of %zu bytes: %s", who, lds, hipGetErrorString(e));
-  }
   return MI_OK;
 }
 
@@ -527,16 +503,19 @@ int32_t mi_predict_fused(const float* table, int64_t table_stride, const float* 
   MI_REQUIRE(B >= 1, "predict_fused: B=%lld (at least one request)", (long long)B);
   ServeArgs a{};
   size_t lds = 0;
-  const int32_t rc = plan_serve(table, table_stride, lin_w, lin_stride, field_off, F, E, n_numeric, dense, layer_off, widths,
-                                n_layers, activation, use_linear, use_fm, use_dnn, numeric_raw, lin_bias_off, num_emb_off,
-                                lin_num_off, wide_fields, ids != nullptr, x_num != nullptr,
+  mi_serve_member_t m{};
+  m.table = table; m.table_stride = table_stride; m.lin_w = lin_w; m.lin_stride = lin_stride; m.E = E; m.dense = dense;
+  m.layer_off = layer_off; m.widths = widths; m.n_layers = n_layers; m.activation = activation;
+  m.use_linear = use_linear; m.use_fm = use_fm; m.use_dnn = use_dnn; m.numeric_raw = numeric_raw;
+  m.lin_bias_off = lin_bias_off; m.num_emb_off = num_emb_off; m.lin_num_off = lin_num_off; m.wide_fields = wide_fields;
+  const int32_t rc = plan_serve(m, field_off, F, n_numeric, ids != nullptr, x_num != nullptr,
                                 logits || logistic || probabilities || class_ids, a, lds);
   if (rc != MI_OK) return rc;
   const int64_t blocks = mi::ceil_div(B, kRB);
   MI_REQUIRE(blocks <= INT32_MAX, "predict_fused: grid too large");
   a.ids = ids; a.x_num = x_num; a.B = B;
   a.logits = logits; a.logistic = logistic; a.probabilities = probabilities; a.class_ids = class_ids;
-  const int32_t rl = raise_lds(&predict_fused_k, lds, "predict_fused");
+  const int32_t rl = mi::raise_lds(&predict_fused_k, lds, "predict_fused");
   if (rl != MI_OK) return rl;
   predict_fused_k<<<dim3(static_cast<unsigned>(blocks)), dim3(kThreads), lds, mi::as_stream(stream)>>>(a);
   MI_CHECK_LAUNCH("predict_fused");
@@ -557,35 +536,20 @@ int32_t mi_predict_group_plan(const mi_serve_member_t* members, int32_t n_member
   MI_REQUIRE(device_table && mi::aligned16(device_table),
              "predict_group_plan: device_table (mi_predict_group_plan_bytes bytes of device memory, 16-byte aligned)");
   const size_t need = mi_predict_group_plan_bytes(n_members);
-  ServeArgs* tab = static_cast<ServeArgs*>(malloc(need));
+  const std::unique_ptr<ServeArgs[]> tab(new (std::nothrow) ServeArgs[n_members]());
   MI_REQUIRE(tab, "predict_group_plan: out of host memory");
   size_t lds = 0;
-  int32_t rc = MI_OK;
   for (int32_t i = 0; i < n_members; ++i) {
-    const mi_serve_member_t& m = members[i];
     size_t lds_i = 0;
-    tab[i] = ServeArgs{};
     // (ids, x_num and the outputs belong to the call: mi_predict_group checks them)
-    rc = plan_serve(m.table, m.table_stride, m.lin_w, m.lin_stride, field_off, F, m.E, n_numeric, m.dense, m.layer_off, m.widths,
-                    m.n_layers, m.activation, m.use_linear, m.use_fm, m.use_dnn, m.numeric_raw, m.lin_bias_off, m.num_emb_off,
-                    m.lin_num_off, m.wide_fields, true, true, true, tab[i], lds_i);
+    const int32_t rc = plan_serve(members[i], field_off, F, n_numeric, true, true, true, tab[i], lds_i);
     if (rc != MI_OK) {
-      char why[512];
-      snprintf(why, sizeof(why), "%s", mi_last_error());
-      mi::set_error("predict_group_plan: member %d: %s", i, why);
-      break;
+      mi::member_error("predict_group_plan", i);
+      return rc;
     }
     if (lds_i > lds) lds = lds_i;
   }
-  if (rc == MI_OK) {
-    hipError_t e = hipMemcpyAsync(device_table, tab, need, hipMemcpyHostToDevice, mi::as_stream(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(mi::as_stream(stream));      // (tab is freed below)
-    if (e != hipSuccess) {
-      mi::set_error("predict_group_plan: copying the member table: %s", hipGetErrorString(e));
-      rc = MI_ERR_LAUNCH;
-    }
-  }
-  free(tab);
+  const int32_t rc = mi::upload_table(device_table, tab.get(), need, stream, "predict_group_plan");
   if (rc != MI_OK) return rc;
   plan->device_table = device_table; plan->n_members = n_members; plan->F = F; plan->n_numeric = n_numeric;
   plan->lds_bytes = static_cast<uint32_t>(lds); plan->magic = kGroupMagic;
@@ -607,7 +571,7 @@ int32_t mi_predict_group(const mi_serve_group_plan_t* plan, int32_t n_members, c
   MI_REQUIRE(logits || logistic || probabilities || class_ids, "predict_group: no output requested");
   const int64_t blocks = mi::ceil_div(B, kRB);
   MI_REQUIRE(blocks <= INT32_MAX, "predict_group: grid too large");
-  const int32_t rl = raise_lds(&predict_group_k, plan->lds_bytes, "predict_group");
+  const int32_t rl = mi::raise_lds(&predict_group_k, plan->lds_bytes, "predict_group");
   if (rl != MI_OK) return rl;
   predict_group_k<<<dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(n_members)), dim3(kThreads), plan->lds_bytes,
                     mi::as_stream(stream)>>>(static_cast<const ServeArgs*>(plan->device_table), n_members, ids, x_num, B,

@@ -36,6 +36,9 @@
 //
 // Arithmetic: fp32 throughout; compiled with -ffp-contract=off (the update rules and the FM term are written one
 // rounding per operation); the MLP's dot products use explicit fmaf.
+#include <memory>
+#include <new>
+
 #include "common.h"
 #include "eval_rules.h"
 #include "optim_rules.h"
@@ -443,7 +446,6 @@ struct Member {
   uint64_t seed_base;
   int64_t lr_len;
 };
-static_assert(sizeof(Args) % sizeof(uint32_t) == 0 && sizeof(Member) % 8 == 0, "Member is copied word by word");
 
 __global__ __launch_bounds__(kThreads) void train_fused_group_k(const Member* __restrict__ members, const int32_t* __restrict__ ids,
                                                                 int64_t ids_stride, const uint8_t* __restrict__ labels,
@@ -455,11 +457,7 @@ __global__ __launch_bounds__(kThreads) void train_fused_group_k(const Member* __
   __shared__ float red[2][kThreads / 64];
   const int y = blockIdx.y;
   const Member* me = members + y;
-  {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(&me->a);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&sp);
-    for (int i = threadIdx.x; i < static_cast<int>(sizeof(Args) / sizeof(uint32_t)); i += kThreads) dst[i] = src[i];
-  }
+  mi_copy_words<kThreads>(&sp, &me->a);
   __syncthreads();
   if (threadIdx.x == 0) {
     const int64_t s = step < me->lr_len ? step : me->lr_len - 1;           // (mi_train_group_step checked it: stay inside)
@@ -511,11 +509,7 @@ __global__ __launch_bounds__(kThreads) void eval_fused_group_k(const Member* __r
   __shared__ EvalShared es;
   const int tid = threadIdx.x;
   const int y = blockIdx.y;
-  {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(&members[y].a);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&es.sp);
-    for (int i = tid; i < static_cast<int>(sizeof(Args) / sizeof(uint32_t)); i += kThreads) dst[i] = src[i];
-  }
+  mi_copy_words<kThreads>(&es.sp, &members[y].a);
   mi_eval_init(es.th, es.lh, es.lc, tid, kThreads);
   __syncthreads();
   if (tid < kMaxLayers) es.layers[tid] = es.sp.l[tid];
@@ -555,16 +549,7 @@ __global__ __launch_bounds__(kThreads) void eval_fused_group_k(const Member* __r
   mi_eval_flush(es.lh, es.lc, hist + static_cast<int64_t>(y) * kEvalHist, counts + static_cast<int64_t>(y) * kEvalCounts, tid, kThreads);
 }
 
-int32_t unsupported(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-int32_t unsupported(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  mi::set_error("%s", buf);
-  return MI_ERR_UNSUPPORTED;
-}
+using mi::unsupported;
 
 int64_t align4(int64_t n) { return (n + 3) & ~int64_t(3); }
 
@@ -582,52 +567,50 @@ size_t workspace_bytes_of(int64_t B, int32_t F, int32_t E, int64_t n_dense) {
 
 // The checks of one model, in mi_train_step_fused's order, and its Args (everything but ids / labels / logits / loss / step /
 // seed / lr_t, which the caller fills in; have_batch / have_outputs: the caller holds those pointers — a plan has none yet),
-// the dynamic LDS of its workgroups and the built-in number of sweep workgroups.  Writes nothing but `a`.
-int32_t plan_model(float* table, float* t_m, float* t_v, int64_t table_stride, float* lin_w, float* l_m, float* l_v,
-                   int32_t lin_stride, int32_t* last_step, const int64_t* field_off, int64_t R, int64_t B, int32_t F, int32_t E,
-                   float* dense, float* d_m, float* d_v, int64_t n_dense, const int64_t* layer_off, const int32_t* widths,
-                   int32_t n_layers, int32_t activation, int32_t use_linear, int32_t use_fm, int32_t use_dnn,
-                   int64_t lin_bias_off, float keep_prob, float scale, int32_t step, const mi_opt_hparams* hp, bool have_batch,
-                   bool have_outputs, int32_t sweep_blocks, void* workspace, size_t workspace_bytes, Args& a, size_t& lds_out,
-                   int& blocks_out) {
-  MI_REQUIRE(hp, "train_step_fused: hp");
-  if (hp->kind != MI_OPT_ADAM) return unsupported("train_step_fused: optimizer kind %d (Adam only)", hp->kind);
-  MI_REQUIRE(use_linear || use_fm || use_dnn, "train_step_fused: no part of the model is switched on");
-  MI_REQUIRE(activation >= 0 && activation <= 3, "train_step_fused: activation %d", activation);
+// the dynamic LDS of its workgroups and the built-in number of sweep workgroups.  Writes nothing but `a`.  (m's lr_table,
+// lr_table_len and seed_base belong to the group plan.)
+int32_t plan_model(const mi_fused_member_t& m, const int64_t* field_off, int64_t B, int32_t F, int32_t step, bool have_batch,
+                   bool have_outputs, int32_t sweep_blocks, Args& a, size_t& lds_out, int& blocks_out) {
+  const int64_t R = m.R, n_dense = m.n_dense;
+  const int32_t n_layers = m.n_layers;
+  const int32_t* widths = m.widths;
+  if (m.hp.kind != MI_OPT_ADAM) return unsupported("train_step_fused: optimizer kind %d (Adam only)", m.hp.kind);
+  MI_REQUIRE(m.use_linear || m.use_fm || m.use_dnn, "train_step_fused: no part of the model is switched on");
+  MI_REQUIRE(m.activation >= 0 && m.activation <= 3, "train_step_fused: activation %d", m.activation);
   MI_REQUIRE(step >= 1, "train_step_fused: step=%d (the global step after this call, 1-based)", step);
-  MI_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, "train_step_fused: keep_prob=%g (in (0, 1])", keep_prob);
+  MI_REQUIRE(m.keep_prob > 0.f && m.keep_prob <= 1.f, "train_step_fused: keep_prob=%g (in (0, 1])", m.keep_prob);
   if (B < 1 || B > kMaxBatch) return unsupported("train_step_fused: B=%lld (1 to %d examples)", (long long)B, kMaxBatch);
   if (F < 1 || F > kMaxFields) return unsupported("train_step_fused: F=%d categorical fields (1 to %d)", F, kMaxFields);
-  const bool emb = use_fm || use_dnn;
-  if (emb && (E < 4 || E > kMaxEmb || (E & 3)))
-    return unsupported("train_step_fused: embedding size %d (a multiple of 4, at most %d)", E, kMaxEmb);
-  if (!emb) E = 4;
+  const bool emb = m.use_fm || m.use_dnn;
+  if (emb && (m.E < 4 || m.E > kMaxEmb || (m.E & 3)))
+    return unsupported("train_step_fused: embedding size %d (a multiple of 4, at most %d)", m.E, kMaxEmb);
+  const int32_t E = emb ? m.E : 4;
   if (B * F * E > kMaxConcat)
     return unsupported("train_step_fused: B F E = %lld (at most %lld)", (long long)(B * F * E), (long long)kMaxConcat);
   if (R < 1 || R > kMaxRows) return unsupported("train_step_fused: R=%lld table rows (1 to %lld)", (long long)R, (long long)kMaxRows);
   if (sweep_blocks < 0 || sweep_blocks > kMaxSweepBlocks)
     return unsupported("train_step_fused: sweep_blocks=%d (0 = the built-in choice, at most %d)", sweep_blocks, kMaxSweepBlocks);
-  MI_REQUIRE(field_off && have_batch && last_step, "train_step_fused: field_off / ids / labels / last_step");
+  MI_REQUIRE(field_off && have_batch && m.last_step, "train_step_fused: field_off / ids / labels / last_step");
   MI_REQUIRE(have_outputs, "train_step_fused: logits / loss");
-  MI_REQUIRE(!emb || (table && t_m && t_v && mi::aligned16(table) && mi::aligned16(t_m) && mi::aligned16(t_v)),
+  MI_REQUIRE(!emb || (m.table && m.t_m && m.t_v && mi::aligned16(m.table) && mi::aligned16(m.t_m) && mi::aligned16(m.t_v)),
              "train_step_fused: table / t_m / t_v (16-byte aligned)");
-  MI_REQUIRE(table_stride == 0 || (table_stride >= E && (table_stride & 3) == 0),
-             "train_step_fused: table_stride=%lld (0 = E, else >= E and a multiple of 4)", (long long)table_stride);
-  MI_REQUIRE(lin_stride >= 1, "train_step_fused: lin_stride=%d", lin_stride);
-  MI_REQUIRE(!use_linear || (lin_w && l_m && l_v), "train_step_fused: lin_w / l_m / l_v");
-  MI_REQUIRE(dense && d_m && d_v && n_dense >= 1, "train_step_fused: dense / d_m / d_v / n_dense");
-  MI_REQUIRE(!use_linear || (lin_bias_off >= 0 && lin_bias_off < n_dense), "train_step_fused: lin_bias_off");
-  MI_REQUIRE(use_dnn ? n_layers >= 1 : n_layers == 0, "train_step_fused: %d layers (a DNN has at least its logits layer)", n_layers);
+  MI_REQUIRE(m.table_stride == 0 || (m.table_stride >= E && (m.table_stride & 3) == 0),
+             "train_step_fused: table_stride=%lld (0 = E, else >= E and a multiple of 4)", (long long)m.table_stride);
+  MI_REQUIRE(m.lin_stride >= 1, "train_step_fused: lin_stride=%d", m.lin_stride);
+  MI_REQUIRE(!m.use_linear || (m.lin_w && m.l_m && m.l_v), "train_step_fused: lin_w / l_m / l_v");
+  MI_REQUIRE(m.dense && m.d_m && m.d_v && n_dense >= 1, "train_step_fused: dense / d_m / d_v / n_dense");
+  MI_REQUIRE(!m.use_linear || (m.lin_bias_off >= 0 && m.lin_bias_off < n_dense), "train_step_fused: lin_bias_off");
+  MI_REQUIRE(m.use_dnn ? n_layers >= 1 : n_layers == 0, "train_step_fused: %d layers (a DNN has at least its logits layer)", n_layers);
   if (n_layers > kMaxLayers)
     return unsupported("train_step_fused: %d hidden layers (at most %d)", n_layers - 1, kMaxHidden);
-  MI_REQUIRE(n_layers == 0 || (layer_off && widths), "train_step_fused: layer_off / widths");
+  MI_REQUIRE(n_layers == 0 || (m.layer_off && widths), "train_step_fused: layer_off / widths");
   a = Args{};
   for (int i = 0; i < n_layers; ++i) {
     const int fi = widths[i], fo = widths[i + 1];
     MI_REQUIRE(fi >= 1 && fo >= 1, "train_step_fused: width %d -> %d", fi, fo);
     MI_REQUIRE(i + 1 < n_layers || fo == 1, "train_step_fused: the last layer has %d outputs (1 expected)", fo);
     if (i + 1 < n_layers && fo > kMaxWidth) return unsupported("train_step_fused: hidden width %d (at most %d)", fo, kMaxWidth);
-    const int64_t wo = layer_off[2 * i], bo = layer_off[2 * i + 1];
+    const int64_t wo = m.layer_off[2 * i], bo = m.layer_off[2 * i + 1];
     MI_REQUIRE(wo >= 0 && bo >= 0 && wo + static_cast<int64_t>(fi) * fo <= n_dense && bo + fo <= n_dense,
                "train_step_fused: layer %d lies outside the %lld dense variables", i, (long long)n_dense);
     a.l[i].w_off = wo; a.l[i].b_off = bo; a.l[i].fan_in = fi; a.l[i].fan_out = fo;
@@ -635,11 +618,11 @@ int32_t plan_model(float* table, float* t_m, float* t_v, int64_t table_stride, f
   MI_REQUIRE(n_layers == 0 || widths[0] == F * E, "train_step_fused: widths[0]=%d, the %d input columns expected",
              n_layers ? widths[0] : 0, F * E);
   const size_t need = workspace_bytes_of(B, F, E, n_dense);
-  if (workspace_bytes < need || !workspace) {
-    mi::set_error("train_step_fused: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  if (m.workspace_bytes < need || !m.workspace) {
+    mi::set_error("train_step_fused: workspace of %zu bytes, %zu needed", m.workspace_bytes, need);
     return MI_ERR_WORKSPACE;
   }
-  MI_REQUIRE(mi::aligned16(workspace), "train_step_fused: workspace (16-byte aligned)");
+  MI_REQUIRE(mi::aligned16(m.workspace), "train_step_fused: workspace (16-byte aligned)");
 
   // LDS plan of the batch workgroup
   const int iB = static_cast<int>(B);
@@ -650,7 +633,7 @@ int32_t plan_model(float* table, float* t_m, float* t_v, int64_t table_stride, f
   a.o_dl = static_cast<int32_t>(o); o += align4(B);
   for (int i = 0; i < n_layers; ++i) { a.l[i].out_off = static_cast<int32_t>(o); o += align4(B * widths[i + 1]); }
   const int64_t dcat = n_layers ? align4(B * F * E) : 0;
-  a.gdense = static_cast<float*>(workspace);
+  a.gdense = static_cast<float*>(m.workspace);
   a.dcat_ws = nullptr;
   a.o_dcat = static_cast<int32_t>(o);
   if (sizeof(float) * static_cast<size_t>(o + dcat) <= kMaxLds) o += dcat;
@@ -660,29 +643,19 @@ int32_t plan_model(float* table, float* t_m, float* t_v, int64_t table_stride, f
   const size_t bitmap = sizeof(uint32_t) * static_cast<size_t>((R + 31) / 32);
   if (bitmap > lds) lds = bitmap;
 
-  a.table = emb ? table : nullptr; a.tm = emb ? t_m : nullptr; a.tv = emb ? t_v : nullptr;
-  a.lin_w = use_linear ? lin_w : nullptr; a.lm = use_linear ? l_m : nullptr; a.lv = use_linear ? l_v : nullptr;
-  a.last_step = last_step; a.field_off = field_off;
-  a.dense = dense; a.dm = d_m; a.dv = d_v;
-  a.ts = table_stride ? table_stride : E; a.R = R; a.lin_bias_off = lin_bias_off;
-  a.B = iB; a.F = F; a.E = E; a.ls = lin_stride; a.act = activation; a.n_layers = n_layers;
-  a.use_linear = use_linear != 0; a.use_fm = use_fm != 0;
-  a.keep = keep_prob; a.scale = scale; a.hp = make_hp(hp);
+  a.table = emb ? m.table : nullptr; a.tm = emb ? m.t_m : nullptr; a.tv = emb ? m.t_v : nullptr;
+  a.lin_w = m.use_linear ? m.lin_w : nullptr; a.lm = m.use_linear ? m.l_m : nullptr; a.lv = m.use_linear ? m.l_v : nullptr;
+  a.last_step = m.last_step; a.field_off = field_off;
+  a.dense = m.dense; a.dm = m.d_m; a.dv = m.d_v;
+  a.ts = m.table_stride ? m.table_stride : E; a.R = R; a.lin_bias_off = m.lin_bias_off;
+  a.B = iB; a.F = F; a.E = E; a.ls = m.lin_stride; a.act = m.activation; a.n_layers = n_layers;
+  a.use_linear = m.use_linear != 0; a.use_fm = m.use_fm != 0;
+  a.keep = m.keep_prob; a.scale = m.scale; a.hp = make_hp(&m.hp);
 
   const int64_t items = R * (emb ? E / 4 : 1);
   const int64_t want = mi::ceil_div(items, static_cast<int64_t>(kThreads) * kRowsInFlight);
   blocks_out = sweep_blocks ? sweep_blocks : static_cast<int>(want < 1 ? 1 : (want > 128 ? 128 : want));
   lds_out = lds;
-  return MI_OK;
-}
-
-template <typename K>
-int32_t raise_lds(K kernel, size_t lds, const char* what) {
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             static_cast<int>(lds));
-    MI_REQUIRE(e == hipSuccess, "%s: LDS of %zu bytes: %s", what, lds, hipGetErrorString(e));
-  }
   return MI_OK;
 }
 
@@ -706,16 +679,23 @@ int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_
                             float keep_prob, uint64_t seed, float scale, int32_t step, const mi_opt_hparams* hp,
                             float* logits, float* loss, int32_t sweep_blocks, void* workspace, size_t workspace_bytes,
                             mi_stream_t stream) {
+  MI_REQUIRE(hp, "train_step_fused: hp");
+  mi_fused_member_t m{};                 // (lr_table, lr_table_len and seed_base stay unused: the call brings lr_t and the seed)
+  m.table = table; m.t_m = t_m; m.t_v = t_v; m.table_stride = table_stride;
+  m.lin_w = lin_w; m.l_m = l_m; m.l_v = l_v; m.lin_stride = lin_stride;
+  m.last_step = last_step; m.R = R; m.E = E;
+  m.dense = dense; m.d_m = d_m; m.d_v = d_v; m.n_dense = n_dense;
+  m.layer_off = layer_off; m.widths = widths; m.n_layers = n_layers; m.activation = activation;
+  m.use_linear = use_linear; m.use_fm = use_fm; m.use_dnn = use_dnn; m.lin_bias_off = lin_bias_off;
+  m.keep_prob = keep_prob; m.scale = scale; m.hp = *hp;
+  m.workspace = workspace; m.workspace_bytes = workspace_bytes;
   Args a;
   size_t lds = 0;
   int blocks = 0;
-  const int32_t rc = plan_model(table, t_m, t_v, table_stride, lin_w, l_m, l_v, lin_stride, last_step, field_off, R, B, F, E,
-                                dense, d_m, d_v, n_dense, layer_off, widths, n_layers, activation, use_linear, use_fm, use_dnn,
-                                lin_bias_off, keep_prob, scale, step, hp, ids && labels, logits && loss, sweep_blocks, workspace,
-                                workspace_bytes, a, lds, blocks);
+  const int32_t rc = plan_model(m, field_off, B, F, step, ids && labels, logits && loss, sweep_blocks, a, lds, blocks);
   if (rc != MI_OK) return rc;
   a.ids = ids; a.labels = labels; a.logits = logits; a.loss = loss; a.seed = seed; a.step = step;
-  const int32_t rl = raise_lds(&train_fused_k, lds, "train_step_fused");
+  const int32_t rl = mi::raise_lds(&train_fused_k, lds, "train_step_fused");
   if (rl != MI_OK) return rl;
   train_fused_k<<<dim3(1 + blocks), dim3(kThreads), lds, mi::as_stream(stream)>>>(a);
   MI_CHECK_LAUNCH("train_step_fused");
@@ -739,32 +719,25 @@ int32_t mi_train_group_plan(const mi_fused_member_t* members, int32_t n_members,
     return MI_ERR_WORKSPACE;
   }
   MI_REQUIRE(mi::aligned16(device_table), "train_group_plan: device_table (16-byte aligned)");
-  Member* tab = static_cast<Member*>(malloc(need));
-  MI_REQUIRE(tab, "train_group_plan: out of host memory");
   struct Owned { const void* p; int32_t member; };
-  Owned* owned = static_cast<Owned*>(malloc(sizeof(Owned) * 11 * static_cast<size_t>(n_members)));
-  if (!owned) { free(tab); mi::set_error("train_group_plan: out of host memory"); return MI_ERR_INVALID; }
+  const std::unique_ptr<Member[]> tab(new (std::nothrow) Member[n_members]);
+  const std::unique_ptr<Owned[]> owned(new (std::nothrow) Owned[11 * static_cast<size_t>(n_members)]);
+  MI_REQUIRE(tab && owned, "train_group_plan: out of host memory");
   size_t n_owned = 0, lds = 0;
   int blocks = 1;
   int64_t max_step = INT32_MAX;
-  int32_t rc = MI_OK;
-  for (int32_t i = 0; i < n_members && rc == MI_OK; ++i) {
+  for (int32_t i = 0; i < n_members; ++i) {
     const mi_fused_member_t& m = members[i];
     size_t lds_i = 0;
     int blocks_i = 0;
-    rc = plan_model(m.table, m.t_m, m.t_v, m.table_stride, m.lin_w, m.l_m, m.l_v, m.lin_stride, m.last_step, field_off, m.R, B, F,
-                    m.E, m.dense, m.d_m, m.d_v, m.n_dense, m.layer_off, m.widths, m.n_layers, m.activation, m.use_linear,
-                    m.use_fm, m.use_dnn, m.lin_bias_off, m.keep_prob, m.scale, 1, &m.hp, true, true, 0, m.workspace,
-                    m.workspace_bytes, tab[i].a, lds_i, blocks_i);
+    int32_t rc = plan_model(m, field_off, B, F, 1, true, true, 0, tab[i].a, lds_i, blocks_i);
     if (rc == MI_OK && (!m.lr_table || m.lr_table_len < 2)) {
       mi::set_error("train_step_fused: lr_table of %lld entries (lr_t of step s at [s], s >= 1)", (long long)m.lr_table_len);
       rc = MI_ERR_INVALID;
     }
     if (rc != MI_OK) {
-      char why[512];
-      snprintf(why, sizeof(why), "%s", mi_last_error());
-      mi::set_error("train_group_plan: member %d: %s", i, why);
-      break;
+      mi::member_error("train_group_plan", i);
+      return rc;
     }
     tab[i].lr_table = m.lr_table; tab[i].seed_base = m.seed_base; tab[i].lr_len = m.lr_table_len;
     if (lds_i > lds) lds = lds_i;
@@ -775,31 +748,17 @@ int32_t mi_train_group_plan(const mi_fused_member_t* members, int32_t n_members,
     for (const void* p : own)
       if (p) owned[n_owned++] = Owned{p, i};
   }
-  if (rc == MI_OK) {
-    // two members (or two roles of one member) on the same memory: every pointer above is written by its member's workgroups
-    qsort(owned, n_owned, sizeof(Owned), [](const void* x, const void* y) {
-      const Owned* a = static_cast<const Owned*>(x);
-      const Owned* b = static_cast<const Owned*>(y);
-      return a->p < b->p ? -1 : (a->p > b->p ? 1 : (a->member < b->member ? -1 : (a->member > b->member ? 1 : 0)));
-    });
-    for (size_t j = 1; j < n_owned; ++j)
-      if (owned[j].p == owned[j - 1].p) {
-        mi::set_error("train_group_plan: member %d and member %d share a state or workspace pointer (%p): members are independent",
-                      owned[j - 1].member, owned[j].member, owned[j].p);
-        rc = MI_ERR_INVALID;
-        break;
-      }
-  }
-  if (rc == MI_OK) {
-    hipError_t e = hipMemcpyAsync(device_table, tab, need, hipMemcpyHostToDevice, mi::as_stream(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(mi::as_stream(stream));      // (tab is freed below)
-    if (e != hipSuccess) {
-      mi::set_error("train_group_plan: copying the member table: %s", hipGetErrorString(e));
-      rc = MI_ERR_LAUNCH;
-    }
-  }
-  free(owned);
-  free(tab);
+  // two members (or two roles of one member) on the same memory: every pointer above is written by its member's workgroups
+  qsort(owned.get(), n_owned, sizeof(Owned), [](const void* x, const void* y) {
+    const Owned* a = static_cast<const Owned*>(x);
+    const Owned* b = static_cast<const Owned*>(y);
+    return a->p < b->p ? -1 : (a->p > b->p ? 1 : (a->member < b->member ? -1 : (a->member > b->member ? 1 : 0)));
+  });
+  for (size_t j = 1; j < n_owned; ++j)
+    MI_REQUIRE(owned[j].p != owned[j - 1].p,
+               "train_group_plan: member %d and member %d share a state or workspace pointer (%p): members are independent",
+               owned[j - 1].member, owned[j].member, owned[j].p);
+  const int32_t rc = mi::upload_table(device_table, tab.get(), need, stream, "train_group_plan");
   if (rc != MI_OK) return rc;
   while (blocks > 1 && static_cast<int64_t>(1 + blocks) * n_members > kGroupGridBlocks) --blocks;
   plan->device_table = device_table; plan->n_members = n_members; plan->B = static_cast<int32_t>(B); plan->F = F;
@@ -827,7 +786,7 @@ int32_t mi_train_group_step(const mi_fused_group_plan_t* plan, int32_t n_members
     return unsupported("train_group_step: sweep_blocks=%d (0 = the built-in choice, at most %d)", sweep_blocks, kMaxSweepBlocks);
   const int blocks = sweep_blocks ? sweep_blocks : plan->sweep_blocks;
   MI_REQUIRE(blocks >= 1 && blocks <= kMaxSweepBlocks && plan->lds_bytes <= kMaxLds, "train_group_step: plan (damaged)");
-  const int32_t rl = raise_lds(&train_fused_group_k, plan->lds_bytes, "train_group_step");
+  const int32_t rl = mi::raise_lds(&train_fused_group_k, plan->lds_bytes, "train_group_step");
   if (rl != MI_OK) return rl;
   train_fused_group_k<<<dim3(1 + blocks, n_members), dim3(kThreads), plan->lds_bytes, mi::as_stream(stream)>>>(
       static_cast<const Member*>(plan->device_table), ids, ids_member_stride, labels, labels_member_stride, logits, loss, step);
@@ -861,7 +820,7 @@ int32_t mi_eval_group(const mi_fused_group_plan_t* plan, int32_t n_members, cons
   MI_REQUIRE(X * n_members <= kGroupGridBlocks, "eval_group: blocks=%d for %d members (at most %d workgroups in all)", blocks,
              n_members, kGroupGridBlocks);
   const size_t lds = plan->lds_bytes < kMaxForwardLds ? plan->lds_bytes : kMaxForwardLds;
-  const int32_t rl = raise_lds(&eval_fused_group_k, lds, "eval_group");
+  const int32_t rl = mi::raise_lds(&eval_fused_group_k, lds, "eval_group");
   if (rl != MI_OK) return rl;
   eval_fused_group_k<<<dim3(static_cast<unsigned>(X), n_members), dim3(kThreads), lds, mi::as_stream(stream)>>>(
       static_cast<const Member*>(plan->device_table), ids, labels, N, T, tail_scale, logits, batch_loss,

@@ -253,6 +253,12 @@ def ptr(t):
     return t.ctypes.data
 
 
+def set_ptrs(struct, **tensors):
+    """struct.name = ptr(tensor) for every name=tensor given"""
+    for name, t in tensors.items():
+        setattr(struct, name, ptr(t))
+
+
 def cur_stream():
     return torch.cuda.current_stream().cuda_stream
 

@@ -42,6 +42,37 @@ def _align(n, a=16):
     return (n + a - 1) // a * a
 
 
+def predict_buffers(B, device):
+    """The head's PREDICT dict for B requests, unwritten: logits [B, 1], logistic [B, 1], probabilities [B, 2] float32 and
+    class_ids = classes [B, 1] int64 (one tensor)."""
+    cls = torch.empty(B, 1, dtype=torch.int64, device=device)
+    return {"logits": torch.empty(B, 1, dtype=torch.float32, device=device),
+            "logistic": torch.empty(B, 1, dtype=torch.float32, device=device),
+            "probabilities": torch.empty(B, 2, dtype=torch.float32, device=device), "class_ids": cls, "classes": cls}
+
+
+def check_members(who, engines, most, limit):
+    """The members of a group launch (`who`, for the texts): 1 to `most` engines on member 0's device over member 0's
+    feature columns, none with a limit(engine) — what keeps it out of the group's kernel, as text, or None.  ValueError
+    otherwise; returns the engines as a list."""
+    engines = list(engines)
+    if len(engines) < 1:
+        raise ValueError("%s: no members" % who)
+    if len(engines) > most:
+        raise ValueError("%s: %d members (at most %d in one launch)" % (who, len(engines), most))
+    lead = engines[0]
+    for i, e in enumerate(engines):
+        if e.device != lead.device:
+            raise ValueError("%s: member %d is on %s, member 0 on %s" % (who, i, e.device, lead.device))
+        if list(e.vocab_sizes) != list(lead.vocab_sizes) or e.n_numeric != lead.n_numeric:
+            raise ValueError("%s: member %d has columns (%s buckets, %d numeric), member 0 (%s, %d)" % (
+                who, i, list(e.vocab_sizes), e.n_numeric, list(lead.vocab_sizes), lead.n_numeric))
+        why = limit(e)
+        if why is not None:
+            raise ValueError("%s: member %d: the model has %s" % (who, i, why))
+    return engines
+
+
 class HipKernels:
     """The device entry points of libmi355x_rec.so, called with torch tensors.
 
@@ -449,6 +480,13 @@ class DeepFM:
                 self.layers.append((k_off, b_off, fan, h))
                 fan = h
         self.dnn_end = o                         # end of the MLP parameter block
+        # layer_tables(): (layer_off, widths) of all layers, and of the layers behind layer 1
+        self._layer_tabs = tuple(
+            (torch.tensor([o for (ko, bo, _, _) in layers for o in (ko, bo)] or [0], dtype=torch.int64),
+             torch.tensor([first] + [h for (_, _, _, h) in layers], dtype=torch.int32))
+            for layers, first in ((self.layers, self.layers[0][2] if self.layers else 0),
+                                  (self.layers[1:], self.layers[0][3] if self.layers else 0)))
+        self._fused_step_tabs = {}               # B -> fused_train_step's workspace, loss and logits
         self.num_emb_off = self.lin_num_off = None
         if self.n_numeric and not self.raw_numeric:
             self.num_emb_off = o; o = _align(o + self.n_numeric * self.E)
@@ -1103,19 +1141,22 @@ class DeepFM:
         """Can predict_fused score this model?  (One GPU, within the kernel's limits.)"""
         return self.shard is None and self._fused_limit() is None
 
+    def layer_tables(self, after_first=False):
+        """(layer_off int64 [2 L], widths int32 [L + 1]): the layers' (kernel, bias) offsets into dense and their widths from
+        layer 1's input on, as host tensors made once — what the fused entries take ([0] and [0] without a DNN).
+        after_first: the layers behind layer 1 and the widths from layer 1's output on (mi_pair_topk)."""
+        return self._layer_tabs[1 if after_first else 0]
+
     def _fused_tables(self):
-        """(layer_off int64 [2 L], widths int32 [L + 1], wide_fields mask): the host tables of mi_predict_fused, made once"""
+        """(layer_off, widths, wide_fields mask): the host tables of mi_predict_fused, made once"""
         tabs = getattr(self, "_fused_tabs", None)
         if tabs is None:
-            layer_off = torch.tensor([o for (ko, bo, _, _) in self.layers for o in (ko, bo)] or [0], dtype=torch.int64)
-            widths = torch.tensor(([self.layers[0][2]] + [h for (_, _, _, h) in self.layers]) if self.layers else [0],
-                                  dtype=torch.int32)
             wide = 0
             if self.use_linear:
                 for f in range(self.F):
                     if self.wide_fields is None or self.wide_fields[f]:
                         wide |= 1 << f
-            tabs = self._fused_tabs = (layer_off, widths, wide)
+            tabs = self._fused_tabs = self._layer_tabs[0] + (wide,)      # (the one tuple a call unpacks: nothing is built per call)
         return tabs
 
     def predict_fused(self, ids, x_num=None, out=None):
@@ -1135,11 +1176,7 @@ class DeepFM:
         self.finalize_rows()
         layer_off, widths, wide = self._fused_tables()
         if out is None:
-            dev = self.device
-            cls = torch.empty(B, 1, dtype=torch.int64, device=dev)
-            out = {"logits": torch.empty(B, 1, dtype=torch.float32, device=dev),
-                   "logistic": torch.empty(B, 1, dtype=torch.float32, device=dev),
-                   "probabilities": torch.empty(B, 2, dtype=torch.float32, device=dev), "class_ids": cls, "classes": cls}
+            out = predict_buffers(B, self.device)
         self.k.mi_predict_fused(self.table, self.ts, self.lin_w, self.ls, self.field_off, ids, x_num, B, self.F, self.E,
                                 self.n_numeric, self.dense, layer_off, widths, len(self.layers), self.act,
                                 int(self.use_linear), int(self.use_mf), int(self.use_dnn), int(self.raw_numeric),
@@ -1221,13 +1258,8 @@ class DeepFM:
         self._prep(ids, labels, None)
         self.finalize_rows()                      # (a no-op after a fused step)
         k = self.k
-        tabs = getattr(self, "_fused_step_tabs", None)
-        if tabs is None:
-            layer_off = torch.tensor([o for (ko, bo, _, _) in self.layers for o in (ko, bo)] or [0], dtype=torch.int64)
-            widths = torch.tensor(([self.layers[0][2]] + [h for (_, _, _, h) in self.layers]) if self.layers else [0],
-                                  dtype=torch.int32)
-            tabs = self._fused_step_tabs = (layer_off, widths, {})
-        layer_off, widths, per_b = tabs
+        layer_off, widths = self._layer_tabs[0]
+        per_b = self._fused_step_tabs
         bufs = per_b.get(B)
         if bufs is None:
             E = self.E if self.use_emb else 4
@@ -1340,12 +1372,9 @@ class DeepFM:
         self.finalize_rows()
         self.k.query("mi_set_gemm_mode", 0)           # (layer 1 per side on the fp32-input MFMA; every forward sets its own mode)
         (a_q, s_q, w_q), (a_c, s_c, w_c) = [self._side_tensors(*s[:4], candidate=i == 1) for i, s in enumerate(sides)]
-        H1 = self.layers[0][3] if self.use_dnn else 0
-        rest = self.layers[1:] if self.use_dnn else []
-        layer_off = torch.tensor([o for (ko, bo, _, _) in rest for o in (ko, bo)] or [0], dtype=torch.int64)
-        widths = torch.tensor([H1] + [h for (_, _, _, h) in rest], dtype=torch.int32)
+        layer_off, widths = self.layer_tables(after_first=True)
         return {"a_q": a_q, "s_q": s_q, "w_q": w_q, "a_c": a_c, "s_c": s_c, "w_c": w_c, "layer_off": layer_off,
-                "widths": widths, "H1": H1, "E": self.E if self.use_mf else 0, "n_layers": len(rest)}
+                "widths": widths, "H1": int(widths[0]), "E": self.E if self.use_mf else 0, "n_layers": widths.numel() - 1}
 
     TOP_K_GROUP_MAX_WIDTH = 32     # mi_pair_topk_group: the VALU pair path (include/mi355x_rec.h)
 
@@ -2118,30 +2147,15 @@ def top_k_group(engines, query_ids, candidate_ids, query_fields, k, query_x=None
     checked and the exclusions built once (member 0), the per-side precompute runs once per member with the member's own
     kernels, then ONE pair scoring and selection launch.  ValueError (naming the member and the limit) for a member
     outside the group kernel's scope."""
-    engines = list(engines)
-    M = len(engines)
-    if M < 1:
-        raise ValueError("top_k_group: no members")
-    if M > _lib.PAIR_TOPK_GROUP_MAX_MEMBERS:
-        raise ValueError("top_k_group: %d members (at most %d in one launch)" % (M, _lib.PAIR_TOPK_GROUP_MAX_MEMBERS))
-    lead = engines[0]
-    for i, e in enumerate(engines):
-        if e.device != lead.device:
-            raise ValueError("top_k_group: member %d is on %s, member 0 on %s" % (i, e.device, lead.device))
-        if list(e.vocab_sizes) != list(lead.vocab_sizes) or e.n_numeric != lead.n_numeric:
-            raise ValueError("top_k_group: member %d has columns (%s buckets, %d numeric), member 0 (%s, %d)" % (
-                i, list(e.vocab_sizes), e.n_numeric, list(lead.vocab_sizes), lead.n_numeric))
-        why = e._top_k_group_limit()
-        if why is not None:
-            raise ValueError("top_k_group: member %d: the model has %s" % (i, why))
+    engines = check_members("top_k_group", engines, _lib.PAIR_TOPK_GROUP_MAX_MEMBERS, DeepFM._top_k_group_limit)
+    M, lead = len(engines), engines[0]
     sides, U, I, k = lead._top_k_check(query_ids, candidate_ids, query_fields, k, query_x, candidate_x)
     excl_off, excl_idx = lead._top_k_exclusions(exclude, U, I) if exclude is not None else (None, None)
     args = [e._top_k_sides(sides) for e in engines]          # (kept alive until the launch is enqueued)
     members = (_lib.RankMember * M)()
     for m, e, a in zip(members, engines, args):
-        for name in ("a_q", "s_q", "w_q", "a_c", "s_c", "w_c", "layer_off", "widths"):
-            setattr(m, name, ptr(a[name]))
-        m.dense = ptr(e.dense)
+        _lib.set_ptrs(m, a_q=a["a_q"], s_q=a["s_q"], w_q=a["w_q"], a_c=a["a_c"], s_c=a["s_c"], w_c=a["w_c"], dense=e.dense,
+                      layer_off=a["layer_off"], widths=a["widths"])
         m.H1, m.E, m.n_layers, m.activation = a["H1"], a["E"], a["n_layers"], e.act
     dev, k_ = lead.device, lead.k
     top_score = torch.empty(U, k, dtype=torch.float32, device=dev)

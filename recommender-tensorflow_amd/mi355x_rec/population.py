@@ -66,17 +66,15 @@ class FusedPopulation:
 
     def _describe(self, e, B, keep_alive):
         """engine e as a mi_fused_member_t for batches of B (keep_alive: the tensors the struct points to and e does not hold)"""
-        layer_off = torch.tensor([o for (ko, bo, _, _) in e.layers for o in (ko, bo)] or [0], dtype=torch.int64)
-        widths = torch.tensor(([e.layers[0][2]] + [h for (_, _, _, h) in e.layers]) if e.layers else [0], dtype=torch.int32)
+        layer_off, widths = e.layer_tables()
         E = e.E if e.use_emb else 4
         nbytes = int(self.k.query("mi_train_step_fused_workspace_bytes", B, e.F, E, e.P))
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=e.device)
         keep_alive += [layer_off, widths, ws, e.sched.table]
         m = _lib.FusedMember()
-        for name, t in (("table", e.table), ("t_m", e.t_s0), ("t_v", e.t_s1), ("lin_w", e.lin_w), ("l_m", e.l_s0), ("l_v", e.l_s1),
-                        ("last_step", e.last_step), ("dense", e.dense), ("d_m", e.d_s0), ("d_v", e.d_s1),
-                        ("layer_off", layer_off), ("widths", widths), ("lr_table", e.sched.table), ("workspace", ws)):
-            setattr(m, name, _lib.ptr(t))
+        _lib.set_ptrs(m, table=e.table, t_m=e.t_s0, t_v=e.t_s1, lin_w=e.lin_w, l_m=e.l_s0, l_v=e.l_s1, last_step=e.last_step,
+                      dense=e.dense, d_m=e.d_s0, d_v=e.d_s1, layer_off=layer_off, widths=widths, lr_table=e.sched.table,
+                      workspace=ws)
         m.table_stride, m.lin_stride, m.R, m.E, m.n_dense = e.ts, e.ls, e.R, e.E, e.P
         m.n_layers, m.activation = len(e.layers), e.act
         m.use_linear, m.use_fm, m.use_dnn = int(e.use_linear), int(e.use_mf), int(e.use_dnn)

@@ -171,13 +171,10 @@ class Predictor:
             if len(self._bufs) >= 64:                 # (a server sees a handful of batch sizes; a sweep does not pile them up)
                 self._bufs.clear()
             eng, dev = self.engine, self.engine.device
-            cls = torch.empty(B, 1, dtype=torch.int64, device=dev)
             b = self._bufs[B] = {
                 "ids": torch.empty(B, eng.F, dtype=torch.int32, device=dev),
                 "x": torch.empty(B, eng.n_numeric, dtype=torch.float32, device=dev) if eng.n_numeric else None,
-                "out": {"logits": torch.empty(B, 1, dtype=torch.float32, device=dev),
-                        "logistic": torch.empty(B, 1, dtype=torch.float32, device=dev),
-                        "probabilities": torch.empty(B, 2, dtype=torch.float32, device=dev), "class_ids": cls, "classes": cls}}
+                "out": _engine.predict_buffers(B, dev)}
         return b
 
     def predict_ids(self, ids, x=None):
@@ -240,8 +237,7 @@ def _serve_member(eng, keep_alive):
     layer_off, widths, wide = eng._fused_tables()
     keep_alive += [layer_off, widths]
     m = _lib.ServeMember()
-    for name, t in (("table", eng.table), ("lin_w", eng.lin_w), ("dense", eng.dense), ("layer_off", layer_off), ("widths", widths)):
-        setattr(m, name, _lib.ptr(t))
+    _lib.set_ptrs(m, table=eng.table, lin_w=eng.lin_w, dense=eng.dense, layer_off=layer_off, widths=widths)
     m.table_stride, m.lin_stride, m.E, m.n_layers, m.activation = eng.ts, eng.ls, eng.E, len(eng.layers), eng.act
     m.use_linear, m.use_fm, m.use_dnn, m.numeric_raw = int(eng.use_linear), int(eng.use_mf), int(eng.use_dnn), int(eng.raw_numeric)
     m.lin_bias_off = eng.lin_bias_off
@@ -259,22 +255,9 @@ class FusedGroup:
     MAX_MEMBERS = _lib.PREDICT_GROUP_MAX_MEMBERS
 
     def __init__(self, engines):
-        self.engines = list(engines)
-        self.M = len(self.engines)
-        if self.M < 1:
-            raise ValueError("FusedGroup: no members")
-        if self.M > self.MAX_MEMBERS:
-            raise ValueError("FusedGroup: %d members (at most %d in one launch)" % (self.M, self.MAX_MEMBERS))
-        lead = self.engines[0]
-        for i, e in enumerate(self.engines):
-            if e.device != lead.device:
-                raise ValueError("FusedGroup: member %d is on %s, member 0 on %s" % (i, e.device, lead.device))
-            if list(e.vocab_sizes) != list(lead.vocab_sizes) or e.n_numeric != lead.n_numeric:
-                raise ValueError("FusedGroup: member %d has columns (%s buckets, %d numeric), member 0 (%s, %d)" % (
-                    i, list(e.vocab_sizes), e.n_numeric, list(lead.vocab_sizes), lead.n_numeric))
-            why = "row-sharded tables" if e.shard is not None else e._fused_limit()
-            if why is not None:
-                raise ValueError("FusedGroup: member %d: the model has %s" % (i, why))
+        self.engines = _engine.check_members("FusedGroup", engines, self.MAX_MEMBERS,
+                                             lambda e: "row-sharded tables" if e.shard is not None else e._fused_limit())
+        self.M, lead = len(self.engines), self.engines[0]
         self.k, self.device, self.F, self.n_numeric = lead.k, lead.device, lead.F, lead.n_numeric
         self._keep = []
         members = (_lib.ServeMember * self.M)(*[_serve_member(e, self._keep) for e in self.engines])
@@ -286,12 +269,9 @@ class FusedGroup:
     def buffers(self, B):
         """member_logits [M, B], the tickets (zero: every call leaves them zero) and the PREDICT dict for batches of B"""
         dev = self.device
-        cls = torch.empty(B, 1, dtype=torch.int64, device=dev)
         return {"member_logits": torch.empty(self.M, B, dtype=torch.float32, device=dev),
                 "tickets": torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev),
-                "out": {"logits": torch.empty(B, 1, dtype=torch.float32, device=dev),
-                        "logistic": torch.empty(B, 1, dtype=torch.float32, device=dev),
-                        "probabilities": torch.empty(B, 2, dtype=torch.float32, device=dev), "class_ids": cls, "classes": cls}}
+                "out": _engine.predict_buffers(B, dev)}
 
     def run(self, ids, x_num=None, bufs=None):
         """ids int32 [B, F] / x_num float32 [B, n_numeric] on the device -> bufs["out"] (device tensors, as

@@ -225,8 +225,7 @@ def test_one_field_fm_only_gives_exactly_zero():
 def _raw_step(m, ids, y, logits, loss, sweep_blocks=0, **over):
     """mi_train_step_fused through the binding, as engine.fused_train_step calls it, with overrides."""
     B = over.get("B", ids.shape[0])
-    layer_off = torch.tensor([o for (ko, bo, _, _) in m.layers for o in (ko, bo)] or [0], dtype=torch.int64)
-    widths = torch.tensor(([m.layers[0][2]] + [h for (_, _, _, h) in m.layers]) if m.layers else [0], dtype=torch.int32)
+    layer_off, widths = m.layer_tables()
     F, E = over.get("F", m.F), over.get("E", m.E)
     nbytes = int(m.k.query("mi_train_step_fused_workspace_bytes", B, F, E, m.P))
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device="cuda")
