@@ -29,8 +29,8 @@ import numpy as np
 
 from oracle import deepfm as O
 from oracle import optimizers as OO
-from tests.test_hip_fused_step import FLAGS, ML100K_VOCAB, TRAJECTORIES
-from tests.test_hip_fused_step import _fresh_ids as fresh_ids
+from tests.cases import FLAGS, ML100K_VOCAB, TRAJECTORIES
+from tests.util import _fresh_ids as fresh_ids
 from tests.util import dev, dropout_mask, make_problem, max_err_scaled
 
 RELU_MARGIN = 1e-6

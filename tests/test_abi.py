@@ -1,22 +1,12 @@
 """CPU: the C-ABI library loads here (no GPU, no compute calls) and exports every symbol that
 include/mi355x_rec.h declares, with the argument counts the ctypes binding assumes."""
-import os
+import inspect
 import re
 import subprocess
 
 from mi355x_rec import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header_decls():
-    src = open(os.path.join(ROOT, "include", "mi355x_rec.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    decls = {}
-    for m in re.finditer(r"\b(mi_\w+)\s*\(([^;{}]*?)\)\s*;", src, flags=re.S):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else args.count(",") + 1
-    return decls
+from tests.cpu_kernels import NumpyKernels
+from tests.util import _header_decls
 
 
 def test_header_binding_and_library_agree(lib):
@@ -31,6 +21,18 @@ def test_header_binding_and_library_agree(lib):
     assert set(decls) <= exported
     # nothing but the C ABI leaks out of the library
     assert all(s.startswith("mi_") for s in exported), exported
+
+
+def test_numpy_stand_ins_take_what_the_binding_passes():
+    """tests/cpu_kernels.py: the engine calls a stand-in with the arguments it gives the binding, positionally — every
+    SIGNATURES argument but the stream, which the binding adds"""
+    stand_ins = {n: f for n, f in vars(NumpyKernels).items() if n.startswith("mi_")}
+    assert len(stand_ins) >= 41
+    for name, f in stand_ins.items():
+        assert name in _lib.SIGNATURES, name
+        params = list(inspect.signature(f).parameters.values())[1:]               # (self)
+        assert all(p.kind == p.POSITIONAL_OR_KEYWORD for p in params), (name, [str(p) for p in params])
+        assert len(params) == len(_lib.SIGNATURES[name][1]) - 1, (name, len(params), len(_lib.SIGNATURES[name][1]) - 1)
 
 
 def test_library_identity(lib):

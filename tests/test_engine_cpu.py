@@ -9,7 +9,7 @@ import torch
 from oracle import deepfm as O
 from oracle import optimizers as OO
 from tests.cpu_kernels import NumpyKernels
-from tests.util import make_problem
+from tests.util import _check_vars, _t, make_problem
 
 
 def _engine(vocab, E, hidden, nn=0, **kw):
@@ -17,20 +17,6 @@ def _engine(vocab, E, hidden, nn=0, **kw):
     opt = kw.pop("optimizer", OptimizerSpec("Adam", 0.001))
     return DeepFM(vocab, n_numeric=nn, embedding_size=E, hidden_units=hidden, optimizer=opt, device="cpu",
                   _kernels=NumpyKernels(), **kw)
-
-
-def _t(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a))
-
-
-def _check_vars(m, p, atol):
-    g = m.export_numpy()
-    for f in range(len(p.emb)):
-        assert np.max(np.abs(g["emb"][f] - p.emb[f])) < atol
-        assert np.max(np.abs(g["lin_w"][f] - p.lin_w[f])) < atol
-    for i, (k, b) in enumerate(g["mlp"]):
-        assert np.max(np.abs(k - p.mlp[i][0])) < atol and np.max(np.abs(b - p.mlp[i][1])) < atol
-    assert abs(g["lin_bias"][0] - p.lin_bias[0]) < atol
 
 
 @pytest.mark.parametrize("vocab,E,hidden,B,nn", [([9, 13, 5, 6], 8, [16, 8], 64, 0), ([11, 5, 9], 4, [12], 33, 2)])

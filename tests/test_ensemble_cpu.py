@@ -1,7 +1,7 @@
 """CPU: the host side of serving an ensemble — EnsemblePredictor (its refusals, from_exports / from_sweep, the three modes,
 its buffers) and the two CLIs' new flags.  mi_predict_group_plan / mi_predict_group are stood in by a numpy restatement of
-their contract in include/mi355x_rec.h (EnsembleKernels below: member i's logit is that engine's predict_logits on the
-CPU, the mean is formed in fp32 in member order); the real kernel is tested in test_hip_ensemble.py.  The binding is
+their contract in include/mi355x_rec.h (tests.cpu_kernels.NumpyKernels: member i's logit is that engine's predict_logits on
+the CPU, the mean is formed in fp32 in member order); the real kernel is tested in test_hip_ensemble.py.  The binding is
 checked against the real library."""
 import copy
 import csv
@@ -15,64 +15,12 @@ import torch
 from mi355x_rec import _lib, engine
 from mi355x_rec.engine import DeepFM
 from mi355x_rec.predictor import EnsemblePredictor, FusedGroup, Predictor
-from oracle import deepfm as O
-from tests.test_abi import _header_decls
-from tests.test_population_cpu import _sweep_args
-from tests.test_population_eval_cpu import EvalKernels
-from tests.util import max_err_scaled
-from trainers import _cli, ml_100k, predict, recommend
+from tests.cases import _sweep_args
+from tests.cpu_kernels import NumpyKernels, cpu_kernels  # noqa: F401  (a fixture)
+from tests.util import _fake_sweep, _header_decls, _requests, _train_deep_fm_export, max_err_scaled
+from trainers import ml_100k, predict
 
 F32 = np.float32
-
-
-class EnsembleKernels(EvalKernels):
-    """EvalKernels + the two ensemble entries restated from the header.  A member is recognised by its `dense` pointer
-    (ENGINES: every engine built on these kernels that a test registered)."""
-    GROUP_MAGIC = 0x7072
-    ENGINES = {}
-
-    @classmethod
-    def register(cls, engines):
-        for e in engines:
-            cls.ENGINES[e.dense.data_ptr()] = e
-
-    def mi_predict_group_plan(self, members, M, F, nd, field_off, table, plan):
-        assert 1 <= M <= _lib.PREDICT_GROUP_MAX_MEMBERS and len(members) == M
-        self.group = [self.ENGINES[members[i].dense] for i in range(M)]
-        for m, e in zip(members, self.group):
-            assert (m.E, m.n_layers, m.activation) == (e.E, len(e.layers), e.act) and e.F == F and e.n_numeric == nd
-            assert (m.use_linear, m.use_fm, m.use_dnn, m.numeric_raw) == (int(e.use_linear), int(e.use_mf), int(e.use_dnn),
-                                                                           int(e.raw_numeric))
-        plan.device_table, plan.magic, plan.n_members, plan.F, plan.n_numeric = table.data_ptr(), self.GROUP_MAGIC, M, F, nd
-
-    def mi_predict_group(self, plan, M, ids, x_num, B, member_logits, tickets, logits, logistic, probabilities, class_ids):
-        assert plan.magic == self.GROUP_MAGIC and M == plan.n_members == len(self.group) and B >= 1
-        assert tuple(ids.shape) == (B, plan.F) and tuple(member_logits.shape) == (M, B)
-        assert tuple(tickets.shape) == ((B + 31) // 32,) and tickets.dtype == torch.int32 and not bool(tickets.any())
-        acc = None
-        for i, e in enumerate(self.group):
-            z = e.predict_logits(ids, x_num).numpy().astype(F32)
-            member_logits[i] = torch.from_numpy(z)
-            acc = z if acc is None else (acc + z).astype(F32)
-        z = (acc / F32(M)).astype(F32)
-        sig = O.predictions(z)["logistic"]
-        logits.numpy().reshape(-1)[:] = z
-        logistic.numpy().reshape(-1)[:] = sig
-        probabilities.numpy().reshape(-1, 2)[:] = np.stack([1 - sig, sig], 1)
-        class_ids.numpy().reshape(-1)[:] = sig > 0.5
-
-
-@pytest.fixture
-def cpu_kernels(monkeypatch):
-    monkeypatch.setattr(engine, "HipKernels", EnsembleKernels)
-
-
-def _train(root, name, extra):
-    trainer, opt = recommend.MODELS["deep_fm"]
-    job = os.path.join(root, name)
-    argv = ["--synthetic", "300", "--job-dir", job, "--train-steps", "10", "--batch-size", "16", "--device", "cpu"] + list(extra)
-    trainer.train_and_evaluate(_cli.make_parser("deep_fm", opt).parse_args(argv))
-    return os.path.join(job, "export", "exporter")
 
 
 @pytest.fixture(scope="module")
@@ -80,20 +28,14 @@ def exports(tmp_path_factory):
     """two small trained deep_fm exports that differ in embedding size and layers (trained once for the module)"""
     root = str(tmp_path_factory.mktemp("ens"))
     with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(engine, "HipKernels", EnsembleKernels)
-        return [_train(root, "a", ["--embedding-size", "4", "--hidden-units", "8", "8"]),
-                _train(root, "b", ["--embedding-size", "8", "--hidden-units", "8"])]
-
-
-def _requests(n=30, seed=2):
-    cols, _ = ml_100k._read_csv("synthetic:%d:%d" % (n, seed))
-    recv = set(ml_100k.serving_input_fn().receiver_tensors)
-    return {k: v for k, v in cols.items() if k in recv}
+        mp.setattr(engine, "HipKernels", NumpyKernels)
+        return [_train_deep_fm_export(root, "a", ["--embedding-size", "4", "--hidden-units", "8", "8"]),
+                _train_deep_fm_export(root, "b", ["--embedding-size", "8", "--hidden-units", "8"])]
 
 
 def _members(exports, **kw):
     ps = [Predictor.from_export(d, device="cpu", **kw) for d in exports]
-    EnsembleKernels.register([p.engine for p in ps])
+    NumpyKernels.register([p.engine for p in ps])
     return ps
 
 
@@ -199,17 +141,6 @@ def test_the_plan_is_built_once_buffers_are_kept_per_batch_size_and_ids_are_tran
     assert np.array_equal(a["logits"], b["logits"]) and a["logits"] is not b["logits"]     # host copies, not views of the buffer
 
 
-def _fake_sweep(root, exports, order=(1, 0)):
-    """a sweep directory whose sweep.json lists the two exports as members `order`, best first"""
-    job = os.path.join(root, "sweep")
-    os.makedirs(job, exist_ok=True)
-    rows = [{"member": m, "dir": os.path.dirname(os.path.dirname(exports[m])), "export": exports[m], "metrics": {"auc": 0.9 - 0.1 * r}}
-            for r, m in enumerate(order)]
-    with open(os.path.join(job, "sweep.json"), "w") as f:
-        json.dump({"select": "auc", "members": rows}, f)
-    return job
-
-
 def test_from_sweep_takes_the_first_rows_in_order(cpu_kernels, exports, tmp_path):
     job = _fake_sweep(str(tmp_path), exports)
     ens = EnsemblePredictor.from_sweep(job, top=2, device="cpu")
@@ -221,7 +152,7 @@ def test_from_sweep_takes_the_first_rows_in_order(cpu_kernels, exports, tmp_path
             EnsemblePredictor.from_sweep(job, top=top, device="cpu")
     with pytest.raises(FileNotFoundError, match="no sweep.json"):
         EnsemblePredictor.from_sweep(str(tmp_path / "nothing"), top=1, device="cpu")
-    EnsembleKernels.register([p.engine for p in ens.members])
+    NumpyKernels.register([p.engine for p in ens.members])
     got = ens(_requests(9), return_members=True)
     solo = [Predictor.from_export(exports[m], device="cpu", mode="layered")(_requests(9))["logits"][:, 0] for m in (1, 0)]
     for i in range(2):
@@ -240,7 +171,7 @@ def test_predict_cli_top(cpu_kernels, exports, tmp_path, monkeypatch):
 
     def registered(cls, *a, **kw):
         ens = real(cls, *a, **kw)
-        EnsembleKernels.register([p.engine for p in ens.members])
+        NumpyKernels.register([p.engine for p in ens.members])
         return ens
     monkeypatch.setattr(EnsemblePredictor, "from_sweep", classmethod(registered))
     out = predict.main(["--job-dir", job, "--input", "synthetic:23:5", "--top", "2", "--device", "cpu", "--batch-size", "10"])
@@ -259,7 +190,7 @@ def test_sweep_ensemble_flag(cpu_kernels, tmp_path, capsys, monkeypatch):
 
     def registered(cls, *a, **kw):
         ens = real(cls, *a, **kw)
-        EnsembleKernels.register([p.engine for p in ens.members])
+        NumpyKernels.register([p.engine for p in ens.members])
         return ens
     monkeypatch.setattr(EnsemblePredictor, "from_sweep", classmethod(registered))
     grid = ["--learning-rate", "0.001", "0.01", "--seeds", "2"]

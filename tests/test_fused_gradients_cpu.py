@@ -1,5 +1,5 @@
-"""CPU: tests/fused_grad_check.py's checker on the numpy restatement of mi_train_step_fused (FusedStepKernels of
-test_fused_step_cpu.py).  Every case of test_hip_fused_gradients.py passes here first — this is where the relu margins
+"""CPU: tests/fused_grad_check.py's checker on the numpy restatement of mi_train_step_fused (NumpyKernels of
+tests/cpu_kernels.py).  Every case of test_hip_fused_gradients.py passes here first — this is where the relu margins
 and the E32 values are first seen (pytest -s) — and the checker FAILS when the step's backward is subtly wrong:
 
   * a gradient wrong by 1 % everywhere (the stand-in called with scale x 1.01, its loss put back);
@@ -16,15 +16,15 @@ from mi355x_rec.engine import DeepFM, OptimizerSpec
 from oracle import deepfm as O
 from oracle import optimizers as OO
 from tests import fused_grad_check as C
-from tests.test_fused_step_cpu import FusedStepKernels, _check_vars, _t
-from tests.util import make_problem
+from tests.cpu_kernels import NumpyKernels
+from tests.util import _check_vars, _t, make_problem
 
 _SCALE, _LOSS = 30, 34                                       # positions in mi_train_step_fused's argument list
 _SLOT_ARG = {"t_s0": 1, "t_s1": 2, "l_s0": 5, "l_s1": 6, "d_s0": 17, "d_s1": 18}
 _SLOT_OF = {"t_s0": ("table", "m"), "t_s1": ("table", "v"), "l_s0": ("lin_w", "m"), "l_s1": ("lin_w", "v")}
 
 
-class GradientOffByOnePercent(FusedStepKernels):
+class GradientOffByOnePercent(NumpyKernels):
     """every gradient of the step x 1.01 (dlogit carries `scale`); the reported loss is the unperturbed one"""
 
     def mi_train_step_fused(self, *a):
@@ -34,7 +34,7 @@ class GradientOffByOnePercent(FusedStepKernels):
         a[_LOSS].numpy()[0] /= np.float32(1.01)
 
 
-class NoisySlots(FusedStepKernels):
+class NoisySlots(NumpyKernels):
     """after the step, one slot class x (1 + 1e-4 N(0, 1)) element by element"""
 
     def __init__(self, which):
@@ -48,7 +48,7 @@ class NoisySlots(FusedStepKernels):
         s *= (1 + 1e-4 * self.rng.standard_normal(s.shape)).astype(np.float32)
 
 
-def _maker(kernels=FusedStepKernels):
+def _maker(kernels=NumpyKernels):
     def make(vocab, E, hidden, **kw):
         return DeepFM(vocab, embedding_size=E, hidden_units=hidden, optimizer=OptimizerSpec("Adam", 0.001), device="cpu",
                       _kernels=kernels(), **kw)

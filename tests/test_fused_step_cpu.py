@@ -1,164 +1,27 @@
 """CPU: the host side of the one-launch train step — DeepFM.fused_train_step / fused_step_ok, model.run_batch's
 params["fused_step"], the trainers' --fused-step flag.  mi_train_step_fused is stood in by a numpy restatement of its
-contract in include/mi355x_rec.h on top of the other numpy stand-ins (FusedStepKernels below); the real kernel is
-tested in test_hip_fused_step.py."""
+contract in include/mi355x_rec.h (tests.cpu_kernels.NumpyKernels); the real kernel is tested in test_hip_fused_step.py."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from mi355x_rec import engine
 from mi355x_rec.engine import DeepFM, OptimizerSpec
 from mi355x_rec.predictor import Predictor
 from oracle import deepfm as O
 from oracle import optimizers as OO
-from tests.cpu_kernels import _hyper
-from tests.test_predictor_cpu import ServeKernels
-from tests.util import MASK64, dropout_mask, make_problem
+from tests.cases import ML100K_VOCAB
+from tests.cpu_kernels import NumpyKernels, cpu_kernels  # noqa: F401  (a fixture)
+from tests.util import _check_vars, _fresh_ids, _t, dropout_mask, make_problem
 from trainers import _cli, deep, deep_fm, linear, linear_deep, ml_100k
 
-ML100K_VOCAB = [2, 2, 7, 2, 2, 2, 2, 2, 2, 2, 2, 3, 2, 2000, 2, 2, 50, 8, 2, 2, 2, 2, 1000, 2, 2, 1000]
-_ACT = {0: lambda v: v, 1: lambda v: np.maximum(v, 0), 2: lambda v: 1 / (1 + np.exp(-v)), 3: np.tanh}
 _DEEP_FM_OPT = ("exclude_linear", "exclude_mf", "exclude_dnn", "hidden_units", "dropout")
-
-
-class FusedStepKernels(ServeKernels):
-    """The numpy stand-ins + mi_train_step_fused restated from include/mi355x_rec.h (fp32 numpy, independent of the layered
-    stand-ins: its own forward, backward, touched-row apply and all-rows sweep).  `calls` counts the entries fetched."""
-
-    def __init__(self):
-        self.calls = {}
-
-    def __getattribute__(self, name):
-        value = object.__getattribute__(self, name)
-        if name.startswith("mi_"):
-            calls = object.__getattribute__(self, "calls")
-            calls[name] = calls.get(name, 0) + 1
-        return value
-
-    def mi_train_step_fused(self, table, t_m, t_v, ts, lin_w, l_m, l_v, ls, last_step, field_off, R, ids, labels, B, F, E,
-                            dense, d_m, d_v, n_dense, layer_off, widths, n_layers, act, use_linear, use_fm, use_dnn,
-                            lin_bias_off, keep, seed, scale, step, hp, logits, loss, sweep_blocks, ws, wsb):
-        f32 = np.float32
-        assert hp.kind == 0 and 1 <= B <= 128 and 1 <= F <= 32 and R <= 1 << 18 and n_layers <= 4
-        assert bool((last_step.numpy() == step - 1).all()) or step == 1, "every row must be current"
-        keep, scale, lr_t = f32(keep), f32(scale), f32(hp.lr_t)
-        b1, b2, eps = f32(hp.beta1), f32(hp.beta2), f32(hp.epsilon)
-        d = dense.numpy()
-        rows = ids.numpy().astype(np.int64) + field_off.numpy()[None, :]
-        emb = bool(use_fm or use_dnn)
-        T = table.numpy() if emb else None
-        V = T[rows] if emb else None                                  # [B, F, E]
-        z = np.zeros(B, f32)
-        if use_linear:
-            z = z + (lin_w.numpy()[rows].sum(1, dtype=f32) + d[lin_bias_off])
-        s = None
-        if use_fm:
-            s = V.sum(1, dtype=f32)
-            z = z + f32(0.5) * (s * s - (V * V).sum(1, dtype=f32)).sum(1, dtype=f32)
-        acts, Ws = [], []
-        lo, wd = layer_off.numpy(), widths.numpy()
-        if use_dnn:
-            h = V.reshape(B, F * E)
-            for i in range(n_layers):
-                W = d[lo[2 * i]:lo[2 * i] + wd[i] * wd[i + 1]].reshape(wd[i], wd[i + 1])
-                acts.append(h)
-                Ws.append(W.copy())
-                h = (h @ W + d[lo[2 * i + 1]:lo[2 * i + 1] + wd[i + 1]]).astype(f32)
-                if i + 1 < n_layers:
-                    h = _ACT[act](h).astype(f32)
-                    if keep < 1:
-                        h = (h / keep) * dropout_mask((seed + 7919 * i) & MASK64, B, int(wd[i + 1]), keep)
-            z = z + h[:, 0]
-        y = labels.numpy().astype(f32)
-        logits.numpy()[:] = z
-        e = np.exp(-np.abs(z))
-        loss.numpy()[0] = ((np.maximum(z, 0) - z * y + np.log1p(e)) * scale).sum(dtype=f32)
-        dl = ((np.where(z >= 0, 1 / (1 + e), e / (1 + e)).astype(f32) - y) * scale).astype(f32)
-        # backward
-        gd = np.zeros(n_dense, f32)
-        d_concat = None
-        if use_dnn:
-            dy = dl[:, None]
-            for i in reversed(range(n_layers)):
-                gd[lo[2 * i]:lo[2 * i] + wd[i] * wd[i + 1]] = (acts[i].T @ dy).reshape(-1)
-                gd[lo[2 * i + 1]:lo[2 * i + 1] + wd[i + 1]] = dy.sum(0, dtype=f32)
-                g = (dy @ Ws[i].T).astype(f32)
-                if i:
-                    x = acts[i]                                        # the layer's stored output: act(pre) / keep, or 0
-                    if act == 1:
-                        g = np.where(x > 0, g / keep, 0).astype(f32)
-                    else:
-                        o = x * keep
-                        der = {0: np.ones_like(o), 2: o * (1 - o), 3: 1 - o * o}[act]
-                        g = np.where((keep < 1) & (x == 0), 0, (g / keep) * der).astype(f32)
-                    dy = g
-                else:
-                    d_concat = g.reshape(B, F, E)
-        if use_linear:
-            gd[lin_bias_off] = dl.sum(dtype=f32)
-        # touched rows: entries summed in ascending entry order, TF's sparse Adam; every other row: one step of the sweep
-        flat = rows.reshape(-1)
-        touched = np.zeros(R, bool)
-        touched[flat] = True
-        G = None
-        if emb:
-            G = np.zeros((B, F, E), f32)
-            if d_concat is not None:
-                G = G + d_concat
-            if use_fm:
-                G = G + dl[:, None, None] * (s[:, None, :] - V)
-            G = G.reshape(B * F, E)
-        gl = np.repeat(dl, F)
-        for w, m, v, grad in ((table, t_m, t_v, G), (lin_w, l_m, l_v, gl)):
-            if w is None or grad is None or (w is lin_w and not use_linear):
-                continue
-            Wn, Mn, Vn = w.numpy(), m.numpy(), v.numpy()
-            for r in np.flatnonzero(touched):
-                g = np.zeros_like(Wn[r])
-                for en in np.flatnonzero(flat == r):
-                    g = g + grad[en]
-                Mn[r] = Mn[r] * b1 + g * (f32(1) - b1)
-                Vn[r] = Vn[r] * b2 + (g * g) * (f32(1) - b2)
-                Wn[r] = Wn[r] - (lr_t * Mn[r]) / (np.sqrt(Vn[r]) + eps)
-            u = ~touched
-            Mn[u] = Mn[u] * b1
-            Vn[u] = Vn[u] * b2
-            Wn[u] = Wn[u] - (lr_t * Mn[u]) / (np.sqrt(Vn[u]) + eps)
-        last_step.numpy()[:] = step
-        OO.dense_apply(_hyper(hp), d, d_m.numpy(), d_v.numpy(), gd, lr_t)
-
-
-@pytest.fixture
-def cpu_kernels(monkeypatch):
-    monkeypatch.setattr(engine, "HipKernels", FusedStepKernels)
 
 
 def _engine(vocab, E, hidden, **kw):
     opt = kw.pop("optimizer", OptimizerSpec("Adam", 0.001))
-    return DeepFM(vocab, embedding_size=E, hidden_units=hidden, optimizer=opt, device="cpu", _kernels=FusedStepKernels(), **kw)
-
-
-def _t(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a))
-
-
-def _check_vars(m, p, atol):
-    g = m.export_numpy()
-    for f in range(len(p.emb)):
-        assert np.max(np.abs(g["emb"][f] - p.emb[f])) < atol, ("emb", f)
-        assert np.max(np.abs(g["lin_w"][f] - p.lin_w[f])) < atol, ("lin_w", f)
-    for i, (k, b) in enumerate(g["mlp"]):
-        assert np.max(np.abs(k - p.mlp[i][0])) < atol and np.max(np.abs(b - p.mlp[i][1])) < atol, ("mlp", i)
-    assert abs(g["lin_bias"][0] - p.lin_bias[0]) < atol
-
-
-def _fresh_ids(rng, vocab, B):
-    ids = np.stack([rng.integers(0, v, B) for v in vocab], 1).astype(np.int32)
-    if B > 1:
-        ids[B // 2] = ids[0]
-    return ids
+    return DeepFM(vocab, embedding_size=E, hidden_units=hidden, optimizer=opt, device="cpu", _kernels=NumpyKernels(), **kw)
 
 
 @pytest.mark.parametrize("vocab,E,hidden,B,dropout", [(ML100K_VOCAB, 4, [16, 16], 32, 0.0), ([9, 13, 5, 6], 8, [16, 8], 64, 0.25)])
@@ -235,7 +98,7 @@ def test_models_outside_the_scope_are_refused_before_any_launch(kw, B, msg):
     kw = dict(kw)
     vocab, E, hidden = kw.pop("vocab", [9, 13, 5]), kw.pop("E", 4), kw.pop("hidden", [8])
     nn = kw.pop("n_numeric", 0)
-    m = DeepFM(vocab, n_numeric=nn, embedding_size=E, hidden_units=hidden, device="cpu", _kernels=FusedStepKernels(),
+    m = DeepFM(vocab, n_numeric=nn, embedding_size=E, hidden_units=hidden, device="cpu", _kernels=NumpyKernels(),
                optimizer=kw.pop("optimizer", OptimizerSpec("Adam", 0.001)), **kw)
     assert not m.fused_step_ok(B) and m._fused_step_limit(B)
     ids = torch.zeros(B, len(vocab), dtype=torch.int32)

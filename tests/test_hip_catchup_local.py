@@ -8,26 +8,12 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import dev, make_problem
+from tests.util import _chk, _p, _st, dev, make_problem
 
 pytestmark = pytest.mark.gpu
 
 BOUNDED_DEFER, LOCAL = 3, 8
 INVALID = -1                                         # MI_ERR_INVALID
-
-
-def _st():
-    from mi355x_rec import _lib
-    return _lib.cur_stream()
-
-
-def _chk(rc, what="call"):
-    from mi355x_rec import _lib
-    _lib.check(rc, what)
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 def _chunk(lib):

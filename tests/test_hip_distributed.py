@@ -6,18 +6,18 @@
 The 8-GPU RCCL run itself is the driver's (bench.py --gpus N)."""
 import pytest
 
-from tests.test_distributed_cpu import CASES, _run, check_against_big_batch
+from tests.cases import DISTRIBUTED_CASES, _run_ranks, check_against_big_batch
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("cfg", [CASES[0], CASES[1], ([50, 30, 20, 40], 64, [64, 32], 128, 0, "Adam", 0.001, 3, (True, True, True)),
-                                 CASES[4],                                                                        # pipelined, 4 chunks
+@pytest.mark.parametrize("cfg", [DISTRIBUTED_CASES[0], DISTRIBUTED_CASES[1], ([50, 30, 20, 40], 64, [64, 32], 128, 0, "Adam", 0.001, 3, (True, True, True)),
+                                 DISTRIBUTED_CASES[4],                                                                        # pipelined, 4 chunks
                                  ([50, 30, 20, 40], 64, [64, 32], 256, 0, "Adam", 0.001, 3, (True, True, True), 2),   # 2 chunks of 128
                                  # BASELINE config 5's model shape: 40 fields, E=128, [512,256,128], row-sharded, pipelined
                                  ([13] * 40, 128, [512, 256, 128], 128, 0, "Adam", 0.001, 2, (True, True, True), 2),
                                  # BASELINE config 4's model: Wide&Deep + raw numeric columns, Ftrl + Adagrad, SUM loss
-                                 CASES[7],
+                                 DISTRIBUTED_CASES[7],
                                  # chunked exchanges, one forward / backward (the default from 8 ranks on), config-5 shape
                                  ([13] * 40, 128, [512, 256, 128], 128, 0, "Adam", 0.001, 2, (True, True, True), 2, dict(chunk_compute=False)),
                                  ([50, 30, 20, 40], 64, [64, 32], 256, 0, "Adam", 0.001, 3, (True, True, True), 2,
@@ -45,7 +45,7 @@ pytestmark = pytest.mark.gpu
                                  pytest.param(([50, 30, 20, 40], 32, [128, 128], 8192, 0, "Adam", 0.001, 2, (True, True, True), 2,
                                                dict(chunk_compute=True, reduction="sum")), id="cfg15")])
 def test_two_ranks_one_gpu_gloo(cfg):
-    check_against_big_batch(cfg, _run(cfg, 2, device="cuda", backend="gloo"), 2, tol=3.0)
+    check_against_big_batch(cfg, _run_ranks(cfg, 2, device="cuda", backend="gloo"), 2, tol=3.0)
 
 
 @pytest.mark.parametrize("chunks,chunk_compute,route_ahead", [(1, True, True), (3, True, True), (3, False, True), (3, False, False)])
@@ -54,7 +54,7 @@ def test_single_rank_rccl_path(chunks, chunk_compute, route_ahead):
     second RCCL communicator for the batch routed ahead / one communicator for the whole step)"""
     cfg = ([50, 30, 20, 40], 16, [32, 16], 96, 0, "Adam", 0.001, 3, (True, True, True), chunks,
            dict(chunk_compute=chunk_compute, announce=True, route_ahead=route_ahead))
-    check_against_big_batch(cfg, _run(cfg, 1, device="cuda", backend="nccl"), 1, tol=3.0)
+    check_against_big_batch(cfg, _run_ranks(cfg, 1, device="cuda", backend="nccl"), 1, tol=3.0)
 
 
 @pytest.mark.parametrize("chunks,chunk_compute", [(1, True), (2, True), (2, False)])
@@ -65,4 +65,4 @@ def test_modelled_link_time_changes_no_number(chunks, chunk_compute):
     cfg = ([50, 30, 20, 40], 16, [32, 16], 96, 0, "Adam", 0.001, 3, (True, True, True), chunks,
            dict(chunk_compute=chunk_compute, announce=True, route_ahead=False,
                 sim_links={"world": 8, "gbs": 7 * 45.0, "latency_us": 40.0}))
-    check_against_big_batch(cfg, _run(cfg, 1, device="cuda", backend="nccl"), 1, tol=3.0)
+    check_against_big_batch(cfg, _run_ranks(cfg, 1, device="cuda", backend="nccl"), 1, tol=3.0)

@@ -19,13 +19,11 @@ import torch
 from mi355x_rec import _lib
 from mi355x_rec.engine import DeepFM, HipKernels, OptimizerSpec
 from mi355x_rec.predictor import EnsemblePredictor, FusedGroup, _serve_member
-from tests.util import guarded_nan, guards_intact, max_err_scaled
+from tests.util import PKG, ROOT, _run_module, guarded_nan, guards_intact, max_err_scaled
 from trainers import ml_100k
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "recommender-tensorflow_amd")
 VOCAB = [9, 13, 5, 50, 7, 3]
 BATCHES = (1, 31, 32, 33, 70)
 # the mixed population: the CLI shape; no FM term; two output tiles per wave in a layer; no DNN; four tiles per wave
@@ -256,14 +254,6 @@ def test_host_side_refusals(mixed):
 
 
 # ---- end to end: exports and a sweep ----------------------------------------------------------------------------------
-def _run(mod, args):
-    env = dict(os.environ)
-    env["PYTHONPATH"] = os.pathsep.join([PKG, ROOT])
-    r = subprocess.run([sys.executable, "-m", mod] + args, cwd=PKG, env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r
-
-
 def _requests(spec):
     cols, _ = ml_100k._read_csv(spec)
     recv = set(ml_100k.serving_input_fn().receiver_tensors)
@@ -274,7 +264,7 @@ def test_ensemble_predictor_fused_equals_layered(tmp_path):
     dirs = []
     for name, E in (("a", "4"), ("b", "8")):
         job = str(tmp_path / name)
-        _run("trainers.deep_fm", ["--synthetic", "400", "--job-dir", job, "--train-steps", "20", "--embedding-size", E])
+        _run_module("trainers.deep_fm", ["--synthetic", "400", "--job-dir", job, "--train-steps", "20", "--embedding-size", E])
         dirs.append(os.path.join(job, "export", "exporter"))
     feats = _requests("synthetic:70:3")
     fused = EnsemblePredictor.from_exports(dirs, mode="fused")(feats, return_members=True)
@@ -292,14 +282,14 @@ def test_ensemble_predictor_fused_equals_layered(tmp_path):
 
 def test_sweep_to_ensemble_predictions(tmp_path):
     job = str(tmp_path / "sweep")
-    r = _run("trainers.sweep", ["--synthetic", "600", "--train-steps", "30", "--seeds", "3", "--ensemble", "2", "--job-dir", job])
+    r = _run_module("trainers.sweep", ["--synthetic", "600", "--train-steps", "30", "--seeds", "3", "--ensemble", "2", "--job-dir", job])
     assert "INFO: ensemble of the 2 best members" in r.stdout
     doc = json.load(open(os.path.join(job, "sweep.json")))
     ens = doc["ensemble"]
     assert ens["members"] == [row["member"] for row in doc["members"][:2]] and len(ens["members"]) == 2
     assert ens["metrics"] and all(np.isfinite(v) for v in ens["metrics"].values()) and doc["select"] in ens["metrics"]
     out = str(tmp_path / "pred.csv")
-    _run("trainers.predict", ["--job-dir", job, "--top", "2", "--input", "synthetic:70:3", "--output", out])
+    _run_module("trainers.predict", ["--job-dir", job, "--top", "2", "--input", "synthetic:70:3", "--output", out])
     rows = list(csv.DictReader(open(out)))
     assert len(rows) == 70
     got = np.asarray([float(row["logit"]) for row in rows], np.float32)

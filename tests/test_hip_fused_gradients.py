@@ -15,7 +15,7 @@ FGRAD <case> <variable> <slot> device ... fp32-oracle ... bar ...; the worst per
 import pytest
 
 from tests import fused_grad_check as C
-from tests.test_hip_fused_step import _engine
+from tests.cases import _hip_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("case", C.CASES, ids=[c.name for c in C.CASES])
 def test_slots_after_one_step_match_the_fp64_oracle(case, warm):
     m_kw = dict(case.kw)
-    rep = C.run_case(case, _engine, warm)
+    rep = C.run_case(case, _hip_engine, warm)
     assert not rep.failures
     if m_kw.get("use_dnn", True):
         assert ("kernel_0", "m") in rep.figures and ("kernel_%d" % len(case.hidden), "v") in rep.figures

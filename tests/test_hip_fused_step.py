@@ -14,55 +14,16 @@ import torch
 from mi355x_rec import _lib
 from oracle import deepfm as O
 from oracle import optimizers as OO
-from tests.util import dev, dropout_mask, guarded_nan, guards_intact, make_problem, max_err_scaled
+from tests.cases import FLAGS, ML100K_VOCAB, TRAJECTORIES, _hip_engine
+from tests.util import (_compare_vars, _fresh_ids, dev, dropout_mask, guarded_nan, guards_intact, make_problem,
+                        max_err_scaled)
 
 pytestmark = pytest.mark.gpu
-
-ML100K_VOCAB = [2, 2, 7, 2, 2, 2, 2, 2, 2, 2, 2, 3, 2, 2000, 2, 2, 50, 8, 2, 2, 2, 2, 1000, 2, 2, 1000]  # sorted order
-
-
-def _engine(vocab, E, hidden, **kw):
-    from mi355x_rec.engine import DeepFM, OptimizerSpec
-    opt = kw.pop("optimizer", OptimizerSpec("Adam", 0.001))
-    kw.setdefault("catchup", "exact")
-    return DeepFM(vocab, embedding_size=E, hidden_units=hidden, optimizer=opt, **kw)
-
-
-def _compare_vars(m, p, atol):
-    g = m.export_numpy()
-    for f in range(len(p.emb)):
-        if g["emb"] is not None:
-            assert np.max(np.abs(g["emb"][f] - p.emb[f])) < atol, ("emb", f, float(np.max(np.abs(g["emb"][f] - p.emb[f]))))
-        if g["lin_w"] is not None:
-            assert np.max(np.abs(g["lin_w"][f] - p.lin_w[f])) < atol, ("lin_w", f)
-    for i, (k, b) in enumerate(g["mlp"]):
-        assert np.max(np.abs(k - p.mlp[i][0])) < atol, ("kernel", i, float(np.max(np.abs(k - p.mlp[i][0]))))
-        assert np.max(np.abs(b - p.mlp[i][1])) < atol, ("bias", i)
-    assert abs(g["lin_bias"][0] - p.lin_bias[0]) < atol
-
-
-def _fresh_ids(rng, vocab, B):
-    ids = np.stack([rng.integers(0, v, B) for v in vocab], 1).astype(np.int32)
-    ids[B // 2] = ids[0]
-    return ids
-
-
-# Cases whose oracle trajectory keeps every hidden pre-activation at least 1e-6 away from 0 over the five steps (the
-# margin found on the CPU is in the comment; the test asserts it), so that no relu decision can depend on summation order.
-TRAJECTORIES = [
-    (ML100K_VOCAB, 4, [16, 16], 32, 300),                    # trainers.deep_fm's defaults: 3.1e-4
-    (ML100K_VOCAB, 4, [16, 16], 1, 301),                     # 1.0e-2
-    (ML100K_VOCAB, 4, [16, 16], 128, 305),                   # 3.4e-5
-    (ML100K_VOCAB, 16, [64, 64, 32], 32, 308),               # the top of the envelope: 2.3e-5
-    ([9, 13, 5, 6], 8, [16, 8], 64, 301),                    # 7.2e-5
-    ([50, 30, 20, 40, 11, 7], 16, [64, 32], 96, 307),        # 2.1e-5
-]
-
 
 @pytest.mark.parametrize("vocab,E,hidden,B,seed", TRAJECTORIES)
 def test_trajectory_matches_oracle(vocab, E, hidden, B, seed):
     p, _, _, y = make_problem(seed, vocab, E, hidden, B)
-    m = _engine(vocab, E, hidden)
+    m = _hip_engine(vocab, E, hidden)
     assert m.fused_step_ok(B)
     m.load_oracle_params(p)
     st = O.TrainState(p, OO.Hyper("Adam", 0.001))
@@ -87,12 +48,12 @@ def test_trajectory_matches_oracle(vocab, E, hidden, B, seed):
 def test_untouched_rows_get_the_layered_steps_exact_sweep_bit_for_bit(catchup_b):
     vocab, E, hidden, B = ML100K_VOCAB, 4, [16, 16], 32
     p, _, _, y = make_problem(41, vocab, E, hidden, B)
-    a = _engine(vocab, E, hidden, catchup="exact", gemm="fp32")        # (exact fp32 products, as the fused step's)
+    a = _hip_engine(vocab, E, hidden, catchup="exact", gemm="fp32")        # (exact fp32 products, as the fused step's)
     a.load_oracle_params(p)
     rng = np.random.default_rng(41)
     for _ in range(4):                                       # m and v of many rows are non-zero afterwards
         a.train_step(dev(_fresh_ids(rng, vocab, B)), dev(y))
-    b = _engine(vocab, E, hidden, catchup=catchup_b)
+    b = _hip_engine(vocab, E, hidden, catchup=catchup_b)
     b.load_state_dict(a.state_dict())                        # (state_dict brings every row up to date: both start current)
     assert torch.equal(a.t_rec, b.t_rec) and torch.equal(a.lin_state, b.lin_state) and torch.equal(a.dense, b.dense)
     ids = _fresh_ids(rng, vocab, B)
@@ -116,16 +77,12 @@ def test_untouched_rows_get_the_layered_steps_exact_sweep_bit_for_bit(catchup_b)
     assert int(moved.sum()) > 0
 
 
-FLAGS = [(True, True, True), (True, False, False), (False, True, False), (False, False, True), (True, False, True),
-         (False, True, True)]
-
-
 @pytest.mark.parametrize("flags", FLAGS)
 def test_component_flags(flags):
     ul, um, ud = flags
     vocab, E, hidden, B = [9, 13, 5, 6], 8, [16, 8], 64
     p, ids, x, y = make_problem(2, vocab, E, hidden, B, use_dnn=ud)
-    m = _engine(vocab, E, hidden, use_linear=ul, use_mf=um, use_dnn=ud)
+    m = _hip_engine(vocab, E, hidden, use_linear=ul, use_mf=um, use_dnn=ud)
     m.load_oracle_params(p)
     st = O.TrainState(p, OO.Hyper("Adam", 0.001))
     for _ in range(3):
@@ -140,7 +97,7 @@ def test_component_flags(flags):
 def test_activations(activation, dropout):
     vocab, E, hidden, B = [9, 13, 5, 6], 8, [16, 8], 48
     p, _, _, _ = make_problem(21, vocab, E, hidden, B)
-    m = _engine(vocab, E, hidden, activation=activation, dropout=dropout, seed=3)
+    m = _hip_engine(vocab, E, hidden, activation=activation, dropout=dropout, seed=3)
     m.load_oracle_params(p)
     st = O.TrainState(p, OO.Hyper("Adam", 0.001))
     rng = np.random.default_rng(22)
@@ -159,7 +116,7 @@ def test_activations(activation, dropout):
 def test_sum_reduction():
     vocab, E, hidden, B = [9, 13, 5], 4, [8], 40
     p, ids, x, y = make_problem(6, vocab, E, hidden, B)
-    m = _engine(vocab, E, hidden, reduction="sum")
+    m = _hip_engine(vocab, E, hidden, reduction="sum")
     m.load_oracle_params(p)
     st = O.TrainState(p, OO.Hyper("Adam", 0.001))
     for _ in range(3):
@@ -172,7 +129,7 @@ def test_sum_reduction():
 def test_dropout_training_step_matches_oracle_with_same_mask():
     vocab, E, hidden, B = [9, 13, 5, 6], 8, [32, 16], 128
     p, ids, x, y = make_problem(5, vocab, E, hidden, B)
-    m = _engine(vocab, E, hidden, dropout=0.25, seed=7)
+    m = _hip_engine(vocab, E, hidden, dropout=0.25, seed=7)
     m.load_oracle_params(p)
     st = O.TrainState(p, OO.Hyper("Adam", 0.001))
     for _ in range(2):
@@ -187,7 +144,7 @@ def test_fused_and_layered_steps_draw_the_same_dropout_masks_and_interleave():
     """fused, layered, graph, fused, loss, fused against the oracle with the masks of _layer_seed."""
     vocab, E, hidden, B = ML100K_VOCAB, 4, [16, 16], 32
     p, _, _, y = make_problem(300, vocab, E, hidden, B)
-    m = _engine(vocab, E, hidden, dropout=0.1, seed=5)
+    m = _hip_engine(vocab, E, hidden, dropout=0.1, seed=5)
     m.load_oracle_params(p)
     st = O.TrainState(p, OO.Hyper("Adam", 0.001))
     rng = np.random.default_rng(300)
@@ -211,7 +168,7 @@ def test_fused_and_layered_steps_draw_the_same_dropout_masks_and_interleave():
 def test_one_field_fm_only_gives_exactly_zero():
     vocab, E, B = [50], 8, 32
     p, ids, x, y = make_problem(9, vocab, E, [], B, use_dnn=False)
-    m = _engine(vocab, E, [], use_linear=False, use_mf=True, use_dnn=False)
+    m = _hip_engine(vocab, E, [], use_linear=False, use_mf=True, use_dnn=False)
     m.load_oracle_params(p)
     t0 = m.table.clone()
     for step in range(2):
@@ -241,7 +198,7 @@ def _raw_step(m, ids, y, logits, loss, sweep_blocks=0, **over):
 @pytest.mark.parametrize("vocab,E,hidden,B", [(ML100K_VOCAB, 4, [16, 16], 32), (ML100K_VOCAB, 16, [64, 64, 32], 32)])
 def test_same_bits_twice_and_for_every_sweep_grid(vocab, E, hidden, B):
     p, _, _, y = make_problem(51, vocab, E, hidden, B)
-    a = _engine(vocab, E, hidden, dropout=0.1, seed=2)
+    a = _hip_engine(vocab, E, hidden, dropout=0.1, seed=2)
     a.load_oracle_params(p)
     rng = np.random.default_rng(51)
     for _ in range(3):
@@ -250,7 +207,7 @@ def test_same_bits_twice_and_for_every_sweep_grid(vocab, E, hidden, B):
     ids = dev(_fresh_ids(rng, vocab, B))
     results = []
     for blocks in (0, 0, 1, 7, 64):
-        m = _engine(vocab, E, hidden, dropout=0.1, seed=2)
+        m = _hip_engine(vocab, E, hidden, dropout=0.1, seed=2)
         m.load_state_dict(sd)
         gl, logits = guarded_nan(B)
         gs, loss = guarded_nan(1)
@@ -265,7 +222,7 @@ def test_same_bits_twice_and_for_every_sweep_grid(vocab, E, hidden, B):
         for x, z in zip(results[0], r):
             assert torch.equal(x, z)
     # and the engine's own call is that step
-    m = _engine(vocab, E, hidden, dropout=0.1, seed=2)
+    m = _hip_engine(vocab, E, hidden, dropout=0.1, seed=2)
     m.load_state_dict(sd)
     loss, logits = m.fused_train_step(ids, dev(y))
     assert torch.equal(m.t_rec, results[0][0]) and torch.equal(m.dense, results[0][2])
@@ -287,7 +244,7 @@ def _snapshot(m):
     ([(1 << 18) - 21, 7, 7, 7], 4, [8], 16, True), ([(1 << 18) - 20, 7, 7, 7], 4, [8], 16, False),   # R = 2^18 / 2^18 + 1
 ])
 def test_limits_through_the_entry(vocab, E, hidden, B, inside):
-    m = _engine(vocab, E, hidden)
+    m = _hip_engine(vocab, E, hidden)
     g = torch.Generator(device="cuda")
     g.manual_seed(1)
     m.init_variables(g, lin_scale=0.05)
@@ -304,7 +261,7 @@ def test_limits_through_the_entry(vocab, E, hidden, B, inside):
         assert guards_intact(gl) and guards_intact(gs) and bool(torch.isfinite(logits).all()) and bool(torch.isfinite(loss).all())
         assert bool((m.last_step == 1).all())
         # the same step by the layered path, from the same start
-        n = _engine(vocab, E, hidden, gemm="fp32")
+        n = _hip_engine(vocab, E, hidden, gemm="fp32")
         n.t_rec.copy_(before[0]); n.lin_state.copy_(before[1]); n.dense.copy_(before[2])
         ln, zn = n.train_step(ids, y)
         n.finalize_rows()
@@ -324,7 +281,7 @@ def test_limits_through_the_entry(vocab, E, hidden, B, inside):
 def test_other_refusals_through_the_entry():
     from mi355x_rec.engine import OptimizerSpec
     vocab, E, hidden, B = [9, 13, 5], 4, [8], 16
-    m = _engine(vocab, E, hidden)
+    m = _hip_engine(vocab, E, hidden)
     rng = np.random.default_rng(3)
     ids, y = dev(_fresh_ids(rng, vocab, B)), dev((rng.random(B) < 0.3).astype(np.uint8))
     logits, loss = torch.empty(B, device="cuda"), torch.empty(1, device="cuda")

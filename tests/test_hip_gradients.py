@@ -27,9 +27,9 @@ import torch
 
 from oracle import deepfm as O
 from oracle import optimizers as OO
-from tests.test_hip_model import _compare_vars, _device_relu_masks, _engine
-from tests.test_hip_planes import planned_splits, row_rel_err
-from tests.util import dev, dropout_mask, make_problem
+from tests.cases import _hip_engine
+from tests.util import (_compare_vars, _device_relu_masks, dev, dropout_mask, make_problem, planned_splits,
+                        row_rel_err)
 
 pytestmark = pytest.mark.gpu
 
@@ -167,7 +167,7 @@ def _one_step(case, vocab, E, hidden, B, nn=0, numeric="embed", dropout=0.0, fla
         y = (rng.random(B) < 0.3).astype(np.uint8)
     if prepare is not None:
         y = prepare(p, ids, x, y)
-    m = _engine(vocab, E, hidden, nn, gemm="f16x2", numeric=numeric, dropout=dropout, seed=7, reduction=reduction,
+    m = _hip_engine(vocab, E, hidden, nn, gemm="f16x2", numeric=numeric, dropout=dropout, seed=7, reduction=reduction,
                 use_linear=flags[0], use_mf=flags[1], use_dnn=flags[2])
     assert bool(m.planes) == expect_planes
     m.load_oracle_params(p)
@@ -385,7 +385,7 @@ def test_non_normalising_optimizers_on_the_planes_path(name, lr):
     from mi355x_rec.engine import OptimizerSpec
     hidden, B = [512, 256, 128], 1024
     p, ids, x, y = make_problem(SEED, VOCAB3, 64, hidden, B)
-    m = _engine(VOCAB3, 64, hidden, gemm="f16x2", optimizer=OptimizerSpec(name, lr))
+    m = _hip_engine(VOCAB3, 64, hidden, gemm="f16x2", optimizer=OptimizerSpec(name, lr))
     assert m.planes
     m.load_oracle_params(p)
     st = O.TrainState(p, OO.Hyper(name, lr))
@@ -452,7 +452,7 @@ def test_full_size_gradients():
     the device made from the engine's own tables (the rows and dense variables as they were before the step); the bar's
     second term from the same code in torch fp32."""
     F, V, E, B = 26, 1_000_000, 64, 65536
-    m = _engine([V] * F, E, [512, 256, 128], gemm="f16x2")
+    m = _hip_engine([V] * F, E, [512, 256, 128], gemm="f16x2")
     g = torch.Generator(device="cuda"); g.manual_seed(1)
     m.init_variables(g, lin_scale=1e-3)
     for i in range(len(m.layers)):

@@ -13,26 +13,12 @@ import torch
 
 from oracle import deepfm as O
 from oracle import optimizers as OO
-from tests.util import (dev, dropout_mask, exact_workspace, guarded_nan, guards_intact, max_err_scaled,
+from tests.util import (_chk, _p, _st, dev, dropout_mask, exact_workspace, guarded_nan, guards_intact, max_err_scaled,
                         workspace_surroundings_intact)
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
-
-
-def _st():
-    from mi355x_rec import _lib
-    return _lib.cur_stream()
-
-
-def _chk(rc, what="call"):
-    from mi355x_rec import _lib
-    _lib.check(rc, what)
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 def test_single_hip_runtime(lib):

@@ -13,19 +13,10 @@ import torch
 
 from oracle import deepfm as O
 from oracle import optimizers as OO
-from tests.util import dev, dropout_mask, make_problem, max_err_scaled
+from tests.cases import ML100K_VOCAB, _hip_engine
+from tests.util import _compare_vars, _device_relu_masks, dev, dropout_mask, make_problem, max_err_scaled
 
 pytestmark = pytest.mark.gpu
-
-ML100K_VOCAB = [2, 2, 7, 2, 2, 2, 2, 2, 2, 2, 2, 3, 2, 2000, 2, 2, 50, 8, 2, 2, 2, 2, 1000, 2, 2, 1000]  # sorted order
-
-
-def _engine(vocab, E, hidden, n_numeric=0, **kw):
-    from mi355x_rec.engine import DeepFM, OptimizerSpec
-    opt = kw.pop("optimizer", OptimizerSpec("Adam", 0.001))
-    kw.setdefault("catchup", "exact")       # (the library's default is "bounded": the tests that mean it say so)
-    return DeepFM(vocab, n_numeric=n_numeric, embedding_size=E, hidden_units=hidden, optimizer=opt, **kw)
-
 
 CONFIGS = [
     # vocab, E, hidden, B, n_numeric
@@ -40,7 +31,7 @@ CONFIGS = [
 @pytest.mark.parametrize("vocab,E,hidden,B,nn", CONFIGS)
 def test_forward_logits_and_loss(vocab, E, hidden, B, nn):
     p, ids, x, y = make_problem(1, vocab, E, hidden, B, n_numeric=nn)
-    m = _engine(vocab, E, hidden, nn)
+    m = _hip_engine(vocab, E, hidden, nn)
     m.load_oracle_params(p)
     loss, logits = m.loss(dev(ids), dev(y), dev(x))
     p64 = p.astype(np.float64)
@@ -57,7 +48,7 @@ def test_component_flags(flags):
     ul, um, ud = flags
     vocab, E, hidden, B = [9, 13, 5, 6], 8, [16, 8], 64
     p, ids, x, y = make_problem(2, vocab, E, hidden, B, use_dnn=ud)
-    m = _engine(vocab, E, hidden, use_linear=ul, use_mf=um, use_dnn=ud)
+    m = _hip_engine(vocab, E, hidden, use_linear=ul, use_mf=um, use_dnn=ud)
     m.load_oracle_params(p)
     st = O.TrainState(p, OO.Hyper("Adam", 0.001))
     for _ in range(3):
@@ -73,36 +64,6 @@ def test_model_fn_errors():
         DeepFM([], n_numeric=0)
     with pytest.raises(ValueError, match="At least 1 of linear, mf or dnn"):
         DeepFM([3, 4], use_linear=False, use_mf=False, use_dnn=False)
-
-
-def _compare_vars(m, p, atol):
-    g = m.export_numpy()
-    for f in range(len(p.emb)):
-        if g["emb"] is not None:
-            assert np.max(np.abs(g["emb"][f] - p.emb[f])) < atol, ("emb", f)
-        if g["lin_w"] is not None:
-            assert np.max(np.abs(g["lin_w"][f] - p.lin_w[f])) < atol, ("lin_w", f)
-    for i, (k, b) in enumerate(g["mlp"]):
-        assert np.max(np.abs(k - p.mlp[i][0])) < atol, ("kernel", i)
-        assert np.max(np.abs(b - p.mlp[i][1])) < atol, ("bias", i)
-    assert abs(g["lin_bias"][0] - p.lin_bias[0]) < atol
-    if "num_emb" in g:
-        assert np.max(np.abs(g["num_emb"] - p.num_emb)) < atol
-        assert np.max(np.abs(g["lin_num"] - p.lin_num)) < atol
-
-
-def _device_relu_masks(m, B):
-    """Which hidden units the device's last train step let through (activation > 0), per hidden layer: read from the
-    stored activations — fp32, or the planes where a layer's output exists as planes only."""
-    out = []
-    for i, h in enumerate(m.hidden):
-        if i in m._acts_in_planes:
-            a = torch.empty(B, h, device="cuda")
-            m.k.mi_merge_rows(m._pl["x%dp" % (i + 1)].struct, B, h, a, h)
-        else:
-            a = m._ws["act%d" % i][:B * h].view(B, h)
-        out.append((a > 0).cpu().numpy())
-    return out
 
 
 # Multi-step Adam trajectories amplify last-bit differences: a hidden unit whose pre-activation is 0 to within the
@@ -129,7 +90,7 @@ def test_adam_training_matches_oracle(vocab, E, hidden, B, nn, gemm):
     # level, which the forward tests pin on the final weights of other trajectories.
     logit_tol, var_atol = 5e-5, 2e-6
     p, ids, x, y = make_problem(3, vocab, E, hidden, B, n_numeric=nn)
-    m = _engine(vocab, E, hidden, nn, gemm=gemm, catchup=catchup)
+    m = _hip_engine(vocab, E, hidden, nn, gemm=gemm, catchup=catchup)
     if gemm == "fp32":
         m.GAP_SORT_MIN = 1               # also exercise the sort-rows-by-staleness path of the catch-up
     m.load_oracle_params(p)
@@ -169,7 +130,7 @@ CONFIG3_SAFE_SEED = 319
 def test_config3_shape_trajectory_is_tight(gemm, catchup):
     vocab, E, hidden, B = [40 + 3 * i for i in range(26)], 64, [512, 256, 128], 64
     p, ids, x, y = make_problem(CONFIG3_SAFE_SEED, vocab, E, hidden, B)
-    m = _engine(vocab, E, hidden, gemm=gemm, catchup=catchup)
+    m = _hip_engine(vocab, E, hidden, gemm=gemm, catchup=catchup)
     assert m.planes == (gemm == "f16x2")
     m.load_oracle_params(p)
     st = O.TrainState(p, OO.Hyper("Adam", 0.001))
@@ -193,7 +154,7 @@ def test_other_optimizers_training(name, lr):
     from mi355x_rec.engine import OptimizerSpec
     vocab, E, hidden, B = [9, 13, 5, 6], 8, [16, 8], 64
     p, ids, x, y = make_problem(4, vocab, E, hidden, B)
-    m = _engine(vocab, E, hidden, optimizer=OptimizerSpec(name, lr))
+    m = _hip_engine(vocab, E, hidden, optimizer=OptimizerSpec(name, lr))
     m.load_oracle_params(p)
     st = O.TrainState(p, OO.Hyper(name, lr))
     for _ in range(3):
@@ -208,7 +169,7 @@ def test_dropout_training_step_matches_oracle_with_same_mask():
     host and handed to the oracle, so both sides drop the same units."""
     vocab, E, hidden, B = [9, 13, 5, 6], 8, [32, 16], 128
     p, ids, x, y = make_problem(5, vocab, E, hidden, B)
-    m = _engine(vocab, E, hidden, dropout=0.25, seed=7)
+    m = _hip_engine(vocab, E, hidden, dropout=0.25, seed=7)
     m.load_oracle_params(p)
     st = O.TrainState(p, OO.Hyper("Adam", 0.001))
     for _ in range(2):
@@ -223,7 +184,7 @@ def test_sum_reduction_head():
     """canned estimators: loss_reduction=SUM."""
     vocab, E, hidden, B = [9, 13, 5], 4, [8], 40
     p, ids, x, y = make_problem(6, vocab, E, hidden, B)
-    m = _engine(vocab, E, hidden, reduction="sum")
+    m = _hip_engine(vocab, E, hidden, reduction="sum")
     m.load_oracle_params(p)
     loss, logits = m.loss(dev(ids), dev(y))
     c = O.forward(p.astype(np.float64), ids)
@@ -256,7 +217,7 @@ def test_full_size_properties():
     pairwise-dot identity on sampled examples, the loss falls over a few steps, only touched rows
     change, and a replay from the same state gives the same bits (determinism)."""
     F, V, E, B = 26, 1_000_000, 64, 65536
-    m = _engine([V] * F, E, [512, 256, 128])
+    m = _hip_engine([V] * F, E, [512, 256, 128])
     g = torch.Generator(device="cuda"); g.manual_seed(1)
     m.init_variables(g, lin_scale=1e-3)
     ids = torch.randint(0, V, (B, F), device="cuda", dtype=torch.int32, generator=g)
@@ -333,7 +294,7 @@ def test_config4_full_size_properties():
     model shape with small vocabularies is tests/test_canned_parity.py::test_config4_shape_small_vocab)."""
     from mi355x_rec.engine import OptimizerSpec
     F, V, E, B, ND = 26, 1_000_000, 64, 65536, 13
-    m = _engine([V] * F, E, [512, 256, 128], ND, numeric="raw", use_mf=False, dropout=0.1, reduction="sum",
+    m = _hip_engine([V] * F, E, [512, 256, 128], ND, numeric="raw", use_mf=False, dropout=0.1, reduction="sum",
                 optimizer=OptimizerSpec("Adagrad", 0.05), linear_optimizer=OptimizerSpec("Ftrl", min(0.2, 1 / np.sqrt(F + ND))))
     g = torch.Generator(device="cuda"); g.manual_seed(4)
     m.init_variables(g, lin_scale=1e-3)
@@ -376,7 +337,7 @@ def test_config5_one_rank_share_properties():
     whose element offsets pass 2^31.  Exact-copy gather across the whole table, then the training
     properties."""
     F, V, E, B = 40, 1_250_000, 128, 16384
-    m = _engine([V] * F, E, [512, 256, 128])
+    m = _hip_engine([V] * F, E, [512, 256, 128])
     assert m.table.numel() * 4 > 2 ** 34 and m.table.numel() > 2 ** 32
     g = torch.Generator(device="cuda"); g.manual_seed(5)
     # row-dependent contents without a 25 GB random fill: value = hash-like function of (row, col)
@@ -429,7 +390,7 @@ def test_graph_train_step_replays_the_eager_step_bitwise(vocab, E, hidden, B):
     p, ids, x, y = make_problem(9, vocab, E, hidden, B)
     ms = []
     for _ in range(2):
-        m = _engine(vocab, E, hidden, dropout=0.25, seed=5, optimizer=OptimizerSpec("Adam", 0.001))
+        m = _hip_engine(vocab, E, hidden, dropout=0.25, seed=5, optimizer=OptimizerSpec("Adam", 0.001))
         m.load_oracle_params(p)
         ms.append(m)
     eager, graph = ms
@@ -459,7 +420,7 @@ def test_graph_train_step_with_column_subsets_and_two_batch_shapes_replays_the_e
               field_dims=[8, 3, 0, 4], wide_fields=[True, False, True, True], deep_numeric=[True, False, True], wide_numeric=[False, True, True])
     ms = []
     for _ in range(2):
-        m = _engine(vocab, E, hidden, nn, dropout=0.25, seed=5, **kw)
+        m = _hip_engine(vocab, E, hidden, nn, dropout=0.25, seed=5, **kw)
         g = torch.Generator(device="cuda"); g.manual_seed(3)
         m.init_variables(g, lin_scale=1e-2)
         ms.append(m)
@@ -490,7 +451,7 @@ def test_layer_summaries_after_a_replay_know_what_the_captured_step_kept_on_the_
     an eval forward (which writes every layer) show it again."""
     from mi355x_rec.engine import OptimizerSpec
     vocab, E, hidden, B = [50, 30, 20, 40], 64, [256, 128], 4096
-    m = _engine(vocab, E, hidden, dropout=0.1, seed=5, optimizer=OptimizerSpec("Adam", 0.001))
+    m = _hip_engine(vocab, E, hidden, dropout=0.1, seed=5, optimizer=OptimizerSpec("Adam", 0.001))
     g = torch.Generator(device="cuda"); g.manual_seed(3)
     m.init_variables(g, lin_scale=1e-2)
     rng = np.random.default_rng(2)
@@ -522,7 +483,7 @@ def test_graph_train_step_with_numeric_columns_replays_the_eager_step_bitwise(ki
               linear_optimizer=OptimizerSpec("Ftrl", 0.18)) if raw else dict(optimizer=OptimizerSpec("Adam", 0.001))
     ms = []
     for _ in range(2):
-        m = _engine(vocab, E, hidden, nn, dropout=0.25, seed=5, **kw)
+        m = _hip_engine(vocab, E, hidden, nn, dropout=0.25, seed=5, **kw)
         g = torch.Generator(device="cuda"); g.manual_seed(3)
         m.init_variables(g, lin_scale=1e-2)
         ms.append(m)
@@ -551,7 +512,7 @@ def test_captured_step_has_no_memset_nodes():
     from mi355x_rec.engine import OptimizerSpec
     vocab, B = ML100K_VOCAB, 1024
     p, ids, x, y = make_problem(23, vocab, 4, [16, 16], B)
-    m = _engine(vocab, 4, [16, 16], dropout=0.1, seed=3, optimizer=OptimizerSpec("Adam", 0.001))
+    m = _hip_engine(vocab, 4, [16, 16], dropout=0.1, seed=3, optimizer=OptimizerSpec("Adam", 0.001))
     m.load_oracle_params(p)
     di, dy = dev(ids), dev(y)
     m.train_step(di, dy)
@@ -594,7 +555,7 @@ def test_graph_is_recaptured_when_its_buffers_moved():
     p, ids, x, y = make_problem(21, vocab, E, hidden, B)
     ms = []
     for _ in range(2):
-        m = _engine(vocab, E, hidden, dropout=0.1, seed=3, optimizer=OptimizerSpec("Adam", 0.001))
+        m = _hip_engine(vocab, E, hidden, dropout=0.1, seed=3, optimizer=OptimizerSpec("Adam", 0.001))
         m.load_oracle_params(p)
         ms.append(m)
     eager, graph = ms
@@ -636,7 +597,7 @@ def test_presorted_next_batch_is_bitwise_the_plain_step(vocab, E, hidden, B):
     p, ids0, x, y = make_problem(13, vocab, E, hidden, B)
     ms = []
     for _ in range(2):
-        m = _engine(vocab, E, hidden, dropout=0.1, seed=7, optimizer=OptimizerSpec("Adam", 0.001))
+        m = _hip_engine(vocab, E, hidden, dropout=0.1, seed=7, optimizer=OptimizerSpec("Adam", 0.001))
         m.load_oracle_params(p)
         ms.append(m)
     plain, pre = ms
@@ -669,7 +630,7 @@ def test_bench_configuration_at_full_size_is_bitwise_the_plain_sequence(catchup)
     F, V, E, B = 26, 1_000_000, 64, 65536
     ms = []
     for _ in range(2):
-        m = _engine([V] * F, E, [512, 256, 128], dropout=0.1, seed=11, optimizer=OptimizerSpec("Adam", 0.001), catchup=catchup)
+        m = _hip_engine([V] * F, E, [512, 256, 128], dropout=0.1, seed=11, optimizer=OptimizerSpec("Adam", 0.001), catchup=catchup)
         g = torch.Generator(device="cuda"); g.manual_seed(7)
         m.init_variables(g, lin_scale=1e-3)
         ms.append(m)
@@ -708,7 +669,7 @@ def test_last_hidden_layer_inside_the_fused_head_launch_matches_the_oracle():
     layer_summaries() sees that layer's output; after a fused step the entry is left out rather than stale."""
     vocab, E, hidden, B = [50, 40, 30, 60, 20, 35, 45, 25], 32, [256, 128], 4096
     p, ids, x, y = make_problem(17, vocab, E, hidden, B)
-    m = _engine(vocab, E, hidden, dropout=0.1, seed=11)
+    m = _hip_engine(vocab, E, hidden, dropout=0.1, seed=11)
     assert m.planes
     m.load_oracle_params(p)
     st = O.TrainState(p, OO.Hyper("Adam", 0.001))

@@ -13,20 +13,10 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import (WS_FILL, dev, dropout_mask, exact_workspace, guarded_nan, guards_intact,
-                        workspace_surroundings_intact)
+from tests.util import (WS_FILL, _chk, _st, dev, dropout_mask, exact_workspace, guarded_nan, guards_intact, planned_splits,
+                        row_rel_err, workspace_surroundings_intact)
 
 pytestmark = pytest.mark.gpu
-
-
-def _st():
-    from mi355x_rec import _lib
-    return _lib.cur_stream()
-
-
-def _chk(rc, what="call"):
-    from mi355x_rec import _lib
-    _lib.check(rc, what)
 
 
 class PB:
@@ -87,36 +77,11 @@ def host_planes(X, keep_positive):
     return np.where(bits == -32768, 0, bits), s
 
 
-def row_rel_err(got, ref):
-    """max over rows of max|got - ref| / rms(ref row)  (rows that are exactly zero must match exactly)"""
-    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
-    rms = np.sqrt(np.mean(ref * ref, 1))
-    err = np.abs(got - ref).max(1)
-    z = rms == 0
-    assert np.all(err[z] == 0)
-    return float((err[~z] / rms[~z]).max()) if (~z).any() else 0.0
-
-
 def rows_spread(rng, M, K, lo_exp=-30):
     """rows whose magnitudes span 2^lo_exp .. 1"""
     X = rng.standard_normal((M, K)).astype(np.float32)
     X *= np.exp2(rng.integers(lo_exp, 1, M)).astype(np.float32)[:, None]
     return X
-
-
-def planned_splits(M, N, K):
-    """Split-K slabs of mi_dense_bwd_weight_planes for one job, restated from the library's two launch plans — wgrad_pl.hip's
-    wgrad_pl_plan (LDS-DMA kernel: N = 128 / 256 / 512; at least 32 k-steps of 16 examples per split, one round of
-    workgroups) and gemm.hip's wgrad_splits (register-staged kernel, every other whole-tile shape; at least four k-tiles
-    of 32 examples per split, about two rounds).  One split: the job is `direct` (the GEMM writes dW itself, no fold)."""
-    cdiv = lambda a, b: -(-a // b)
-    if N in (128, 256, 512) and K % 128 == 0 and M % 16 == 0:
-        tiles_k = cdiv(K, 128)
-        target = (512 if N == 128 else 256) // tiles_k
-        target = max(1, min(target, max(M // 512, 1)))
-        k_per_split = cdiv(cdiv(M, target), 16) * 16
-        return cdiv(M, k_per_split)
-    return max(1, min(1024 // (cdiv(K, 128) * cdiv(N, 128)), cdiv(M, 128), 256))
 
 
 @pytest.mark.parametrize("rows,K", [(1, 16), (5, 104), (300, 1664), (64, 48), (1000, 128), (130, 512), (37, 32)])

@@ -11,71 +11,12 @@ import torch
 from mi355x_rec import _lib
 from oracle import deepfm as O
 from oracle import optimizers as OO
-from tests.test_hip_fused_step import FLAGS, ML100K_VOCAB, _compare_vars, _fresh_ids
-from tests.util import dev, dropout_mask, guarded_nan, guards_intact, make_problem, max_err_scaled
+from tests.cases import (MIXED, ML100K_VOCAB, ORACLE_MEMBERS, STATE, _clones, _fresh, _population, _same_state, _spec,
+                         _spec_engine)
+from tests.util import (_compare_vars, _fresh_ids, dev, dropout_mask, guarded_nan, guards_intact, make_problem,
+                        max_err_scaled)
 
 pytestmark = pytest.mark.gpu
-
-STATE = ("t_rec", "lin_state", "dense", "d_s0", "d_s1", "last_step")
-
-
-def _spec(E=4, hidden=(16, 16), lr=0.001, beta2=0.999, **kw):
-    return dict(E=E, hidden=list(hidden), lr=lr, beta2=beta2, kw=kw)
-
-
-# the mixed list of the bit tests: members differ in everything a fused step accepts
-MIXED = ([_spec(), _spec(16, [64, 64, 32]), _spec(8, [32]), _spec(12, [32, 16])] +
-         [_spec(8, [16, 8], use_linear=ul, use_mf=um, use_dnn=ud) for ul, um, ud in FLAGS] +
-         [_spec(8, [16, 8], activation=a) for a in ("relu", "sigmoid", "tanh", None)] +
-         [_spec(4, [16, 16], dropout=d, seed=11 + i) for i, d in enumerate((0.0, 0.1, 0.25))] +
-         [_spec(4, [16, 16], lr=lr) for lr in (0.001, 0.003, 0.01)] +
-         [_spec(8, [32, 16], beta2=0.99, dropout=0.1, seed=5), _spec(4, [16], reduction="sum"),
-          _spec(16, [64, 32], lr=0.005, dropout=0.25, activation="tanh", seed=77)])
-
-
-def _engine(spec, vocab=ML100K_VOCAB):
-    from mi355x_rec.engine import DeepFM, OptimizerSpec
-    return DeepFM(vocab, embedding_size=spec["E"], hidden_units=spec["hidden"], catchup="exact",
-                  optimizer=OptimizerSpec("Adam", spec["lr"], beta2=spec["beta2"]), **spec["kw"])
-
-
-def _fresh(specs, vocab=ML100K_VOCAB):
-    """engines of `specs` with variables drawn per member, and the state_dicts they start from"""
-    out = []
-    for i, s in enumerate(specs):
-        m = _engine(s, vocab)
-        g = torch.Generator(device="cuda")
-        g.manual_seed(100 + i)
-        m.init_variables(g, lin_scale=0.05)
-        out.append(m)
-    return out, [m.state_dict() for m in out]
-
-
-def _clones(specs, sds, vocab=ML100K_VOCAB):
-    out = []
-    for s, sd in zip(specs, sds):
-        m = _engine(s, vocab)
-        m.load_state_dict(sd)
-        out.append(m)
-    return out
-
-
-def _same_state(a, b):
-    for name in STATE:
-        x, z = getattr(a, name), getattr(b, name)
-        if x is None and z is None:
-            continue
-        if not torch.equal(x, z):
-            return name
-    return None
-
-
-def _population(engines, sweep_blocks=0):
-    from mi355x_rec.population import FusedPopulation
-    pop = FusedPopulation(engines)
-    pop.SWEEP_BLOCKS = sweep_blocks
-    return pop
-
 
 def _guarded_step(pop, ids, y, B):
     gs, loss = guarded_nan(len(pop))
@@ -131,10 +72,6 @@ def test_bits_do_not_depend_on_neighbours_position_or_sweep_grid():
             assert _same_state(group[j], first[i]) is None, (blocks, members, i)
 
 
-# (seed of make_problem, E, hidden, learning rate): every hidden pre-activation of the oracle stays >= 1e-6 from 0 over the
-# five steps on the batches of default_rng(300) (found on the CPU: 3.1e-4, 2.2e-5, 2.0e-5, 7.9e-5, 1.1e-4, 1.8e-5; asserted)
-ORACLE_MEMBERS = [(300, 4, [16, 16], 0.001), (301, 4, [16, 16], 0.01), (308, 16, [64, 64, 32], 0.001), (302, 8, [32], 0.003),
-                  (304, 4, [16, 16], 0.003), (305, 12, [32, 16], 0.001)]
 # two more without the margin, as the existing dropout and activation tests: (seed, E, hidden, lr, engine keywords)
 ORACLE_EXTRA = [(306, 4, [16, 16], 0.001, dict(dropout=0.25, seed=7)), (307, 8, [32], 0.001, dict(activation="tanh"))]
 
@@ -146,7 +83,7 @@ def test_members_match_the_oracle():
     engines, params, states = [], [], []
     for seed, E, hidden, lr, kw in members:
         p = make_problem(seed, ML100K_VOCAB, E, hidden, B)[0]
-        m = _engine(_spec(E, hidden, lr, **kw))
+        m = _spec_engine(_spec(E, hidden, lr, **kw))
         m.load_oracle_params(p)
         engines.append(m)
         params.append(p)
@@ -289,9 +226,9 @@ OUTSIDE = [  # test_limits_through_the_entry's "outside" rows: (vocab, E, hidden
 
 @pytest.mark.parametrize("vocab,E,hidden,B,inside,who", OUTSIDE)
 def test_members_over_a_limit_are_refused_through_the_entry(vocab, E, hidden, B, inside, who):
-    good = _engine(_spec(*(inside or (4, [8]))), [3] * 8 if inside is None else vocab)
-    bad = _engine(_spec(E, hidden), vocab)
-    engines = [good, bad] if inside else [bad, _engine(_spec(E, hidden), vocab)]
+    good = _spec_engine(_spec(*(inside or (4, [8]))), [3] * 8 if inside is None else vocab)
+    bad = _spec_engine(_spec(E, hidden), vocab)
+    engines = [good, bad] if inside else [bad, _spec_engine(_spec(E, hidden), vocab)]
     pop = _population([good])
     before = _snapshot(engines)
     with pytest.raises(_lib.MiError, match=r"\(-2\): train_group_plan: member %d: train_step_fused: " % who):
@@ -307,7 +244,7 @@ def test_members_over_a_limit_are_refused_through_the_entry(vocab, E, hidden, B,
 def test_other_refusals_through_the_entry():
     from mi355x_rec.engine import OptimizerSpec
     vocab, B = [9, 13, 5], 16
-    engines = [_engine(_spec(4, [8]), vocab) for _ in range(3)]
+    engines = [_spec_engine(_spec(4, [8]), vocab) for _ in range(3)]
     k = engines[0].k
     pop = _population(engines)
     rng = np.random.default_rng(3)

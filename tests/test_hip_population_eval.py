@@ -18,9 +18,9 @@ import torch
 from mi355x_rec import _lib
 from oracle import deepfm as O
 from oracle.metrics import BinaryMetrics, auc_thresholds
-from tests.test_hip_fused_step import ML100K_VOCAB, _fresh_ids
-from tests.test_hip_population import MIXED, ORACLE_MEMBERS, STATE, _clones, _engine, _fresh, _population, _same_state, _spec
-from tests.util import GUARD, dev, guarded_nan, guards_intact, make_problem, max_err_scaled
+from tests.cases import (MIXED, ML100K_VOCAB, ORACLE_MEMBERS, STATE, _clones, _fresh, _population, _same_state, _spec,
+                         _spec_engine)
+from tests.util import GUARD, _fresh_ids, dev, guarded_nan, guards_intact, make_problem, max_err_scaled
 
 pytestmark = pytest.mark.gpu
 
@@ -292,7 +292,7 @@ def test_logits_and_metrics_match_the_oracle():
     ids, y, side = _oracle_side(301)
     engines = []
     for s in side:
-        m = _engine(_spec(s["E"], s["hidden"], s["lr"]))
+        m = _spec_engine(_spec(s["E"], s["hidden"], s["lr"]))
         m.load_oracle_params(s["p"])
         engines.append(m)
     pop = _population(engines)

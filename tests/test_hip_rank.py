@@ -15,13 +15,13 @@ import torch
 
 from mi355x_rec.engine import DeepFM, OptimizerSpec
 from oracle import deepfm as O
-from tests.util import make_problem, max_err_scaled
+from tests.cases import RANK_CASES, VOCAB26
+from tests.util import host_topk, make_problem, max_err_scaled
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "recommender-tensorflow_amd")
-VOCAB26 = [30 + 7 * i for i in range(26)]
 Q5 = [0, 1, 2, 3, 4]
 
 
@@ -63,32 +63,7 @@ def _run(m, parts, qid, cid, qx, cx, qf, k=10, exclude=None):
     return m.top_k(_t(qid), _t(cid), qf, k, _t(qx), _t(cx), exclude=exclude, return_scores=True)
 
 
-CASES = [
-    # (E, hidden, activation, flags (linear, mf, dnn), U, I)
-    (4, [16, 16], "relu", (True, True, True), 37, 1682),
-    (4, [16, 16], "relu", (True, True, True), 1, 70001),
-    (64, [512, 256, 128], "relu", (True, True, True), 37, 5),
-    (64, [512, 256, 128], "tanh", (True, True, True), 1, 33),
-    (64, [24, 8], "tanh", (True, True, True), 33, 45),
-    (4, [24, 8], "sigmoid", (True, True, True), 5, 1),
-    (4, [16, 16], "identity", (True, True, True), 40, 70),
-    (64, [], "relu", (True, True, True), 37, 40),
-    (4, [], "relu", (True, True, True), 3, 7),
-    (64, [64, 32], "sigmoid", (True, True, True), 35, 66),
-    (4, [16, 16], "relu", (False, True, True), 20, 30),
-    (4, [16, 16], "relu", (True, False, True), 20, 30),
-    (4, [16, 16], "relu", (True, True, False), 20, 30),
-    (4, [16, 16], "relu", (True, False, False), 20, 30),
-    (64, [128], "relu", (False, False, True), 9, 50),
-    # MFMA widths that are not multiples of 32, and the <2,2> / <4,4> register tilings
-    (64, [512, 200, 48], "relu", (True, True, True), 35, 41),
-    (16, [96, 64], "tanh", (True, True, True), 33, 70),
-    (16, [128, 100, 40], "sigmoid", (True, True, True), 34, 67),
-    (8, [40, 33, 1], "relu", (True, True, True), 3, 29),
-]
-
-
-@pytest.mark.parametrize("E,hidden,act,flags,U,I", CASES)
+@pytest.mark.parametrize("E,hidden,act,flags,U,I", RANK_CASES)
 def test_pair_scores_match_oracle(E, hidden, act, flags, U, I):
     use_linear, use_mf, use_dnn = flags
     p, _, _, _ = make_problem(3, VOCAB26, E, hidden, 4, use_dnn=use_dnn)
@@ -147,22 +122,6 @@ def test_pair_scores_canned_wide_and_deep():
     assert max_err_scaled(scores.cpu().numpy(), ref) < 1e-5
 
 
-def _host_topk(scores, k, excl_rows):
-    """(-score, index) order with NaN last, excluded candidates removed, -1 / -inf padding; a -0 score comes back as +0
-    (include/mi355x_rec.h)"""
-    U, I = scores.shape
-    out_s = np.full((U, k), -np.inf, np.float32)
-    out_i = np.full((U, k), -1, np.int32)
-    for u in range(U):
-        ok = np.setdiff1d(np.arange(I), np.asarray(sorted(excl_rows[u]), np.int64))
-        s = scores[u, ok]
-        key = np.where(np.isnan(s), np.inf, -s)
-        order = np.lexsort((ok, key))[:k]
-        out_s[u, :len(order)] = s[order] + np.float32(0.0)
-        out_i[u, :len(order)] = ok[order]
-    return out_s, out_i
-
-
 @pytest.mark.parametrize("k,I", [(1, 300), (10, 300), (100, 300), (256, 300), (100, 50), (256, 131)])
 def test_selection_bit_for_bit(k, I):
     p, _, _, _ = make_problem(7, VOCAB26, 4, [16, 16], 4)
@@ -177,7 +136,7 @@ def test_selection_bit_for_bit(k, I):
     excl[5] = list(range(I))                    # every candidate excluded
     excl[6] = []
     score, idx, scores = _run(m, parts, qid, cid, qx, cx, Q5, k=k, exclude=excl)
-    s_ref, i_ref = _host_topk(scores.cpu().numpy(), k, excl)
+    s_ref, i_ref = host_topk(scores.cpu().numpy(), k, excl)
     got_s, got_i = score.cpu().numpy(), idx.cpu().numpy()
     assert np.array_equal(got_i, i_ref)
     assert np.array_equal(got_s.view(np.uint32), s_ref.view(np.uint32))
@@ -199,7 +158,7 @@ def test_selection_mfma_path_bit_for_bit():
     parts, qid, cid, qx, cx = _sides(rng, VOCAB26, Q5, 40, 700)
     excl = [sorted(set(rng.integers(0, 700, 50).tolist())) for _ in range(40)]
     score, idx, scores = _run(m, parts, qid, cid, qx, cx, Q5, k=100, exclude=excl)
-    s_ref, i_ref = _host_topk(scores.cpu().numpy(), 100, excl)
+    s_ref, i_ref = host_topk(scores.cpu().numpy(), 100, excl)
     assert np.array_equal(idx.cpu().numpy(), i_ref)
     assert np.array_equal(score.cpu().numpy().view(np.uint32), s_ref.view(np.uint32))
 
@@ -218,7 +177,7 @@ def test_selection_under_heavy_survivor_traffic(k, U, I):
     cid = np.arange(I, dtype=np.int32).reshape(I, 1)
     excl = [sorted(set(rng.integers(I - 3 * k, I, k // 2).tolist())) for _ in range(U)]
     s1, i1, scores = m.top_k(_t(qid), _t(cid), [0], k, exclude=excl, return_scores=True)
-    s_ref, i_ref = _host_topk(scores.cpu().numpy(), k, excl)
+    s_ref, i_ref = host_topk(scores.cpu().numpy(), k, excl)
     assert np.array_equal(i1.cpu().numpy(), i_ref)
     assert np.array_equal(s1.cpu().numpy().view(np.uint32), s_ref.view(np.uint32))
     for _ in range(2):

@@ -16,19 +16,15 @@ from mi355x_rec import _lib, engine
 from mi355x_rec.engine import DeepFM
 from mi355x_rec.predictor import EnsemblePredictor, Predictor
 from oracle import deepfm as O
-from tests.util import guarded_nan, guards_intact, make_problem, max_err_scaled
+from tests.cases import VOCAB26
+from tests.util import _fake_sweep, dev, guarded_nan, guards_intact, host_topk, make_problem, max_err_scaled
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-VOCAB26 = [30 + 7 * i for i in range(26)]
 Q5 = [0, 1, 2, 3, 4]
 # (E, hidden, activation, (linear, mf, dnn)): the three kinds of member the group kernel takes
 MIXED = [(4, [16, 16], "relu", (True, True, True)), (8, [64, 16], "tanh", (False, True, True)), (4, [], "relu", (True, True, False))]
-
-
-def _t(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _ids(rng, U, I):
@@ -58,7 +54,7 @@ def mixed_run(mixed):
     rng = np.random.default_rng(5)
     qid, cid = _ids(rng, 70, 333)
     engines = [m for m, _ in mixed]
-    top_s, top_i, scores, member_scores = engine.top_k_group(engines, _t(qid), _t(cid), Q5, 10, return_scores=True,
+    top_s, top_i, scores, member_scores = engine.top_k_group(engines, dev(qid), dev(cid), Q5, 10, return_scores=True,
                                                              return_member_scores=True)
     return qid, cid, top_s.cpu(), top_i.cpu(), scores.cpu(), member_scores.cpu()
 
@@ -67,7 +63,7 @@ def test_member_scores_are_the_members_own_bits_and_the_mean_is_fp32_in_member_o
     qid, cid, top_s, top_i, scores, member_scores = mixed_run
     assert tuple(member_scores.shape) == (3, 70, 333) and tuple(scores.shape) == (70, 333)
     for i, (m, _) in enumerate(mixed):
-        own = m.top_k(_t(qid), _t(cid), Q5, 10, return_scores=True)[2].cpu()
+        own = m.top_k(dev(qid), dev(cid), Q5, 10, return_scores=True)[2].cpu()
         assert torch.equal(member_scores[i].view(torch.int32), own.view(torch.int32)), i
     z = member_scores
     want = ((z[0] + z[1]) + z[2]) / torch.full_like(z[0], 3.0)
@@ -91,21 +87,6 @@ def test_mean_scores_match_the_fp64_oracle(mixed, mixed_run):
     assert err < 1e-5, err
 
 
-def _host_topk(scores, k, excl_rows):
-    """The header's rule (include/mi355x_rec.h): score descending, equal scores by ascending index, NaN below every number,
-    excluded candidates removed, index -1 / score -inf past the eligible ones; a -0 score comes back as +0"""
-    U, I = scores.shape
-    out_s = np.full((U, k), -np.inf, np.float32)
-    out_i = np.full((U, k), -1, np.int32)
-    for u in range(U):
-        ok = np.setdiff1d(np.arange(I), np.asarray(sorted(excl_rows[u]), np.int64))
-        s = scores[u, ok]
-        order = np.lexsort((ok, np.where(np.isnan(s), np.inf, -s)))[:k]
-        out_s[u, :len(order)] = s[order] + np.float32(0.0)
-        out_i[u, :len(order)] = ok[order]
-    return out_s, out_i
-
-
 @pytest.mark.parametrize("k,I", [(1, 300), (10, 300), (256, 300), (1, 131), (10, 131), (256, 131)])
 def test_selection_bit_for_bit(mixed, k, I):
     engines = [m for m, _ in mixed[:2]]
@@ -117,10 +98,10 @@ def test_selection_bit_for_bit(mixed, k, I):
     excl = [sorted(set(rng.integers(0, I, rng.integers(0, I // 3 + 1)).tolist())) for _ in range(U)]
     excl[5] = list(range(I))                    # every candidate excluded
     excl[6] = []
-    score, idx, scores = engine.top_k_group(engines, _t(qid), _t(cid), Q5, k, exclude=excl, return_scores=True)
+    score, idx, scores = engine.top_k_group(engines, dev(qid), dev(cid), Q5, k, exclude=excl, return_scores=True)
     sc = scores.cpu().numpy()
     assert np.array_equal(sc[:, I // 2].view(np.uint32), sc[:, 3].view(np.uint32))
-    s_ref, i_ref = _host_topk(sc, k, excl)
+    s_ref, i_ref = host_topk(sc, k, excl)
     got_s, got_i = score.cpu().numpy(), idx.cpu().numpy()
     assert np.array_equal(got_i, i_ref)
     assert np.array_equal(got_s.view(np.uint32), s_ref.view(np.uint32))
@@ -128,7 +109,7 @@ def test_selection_bit_for_bit(mixed, k, I):
     # the same selection through the CSR form of the exclusions, without the optional outputs
     off = np.concatenate([[0], np.cumsum([len(r) for r in excl])]).astype(np.int64)
     ix = np.asarray([c for r in excl for c in r], np.int32)
-    s2, i2 = engine.top_k_group(engines, _t(qid), _t(cid), Q5, k, exclude=(off, ix))
+    s2, i2 = engine.top_k_group(engines, dev(qid), dev(cid), Q5, k, exclude=(off, ix))
     assert np.array_equal(i2.cpu().numpy(), got_i) and np.array_equal(s2.cpu().numpy().view(np.uint32), got_s.view(np.uint32))
 
 
@@ -147,12 +128,12 @@ def test_selection_with_merges_inside_the_candidate_loop():
     qid = rng.integers(0, 7, (U, 1)).astype(np.int32)
     cid = np.arange(I, dtype=np.int32).reshape(I, 1)
     excl = [sorted(set(rng.integers(I - 3 * k, I, k // 2).tolist())) for _ in range(U)]
-    s1, i1, scores = engine.top_k_group(engines, _t(qid), _t(cid), [0], k, exclude=excl, return_scores=True)
-    s_ref, i_ref = _host_topk(scores.cpu().numpy(), k, excl)
+    s1, i1, scores = engine.top_k_group(engines, dev(qid), dev(cid), [0], k, exclude=excl, return_scores=True)
+    s_ref, i_ref = host_topk(scores.cpu().numpy(), k, excl)
     assert np.array_equal(i1.cpu().numpy(), i_ref)
     assert np.array_equal(s1.cpu().numpy().view(np.uint32), s_ref.view(np.uint32))
     for _ in range(2):
-        s2, i2 = engine.top_k_group(engines, _t(qid), _t(cid), [0], k, exclude=excl)
+        s2, i2 = engine.top_k_group(engines, dev(qid), dev(cid), [0], k, exclude=excl)
         assert torch.equal(i1, i2) and torch.equal(s1.view(torch.int32), s2.view(torch.int32))
 
 
@@ -161,15 +142,15 @@ def test_one_member_is_that_members_top_k(mixed):
     rng = np.random.default_rng(8)
     qid, cid = _ids(rng, 45, 200)
     excl = [sorted(set(rng.integers(0, 200, 20).tolist())) for _ in range(45)]
-    s1, i1, sc1 = m.top_k(_t(qid), _t(cid), Q5, 10, exclude=excl, return_scores=True)
-    s2, i2, sc2, ms = engine.top_k_group([m], _t(qid), _t(cid), Q5, 10, exclude=excl, return_scores=True, return_member_scores=True)
+    s1, i1, sc1 = m.top_k(dev(qid), dev(cid), Q5, 10, exclude=excl, return_scores=True)
+    s2, i2, sc2, ms = engine.top_k_group([m], dev(qid), dev(cid), Q5, 10, exclude=excl, return_scores=True, return_member_scores=True)
     assert torch.equal(i1, i2) and torch.equal(s1.view(torch.int32), s2.view(torch.int32))
     assert torch.equal(sc1.view(torch.int32), sc2.view(torch.int32)) and torch.equal(sc1.view(torch.int32), ms[0].view(torch.int32))
 
 
 def _raw_members(engines, qid, cid):
     """the mi_rank_member_t array engine.top_k_group would pass, and what keeps its tensors alive"""
-    sides, U, I, _ = engines[0]._top_k_check(_t(qid), _t(cid), Q5, 10, None, None)
+    sides, U, I, _ = engines[0]._top_k_check(dev(qid), dev(cid), Q5, 10, None, None)
     args = [e._top_k_sides(sides) for e in engines]
     ms = (_lib.RankMember * len(engines))()
     for m, e, a in zip(ms, engines, args):
@@ -220,7 +201,6 @@ def test_refusals_write_nothing(mixed):
 
 
 def test_cli_top_and_predictor_recommend_end_to_end(tmp_path):
-    from tests.test_ensemble_cpu import _fake_sweep
     from trainers import _cli, ml_100k, recommend
     from trainers.conf_utils import get_run_config
     trainer, opt = recommend.MODELS["deep_fm"]

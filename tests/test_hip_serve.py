@@ -5,9 +5,6 @@ Fused logits against the fp64 oracle on identical weights (the project's logit c
 head's outputs bit for bit against mi_binary_predictions, the engine's own forward after lazily-updated Adam steps,
 determinism and independence of a request from its neighbours, the entry's limits, and the CLI end to end."""
 import csv
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,20 +13,14 @@ import torch
 from mi355x_rec import _lib
 from mi355x_rec.engine import DeepFM, HipKernels, OptimizerSpec
 from oracle import deepfm as O
-from tests.test_hip_rank import CASES, VOCAB26
-from tests.util import make_problem, max_err_scaled
+from tests.cases import RANK_CASES, VOCAB26
+from tests.util import _run_module, dev, make_problem, max_err_scaled
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "recommender-tensorflow_amd")
 BATCHES = (1, 31, 32, 33, 257, 4096)
-# the model cases of test_hip_rank.CASES (E, hidden, activation, part flags), each once
-MODELS = list(dict.fromkeys((E, tuple(h), a, fl) for E, h, a, fl, _, _ in CASES))
-
-
-def _t(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+# the model cases of tests.cases.RANK_CASES (E, hidden, activation, part flags), each once
+MODELS = list(dict.fromkeys((E, tuple(h), a, fl) for E, h, a, fl, _, _ in RANK_CASES))
 
 
 def _ids(rng, vocab, B):
@@ -47,7 +38,7 @@ def test_fused_logits_match_oracle(E, hidden, act, flags):
     p64 = p.astype(np.float64)
     for B in BATCHES:
         ids = _ids(np.random.default_rng(B), VOCAB26, B)
-        got = m.predict_fused(_t(ids))["logits"].cpu().numpy()[:, 0]
+        got = m.predict_fused(dev(ids))["logits"].cpu().numpy()[:, 0]
         ref = O.forward(p64, ids, use_linear=use_linear, use_mf=use_mf, use_dnn=use_dnn,
                         activation=act if act != "identity" else None)["logits"]
         err = max_err_scaled(got, ref)
@@ -69,7 +60,7 @@ def test_fused_logits_numeric_columns(numeric):
     for B in BATCHES:
         rng = np.random.default_rng(B + 1)
         ids, x = _ids(rng, vocab, B), rng.standard_normal((B, 2)).astype(np.float32)
-        got = m.predict_fused(_t(ids), _t(x))["logits"].cpu().numpy()[:, 0]
+        got = m.predict_fused(dev(ids), dev(x))["logits"].cpu().numpy()[:, 0]
         ref = O.forward(p.astype(np.float64), ids, x.astype(np.float64), use_mf=use_mf, numeric=numeric)["logits"]
         err = max_err_scaled(got, ref)
         print("numeric=%s B=%d err=%.3g" % (numeric, B, err))
@@ -96,7 +87,7 @@ def test_fused_logits_canned_wide_and_deep():
             m.lin_w[slice(*m._field_rows(f))] = 7.0
     for B in BATCHES:
         ids = _ids(np.random.default_rng(B + 2), vocab, B)
-        got = m.predict_fused(_t(ids))["logits"].cpu().numpy()[:, 0]
+        got = m.predict_fused(dev(ids))["logits"].cpu().numpy()[:, 0]
         ref = O.forward(p.astype(np.float64), ids, use_mf=False, wide_fields=wide)["logits"]
         err = max_err_scaled(got, ref)
         print("wide and deep B=%d err=%.3g" % (B, err))
@@ -111,7 +102,7 @@ def test_fused_logits_config3_shape():
     m.load_oracle_params(p)
     for B in BATCHES:
         ids = _ids(np.random.default_rng(B + 3), vocab, B)
-        got = m.predict_fused(_t(ids))["logits"].cpu().numpy()[:, 0]
+        got = m.predict_fused(dev(ids))["logits"].cpu().numpy()[:, 0]
         ref = O.forward(p.astype(np.float64), ids)["logits"]
         err = max_err_scaled(got, ref)
         print("config 3 shape B=%d err=%.3g" % (B, err))
@@ -124,7 +115,7 @@ def test_one_field_fm_is_exactly_zero():
         m = DeepFM(vocab, embedding_size=E, use_linear=False, use_mf=True, use_dnn=False, device="cuda")
         m.table.copy_(torch.randn(1000, E, device="cuda") * 3.0)
         ids = _ids(np.random.default_rng(E), vocab, 333)
-        out = m.predict_fused(_t(ids))
+        out = m.predict_fused(dev(ids))
         assert (out["logits"] == 0).all() and (out["logistic"] == 0.5).all() and (out["class_ids"] == 0).all()
 
 
@@ -134,7 +125,7 @@ def test_head_outputs_are_binary_predictions_bit_for_bit():
     m = DeepFM(VOCAB26, embedding_size=4, hidden_units=[16, 16], device="cuda")
     m.load_oracle_params(p)
     B = 1000
-    out = m.predict_fused(_t(_ids(np.random.default_rng(0), VOCAB26, B)))
+    out = m.predict_fused(dev(_ids(np.random.default_rng(0), VOCAB26, B)))
     x = out["logits"].reshape(-1).contiguous()
     lg = torch.empty(B, 1, device="cuda")
     pr = torch.empty(B, 2, device="cuda")
@@ -157,8 +148,8 @@ def test_fused_matches_engine_forward_after_lazy_adam(E, hidden, catchup):
     for _ in range(4):                          # small batches: most rows sit out most steps (lazy catch-up)
         ids = _ids(rng, vocab, 16)
         y = (rng.random(16) < 0.4).astype(np.uint8)
-        m.train_step(_t(ids), _t(y))
-    q = _t(_ids(rng, vocab, 23 * 61))
+        m.train_step(dev(ids), dev(y))
+    q = dev(_ids(rng, vocab, 23 * 61))
     got = m.predict_fused(q)["logits"].cpu().numpy()[:, 0]         # (no explicit finalize_rows)
     ref = m.predict_logits(q).cpu().numpy()
     err = max_err_scaled(got, ref)
@@ -172,12 +163,12 @@ def test_deterministic_and_independent_of_neighbours(E, hidden):
     m = DeepFM(VOCAB26, embedding_size=E, hidden_units=hidden, device="cuda")
     m.load_oracle_params(p)
     ids = _ids(np.random.default_rng(1), VOCAB26, 33)
-    a = m.predict_fused(_t(ids))
-    b = m.predict_fused(_t(ids))
+    a = m.predict_fused(dev(ids))
+    b = m.predict_fused(dev(ids))
     for k in ("logits", "logistic", "probabilities"):
         assert torch.equal(a[k].view(torch.int32), b[k].view(torch.int32))
     assert torch.equal(a["class_ids"], b["class_ids"])
-    c = m.predict_fused(_t(ids[:32]))
+    c = m.predict_fused(dev(ids[:32]))
     assert torch.equal(a["logits"][:32].view(torch.int32), c["logits"].view(torch.int32))
     assert torch.equal(a["probabilities"][:32].view(torch.int32), c["probabilities"].view(torch.int32))
 
@@ -227,21 +218,13 @@ def test_limits_raise_before_anything_is_launched():
 
 
 # ---- end to end: train, then python -m trainers.predict in both modes ------------------------------------------------
-def _run(mod, args):
-    env = dict(os.environ)
-    env["PYTHONPATH"] = os.pathsep.join([PKG, ROOT])
-    r = subprocess.run([sys.executable, "-m", mod] + args, cwd=PKG, env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r
-
-
 def test_predict_cli_end_to_end(tmp_path):
     job = str(tmp_path / "job")
-    _run("trainers.deep_fm", ["--synthetic", "4000", "--job-dir", job, "--train-steps", "48", "--batch-size", "32"])
+    _run_module("trainers.deep_fm", ["--synthetic", "4000", "--job-dir", job, "--train-steps", "48", "--batch-size", "32"])
     logits, cls = {}, {}
     for mode in ("fused", "layered"):
         out = str(tmp_path / (mode + ".csv"))
-        _run("trainers.predict", ["--job-dir", job, "--input", "synthetic:400:2", "--mode", mode, "--output", out])
+        _run_module("trainers.predict", ["--job-dir", job, "--input", "synthetic:400:2", "--mode", mode, "--output", out])
         rows = list(csv.DictReader(open(out)))
         assert len(rows) == 400
         logits[mode] = np.asarray([float(r["logit"]) for r in rows])

@@ -14,18 +14,16 @@ from mi355x_rec import _lib
 from mi355x_rec.engine import OptimizerSpec
 from mi355x_rec.population import FusedPopulation
 from mi355x_rec.predictor import _serve_member
-from tests.test_population_cpu import GroupKernels, _engine
+from tests.cases import _numpy_engine
+from tests.cpu_kernels import library_sized
 
 VOCAB = [9, 13, 5]
 F = len(VOCAB)
 
 
 def _engines(lib, **kw):
-    class HostKernels(GroupKernels):
-        def query(self, name, *a):
-            return getattr(lib, name)(*a)
-    k = HostKernels()
-    return [_engine(VOCAB, 4, [8], k, **kw), _engine(VOCAB, 4, [8], k, **kw), _engine(VOCAB, 4, [8], k, **kw)]
+    k = library_sized(lib)
+    return [_numpy_engine(VOCAB, 4, [8], k, **kw), _numpy_engine(VOCAB, 4, [8], k, **kw), _numpy_engine(VOCAB, 4, [8], k, **kw)]
 
 
 def _widths(m):

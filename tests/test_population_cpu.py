@@ -1,8 +1,7 @@
 """CPU: the host side of the population step — mi355x_rec.population.FusedPopulation and the trainers.sweep CLI.
-mi_train_group_plan / mi_train_group_step are stood in by a numpy restatement of their contract in include/mi355x_rec.h on
-top of tests.test_fused_step_cpu.FusedStepKernels (GroupKernels below: a member is what mi_train_step_fused does to its
-buffers with lr_t = lr_table[step] and seed = seed_base + step * 1000003); the real kernel is tested in
-test_hip_population.py."""
+mi_train_group_plan / mi_train_group_step are stood in by a numpy restatement of their contract in include/mi355x_rec.h
+(tests.cpu_kernels.NumpyKernels: a member is what mi_train_step_fused does to its buffers with lr_t = lr_table[step] and
+seed = seed_base + step * 1000003); the real kernel is tested in test_hip_population.py."""
 import ctypes as C
 import json
 import os
@@ -11,106 +10,20 @@ import numpy as np
 import pytest
 import torch
 
-from mi355x_rec import _lib, engine
-from mi355x_rec.engine import AdamSchedule, DeepFM, OptimizerSpec
+from mi355x_rec import _lib
+from mi355x_rec.engine import AdamSchedule, OptimizerSpec
 from mi355x_rec.population import FusedPopulation
 from oracle import deepfm as O
 from oracle import optimizers as OO
-from tests.test_fused_step_cpu import ML100K_VOCAB, FusedStepKernels, _check_vars, _fresh_ids, _t
-from tests.util import MASK64, make_problem
-
-_CT = {np.float32: C.c_float, np.int32: C.c_int32, np.int64: C.c_int64}
-
-
-def _at(ptr, n, dtype, stride=1, width=None):
-    """the host memory at `ptr` as a tensor: n elements `stride` apart, or n rows of `width`"""
-    if not ptr:
-        return None
-    span = (n - 1) * stride + (width or 1)
-    flat = torch.from_numpy(np.ctypeslib.as_array((_CT[dtype] * span).from_address(ptr)))
-    return flat.as_strided((n, width), (stride, 1)) if width else flat.as_strided((n,), (stride,))
-
-
-class GroupKernels(FusedStepKernels):
-    """FusedStepKernels + the two population entries restated from the header"""
-    MAGIC = 0x6d69
-
-    def __init__(self):
-        super().__init__()
-        self.plans = {}
-
-    def query(self, name, *args):
-        return 64 * args[0] if name == "mi_train_group_plan_bytes" else super().query(name, *args)
-
-    def mi_train_group_plan(self, members, M, B, F, field_off, table, nbytes, plan):
-        if M < 1:
-            raise _lib.MiError("mi_train_group_plan failed (-1): train_group_plan: %d members (at least 1)" % M)
-        if M > _lib.FUSED_GROUP_MAX_MEMBERS:
-            raise _lib.MiError("mi_train_group_plan failed (-2): train_group_plan: %d members (at most %d in one launch)"
-                               % (M, _lib.FUSED_GROUP_MAX_MEMBERS))
-        assert nbytes >= 64 * M and len(members) == M
-        decoded, owned = [], {}
-        for i in range(M):
-            m = members[i]
-            assert m.hp.kind == 0 and m.lr_table and m.lr_table_len >= 2 and m.workspace and 0 < m.keep_prob <= 1
-            for p in (m.table, m.t_m, m.t_v, m.lin_w, m.l_m, m.l_v, m.last_step, m.dense, m.d_m, m.d_v, m.workspace):
-                if p and p in owned:
-                    raise _lib.MiError("mi_train_group_plan failed (-1): train_group_plan: member %d and member %d share a "
-                                       "state or workspace pointer" % (owned[p], i))
-                if p:
-                    owned[p] = i
-            E, R, ts, ls, nl = m.E, m.R, m.table_stride or m.E, m.lin_stride, m.n_layers
-            d = dict(table=_at(m.table, R, np.float32, ts, E), t_m=_at(m.t_m, R, np.float32, ts, E),
-                     t_v=_at(m.t_v, R, np.float32, ts, E), lin_w=_at(m.lin_w, R, np.float32, ls),
-                     l_m=_at(m.l_m, R, np.float32, ls), l_v=_at(m.l_v, R, np.float32, ls),
-                     last_step=_at(m.last_step, R, np.int32, ls), dense=_at(m.dense, m.n_dense, np.float32),
-                     d_m=_at(m.d_m, m.n_dense, np.float32), d_v=_at(m.d_v, m.n_dense, np.float32),
-                     layer_off=_at(m.layer_off, max(2 * nl, 1), np.int64), widths=_at(m.widths, nl + 1, np.int32),
-                     lr_table=_at(m.lr_table, m.lr_table_len, np.float32),
-                     scalars=(ts, ls, R, E, m.n_dense, nl, m.activation, m.use_linear, m.use_fm, m.use_dnn, m.lin_bias_off,
-                              m.keep_prob, m.scale, m.seed_base),
-                     hp=(m.hp.kind, m.hp.lr, m.hp.beta1, m.hp.beta2, m.hp.epsilon))
-            decoded.append(d)
-        key = len(self.plans) + 1
-        self.plans[key] = (decoded, field_off, B, F)
-        plan.device_table, plan.magic, plan.n_members, plan.B, plan.F = key, self.MAGIC, M, B, F
-        plan.max_step = min(m.lr_table_len for m in members) - 1
-
-    def mi_train_group_step(self, plan, M, ids, ids_stride, labels, labels_stride, B, step, logits, loss, sweep_blocks):
-        assert plan.magic == self.MAGIC and M == plan.n_members and B == plan.B and 1 <= step <= plan.max_step
-        decoded, field_off, _, F = self.plans[plan.device_table]
-        assert ids_stride in (0, B * F) and labels_stride in (0, B) and tuple(logits.shape) == (M, B) and tuple(loss.shape) == (M,)
-        solo = object.__getattribute__(self, "mi_train_step_fused")          # (not an entry call of the code under test)
-        for i, d in enumerate(decoded):
-            ts, ls, R, E, nd, nl, act, ul, uf, ud, lbo, keep, scale, seed_base = d["scalars"]
-            kind, lr, b1, b2, eps = d["hp"]
-            hp = _lib.OptHparams(kind, lr, b1, b2, eps, float(d["lr_table"][step]), 0, 0, 0, 0, 0)
-            solo(d["table"], d["t_m"], d["t_v"], ts, d["lin_w"], d["l_m"], d["l_v"], ls, d["last_step"], field_off, R,
-                 ids[i] if ids_stride else ids, labels[i] if labels_stride else labels, B, F, E, d["dense"], d["d_m"], d["d_v"],
-                 nd, d["layer_off"], d["widths"], nl, act, ul, uf, ud, lbo, keep, (seed_base + step * 1000003) & MASK64, scale,
-                 step, hp, logits[i], loss[i:i + 1], sweep_blocks, None, 0)
-
-
-@pytest.fixture
-def cpu_kernels(monkeypatch):
-    monkeypatch.setattr(engine, "HipKernels", GroupKernels)
-
-
-def _engine(vocab, E, hidden, k=None, lr=0.001, **kw):
-    return DeepFM(vocab, embedding_size=E, hidden_units=hidden, optimizer=kw.pop("optimizer", OptimizerSpec("Adam", lr)),
-                  device="cpu", _kernels=k if k is not None else GroupKernels(), **kw)
-
-
-# the population of the issue's oracle test: (seed of make_problem, E, hidden, learning rate)
-ORACLE_MEMBERS = [(300, 4, [16, 16], 0.001), (301, 4, [16, 16], 0.01), (308, 16, [64, 64, 32], 0.001), (302, 8, [32], 0.003),
-                  (304, 4, [16, 16], 0.003), (305, 12, [32, 16], 0.001)]
-
+from tests.cases import ML100K_VOCAB, ORACLE_MEMBERS, _numpy_engine, _sweep_args
+from tests.cpu_kernels import NumpyKernels, cpu_kernels, library_sized  # noqa: F401  (cpu_kernels: a fixture)
+from tests.util import _check_vars, _fresh_ids, _t, make_problem
 
 def _oracle_population(k, members=ORACLE_MEMBERS, B=32):
     engines, params, states = [], [], []
     for seed, E, hidden, lr in members:
         p = make_problem(seed, ML100K_VOCAB, E, hidden, B)[0]
-        m = _engine(ML100K_VOCAB, E, hidden, k, lr)
+        m = _numpy_engine(ML100K_VOCAB, E, hidden, k, lr)
         m.load_oracle_params(p)
         engines.append(m)
         params.append(p)
@@ -120,7 +33,7 @@ def _oracle_population(k, members=ORACLE_MEMBERS, B=32):
 
 def test_one_entry_call_per_step_and_members_match_the_oracle():
     B = 32
-    k = GroupKernels()
+    k = NumpyKernels()
     engines, params, states = _oracle_population(k)
     y = make_problem(300, ML100K_VOCAB, 4, [16, 16], B)[3]
     pop = FusedPopulation(engines)
@@ -149,14 +62,14 @@ def test_a_member_is_its_own_fused_step_bit_for_bit_with_shared_and_per_member_b
         out = []
         for j, s in enumerate(specs):
             s = dict(s)
-            m = _engine(vocab, s.pop("E"), s.pop("hidden"), k, s.pop("lr", 0.001), **s)
+            m = _numpy_engine(vocab, s.pop("E"), s.pop("hidden"), k, s.pop("lr", 0.001), **s)
             g = torch.Generator()
             g.manual_seed(j)
             m.init_variables(g, lin_scale=0.05)
             out.append(m)
         return out
-    k = GroupKernels()
-    group, solo = make(k), make(GroupKernels())
+    k = NumpyKernels()
+    group, solo = make(k), make(NumpyKernels())
     pop = FusedPopulation(group)
     rng = np.random.default_rng(4)
     for step in range(4):
@@ -176,8 +89,8 @@ def test_a_member_is_its_own_fused_step_bit_for_bit_with_shared_and_per_member_b
 
 def test_the_plan_is_reused_and_rebuilt_only_when_it_must_be():
     vocab, B = [9, 13, 5], 8
-    k = GroupKernels()
-    engines = [_engine(vocab, 4, [8], k, lr) for lr in (0.001, 0.01, 0.003)]
+    k = NumpyKernels()
+    engines = [_numpy_engine(vocab, 4, [8], k, lr) for lr in (0.001, 0.01, 0.003)]
     engines[1].sched = AdamSchedule(engines[1].opt, engines[1].device, capacity=4)
     pop = FusedPopulation(engines)
     rng = np.random.default_rng(0)
@@ -210,8 +123,8 @@ def test_the_plan_is_reused_and_rebuilt_only_when_it_must_be():
 
 def test_refusals_before_anything_is_launched():
     vocab, B = [9, 13, 5], 8
-    k = GroupKernels()
-    mk = lambda **kw: _engine(kw.pop("vocab", vocab), kw.pop("E", 4), kw.pop("hidden", [8]), k, **kw)
+    k = NumpyKernels()
+    mk = lambda **kw: _numpy_engine(kw.pop("vocab", vocab), kw.pop("E", 4), kw.pop("hidden", [8]), k, **kw)
     ids, y = torch.zeros(B, 3, dtype=torch.int32), torch.zeros(B, dtype=torch.uint8)
     with pytest.raises(ValueError, match="no members"):
         FusedPopulation([])
@@ -255,12 +168,6 @@ def test_refusals_before_anything_is_launched():
 
 
 # ---- the grid-search CLI ----------------------------------------------------------------------------------------------
-def _sweep_args(job, *extra):
-    from trainers import sweep
-    return sweep.make_parser().parse_args(["--synthetic", "300", "--job-dir", str(job), "--batch-size", "16", "--device", "cpu",
-                                           "--hidden-units", "8", "8"] + list(extra))
-
-
 def test_sweep_parser_defaults():
     from trainers import sweep
     a = sweep.make_parser().parse_args([])
@@ -354,11 +261,8 @@ def test_a_sweep_member_is_a_stand_alone_run(cpu_kernels, tmp_path):
 def test_the_library_itself_refuses_on_the_host_before_it_touches_a_device(lib):
     """The real mi_train_group_plan / mi_train_group_step on this machine: every refusal is decided on the host from the
     members' descriptions (which also pins the binding's struct layout to the header's)."""
-    class HostKernels(GroupKernels):
-        def query(self, name, *a):
-            return getattr(lib, name)(*a)
-    k = HostKernels()
-    es = [_engine([9, 13, 5], 4, [8], k), _engine([9, 13, 5], 8, [16, 8], k, dropout=0.25), _engine([9, 13, 5], 4, [8], k)]
+    k = library_sized(lib)
+    es = [_numpy_engine([9, 13, 5], 4, [8], k), _numpy_engine([9, 13, 5], 8, [16, 8], k, dropout=0.25), _numpy_engine([9, 13, 5], 4, [8], k)]
     pop, keep = FusedPopulation(es), []
     table = torch.full((int(lib.mi_train_group_plan_bytes(3)),), 0xA5, dtype=torch.uint8)
 

@@ -1,8 +1,8 @@
 """CPU: the host side of the population evaluation — FusedPopulation.evaluate and trainers.sweep's --eval-every /
---final-eval.  mi_eval_group is stood in by a numpy restatement of its contract in include/mi355x_rec.h on top of
-tests.test_population_cpu.GroupKernels (EvalKernels below: a tile's logits and batch loss are what mi_train_step_fused
-reports for that batch with keep_prob = 1, taken on COPIES of the member's buffers; the counters are mi_eval_accumulate's
-in numpy); the real kernel is tested in test_hip_population_eval.py.  The refusals and the binding are checked against the
+--final-eval.  mi_eval_group is stood in by a numpy restatement of its contract in include/mi355x_rec.h
+(tests.cpu_kernels.NumpyKernels: a tile's logits and batch loss are what mi_train_step_fused reports for that batch with
+keep_prob = 1, taken on COPIES of the member's buffers; the counters are mi_eval_accumulate's in numpy); the real kernel is
+tested in test_hip_population_eval.py.  The refusals and the binding are checked against the
 real library, which decides them on the host."""
 import ctypes as C
 import json
@@ -12,79 +12,14 @@ import numpy as np
 import pytest
 import torch
 
-from mi355x_rec import _lib, engine
+from mi355x_rec import _lib
 from mi355x_rec.metrics import metrics_from_counters
 from mi355x_rec.population import FusedPopulation
-from tests.test_abi import _header_decls
-from tests.test_fused_step_cpu import _fresh_ids, _t
-from tests.test_population_cpu import GroupKernels, _engine, _sweep_args
+from tests.cases import _numpy_engine, _sweep_args
+from tests.cpu_kernels import NumpyKernels, counters, cpu_kernels  # noqa: F401  (a fixture)
+from tests.util import _fresh_ids, _header_decls, _t
 
 F32 = np.float32
-
-
-def thresholds():
-    """tf.metrics.auc's 200 thresholds as mi_eval_accumulate holds them (fp32 of the fp64 values)"""
-    th = np.arange(200, dtype=np.float64) / 199.0
-    th[0], th[-1] = 0.0 - 1e-7, 1.0 + 1e-7
-    return th.astype(F32)
-
-
-def counters(z, y):
-    """mi_eval_accumulate restated: (hist [2, 201], counts [8], sums [3]) of fp32 logits z and labels y"""
-    z = np.asarray(z, F32)
-    y = np.asarray(y).astype(np.int64)
-    e = np.exp(-np.abs(z)).astype(F32)
-    p = np.where(z >= 0, F32(1) / (F32(1) + e), e / (F32(1) + e)).astype(F32)
-    k = np.searchsorted(thresholds(), p, side="left")                    # #{j : th[j] < p}
-    hist = np.zeros((2, 201), np.int64)
-    np.add.at(hist, (y, k), 1)
-    cls = (p > F32(0.5)).astype(np.int64)
-    counts = np.array([len(z), y.sum(), cls.sum(), (cls == y).sum(), (cls & y).sum(), (cls & (1 - y)).sum(),
-                       ((1 - cls) & y).sum(), 0], np.int64)
-    zd = z.astype(np.float64)
-    sums = np.array([(np.maximum(zd, 0) - zd * y + np.log1p(np.exp(-np.abs(zd)))).sum(), p.astype(np.float64).sum(), y.sum()])
-    return hist, counts, sums
-
-
-class EvalKernels(GroupKernels):
-    """GroupKernels + mi_eval_group restated from the header"""
-
-    def mi_eval_group(self, plan, M, ids, labels, N, tail_scale, logits, batch_loss, hist, counts, partials, blocks):
-        assert plan.magic == self.MAGIC and M == plan.n_members and N >= 1 and 0 <= blocks <= 1024
-        decoded, field_off, B, F = self.plans[plan.device_table]
-        T = -(-N // B)
-        assert tuple(ids.shape) == (N, F) and tuple(labels.shape) == (N,) and tuple(batch_loss.shape) == (M, T)
-        assert tuple(hist.shape) == (M, 2, 201) and tuple(counts.shape) == (M, 8) and tuple(partials.shape) == (M, T, 3)
-        assert logits is None or tuple(logits.shape) == (M, N)
-        assert N % B == 0 or tuple(tail_scale.shape) == (M,)
-        assert not bool(hist.any()) and not bool(counts.any()), "the caller zeroes hist and counts"
-        solo = object.__getattribute__(self, "mi_train_step_fused")          # (not an entry call of the code under test)
-        for i, d in enumerate(decoded):
-            ts, ls, R, E, nd, nl, act, ul, uf, ud, lbo, keep, scale, seed_base = d["scalars"]
-            kind, lr, b1, b2, eps = d["hp"]
-            hp = _lib.OptHparams(kind, lr, b1, b2, eps, 0.0, 0, 0, 0, 0, 0)
-            for t in range(T):
-                lo, hi = t * B, min(N, (t + 1) * B)
-                n = hi - lo
-                c = {k: (None if d[k] is None else d[k].clone()) for k in ("table", "t_m", "t_v", "lin_w", "l_m", "l_v", "last_step",
-                                                                           "dense", "d_m", "d_v")}
-                z, lb = torch.zeros(n), torch.zeros(1)
-                solo(c["table"], c["t_m"], c["t_v"], ts, c["lin_w"], c["l_m"], c["l_v"], ls, torch.zeros_like(c["last_step"]),
-                     field_off, R, ids[lo:hi], labels[lo:hi], n, F, E, c["dense"], c["d_m"], c["d_v"], nd, d["layer_off"],
-                     d["widths"], nl, act, ul, uf, ud, lbo, 1.0, 0, float(tail_scale[i]) if n < B else scale, 1, hp, z, lb, 0,
-                     None, 0)
-                batch_loss[i, t] = lb[0]
-                if logits is not None:
-                    logits[i, lo:hi] = z
-                h, cn, sm = counters(z.numpy(), labels[lo:hi].numpy())
-                hist[i] += torch.from_numpy(h)
-                counts[i] += torch.from_numpy(cn)
-                partials[i, t] = torch.from_numpy(sm)
-
-
-@pytest.fixture
-def cpu_kernels(monkeypatch):
-    monkeypatch.setattr(engine, "HipKernels", EvalKernels)
 
 
 SPECS = [dict(E=8, hidden=[16, 8], dropout=0.25, seed=3), dict(E=4, hidden=[8], lr=0.01, activation="tanh"),
@@ -96,7 +31,7 @@ def _members(k, specs=SPECS, vocab=VOCAB):
     out = []
     for j, s in enumerate(specs):
         s = dict(s)
-        m = _engine(vocab, s.pop("E"), s.pop("hidden"), k, s.pop("lr", 0.001), **s)
+        m = _numpy_engine(vocab, s.pop("E"), s.pop("hidden"), k, s.pop("lr", 0.001), **s)
         g = torch.Generator()
         g.manual_seed(j)
         m.init_variables(g, lin_scale=0.3)
@@ -111,7 +46,7 @@ def _eval_set(N, vocab=VOCAB, seed=1):
 
 def test_evaluate_is_metrics_from_counters_on_the_logits_and_the_mean_of_batch_losses():
     N, B = 100, 16                                                       # 6 tiles of 16 and a tail of 4
-    k = EvalKernels()
+    k = NumpyKernels()
     members = _members(k)
     pop = FusedPopulation(members)
     ids, y = _eval_set(N)
@@ -143,7 +78,7 @@ def test_evaluate_is_metrics_from_counters_on_the_logits_and_the_mean_of_batch_l
             if isinstance(v, torch.Tensor):
                 assert torch.equal(v, after[key]), (i, key)
     # dropout is off in evaluation: member 0 (dropout 0.25) gives the logits of its dropout-free twin
-    twin = _members(EvalKernels(), [dict(SPECS[0], dropout=0.0)])[0]
+    twin = _members(NumpyKernels(), [dict(SPECS[0], dropout=0.0)])[0]
     twin.load_state_dict(before[0])
     _, z = FusedPopulation([twin]).evaluate(ids, y, batch_size=B, return_logits=True)
     assert torch.equal(z[0], logits[0])
@@ -154,7 +89,7 @@ def test_evaluate_is_metrics_from_counters_on_the_logits_and_the_mean_of_batch_l
 
 def test_the_tail_batch_is_reduced_with_its_own_scale():
     N, B = 20, 16
-    k = EvalKernels()
+    k = NumpyKernels()
     members = _members(k, SPECS[1:3])                                    # a mean and a sum
     pop = FusedPopulation(members)
     ids, y = _eval_set(N, seed=2)
@@ -172,7 +107,7 @@ def test_the_tail_batch_is_reduced_with_its_own_scale():
 
 
 def test_argument_checks_raise_with_the_populations_wording():
-    k = EvalKernels()
+    k = NumpyKernels()
     pop = FusedPopulation(_members(k))
     ids, y = _eval_set(40)
     for bad_ids, bad_y, kw, msg in ((ids.long(), y, {}, r"ids must be a contiguous int32 \[N, 4\]"),
@@ -189,7 +124,7 @@ def test_argument_checks_raise_with_the_populations_wording():
 
 def test_the_plan_is_built_once_across_alternating_steps_and_evaluations():
     B = 8
-    k = EvalKernels()
+    k = NumpyKernels()
     members = _members(k)
     pop = FusedPopulation(members)
     ids, y = _eval_set(50)

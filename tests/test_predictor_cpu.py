@@ -1,7 +1,7 @@
 """CPU: serving an export — LatestExporter's self-describing signature, Predictor.from_export (columns, FieldPlan and a
 weights-only engine rebuilt from the export alone), the request checks, DeepFM.predict_fused's host side and the
-`python -m trainers.predict` CLI.  mi_predict_fused is stood in by a numpy restatement of include/mi355x_rec.h on top of
-tests.cpu_kernels.NumpyKernels (ServeKernels below); the real kernel is tested in test_hip_serve.py."""
+`python -m trainers.predict` CLI.  mi_predict_fused is stood in by a numpy restatement of include/mi355x_rec.h
+(tests.cpu_kernels.NumpyKernels); the real kernel is tested in test_hip_serve.py."""
 import csv
 import json
 import os
@@ -10,71 +10,13 @@ import numpy as np
 import pytest
 import torch
 
-from mi355x_rec import engine
 from mi355x_rec.engine import DeepFM, OptimizerSpec
 from mi355x_rec.feature_column import FieldPlan, column_from_json
 from mi355x_rec.predictor import Predictor
 from oracle import deepfm as O
-from tests.cpu_kernels import NumpyKernels
-from tests.util import make_problem, max_err_scaled
+from tests.cpu_kernels import NumpyKernels, cpu_kernels  # noqa: F401  (a fixture)
+from tests.util import _requests, make_problem, max_err_scaled
 from trainers import _cli, ml_100k, predict, recommend
-
-_ACT = {0: lambda v: v, 1: lambda v: np.maximum(v, 0), 2: lambda v: 1 / (1 + np.exp(-v)), 3: np.tanh}
-
-
-class ServeKernels(NumpyKernels):
-    """NumpyKernels + mi_predict_fused restated from include/mi355x_rec.h in fp64 (independent of the layered stand-ins)"""
-
-    def mi_predict_fused(self, table, ts, lin_w, ls, field_off, ids, x_num, B, F, E, nd, dense, layer_off, widths, n_layers,
-                         act, use_linear, use_fm, use_dnn, raw, lin_bias_off, num_emb_off, lin_num_off, wide, logits,
-                         logistic, probabilities, class_ids, ws, wsb):
-        f64 = lambda t: t.numpy().astype(np.float64)
-        d = f64(dense)
-        rows = ids.numpy().astype(np.int64) + field_off.numpy()[None, :] if F else None
-        x = f64(x_num) if nd else None
-        z = np.zeros(B)
-        parts = []
-        if (use_fm or use_dnn) and F:
-            parts.append(f64(table)[rows])                                   # [B, F, E]
-        if nd and not raw and (use_fm or use_dnn):
-            parts.append(x[:, :, None] * d[num_emb_off:num_emb_off + nd * E].reshape(nd, E)[None])
-        if use_linear:
-            lin = np.zeros(B)
-            for f in range(F):
-                if (wide >> f) & 1:
-                    lin += f64(lin_w)[rows[:, f]]
-            if nd:
-                lin += x @ d[lin_num_off:lin_num_off + nd]
-            z += lin + d[lin_bias_off]
-        if use_fm:
-            m = np.concatenate(parts, 1)
-            s = m.sum(1)
-            z += 0.5 * (s * s - (m * m).sum(1)).sum(1)
-        if use_dnn:
-            h = np.concatenate([p.reshape(B, -1) for p in parts] + ([x] if (raw and nd) else []), 1)
-            lo, wd = layer_off.numpy(), widths.numpy()
-            for i in range(n_layers):
-                W = d[lo[2 * i]:lo[2 * i] + wd[i] * wd[i + 1]].reshape(wd[i], wd[i + 1])
-                h = h @ W[:h.shape[1]] + d[lo[2 * i + 1]:lo[2 * i + 1] + wd[i + 1]]
-                if i + 1 < n_layers:
-                    h = _ACT[act](h)
-            z += h[:, 0]
-        z = z.astype(np.float32)
-        sig = O.predictions(z)["logistic"]
-        if logits is not None:
-            logits.numpy().reshape(-1)[:] = z
-        if logistic is not None:
-            logistic.numpy().reshape(-1)[:] = sig
-        if probabilities is not None:
-            probabilities.numpy().reshape(-1, 2)[:] = np.stack([1 - sig, sig], 1)
-        if class_ids is not None:
-            class_ids.numpy().reshape(-1)[:] = sig > 0.5
-
-
-@pytest.fixture
-def cpu_kernels(monkeypatch):
-    monkeypatch.setattr(engine, "HipKernels", ServeKernels)
-
 
 def _train(tmp_path, model, extra=()):
     trainer, opt = recommend.MODELS[model]
@@ -82,12 +24,6 @@ def _train(tmp_path, model, extra=()):
     argv = ["--synthetic", "300", "--job-dir", job, "--train-steps", "25", "--batch-size", "16", "--device", "cpu"] + list(extra)
     est = trainer.train_and_evaluate(_cli.make_parser(model, opt).parse_args(argv))
     return est, job
-
-
-def _requests(n=30, seed=2):
-    cols, _ = ml_100k._read_csv("synthetic:%d:%d" % (n, seed))
-    recv = set(ml_100k.serving_input_fn().receiver_tensors)
-    return {k: v for k, v in cols.items() if k in recv}
 
 
 @pytest.mark.parametrize("model,extra", [("deep_fm", ["--hidden-units", "8", "8"]), ("linear", []),
@@ -183,7 +119,7 @@ VOCAB = [11, 7, 5, 9, 13, 6]
 
 def _model(**kw):
     kw.setdefault("hidden_units", [8, 4])
-    m = DeepFM(VOCAB, embedding_size=4, device="cpu", _kernels=ServeKernels(), **kw)
+    m = DeepFM(VOCAB, embedding_size=4, device="cpu", _kernels=NumpyKernels(), **kw)
     p, ids, x, _ = make_problem(1, VOCAB, 4, kw["hidden_units"], 9, n_numeric=kw.get("n_numeric", 0), use_dnn=kw.get("use_dnn", True))
     if kw.get("numeric") == "raw":                                    # kernel_0: one row per raw numeric column
         k0, b0 = p.mlp[0]
@@ -220,11 +156,11 @@ def test_predict_fused_argument_errors_and_refusals():
         m.predict_fused(t, torch.zeros(9, 1))                         # no numeric column in the model
     with pytest.raises(ValueError):
         m.predict_fused(t[:0])                                        # no rows
-    big = DeepFM(VOCAB, embedding_size=4, hidden_units=[1024, 8], device="cpu", _kernels=ServeKernels())
+    big = DeepFM(VOCAB, embedding_size=4, hidden_units=[1024, 8], device="cpu", _kernels=NumpyKernels())
     assert not big.fused_predict_ok()
     with pytest.raises(ValueError, match="1024"):
         big.predict_fused(t)
-    deep = DeepFM(VOCAB, embedding_size=4, hidden_units=[4] * 9, device="cpu", _kernels=ServeKernels())
+    deep = DeepFM(VOCAB, embedding_size=4, hidden_units=[4] * 9, device="cpu", _kernels=NumpyKernels())
     with pytest.raises(ValueError, match="9 hidden layers"):
         deep.predict_fused(t)
     m.shard = object()                                                # a row-sharded engine
@@ -235,7 +171,7 @@ def test_predict_fused_argument_errors_and_refusals():
 
 def test_predict_fused_scores_lazily_updated_adam_rows_at_their_caught_up_value():
     rng = np.random.default_rng(3)
-    m = DeepFM(VOCAB, embedding_size=4, hidden_units=[8], optimizer=OptimizerSpec("Adam", 0.01), device="cpu", _kernels=ServeKernels())
+    m = DeepFM(VOCAB, embedding_size=4, hidden_units=[8], optimizer=OptimizerSpec("Adam", 0.01), device="cpu", _kernels=NumpyKernels())
     p, _, _, _ = make_problem(2, VOCAB, 4, [8], 4)
     m.load_oracle_params(p)
     for _ in range(3):

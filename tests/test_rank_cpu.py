@@ -1,6 +1,6 @@
 """CPU: the host side of top-K recommendation — DeepFM.top_k's argument checks and per-side decomposition, the feature
 dicts' split into sides by key, the CLI's user / item tables, exclusion CSR and ranking metrics.  mi_pair_topk is stood
-in by numpy (RankKernels below); the real kernel is tested in test_hip_rank.py."""
+in by numpy (tests.cpu_kernels.NumpyKernels); the real kernel is tested in test_hip_rank.py."""
 import math
 import os
 
@@ -16,59 +16,12 @@ from tests.cpu_kernels import NumpyKernels
 from tests.util import make_problem, max_err_scaled
 from trainers import ml_100k, recommend
 
-_ACT = {0: lambda v: v, 1: lambda v: np.maximum(v, 0), 2: lambda v: 1 / (1 + np.exp(-v)), 3: np.tanh}
-
-
-class RankKernels(NumpyKernels):
-    """NumpyKernels + mi_pair_topk restated from include/mi355x_rec.h (fp64 scores, host sort)"""
-
-    def mi_sigmoid_ce_head(self, lin, lin_bias, fm, dnn, *rest):
-        # (the header's lin_bias may be NULL: the query side's lin + fm carries no bias)
-        if lin is not None and lin_bias is None:
-            lin_bias = torch.zeros(1)
-        return super().mi_sigmoid_ce_head(lin, lin_bias, fm, dnn, *rest)
-
-    def mi_pair_topk(self, a_q, s_q, w_q, U, a_c, s_c, w_c, I, H1, E, dense, layer_off, widths, n_layers, act,
-                     excl_off, excl_idx, k, top_score, top_idx, scores, ws, wsb):
-        f = lambda t: t.numpy().astype(np.float64)
-        s = np.zeros((U, I))
-        if w_q is not None:
-            s += f(w_q)[:, None]
-        if w_c is not None:
-            s += f(w_c)[None, :]
-        if E:
-            s += f(s_q) @ f(s_c).T
-        if H1:
-            h = f(a_q)[:, None, :] + f(a_c)[None, :, :]
-            if n_layers:
-                h = _ACT[act](h)
-            d, lo, wd = dense.numpy().astype(np.float64), layer_off.numpy(), widths.numpy()
-            for i in range(n_layers):
-                W = d[lo[2 * i]:lo[2 * i] + wd[i] * wd[i + 1]].reshape(wd[i], wd[i + 1])
-                h = h @ W + d[lo[2 * i + 1]:lo[2 * i + 1] + wd[i + 1]]
-                if i + 1 < n_layers:
-                    h = _ACT[act](h)
-            s += h[:, :, 0]
-        s = s.astype(np.float32)
-        if scores is not None:
-            scores.numpy()[:] = s
-        ts, ti = top_score.numpy(), top_idx.numpy()
-        ts[:] = -np.inf
-        ti[:] = -1
-        for u in range(U):
-            ex = set() if excl_off is None else set(excl_idx.numpy()[excl_off.numpy()[u]:excl_off.numpy()[u + 1]].tolist())
-            ok = np.asarray([c for c in range(I) if c not in ex], np.int64)
-            order = np.lexsort((ok, np.where(np.isnan(s[u, ok]), np.inf, -s[u, ok])))[:k]
-            ts[u, :len(order)] = s[u, ok[order]]
-            ti[u, :len(order)] = ok[order]
-
-
 VOCAB = [11, 7, 5, 9, 13, 6]
 
 
 def _model(**kw):
     kw.setdefault("hidden_units", [8, 4])
-    m = DeepFM(VOCAB, embedding_size=4, device="cpu", _kernels=RankKernels(), **kw)
+    m = DeepFM(VOCAB, embedding_size=4, device="cpu", _kernels=NumpyKernels(), **kw)
     p, _, _, _ = make_problem(1, VOCAB, 4, kw["hidden_units"], 4, n_numeric=kw.get("n_numeric", 0),
                               use_dnn=kw.get("use_dnn", True))
     m.load_oracle_params(p)
@@ -208,7 +161,7 @@ def test_recommend_cli_every_model(tmp_path, monkeypatch, model):
     from mi355x_rec import engine
     from trainers import _cli
     from trainers.conf_utils import get_run_config
-    monkeypatch.setattr(engine, "HipKernels", RankKernels)
+    monkeypatch.setattr(engine, "HipKernels", NumpyKernels)
     rng = np.random.default_rng(3)
     users, items = np.arange(1, 13), np.arange(1, 31)
     _write_rows(tmp_path / "train.csv", rng, 200, users, items)

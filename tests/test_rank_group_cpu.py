@@ -1,6 +1,6 @@
 """CPU: the host side of ranking with an ensemble — engine.top_k_group, Predictor.recommend, EnsemblePredictor.recommend
 (its three modes, its refusals, what it does once per call) and trainers.recommend --top.  mi_pair_topk_group is stood in
-by a numpy restatement of its contract in include/mi355x_rec.h (GroupRankKernels below: member m's score is the numpy
+by a numpy restatement of its contract in include/mi355x_rec.h (tests.cpu_kernels.NumpyKernels: member m's score is the numpy
 mi_pair_topk's, the mean is formed in fp32 in member order, the selection is the header's rule); the real kernel is tested
 in test_hip_rank_group.py.  The binding and the library's host-side refusals are checked against the real library."""
 import ctypes as C
@@ -10,88 +10,24 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 from mi355x_rec import _lib, engine, predictor
 from mi355x_rec.engine import DeepFM
 from mi355x_rec.predictor import EnsemblePredictor, Predictor
-from tests.test_abi import _header_decls
-from tests.test_ensemble_cpu import EnsembleKernels, _fake_sweep, _train
-from tests.test_rank_cpu import RankKernels
-from tests.util import max_err_scaled
+from tests.cpu_kernels import NumpyKernels, cpu_kernels  # noqa: F401  (a fixture)
+from tests.util import _fake_sweep, _header_decls, _train_deep_fm_export, max_err_scaled
 from trainers import _cli, ml_100k, recommend
 from trainers.conf_utils import get_run_config
-
-F32 = np.float32
-
-
-def _host(ptr, n, ctype, dtype):
-    """n elements at a host address as a torch tensor (None for NULL)"""
-    if not ptr:
-        return None
-    return torch.from_numpy(np.ctypeslib.as_array((ctype * max(n, 1)).from_address(ptr)).astype(dtype, copy=False))
-
-
-def _select(scores, k, excl_off, excl_idx, top_score, top_idx):
-    """the header's rule: score descending, equal scores by ascending index, NaN last, -1 / -inf padding"""
-    U, I = scores.shape
-    ts, ti = top_score.numpy(), top_idx.numpy()
-    ts[:] = -np.inf
-    ti[:] = -1
-    for u in range(U):
-        ex = set() if excl_off is None else set(excl_idx.numpy()[excl_off.numpy()[u]:excl_off.numpy()[u + 1]].tolist())
-        ok = np.asarray([c for c in range(I) if c not in ex], np.int64)
-        s = scores[u, ok]
-        order = np.lexsort((ok, np.where(np.isnan(s), np.inf, -s)))[:k]
-        ts[u, :len(order)] = s[order] + F32(0)
-        ti[u, :len(order)] = ok[order]
-
-
-class GroupRankKernels(RankKernels, EnsembleKernels):
-    """the numpy stand-ins + mi_pair_topk (RankKernels) + mi_pair_topk_group restated from the header"""
-
-    def mi_pair_topk_group(self, members, M, U, I, excl_off, excl_idx, k, top_score, top_idx, scores, member_scores, ws, wsb):
-        assert 1 <= M <= _lib.PAIR_TOPK_GROUP_MAX_MEMBERS and len(members) == M and 1 <= k <= 256
-        acc = None
-        for i in range(M):
-            m = members[i]
-            after = [] if m.n_layers == 0 else _host(m.widths, m.n_layers + 1, C.c_int32, np.int32).tolist()[1:-1]
-            assert m.n_layers < 2 or max(after) < 32, "member %d is outside the VALU scope" % i
-            f = lambda p, *shape: None if not p else _host(p, int(np.prod(shape)), C.c_float, F32).reshape(*shape)
-            lo = _host(m.layer_off, 2 * max(m.n_layers, 1), C.c_int64, np.int64)
-            wd = _host(m.widths, m.n_layers + 1, C.c_int32, np.int32)
-            n_dense = 1
-            for j in range(m.n_layers):
-                n_dense = max(n_dense, int(lo[2 * j]) + int(wd[j]) * int(wd[j + 1]), int(lo[2 * j + 1]) + int(wd[j + 1]))
-            z = torch.zeros(U, I)
-            s_, i_ = torch.zeros(U, k), torch.zeros(U, k, dtype=torch.int32)
-            RankKernels.mi_pair_topk(self, f(m.a_q, U, m.H1), f(m.s_q, U, m.E), f(m.w_q, U), U, f(m.a_c, I, m.H1),
-                                     f(m.s_c, I, m.E), f(m.w_c, I), I, m.H1, m.E, f(m.dense, n_dense), lo, wd, m.n_layers,
-                                     m.activation, None, None, k, s_, i_, z, None, 0)
-            z = z.numpy().astype(F32)
-            if member_scores is not None:
-                member_scores.numpy()[i] = z
-            acc = z if acc is None else (acc + z).astype(F32)
-        mean = (acc / F32(M)).astype(F32)
-        if scores is not None:
-            scores.numpy()[:] = mean
-        _select(mean, k, excl_off, excl_idx, top_score, top_idx)
-
-
-@pytest.fixture
-def cpu_kernels(monkeypatch):
-    monkeypatch.setattr(engine, "HipKernels", GroupRankKernels)
-
 
 @pytest.fixture(scope="module")
 def exports(tmp_path_factory):
     """three small trained deep_fm exports: two inside the group kernel's scope, one ([64, 64]) outside it"""
     root = str(tmp_path_factory.mktemp("rankens"))
     with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(engine, "HipKernels", GroupRankKernels)
-        return [_train(root, "a", ["--embedding-size", "4", "--hidden-units", "8", "8"]),
-                _train(root, "b", ["--embedding-size", "8", "--hidden-units", "8"]),
-                _train(root, "c", ["--embedding-size", "4", "--hidden-units", "64", "64"])]
+        mp.setattr(engine, "HipKernels", NumpyKernels)
+        return [_train_deep_fm_export(root, "a", ["--embedding-size", "4", "--hidden-units", "8", "8"]),
+                _train_deep_fm_export(root, "b", ["--embedding-size", "8", "--hidden-units", "8"]),
+                _train_deep_fm_export(root, "c", ["--embedding-size", "4", "--hidden-units", "64", "64"])]
 
 
 @pytest.fixture(scope="module")

@@ -3,34 +3,14 @@
 ``get_feature_columns / get_input_fn / serving_input_fn`` and the model_utils helpers
 (reference: trainers/*.py).  The same scenarios run on CPU with numpy stand-ins for the kernels
 (host logic) and, under -m gpu, on the real HIP path."""
-import csv
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from tests.util import _write_csv
 from trainers import deep_fm, deep, linear, linear_deep, ml_100k, model_utils, conf_utils, _cli
-
-
-def _write_csv(path, n, seed):
-    rng = np.random.default_rng(seed)
-    occ = ["technician", "administrator", "student", "homemaker", "none", "engineer"]
-    with open(path, "w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(ml_100k.COLUMNS)
-        for _ in range(n):
-            row = {c: (0 if d[0] == 0 else "null") for c, d in zip(ml_100k.COLUMNS, ml_100k.DEFAULTS)}
-            uid, iid = int(rng.integers(1, 944)), int(rng.integers(1, 1683))
-            g = rng.integers(0, 2, len(ml_100k.GENRE))
-            # a learnable rule so that training visibly reduces the loss
-            like = (g[1] == 1) if rng.random() < 0.9 else (g[1] == 0)
-            row.update(user_id=uid, item_id=iid, rating=5 if like else int(rng.integers(1, 5)),
-                       age=int(rng.integers(7, 74)), gender=str(rng.choice(["F", "M", ""])),
-                       occupation=str(rng.choice(occ)), zipcode="%05d" % rng.integers(0, 99999),
-                       release_year=int(rng.integers(1922, 1999)))
-            row.update({k: int(v) for k, v in zip(ml_100k.GENRE, g)})
-            w.writerow([row[c] for c in ml_100k.COLUMNS])
 
 
 @pytest.fixture(params=["cpu", pytest.param("cuda", marks=pytest.mark.gpu)])

@@ -1,10 +1,21 @@
-"""Shared helpers for the parity tests (oracle side = checker, HIP side = thing under test)."""
+"""Shared helpers for the parity tests (oracle side = checker, HIP side = thing under test).  Case lists and the helpers
+that build engines and populations are in tests/cases.py, the numpy stand-ins for the library in tests/cpu_kernels.py; no
+test module imports another.  pytest does not rewrite the assertions of this module: every assert here carries its message."""
+import csv
+import json
+import os
+import re
+import subprocess
+import sys
+
 import numpy as np
 import torch
 
 from oracle import deepfm as O
 from oracle import optimizers as OO
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "recommender-tensorflow_amd")
 MASK64 = (1 << 64) - 1
 
 
@@ -101,3 +112,187 @@ def exact_workspace(nbytes, offset=32):
 def workspace_surroundings_intact(buf, ws):
     lo = ws.data_ptr() - buf.data_ptr()
     return bool((buf[:lo] == WS_FILL).all()) and bool((buf[lo + ws.numel():] == WS_FILL).all())
+
+
+# ---- raw calls through the C ABI --------------------------------------------------------------------------------------------
+def _st():
+    from mi355x_rec import _lib
+    return _lib.cur_stream()
+
+
+def _chk(rc, what="call"):
+    from mi355x_rec import _lib
+    _lib.check(rc, what)
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _header_decls():
+    """{entry name: number of arguments} of every mi_* declaration in include/mi355x_rec.h"""
+    src = open(os.path.join(ROOT, "include", "mi355x_rec.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    decls = {}
+    for m in re.finditer(r"\b(mi_\w+)\s*\(([^;{}]*?)\)\s*;", src, flags=re.S):
+        args = m.group(2).strip()
+        decls[m.group(1)] = 0 if args in ("", "void") else args.count(",") + 1
+    return decls
+
+
+# ---- inputs, and an engine's variables against the oracle's --------------------------------------------------------------------
+def _t(a):
+    """a host array as a CPU tensor (dev() is the same for the GPU)"""
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a))
+
+
+def _fresh_ids(rng, vocab, B):
+    ids = np.stack([rng.integers(0, v, B) for v in vocab], 1).astype(np.int32)
+    if B > 1:
+        ids[B // 2] = ids[0]
+    return ids
+
+
+def _check_vars(m, p, atol):
+    """the numpy stand-ins' engines: every model they train has a table and a wide part"""
+    g = m.export_numpy()
+    for f in range(len(p.emb)):
+        assert np.max(np.abs(g["emb"][f] - p.emb[f])) < atol, ("emb", f)
+        assert np.max(np.abs(g["lin_w"][f] - p.lin_w[f])) < atol, ("lin_w", f)
+    for i, (k, b) in enumerate(g["mlp"]):
+        assert np.max(np.abs(k - p.mlp[i][0])) < atol and np.max(np.abs(b - p.mlp[i][1])) < atol, ("mlp", i)
+    assert abs(g["lin_bias"][0] - p.lin_bias[0]) < atol, ("lin_bias", float(g["lin_bias"][0]), float(p.lin_bias[0]))
+
+
+def _compare_vars(m, p, atol):
+    """the HIP engines: a model may lack the table or the wide part, and may have numeric columns"""
+    g = m.export_numpy()
+    for f in range(len(p.emb)):
+        if g["emb"] is not None:
+            assert np.max(np.abs(g["emb"][f] - p.emb[f])) < atol, ("emb", f, float(np.max(np.abs(g["emb"][f] - p.emb[f]))))
+        if g["lin_w"] is not None:
+            assert np.max(np.abs(g["lin_w"][f] - p.lin_w[f])) < atol, ("lin_w", f)
+    for i, (k, b) in enumerate(g["mlp"]):
+        assert np.max(np.abs(k - p.mlp[i][0])) < atol, ("kernel", i, float(np.max(np.abs(k - p.mlp[i][0]))))
+        assert np.max(np.abs(b - p.mlp[i][1])) < atol, ("bias", i)
+    assert abs(g["lin_bias"][0] - p.lin_bias[0]) < atol, ("lin_bias", float(g["lin_bias"][0]), float(p.lin_bias[0]))
+    if "num_emb" in g:
+        assert np.max(np.abs(g["num_emb"] - p.num_emb)) < atol, ("num_emb", float(np.max(np.abs(g["num_emb"] - p.num_emb))))
+        assert np.max(np.abs(g["lin_num"] - p.lin_num)) < atol, ("lin_num", float(np.max(np.abs(g["lin_num"] - p.lin_num))))
+
+
+def _device_relu_masks(m, B):
+    """Which hidden units the device's last train step let through (activation > 0), per hidden layer: read from the
+    stored activations — fp32, or the planes where a layer's output exists as planes only."""
+    out = []
+    for i, h in enumerate(m.hidden):
+        if i in m._acts_in_planes:
+            a = torch.empty(B, h, device="cuda")
+            m.k.mi_merge_rows(m._pl["x%dp" % (i + 1)].struct, B, h, a, h)
+        else:
+            a = m._ws["act%d" % i][:B * h].view(B, h)
+        out.append((a > 0).cpu().numpy())
+    return out
+
+
+# ---- the planes GEMMs -------------------------------------------------------------------------------------------------------
+def row_rel_err(got, ref):
+    """max over rows of max|got - ref| / rms(ref row)  (rows that are exactly zero must match exactly)"""
+    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
+    rms = np.sqrt(np.mean(ref * ref, 1))
+    err = np.abs(got - ref).max(1)
+    z = rms == 0
+    assert np.all(err[z] == 0), ("rows that are zero in the reference", np.flatnonzero(z & (err != 0))[:8].tolist())
+    return float((err[~z] / rms[~z]).max()) if (~z).any() else 0.0
+
+
+def planned_splits(M, N, K):
+    """Split-K slabs of mi_dense_bwd_weight_planes for one job, restated from the library's two launch plans — wgrad_pl.hip's
+    wgrad_pl_plan (LDS-DMA kernel: N = 128 / 256 / 512; at least 32 k-steps of 16 examples per split, one round of
+    workgroups) and gemm.hip's wgrad_splits (register-staged kernel, every other whole-tile shape; at least four k-tiles
+    of 32 examples per split, about two rounds).  One split: the job is `direct` (the GEMM writes dW itself, no fold)."""
+    cdiv = lambda a, b: -(-a // b)
+    if N in (128, 256, 512) and K % 128 == 0 and M % 16 == 0:
+        tiles_k = cdiv(K, 128)
+        target = (512 if N == 128 else 256) // tiles_k
+        target = max(1, min(target, max(M // 512, 1)))
+        k_per_split = cdiv(cdiv(M, target), 16) * 16
+        return cdiv(M, k_per_split)
+    return max(1, min(1024 // (cdiv(K, 128) * cdiv(N, 128)), cdiv(M, 128), 256))
+
+
+# ---- top-K ------------------------------------------------------------------------------------------------------------------
+def host_topk(scores, k, excl_rows):
+    """The header's rule (include/mi355x_rec.h): score descending, equal scores by ascending index, NaN below every number,
+    excluded candidates removed, index -1 / score -inf past the eligible ones; a -0 score comes back as +0"""
+    U, I = scores.shape
+    out_s = np.full((U, k), -np.inf, np.float32)
+    out_i = np.full((U, k), -1, np.int32)
+    for u in range(U):
+        ok = np.setdiff1d(np.arange(I), np.asarray(sorted(excl_rows[u]), np.int64))
+        s = scores[u, ok]
+        order = np.lexsort((ok, np.where(np.isnan(s), np.inf, -s)))[:k]
+        out_s[u, :len(order)] = s[order] + np.float32(0.0)
+        out_i[u, :len(order)] = ok[order]
+    return out_s, out_i
+
+
+# ---- the CLIs: data, exports, sweeps ------------------------------------------------------------------------------------------
+def _write_csv(path, n, seed):
+    """n MovieLens-shaped rows with a learnable rule, in trainers.ml_100k's columns"""
+    from trainers import ml_100k
+    rng = np.random.default_rng(seed)
+    occ = ["technician", "administrator", "student", "homemaker", "none", "engineer"]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(ml_100k.COLUMNS)
+        for _ in range(n):
+            row = {c: (0 if d[0] == 0 else "null") for c, d in zip(ml_100k.COLUMNS, ml_100k.DEFAULTS)}
+            uid, iid = int(rng.integers(1, 944)), int(rng.integers(1, 1683))
+            g = rng.integers(0, 2, len(ml_100k.GENRE))
+            # a learnable rule so that training visibly reduces the loss
+            like = (g[1] == 1) if rng.random() < 0.9 else (g[1] == 0)
+            row.update(user_id=uid, item_id=iid, rating=5 if like else int(rng.integers(1, 5)),
+                       age=int(rng.integers(7, 74)), gender=str(rng.choice(["F", "M", ""])),
+                       occupation=str(rng.choice(occ)), zipcode="%05d" % rng.integers(0, 99999),
+                       release_year=int(rng.integers(1922, 1999)))
+            row.update({k: int(v) for k, v in zip(ml_100k.GENRE, g)})
+            w.writerow([row[c] for c in ml_100k.COLUMNS])
+
+
+def _requests(n=30, seed=2):
+    """the serving receivers' columns of n synthetic rows"""
+    from trainers import ml_100k
+    cols, _ = ml_100k._read_csv("synthetic:%d:%d" % (n, seed))
+    recv = set(ml_100k.serving_input_fn().receiver_tensors)
+    return {k: v for k, v in cols.items() if k in recv}
+
+
+def _train_deep_fm_export(root, name, extra):
+    """ten steps of trainers.deep_fm on the CPU in <root>/<name>: the directory of its exports"""
+    from trainers import _cli, recommend
+    trainer, opt = recommend.MODELS["deep_fm"]
+    job = os.path.join(root, name)
+    argv = ["--synthetic", "300", "--job-dir", job, "--train-steps", "10", "--batch-size", "16", "--device", "cpu"] + list(extra)
+    trainer.train_and_evaluate(_cli.make_parser("deep_fm", opt).parse_args(argv))
+    return os.path.join(job, "export", "exporter")
+
+
+def _fake_sweep(root, exports, order=(1, 0)):
+    """a sweep directory whose sweep.json lists the two exports as members `order`, best first"""
+    job = os.path.join(root, "sweep")
+    os.makedirs(job, exist_ok=True)
+    rows = [{"member": m, "dir": os.path.dirname(os.path.dirname(exports[m])), "export": exports[m], "metrics": {"auc": 0.9 - 0.1 * r}}
+            for r, m in enumerate(order)]
+    with open(os.path.join(job, "sweep.json"), "w") as f:
+        json.dump({"select": "auc", "members": rows}, f)
+    return job
+
+
+def _run_module(mod, args):
+    """python -m <mod> <args> in a fresh process, from the package directory; it must succeed"""
+    env = dict(os.environ)
+    env["PYTHONPATH"] = os.pathsep.join([PKG, ROOT])
+    r = subprocess.run([sys.executable, "-m", mod] + args, cwd=PKG, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return r

@@ -5,7 +5,7 @@ Python + id transforms + the launch-bound step)."""
 import os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "recommender-tensorflow_amd"))
-from tests.test_trainers import _write_csv
+from tests.util import _write_csv
 from trainers import _cli, deep_fm
 import pathlib
 d = pathlib.Path(tempfile.mkdtemp())
