@@ -369,11 +369,20 @@ int32_t mi_sparse_apply_fused(float* table, float* t_slot0, float* t_slot1, floa
  * bit-identical, >= 98 % within 1e-7 relative (measured 96.7 % / 98.7 %; a 1-ulp difference alone is up to 1.19e-7, so
  * "1e-7 for every variable" is NOT claimed): tests/test_hip_kernels.py::test_bounded_catchup_stays_within_its_bound_of_the_sweep.  m, v and the
  * stamps are written exactly as in the exact mode.  7 packed VALU operations per element and step (no transcendental)
- * instead of 16 + 2, and no range conditions.  Needs epsilon >= 1e-30 (otherwise the exact form runs).
+ * instead of 16 + 2, and no range conditions on the state (v = 0, denormal m, any gap).  The bound is a statement about the
+ * HYPERPARAMETERS, though: the bounded form runs where mi_catchup_bounded_runs(beta1, beta2, epsilon) is 1, that is for
+ * 1e-30 <= epsilon <= 1e30, 0 < beta2 <= 1, beta1 >= 0, q = beta1 / sqrt(beta2) < 1 and
+ *   (8 + 2.5 / (1 - q)) * 2^-24 + (1 - sqrt(beta2))^3 <= 2e-6
+ * (the per-step error terms weighted over a replay whose updates shrink by q per step, plus the carried reciprocal's
+ * third-order term: csrc/optim.hip, catchup_bounded_runs).  TF's defaults are inside (beta1 up to 0.9017 at beta2 = 0.999;
+ * beta1 = 0.5 down to beta2 = 0.98); beta1 = 0.9 with beta2 <= 0.99, or beta1 = 0.99, are not.  Outside that region the
+ * flag is IGNORED and the exact form runs — the sweep's bits, error 0 — so the bound above holds wherever the entry
+ * accepts the flag (tests/test_hip_optimizer_hparams.py).
  * MI_CATCHUP_KEEP_STAMPS: the rows' stamps are left as they are (m, v ARE written) — for a model whose tables and wide part
  * follow two different Adam optimizers (two lr_t tables: two calls; the first must not move the stamps the second reads).
  * MI_CATCHUP_LOCAL_ORDER (only together with MI_CATCHUP_BOUNDED | MI_CATCHUP_DEFER_SLOTS, uniq_rows and table; lin_w or not;
- * anything else: MI_ERR_INVALID before any launch): the train step's catch-up in ONE launch.  uniq_rows comes in the
+ * anything else: MI_ERR_INVALID before any launch; so are hyperparameters for which mi_catchup_bounded_runs is 0 — this form
+ * has no exact counterpart to fall back to, the caller runs the ordinary sequence instead): the train step's catch-up in ONE launch.  uniq_rows comes in the
  * sort's row order, NOT ordered by staleness: every workgroup orders windows of up to mi_catchup_local_chunk_rows() of its rows
  * by staleness in LDS (within 1-2 % of the replayed steps per wave of the global order of mi_catchup_rows_by_gap, which
  * is then not needed), replays the wide part's scalars from the very {w, m, v, stamp} records it reads the stamps from
@@ -384,6 +393,9 @@ enum mi_catchup_flags { MI_CATCHUP_DEFER_SLOTS = 1, MI_CATCHUP_BOUNDED = 2, MI_C
  * with n_max slots of which num_uniq hold rows plan[0..2] = {workgroups, chunks per workgroup, rows per chunk}: workgroup g
  * takes the chunks g, g + workgroups, ... of the list; the last chunks may be short or empty. */
 int32_t mi_catchup_local_chunk_rows(void);
+/* 1 where mi_sparse_catchup runs the bounded form when MI_CATCHUP_BOUNDED is set, 0 where it ignores the flag (and refuses
+ * MI_CATCHUP_LOCAL_ORDER): the one definition of the region, for callers that choose between the two sequences (host-side query). */
+int32_t mi_catchup_bounded_runs(float beta1, float beta2, float epsilon);
 int32_t mi_catchup_local_plan(int64_t n_max, int64_t num_uniq, int64_t* plan);
 /* keys[u] = how many steps row uniq_rows[u] will be replayed over by mi_sparse_catchup(step_to) (0..62,
  * clamped), 63 for the slots u >= *num_uniq.  Sorting the rows by it (mi_sort_unique_rows with

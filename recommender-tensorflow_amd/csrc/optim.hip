@@ -354,18 +354,44 @@ __device__ __forceinline__ bool catchup_params_in_range(int steps, float lr_last
 //                                       2^-48 (no systematic drift; rounding noise <= sqrt(j) * 2^-24 rms)
 //   w_j = fma(-u_j, r_j, w_{j-1}), r_j ~ 1 / fma(s0, rho_j, eps)    a reciprocal to <= 1 ulp (the wide part: v_rcp_f32; the rows: carried
 //                                       from step to step and corrected against each d_j, see the row kernel); ONE rounding of w per step, like the reference
-// Per element and step: 4 packed-able VALU operations + 1 transcendental instead of 16 + 2; no range conditions at all
-// (v = 0, denormal m, any gap: the same loop), so no wave ever falls back to a slow generic loop.
+// Per element and step: 4 packed-able VALU operations + 1 transcendental instead of 16 + 2; no range conditions on the
+// STATE (v = 0, denormal m, any gap: the same loop), so no wave ever falls back to a slow generic loop.  The
+// HYPERPARAMETERS do have a region (catchup_bounded_runs below): the error bound is a statement about betas.
 // Error against the reference's literal fp32 sweep, per replayed step j of a row: the update t_j = u_j / (sqrt(v_j) + eps)
 // is reproduced to |t~_j / t_j - 1| <= (2 [the reciprocal: <= 1 ulp] + 2 [s0] + 1 [fma] + 2j [rho chain, worst case; ~sqrt(j)/2
-// rms] + 3 [the reference's own sqrt, add and divide roundings] + j/2 [its v chain]) * 2^-24; the updates decay like
-// 0.9^j, so the sum over a replay is off by <~ 1e-6 of its FIRST update in the worst case and ~1e-7 of it typically —
-// of an update that is itself ~1e-3 |w|.  On top of that comes the rare step in which the difference moves RN(w - t)
-// across a rounding boundary (1 ulp of w each, about one step in 300):
-// tests/test_hip_kernels.py::test_bounded_catchup_stays_within_its_bound_of_the_sweep holds every variable to
-// 3 ulp(w) + 2e-6 * sum_j |t_j| (and >= 98 % of them to 1e-7 relative) after 150-200 replayed steps with (m, v) from the
-// smallest to the largest magnitudes Adam can produce.
+// rms] + 3 [the reference's own sqrt, add and divide roundings] + j/2 [its v chain]) * 2^-24 + e^3 [the rows' carried
+// reciprocal, e = 1 - sqrt(beta2): see the row kernel]; at TF's betas the updates decay like 0.9^j, so the sum over a
+// replay is off by <~ 1e-6 of its FIRST update in the worst case and ~1e-7 of it typically — of an update that is itself
+// ~1e-3 |w|.  On top of that comes the rare step in which the difference moves RN(w - t) across a rounding boundary
+// (1 ulp of w each, about one step in 300): tests/test_hip_kernels.py::test_bounded_catchup_stays_within_its_bound_of_the_sweep
+// and tests/test_hip_optimizer_hparams.py hold every variable to 3 ulp(w) + 2e-6 * sum_j |t_j| (at TF's defaults >= 98 %
+// of them to 1e-7 relative) after 150-200 and 1,030-1,100 replayed steps with (m, v) from the smallest to the largest
+// magnitudes Adam can produce.
 // m and v themselves (written back only without defer_slots) are the exact chains in both modes.
+//
+// WHERE the bounded form runs.  The 2e-6 of that bound is the weighted mean of the per-step error over a replay:
+// consecutive updates shrink by q = beta1 / sqrt(beta2) at least (m by beta1; the denominator by sqrt(beta2) at most — not
+// at all where eps dominates it; lr_t of TF's schedule moves by < 1 / (2t) per step), so sum_j j |t_j| <= sum_j |t_j| / (1 - q)
+// and
+//   sum_j |t~_j - t_j| <= ((8 + 2.5 / (1 - q)) 2^-24 + e^3) sum_j |t_j|,        e = 1 - sqrt(beta2).
+// The form runs where that factor is <= 2e-6 (and q < 1: the updates decay at all).  TF's defaults are inside with little
+// to spare (q = 0.9005: 33.1 of the 33.55 * 2^-24 — the bound was sized for them; measured worst case 0.64 of it, the
+// roundings never all align); beta1 = 0.5 admits beta2 down to 0.98 (e^3 = 1.0e-6); beta1 >= 0.903, or beta1 = 0.9 with
+// beta2 <= 0.99 (e^3 = 1.3e-7 and q = 0.9045), are outside.  Measured on an MI355X BEFORE this region existed, worst
+// |err| / bound over 65,536 elements, gaps 150-200 (profiles/catchup_hparams_region.md): beta2 = 0.98: 1.65, 0.95: 8.0,
+// 0.9: 68, 0.5: 2,730 for the rows — the e^3 of the carried reciprocal — and beta1 = 0.99: 1.9 - 2.7 for the rows, 1.4 -
+// 2.1 for the wide part (v_rcp_f32 every step: the 2.5 j of a replay that decays by 0.99 per step); inside the region
+// the worst is 0.86.  Outside the region MI_CATCHUP_BOUNDED is
+// ignored, as it has always been for epsilon < 1e-30: the exact form runs (its generic loop is the sweep's bits for any
+// betas), and MI_CATCHUP_LOCAL_ORDER, which has no exact form, is refused.  One definition: the launcher and
+// mi_catchup_bounded_runs (what engine._local_catchup asks) call it.
+bool catchup_bounded_runs(float b1, float b2, float eps) {
+  // eps: sqrt(v) + eps must stay a normal number whatever v is (TF's default 1e-8 does), and finite
+  if (!(eps >= 1e-30f && eps <= 1e30f) || !(b2 > 0.f && b2 <= 1.f) || !(b1 >= 0.f)) return false;
+  const double rho = std::sqrt(static_cast<double>(b2)), e = 1.0 - rho, q = static_cast<double>(b1) / rho;
+  if (!(q < 1.0)) return false;
+  return (8.0 + 2.5 / (1.0 - q)) * 0x1p-24 + e * e * e <= 2e-6;
+}
 struct RhoSplit { float hi, lo; };
 __device__ __forceinline__ RhoSplit rho_split(float b2) {
   const double r = sqrt(static_cast<double>(b2));
@@ -561,9 +587,9 @@ __device__ __forceinline__ void replay_row_bounded(const RowReplay& c, const flo
       // (two-element vectors: hipcc then packs the fma of the denominators too; two steps per trip of the loop)
       // The reciprocal is CARRIED from step to step instead of taken anew (round 5): v_rcp_f32 is a transcendental
       // instruction (half rate on gfx950, one element each: tools/probe/valu_cost_probe.hip) — four of them per lane and
-      // step next to ~13 packed / scalar ones.  Consecutive denominators differ by at most 1 - sqrt(beta2) (5e-4) relatively, d_j / d_{j-1} in [sqrt(beta2), 1], so with
+      // step next to ~13 packed / scalar ones.  Consecutive denominators differ by at most 1 - sqrt(beta2) (5e-4 at TF's 0.999) relatively, d_j / d_{j-1} in [sqrt(beta2), 1], so with
       // e = 1 - d_j r_{j-1} (one fma: the exact residual, rounded once) the second-order step r_j = r_{j-1} (1 + e + e^2)
-      // lands within e^3 <= 1.3e-10 of 1 / d_j plus ONE rounding (0.5 ulp — tighter than v_rcp_f32's 1 ulp), and since
+      // lands within e^3 (1.3e-10 at 0.999; catchup_bounded_runs counts it against the bound, which ends the form near beta2 = 0.98) of 1 / d_j plus ONE rounding (0.5 ulp — tighter than v_rcp_f32's 1 ulp), and since
       // every step corrects against its own d_j nothing accumulates.  Three packed full-rate fmas per two elements in place
       // of two v_rcp_f32: 35 instead of 29 + 8 transcendental instructions per two steps.  Measured (same box, alternating,
       // profiles/r05_catchup_reciprocal.md): rows sorted by staleness 0.441 against 0.444 ms alone and the step 2.685
@@ -1150,6 +1176,8 @@ int32_t mi_catchup_gap_keys(const int32_t* uniq_rows, const int32_t* num_uniq, c
 
 int32_t mi_catchup_local_chunk_rows(void) { return kLocalChunk; }
 
+int32_t mi_catchup_bounded_runs(float beta1, float beta2, float epsilon) { return catchup_bounded_runs(beta1, beta2, epsilon) ? 1 : 0; }
+
 int32_t mi_catchup_local_plan(int64_t n_max, int64_t num_uniq, int64_t* plan) {
   MI_REQUIRE(n_max >= 0 && num_uniq >= 0 && num_uniq <= n_max && plan, "catchup_local_plan: n_max=%lld num_uniq=%lld", (long long)n_max, (long long)num_uniq);
   const int64_t G = local_grid(n_max);
@@ -1170,13 +1198,15 @@ int32_t mi_sparse_catchup(float* table, float* t_m, float* t_v, float* lin_w, fl
 
   MI_REQUIRE((flags & ~(MI_CATCHUP_DEFER_SLOTS | MI_CATCHUP_BOUNDED | MI_CATCHUP_KEEP_STAMPS | MI_CATCHUP_LOCAL_ORDER)) == 0, "sparse_catchup: flags=%d", flags);
   const bool local_order = (flags & MI_CATCHUP_LOCAL_ORDER) != 0;
-  MI_REQUIRE(!local_order || (flags == (MI_CATCHUP_LOCAL_ORDER | MI_CATCHUP_BOUNDED | MI_CATCHUP_DEFER_SLOTS) && uniq_rows && num_uniq && table &&
-                              epsilon >= 1e-30f && beta2 > 0.f && beta2 <= 1.f),
+  MI_REQUIRE(!local_order || (flags == (MI_CATCHUP_LOCAL_ORDER | MI_CATCHUP_BOUNDED | MI_CATCHUP_DEFER_SLOTS) && uniq_rows && num_uniq && table),
              "sparse_catchup: MI_CATCHUP_LOCAL_ORDER needs MI_CATCHUP_BOUNDED | MI_CATCHUP_DEFER_SLOTS (and no other flag), uniq_rows and a table (flags=%d)", flags);
+  MI_REQUIRE(!local_order || catchup_bounded_runs(beta1, beta2, epsilon),
+             "sparse_catchup: MI_CATCHUP_LOCAL_ORDER has the bounded form only, which does not run at beta1=%g beta2=%g epsilon=%g (mi_catchup_bounded_runs)",
+             (double)beta1, (double)beta2, (double)epsilon);
   const bool keep_stamps = (flags & MI_CATCHUP_KEEP_STAMPS) != 0;
   const int32_t defer_slots = flags & MI_CATCHUP_DEFER_SLOTS;
-  // the bounded form divides by rcp(sqrt(v) + eps): eps must keep that sum a normal number (TF's default 1e-8 does)
-  const bool bounded = (flags & MI_CATCHUP_BOUNDED) != 0 && epsilon >= 1e-30f && beta2 > 0.f && beta2 <= 1.f;
+  // outside the hyperparameters its error bound was derived for, the flag is ignored: the exact form runs
+  const bool bounded = (flags & MI_CATCHUP_BOUNDED) != 0 && catchup_bounded_runs(beta1, beta2, epsilon);
   if (n_max == 0 || (step_to == 0 && !mi::step_state())) return MI_OK;
   MI_REQUIRE(last_step && lr_table, "sparse_catchup: null buffer");
   MI_REQUIRE(table || lin_w, "sparse_catchup: nothing to update");

@@ -156,6 +156,7 @@ SIGNATURES = {
     "mi_catchup_rows_by_gap": (_i32, [_p, _p, _p, _i64, _i32, _i32, _p, _p, _sz, _p]),
     "mi_catchup_local_chunk_rows": (_i32, []),
     "mi_catchup_local_plan": (_i32, [_i64, _i64, _p]),
+    "mi_catchup_bounded_runs": (_i32, [_f32, _f32, _f32]),
     "mi_sparse_catchup": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p, _f32, _f32,
                                  _f32, _i32, _i32, _i64, _p]),
     "mi_set_gemm_mode": (_i32, [_i32]),

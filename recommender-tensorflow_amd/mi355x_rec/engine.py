@@ -305,7 +305,8 @@ class DeepFM:
     config 3).  "exact": TF's fp32 op sequence, the sweep's bits; "bounded": the same m chain and numerators
     with sqrt(v_j) ~ sqrtf(v_0) beta2^(j/2) and a 1-ulp reciprocal: every variable within 3 ulp + 2e-6 of the movement the
     replay covers (98.7 % of them within 1e-7 relative of the sweep, 96.7 % bit-identical; include/mi355x_rec.h,
-    MI_CATCHUP_BOUNDED), a third of the instructions."""
+    MI_CATCHUP_BOUNDED), a third of the instructions.  That bound holds for betas near TF's defaults; for others
+    (beta2 = 0.9, beta1 = 0.99, ...: _bounded_runs) the library ignores the flag and "bounded" trains with the exact form."""
 
     def __init__(self, vocab_sizes, n_numeric=0, embedding_size=4, hidden_units=(16, 16),
                  use_linear=True, use_mf=True, use_dnn=True, dropout=0.0, optimizer=None,
@@ -1540,9 +1541,19 @@ class DeepFM:
         l_adam = (self.lin_opt or self.opt).name == "Adam" and self.lin_w is not None
         return bool(self.LOCAL_CATCHUP and defer and self.catchup == "bounded" and t_adam and l_adam and self.lin_opt is None
                     and (self.lin_sched is None or self.lin_sched is self.sched)
-                    and self.opt.epsilon >= 1e-30 and 0.0 < self.opt.beta2 <= 1.0      # (where the library runs the bounded form at all)
                     and self.shard is None and self.device.type == "cuda"
-                    and self._wide_on_side_stream(n_max // max(self.F, 1)))
+                    and self._wide_on_side_stream(n_max // max(self.F, 1))
+                    and self._bounded_runs())
+
+    def _bounded_runs(self):
+        """Does the library run the bounded replay at this engine's Adam hyperparameters (mi_catchup_bounded_runs: the one
+        definition of the region)?  Where it does not, mi_sparse_catchup ignores MI_CATCHUP_BOUNDED — catchup="bounded"
+        then trains with the exact form — and refuses MI_CATCHUP_LOCAL_ORDER, so the ordinary sequence runs.  A host-side
+        query, asked once (an engine's optimizer does not change)."""
+        ok = self.__dict__.get("_bounded_ok")
+        if ok is None:
+            ok = self._bounded_ok = bool(self.k.query("mi_catchup_bounded_runs", self.opt.beta1, self.opt.beta2, self.opt.epsilon))
+        return ok
 
     def _side_stream(self):
         side = self._ws.get("side_stream")

@@ -35,6 +35,29 @@ def _numpy_engine(vocab, E, hidden, k=None, lr=0.001, **kw):
                   device="cpu", _kernels=k if k is not None else NumpyKernels(), **kw)
 
 
+# ---- optimizers away from TF's defaults: (name, learning rate, constructor arguments of OO.Hyper and OptimizerSpec alike) --------
+# Every term of the apply rules that vanishes at the defaults is switched on by one of them: Adam's betas and epsilon, the
+# accumulators' initial value, Ftrl's l1 clip and 2 * l2, RMSProp's momentum and decay.
+OPTIMIZER_HPARAM_SETS = [
+    ("Adam", 0.001, dict(beta1=0.5, beta2=0.9, epsilon=1e-3)),
+    ("Adagrad", 0.05, dict(initial_accumulator_value=1e-3)),
+    ("Ftrl", 0.05, dict(l1=0.01, l2=0.0)),
+    ("Ftrl", 0.05, dict(l1=0.0, l2=0.1)),
+    ("Ftrl", 0.05, dict(l1=0.01, l2=0.1, initial_accumulator_value=1.0)),
+    ("RMSProp", 0.05, dict(decay=0.99, momentum=0.9, epsilon=1e-6)),
+]
+OPTIMIZER_HPARAM_IDS = ["%s %s" % (n, " ".join("%s=%g" % kv for kv in kw.items())) for n, _, kw in OPTIMIZER_HPARAM_SETS]
+
+
+def ftrl_gradients(rng, shape, rows=None):
+    """Gradients under which both branches of Ftrl's l1 clip occur in every step: the variables of even rows (`rows`: the row
+    each gradient goes to; None: its own index) get gradients of 1e-4 — their `linear` stays inside [-l1, l1] for
+    l1 = 0.01 over a few steps, the weight is exactly 0 — those of odd rows gradients of order 1."""
+    g = rng.standard_normal(shape).astype(np.float32)
+    g[(np.arange(shape if np.isscalar(shape) else shape[0]) if rows is None else rows) % 2 == 0] *= np.float32(1e-4)
+    return g
+
+
 # ---- the one-launch train step ------------------------------------------------------------------------------------------------
 # Cases whose oracle trajectory keeps every hidden pre-activation at least 1e-6 away from 0 over the five steps (the
 # margin found on the CPU is in the comment; the test asserts it), so that no relu decision can depend on summation order.

@@ -8,6 +8,7 @@ import torch
 
 from oracle import deepfm as O
 from oracle import optimizers as OO
+from tests.cases import OPTIMIZER_HPARAM_IDS, OPTIMIZER_HPARAM_SETS, ftrl_gradients
 from tests.cpu_kernels import NumpyKernels
 from tests.util import _check_vars, _t, make_problem
 
@@ -199,3 +200,69 @@ def test_weights_are_split_once_per_step():
     m.dense.add_(0)
     m._split_weights(True)
     assert calls == ["absmax", "split"] * 4
+
+
+def _segments(rows):
+    """(uniq, seg_start, sorted_entry, num_uniq) of a batch's rows, as mi_sort_unique_rows leaves them"""
+    order = np.argsort(rows, kind="stable").astype(np.int32)
+    uniq, first = np.unique(rows[order], return_index=True)
+    seg = np.concatenate([first, [len(rows)]]).astype(np.int32)
+    return _t(uniq.astype(np.int32)), _t(seg), _t(order), _t(np.array([len(uniq)], np.int32))
+
+
+@pytest.mark.parametrize("name,lr,kw", OPTIMIZER_HPARAM_SETS, ids=OPTIMIZER_HPARAM_IDS)
+def test_numpy_stand_ins_apply_the_oracles_rules_at_other_hyperparameters(name, lr, kw):
+    """tests/cpu_kernels.py's mi_dense_apply, mi_sparse_apply and mi_sparse_catchup, given the mi_opt_hparams struct the
+    engine builds, against oracle/optimizers.py given the Hyper — bit for bit, parameter and both slots, with the terms
+    that vanish at TF's defaults switched on: the CPU engine tests' stand-in cannot drift from the oracle there either."""
+    from mi355x_rec.engine import AdamSchedule, OptimizerSpec
+    f32 = np.float32
+    k = NumpyKernels()
+    hp, spec = OO.Hyper(name, lr=lr, **kw), OptimizerSpec(name, lr, **kw)
+    adam = name == "Adam"
+    # dense
+    rng = np.random.default_rng(21)
+    n = 300
+    w = rng.standard_normal(n).astype(f32)
+    s0, s1 = [a.copy() for a in OO.slot_init(hp, w)]
+    tw, t0, t1 = _t(w.copy()), _t(s0.copy()), _t(s1.copy())
+    powers = OO.AdamPowers(hp, f32) if adam else None
+    for step in range(3):
+        g = ftrl_gradients(rng, n)
+        lr_t = powers.lr_t(hp.lr) if powers else 0.0
+        OO.dense_apply(hp, w, s0, s1, g, lr_t)
+        if powers:
+            powers.finish()
+        k.mi_dense_apply(tw, t0, t1, _t(g), n, spec.hparams(float(lr_t)))
+    for got, exp in ((tw, w), (t0, s0), (t1, s1)):
+        assert np.array_equal(got.numpy().view(np.uint32), exp.view(np.uint32))
+    # sparse: rows sit out steps, duplicates inside a batch
+    rng = np.random.default_rng(4)
+    R, E, steps, nb = 50, 4, 7, 40
+    W, L = rng.standard_normal((R, E)).astype(f32), rng.standard_normal((R, 1)).astype(f32)
+    ws0, ws1 = [a.copy() for a in OO.slot_init(hp, W)]
+    ls0, ls1 = [a.copy() for a in OO.slot_init(hp, L)]
+    tW, tw0, tw1 = _t(W.copy()), _t(ws0.copy()), _t(ws1.copy())
+    tL, tl0, tl1 = _t(L[:, 0].copy()), _t(ls0[:, 0].copy()), _t(ls1[:, 0].copy())
+    last = torch.zeros(R, dtype=torch.int32)
+    powers = OO.AdamPowers(hp, f32) if adam else None
+    sched = AdamSchedule(spec, "cpu", 64) if adam else None
+    for step in range(1, steps + 1):
+        rows = rng.integers(0, R // 2 if step % 2 else R, nb).astype(np.int32)
+        rows[5] = rows[0]; rows[6] = rows[0]
+        g, gl = ftrl_gradients(rng, (nb, E), rows), ftrl_gradients(rng, (nb, 1), rows)
+        lr_t = powers.lr_t(hp.lr) if powers else 0.0
+        OO.sparse_apply(hp, W, ws0, ws1, rows, g, lr_t)
+        OO.sparse_apply(hp, L, ls0, ls1, rows, gl, lr_t)
+        if powers:
+            powers.finish()
+        uq, sg, se, nu = _segments(rows)
+        if adam and step > 1:
+            k.mi_sparse_catchup(tW, tw0, tw1, tL, tl0, tl1, last, uq, nu, nb, E, step - 1, sched.table, hp.beta1, hp.beta2, hp.epsilon)
+        k.mi_sparse_apply(tW, tw0, tw1, tL, tl0, tl1, last if adam else None, uq, sg, se, nu, nb, _t(g), _t(gl[:, 0].copy()), E, step,
+                          spec.hparams(float(lr_t)))
+    if adam:
+        k.mi_sparse_catchup(tW, tw0, tw1, tL, tl0, tl1, last, None, None, R, E, steps, sched.table, hp.beta1, hp.beta2, hp.epsilon)
+    for got, exp in ((tW, W), (tw0, ws0), (tw1, ws1), (tL, L[:, 0]), (tl0, ls0[:, 0]), (tl1, ls1[:, 0])):
+        assert np.array_equal(got.numpy().view(np.uint32), np.ascontiguousarray(exp).view(np.uint32))
+    assert name == "Adagrad" or (ws1.any() and ls1.any())

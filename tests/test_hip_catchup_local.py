@@ -72,19 +72,19 @@ def _device_state(w, m, v, lin, stamps, st):
     return d
 
 
-def _catchup(lib, d, rows, nu, n_max, E, step_to, lr, flags, st, table=True, wide=True):
+def _catchup(lib, d, rows, nu, n_max, E, step_to, lr, flags, st, table=True, wide=True, beta1=0.9, beta2=0.999, eps=1e-8):
     return lib.mi_sparse_catchup(_p(d["w"]) if table else None, _p(d["m"]) if table else None, _p(d["v"]) if table else None,
                                  _p(d["lw"]) if wide else None, _p(d["lm"]) if wide else None, _p(d["lv"]) if wide else None,
-                                 _p(d["last"]), _p(rows), _p(nu), n_max, E, step_to, _p(lr), 0.9, 0.999, 1e-8, flags, st, 0, _st())
+                                 _p(d["last"]), _p(rows), _p(nu), n_max, E, step_to, _p(lr), beta1, beta2, eps, flags, st, 0, _st())
 
 
-def _todays_sequence(lib, d, rows, nu, n_max, E, step_to, lr, st, wide):
+def _todays_sequence(lib, d, rows, nu, n_max, E, step_to, lr, st, wide, **hp):
     by_gap = torch.empty(n_max, dtype=torch.int32, device="cuda")
     ws = torch.empty(lib.mi_sort_unique_workspace_bytes(n_max) + 256, dtype=torch.uint8, device="cuda")
     _chk(lib.mi_catchup_rows_by_gap(_p(rows), _p(nu), _p(d["last"]), n_max, step_to, st, _p(by_gap), _p(ws), ws.numel(), _st()))
     if wide:
-        _chk(_catchup(lib, d, by_gap, nu, n_max, E, step_to, lr, BOUNDED_DEFER, st, table=False))
-    _chk(_catchup(lib, d, by_gap, nu, n_max, E, step_to, lr, BOUNDED_DEFER, st, wide=False))
+        _chk(_catchup(lib, d, by_gap, nu, n_max, E, step_to, lr, BOUNDED_DEFER, st, table=False, **hp))
+    _chk(_catchup(lib, d, by_gap, nu, n_max, E, step_to, lr, BOUNDED_DEFER, st, wide=False, **hp))
 
 
 def _same(a, b):
@@ -112,6 +112,41 @@ def _u_values(ch):
 @pytest.mark.parametrize("E", [64, 8])
 @pytest.mark.parametrize("u_name", ["one", "chunk-1", "chunk", "3chunks+37"])
 def test_local_order_equals_todays_sequence_bitwise(lib, u_name, E, st, wide):
+    _local_order_against_todays_sequence(lib, u_name, E, st, wide)
+
+
+HPARAMS = [dict(beta1=0.5, beta2=0.999, eps=1e-3),          # not TF's defaults, and the library still runs the bounded form
+           dict(beta1=0.9, beta2=0.9, eps=1e-8)]            # outside the bounded form's region (mi_catchup_bounded_runs)
+
+
+@pytest.mark.parametrize("hp", HPARAMS, ids=["bounded runs", "bounded does not run"])
+def test_local_order_at_other_hyperparameters(lib, hp):
+    """Where the library runs the bounded form, the one launch equals the three-call sequence bit for bit at those
+    hyperparameters too.  Where it does not, the sequence's calls ignore MI_CATCHUP_BOUNDED (the exact form runs) and the
+    one launch, which has no exact form, is REFUSED before anything is written: the caller — engine._local_catchup asks
+    mi_catchup_bounded_runs — runs the sequence."""
+    runs = bool(lib.mi_catchup_bounded_runs(hp["beta1"], hp["beta2"], hp["eps"]))
+    assert runs == (hp["beta2"] == 0.999)
+    if runs:
+        _local_order_against_todays_sequence(lib, "chunk", 64, 4, True, **hp)
+        return
+    R, E, st, step_to = 20_000, 64, 4, 1200
+    U = _chunk(lib)
+    w, m, v, lin, stamps, _ = _state(1000 + E + st, R, E, st, step_to)
+    rows_np = np.sort(np.random.default_rng(U + E).choice(R, U, replace=False)).astype(np.int32)
+    rows, nu, lr = dev(rows_np), dev(np.array([U], np.int32)), _lr(step_to)
+    a, b = _device_state(w, m, v, lin, stamps, st), _device_state(w, m, v, lin, stamps, st)
+    before = {k: t.clone() for k, t in b.items()}
+    rc = _catchup(lib, b, rows, nu, U, E, step_to, lr, BOUNDED_DEFER | LOCAL, st, **hp)
+    torch.cuda.synchronize()
+    assert rc == INVALID and b"mi_catchup_bounded_runs" in lib.mi_last_error(), (rc, lib.mi_last_error())
+    _same(before, b)
+    _todays_sequence(lib, a, rows, nu, U, E, step_to, lr, st, True, **hp)      # (taken, and it has work)
+    torch.cuda.synchronize()
+    assert not torch.equal(a["w"], before["w"]) and not torch.equal(a["lw"], before["lw"])
+
+
+def _local_order_against_todays_sequence(lib, u_name, E, st, wide, **hp):
     R, step_to = 20_000, 1200
     U = _u_values(_chunk(lib))[u_name]
     if u_name == "3chunks+37":
@@ -133,8 +168,8 @@ def test_local_order_equals_todays_sequence_bitwise(lib, u_name, E, st, wide):
     nu = dev(np.array([U], np.int32))
     lr = _lr(step_to)
     a, b = _device_state(w, m, v, lin, stamps, st), _device_state(w, m, v, lin, stamps, st)
-    _todays_sequence(lib, a, rows, nu, n_max, E, step_to, lr, st, wide)
-    _chk(_catchup(lib, b, rows, nu, n_max, E, step_to, lr, BOUNDED_DEFER | LOCAL, st, wide=wide))
+    _todays_sequence(lib, a, rows, nu, n_max, E, step_to, lr, st, wide, **hp)
+    _chk(_catchup(lib, b, rows, nu, n_max, E, step_to, lr, BOUNDED_DEFER | LOCAL, st, wide=wide, **hp))
     torch.cuda.synchronize()
     _same(a, b)
     # it had work, and only on the rows of the batch; m, v, stamps as they were
@@ -274,3 +309,29 @@ def test_engine_graph_steps_with_and_without_local_catchup_are_bitwise_the_same(
         assert torch.equal(ln, lo) and torch.equal(gn, go), i
     assert new._graph is not None and old._graph is not None
     _same_variables(new, old)
+
+
+def test_engine_outside_the_bounded_region_trains_with_the_exact_form():
+    """catchup="bounded" with Adam(beta2 = 0.9) — betas the bounded replay's error bound does not cover — at a batch size
+    where the default engine takes the one-launch catch-up: not refused, not the one launch (the library would refuse
+    it), and bit for bit the training of catchup="exact"."""
+    from mi355x_rec.engine import DeepFM, OptimizerSpec
+    vocab, E, hidden, B = [3000] * 4, 16, [32, 16], 4096
+    p, _, _, _ = make_problem(17, vocab, E, hidden, B)
+    ms = []
+    for mode in ("bounded", "exact"):
+        m = DeepFM(vocab, embedding_size=E, hidden_units=hidden, optimizer=OptimizerSpec("Adam", 0.001, beta2=0.9), dropout=0.1, seed=5,
+                   catchup=mode)
+        m.load_oracle_params(p)
+        ms.append(m)
+    bounded, exact = ms
+    rng = np.random.default_rng(9)
+    batches = [dev(np.stack([(rng.integers(0, 6) * 500 + rng.integers(0, 500, B)) for _ in vocab], 1).astype(np.int32)) for _ in range(5)]
+    ys = [dev((rng.random(B) < 0.3).astype(np.uint8)) for _ in range(5)]
+    assert not bounded._bounded_runs() and not bounded._local_catchup(True, batches[0].numel())
+    for i in range(4):
+        lb, gb = bounded.train_step(batches[i], ys[i], next_ids=batches[i + 1])
+        le, ge = exact.train_step(batches[i], ys[i], next_ids=batches[i + 1])
+        assert torch.equal(lb, le) and torch.equal(gb, ge), i
+    _same_variables(bounded, exact)
+    assert bounded.step == 4 and torch.isfinite(bounded.table).all()

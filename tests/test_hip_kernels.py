@@ -13,8 +13,8 @@ import torch
 
 from oracle import deepfm as O
 from oracle import optimizers as OO
-from tests.util import (_chk, _p, _st, dev, dropout_mask, exact_workspace, guarded_nan, guards_intact, max_err_scaled,
-                        workspace_surroundings_intact)
+from tests.util import (_chk, _p, _st, bounded_catchup_error, dev, dropout_mask, exact_workspace, guarded_nan, guards_intact,
+                        max_err_scaled, workspace_surroundings_intact)
 
 pytestmark = pytest.mark.gpu
 
@@ -390,9 +390,10 @@ def test_f16x2_gathered_layer1_matches_materialised_bitwise(lib, B, F, E, N):
     assert np.max(np.abs(dW1.cpu().numpy() - ref)) / (np.sqrt(np.mean(ref * ref)) + 1e-30) < TOL
 
 
-@pytest.mark.parametrize("name", ["Adam", "Ftrl"])
+@pytest.mark.parametrize("name", ["Adam", "Ftrl", "Ftrl l1=0.01 l2=0.1"])
 def test_sparse_apply_fused_equals_bwd_then_apply_bitwise(lib, name):
-    """mi_sparse_apply_fused == mi_embed_fm_linear_bwd followed by mi_sparse_apply, bit for bit."""
+    """mi_sparse_apply_fused == mi_embed_fm_linear_bwd followed by mi_sparse_apply, bit for bit (the third case: with Ftrl's
+    l1 clip and 2 * l2 term switched on)."""
     from mi355x_rec.engine import OptimizerSpec
     rng = np.random.default_rng(4)
     B, F, E = 200, 6, 16
@@ -413,7 +414,7 @@ def test_sparse_apply_fused_equals_bwd_then_apply_bitwise(lib, name):
     sg = torch.empty(n + 1, dtype=torch.int32, device="cuda"); nu = torch.empty(1, dtype=torch.int32, device="cuda")
     wsb = torch.empty(lib.mi_sort_unique_workspace_bytes(n) + 256, dtype=torch.uint8, device="cuda")
     _chk(lib.mi_sort_unique_rows(_p(r), n, R, _p(se), _p(uq), _p(sg), _p(nu), _p(wsb), wsb.numel(), _st()))
-    spec = OptimizerSpec(name, 0.01)
+    spec = OptimizerSpec("Ftrl", 0.01, l1=0.01, l2=0.1) if name.startswith("Ftrl l1") else OptimizerSpec(name, 0.01)
     h = spec.hparams(0.00316)
     a, b = spec.slot_init
     res = []
@@ -618,14 +619,7 @@ def test_bounded_catchup_stays_within_its_bound_of_the_sweep(lib):
                 elw[r] = elw[r] - t; lmoved[r] += abs(t)
 
     def check_w(got, exp, mv, what):
-        d = np.abs(got.astype(np.float64) - exp.astype(np.float64))
-        bound = 3 * np.spacing(np.abs(exp)).astype(np.float64) + 2e-6 * mv
-        worst = float((d / bound).max())
-        same = float((got.view(np.uint32) == exp.view(np.uint32)).mean())
-        within = float((d <= 1e-7 * np.abs(exp)).mean())
-        print("bounded catch-up, %s: worst |err| / (3 ulp + 2e-6 sum|t|) = %.3f, bit-identical %.4f, within 1e-7 relative %.4f, "
-              "max relative error %.3g" % (what, worst, same, within, float((d / np.maximum(np.abs(exp), 1e-30)).max())))
-        assert worst <= 1.0, (what, worst)
+        worst, same, within = bounded_catchup_error(got, exp, mv, what)
         assert same >= 0.95 and within >= 0.98, (what, same, within)
 
     # (a) all rows, slots written (the form that runs before an evaluation / a checkpoint)
@@ -970,6 +964,9 @@ def test_dense_apply_bit_exact(lib, name):
     assert np.array_equal(dw.cpu().numpy(), w)
     if name != "SGD":
         assert np.array_equal(d0.cpu().numpy(), s0)
+    if name in ("Adam", "Ftrl", "RMSProp"):                # v, linear, mom (RMSProp's stays 0 at the default momentum)
+        assert np.array_equal(d1.cpu().numpy(), s1)
+        assert s1.any() or name == "RMSProp"
 
 
 @pytest.mark.parametrize("layout", ["arrays", "records"])

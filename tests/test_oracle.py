@@ -212,3 +212,36 @@ def test_torch_cpu_restatement_matches_numpy_oracle():
         assert np.max(np.abs(st_t.lin_w[f].numpy() - p.lin_w[f])) < 1e-6
     for (k, b), (ko, bo) in zip(st_t.mlp, p.mlp):
         assert np.max(np.abs(k.numpy() - ko)) < 1e-6 and np.max(np.abs(b.numpy() - bo)) < 1e-6
+
+
+def _tf_apply_ftrl(var, accum, linear, g, lr, l1, l2):
+    """training_ops.cc ApplyFtrl at lr_power = -0.5, restated on its own in the form TF writes it: the shrinkage
+    x = sign(linear) l1 - linear behind the test |linear| > l1 (oracle/optimizers.py clips instead)."""
+    new_accum = accum + g * g
+    linear = linear + g - (np.sqrt(new_accum) - np.sqrt(accum)) / lr * var
+    x = np.sign(linear) * l1 - linear
+    y = np.sqrt(new_accum) / lr + 2.0 * l2
+    return np.where(np.abs(linear) > l1, x / y, 0.0), new_accum, linear
+
+
+@pytest.mark.parametrize("l1,l2,iav", [(0.01, 0.0, 0.1), (0.0, 0.1, 0.1), (0.01, 0.1, 1.0), (0.0, 0.0, 0.1)])
+def test_ftrl_with_l1_and_l2_equals_tf_apply_ftrl_in_fp64(l1, l2, iav):
+    """The oracle's Ftrl branch with l1, l2 > 0 against an independent restatement of TF's ApplyFtrl, five steps in fp64:
+    1e-12 relative, and both sides of |linear| <= l1 occur in every step where there is a clip."""
+    from tests.cases import ftrl_gradients
+    rng = np.random.default_rng(5)
+    n, lr = 400, 0.05
+    hp = OO.Hyper("Ftrl", lr, l1=l1, l2=l2, initial_accumulator_value=iav)
+    w = rng.standard_normal(n)
+    a, lin = [s.astype(np.float64) for s in OO.slot_init(hp, w)]
+    assert (a == iav).all() and not lin.any()
+    tw, ta, tl = w.copy(), a.copy(), lin.copy()
+    for step in range(5):
+        g = ftrl_gradients(rng, n).astype(np.float64)
+        OO.dense_apply(hp, w, a, lin, g)
+        tw, ta, tl = _tf_apply_ftrl(tw, ta, tl, g, lr, l1, l2)
+        for got, ref in ((w, tw), (a, ta), (lin, tl)):
+            assert np.max(np.abs(got - ref) / np.maximum(np.abs(ref), 1e-300)) <= 1e-12, step
+        if l1 > 0:
+            inside = np.abs(tl) <= l1
+            assert inside.any() and (~inside).any() and (w[inside] == 0).all() and (w[~inside] != 0).all(), step

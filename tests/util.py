@@ -296,3 +296,51 @@ def _run_module(mod, args):
     r = subprocess.run([sys.executable, "-m", mod] + args, cwd=PKG, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     return r
+
+
+# ---- the lazy Adam catch-up against the literal sweep ----------------------------------------------------------------------------
+def adam_lr_table(lr, beta1, beta2, n):
+    """lr_t of steps 0 .. n (index 0 unused) of TF's schedule lr sqrt(1 - beta2^t) / (1 - beta1^t) for the fp32 betas, as
+    float32: an INPUT of mi_sparse_catchup (the tests of the replay do not depend on how it was rounded)"""
+    t = np.arange(n + 1)
+    b1, b2 = float(np.float32(beta1)), float(np.float32(beta2))
+    return (lr * np.sqrt(1 - b2 ** t) / np.maximum(1 - b1 ** t, 1e-30)).astype(np.float32)
+
+
+def catchup_sweep(w, m, v, last, step_to, lr, beta1, beta2, eps):
+    """TF Adam's whole-table sweep over the steps a row sat out, in numpy fp32 (IEEE sqrt and divide, one rounding per
+    operation, denormals kept): for s in (last[r], step_to]: m *= b1; v *= b2; w -= (lr[s] m) / (sqrt(v) + eps), for the
+    rows with 0 < last[r] < step_to — one pass over the steps with a mask s > last[r], every row at once.  w, m, v: [R] or
+    [R, E].  Returns (w, m, v, sum_j |t_j| in fp64); the inputs are not written."""
+    f = np.float32
+    b1, b2, eps = f(beta1), f(beta2), f(eps)
+    ew, em, ev = w.copy(), m.copy(), v.copy()
+    moved = np.zeros(w.shape, np.float64)
+    col = last.reshape((-1,) + (1,) * (w.ndim - 1))
+    live = col > 0
+    if not (live & (col < step_to)).any():
+        return ew, em, ev, moved
+    with np.errstate(all="ignore"):
+        for s in range(int(last[(last > 0) & (last < step_to)].min()) + 1, step_to + 1):
+            on = live & (s > col)
+            mm, vv = em * b1, ev * b2
+            t = (lr[s] * mm) / (np.sqrt(vv) + eps)
+            em, ev, ew = np.where(on, mm, em), np.where(on, vv, ev), np.where(on, ew - t, ew)
+            moved += np.where(on, np.abs(t), 0.0)
+    assert ew.dtype == em.dtype == ev.dtype == np.float32, "the sweep left fp32"
+    return ew, em, ev, moved
+
+
+def bounded_catchup_error(got, exp, moved, what, check=True):
+    """MI_CATCHUP_BOUNDED's contract (include/mi355x_rec.h) for every variable: |w - w_sweep| <= 3 ulp(w) + 2e-6 sum_j |t_j|.
+    Prints and returns (worst |err| / bound, share bit-identical, share within 1e-7 relative); asserts the bound unless
+    check is False (a tool that only measures)."""
+    d = np.abs(got.astype(np.float64) - exp.astype(np.float64))
+    bound = 3 * np.spacing(np.abs(exp)).astype(np.float64) + 2e-6 * moved
+    worst = float((d / bound).max())
+    same = float((got.view(np.uint32) == exp.view(np.uint32)).mean())
+    within = float((d <= 1e-7 * np.abs(exp)).mean())
+    print("bounded catch-up, %s: worst |err| / (3 ulp + 2e-6 sum|t|) = %.3f, bit-identical %.4f, within 1e-7 relative %.4f, "
+          "max relative error %.3g" % (what, worst, same, within, float((d / np.maximum(np.abs(exp), 1e-30)).max())))
+    assert not check or worst <= 1.0, (what, worst)
+    return worst, same, within
