@@ -771,6 +771,36 @@ int32_t mi_pair_topk_group(const mi_rank_member_t* members, int32_t n_members, i
                            const int32_t* excl_idx, int32_t k, float* top_score, int32_t* top_idx, float* scores,
                            float* member_scores, void* workspace, size_t workspace_bytes, mi_stream_t stream);
 
+/* ---- exact ranks of named candidates, every member for itself, one launch (csrc/rank.hip) ---------------------------
+ * For M models, U queries and up to Tq named target candidates per query, where each target stands among ALL eligible
+ * candidates of its query in each model's own order — the [U, I] pair matrix never leaves the chip.  For member m, query
+ * q and target t = targets[q, j]:
+ *   ranks[m, q, j] = #{c in [0, I), c != t, c not excluded for q : key(z_m(q, c), c) > key(z_m(q, t), t)}
+ * with mi_pair_topk's order as the key (score descending, equal scores by ascending index, NaN below every number, -0 as
+ * +0) and z_m bit for bit the score mi_pair_topk gives member m: the 0-based position t would take in that member's
+ * mi_pair_topk list were k unbounded.  ranks[m, q, j] = -1 where t < 0 (padding), t >= I or t is excluded for q.  Other
+ * targets of the query count as ordinary candidates; duplicate targets each get their own, equal, answer.
+ *   members, n_members, U, I, excl_off, excl_idx: as mi_pair_topk_group (same scope: the VALU pair path; same checks and
+ *     messages, prefixed "member i:").
+ *   targets [U, Tq] int32 (device), 1 <= Tq <= MI_PAIR_RANKS_MAX_TARGETS.
+ * Outputs: ranks [M, U, Tq] int32; target_scores [M, U, Tq] (optional, NULL to skip): the bits of z_m(q, t), the canonical
+ *   quiet NaN where the rank is -1.
+ * workspace: mi_pair_target_ranks_workspace_bytes(members, n_members, U, I, Tq) (only H1 and E of a member are read; 0
+ *   for arguments out of range) — the member table, the transposes, the exclusion mask and the splits' partial counts.
+ * Launches: the member table (through the kernel arguments), one transpose launch, the exclusion mask, ONE scoring and
+ *   counting launch over (query blocks) x (candidate splits) x (members) and the sum of the splits' counts; no copy, no
+ *   synchronisation.  The counts are integers written plainly and added in a second launch: the result depends neither on
+ *   the split count nor on timing, and no workgroup waits for another.
+ * Refused on the host before anything is launched: n_members < 1 (MI_ERR_INVALID) or above
+ *   MI_PAIR_TOPK_GROUP_MAX_MEMBERS (MI_ERR_UNSUPPORTED), Tq outside [1, MI_PAIR_RANKS_MAX_TARGETS], NULL targets / ranks,
+ *   excl_off without excl_idx (MI_ERR_INVALID), a member outside the scope (MI_ERR_UNSUPPORTED) or failing mi_pair_topk's
+ *   checks, a short workspace (MI_ERR_INVALID). */
+#define MI_PAIR_RANKS_MAX_TARGETS 64 /* per query and call */
+size_t mi_pair_target_ranks_workspace_bytes(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, int32_t Tq);
+int32_t mi_pair_target_ranks(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, const int64_t* excl_off,
+                             const int32_t* excl_idx, const int32_t* targets, int32_t Tq, int32_t* ranks, float* target_scores,
+                             void* workspace, size_t workspace_bytes, mi_stream_t stream);
+
 /* ---- serving: the forward of a request batch as one launch (csrc/serve.hip) ---------------------------------------
  * For B requests, what DeepFM.predict_logits followed by mi_binary_predictions computes (deep_fm.py:36-125 in PREDICT
  * mode, model_utils.py:9-20; the requests of ml_100k.py:64-88's receiver after the columns' id transforms):

@@ -16,6 +16,9 @@
 //                      sorted top-K list in LDS; a candidate that does not beat the list's K-th key is rejected by one
 //                      64-bit compare, survivors are appended and merged into the list in batches (rank merge).
 //   topk_merge_k       one workgroup per query: the splits' partial lists merged into the final [U, K].
+//   pair_target_ranks_k  grid (query blocks) x (candidate splits) x (members): the exact rank of named target candidates
+//                      by each member's own score — the targets' keys in LDS, the candidate loop above, integer counters;
+//                      rank_sum_k adds the splits' counts (mi_pair_target_ranks).
 //
 // Order: one 64-bit key per (score, candidate): the score's bits made monotone in the high word (NaN -> 0, below every
 // number; -0 as +0, and returned as +0), the complemented index in the low word, so "larger key" = higher score, then lower index.  Key 0 is
@@ -466,6 +469,88 @@ __global__ __launch_bounds__(kThreads) void pair_score_topk_group_k(const GroupM
   }
 }
 
+// ---- exact ranks of named targets, every member for itself (mi_pair_target_ranks) ----------------------------------
+// Grid (query blocks of 32) x (candidate splits) x (members).  A workgroup first scores its 32 queries' targets with its
+// member's pair_score (the candidate differs per lane: a_c, s_c and w_c become per-lane loads) and keeps their keys in LDS,
+// then runs pair_score_topk_k's candidate loop over its chunk — a wave scores ONE candidate against the 32 queries — and
+// counts, per target of the query, whether the candidate's key is larger.  Keys of one query are distinct and a target's
+// own pair scores to the target's own bits, so the count never includes the target.
+//   tkey [Tq][kQB]          the targets' keys; ~0 (above every key) where the target has no rank
+//   cnt  [kWaves][Tq][kQB]  one set of counters per wave: lane (col, h) alone adds to targets j = h, h + 2, ... of query
+//                           col in its wave's set, so the adds are plain LDS read-modify-writes — no atomics, no barrier in
+//                           the candidate loop, and the idle half of the VALU path's wave does half of the compares
+// The split's counts go plainly to part [M][splits][U][Tq] (-1: no rank); rank_sum_k adds the splits.  Integers only: the
+// result depends neither on the split count nor on timing, and no workgroup waits for another.
+constexpr uint64_t kNoRank = ~static_cast<uint64_t>(0);
+
+__global__ __launch_bounds__(kThreads) void pair_target_ranks_k(const GroupMember* __restrict__ tab,
+                                                               const uint32_t* __restrict__ excl,
+                                                               const int32_t* __restrict__ targets,
+                                                               float* __restrict__ target_scores, int32_t* __restrict__ part,
+                                                               int64_t U, int64_t I, int64_t chunk, int Tq, int splits, int words) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  uint64_t* tkey = reinterpret_cast<uint64_t*>(lds);             // [Tq][kQB]
+  int* cnt = reinterpret_cast<int*>(tkey + Tq * kQB);             // [kWaves][Tq][kQB]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31, h = lane >> 5;
+  const int64_t q0 = static_cast<int64_t>(blockIdx.x) * kQB;
+  const int split = blockIdx.y, m = blockIdx.z;
+  const int64_t c_begin = split * chunk;
+  const int64_t c_end = c_begin + chunk < I ? c_begin + chunk : I;
+  const PairArgs p = load_member(tab + m);
+  const int64_t q = q0 + col;
+  const bool q_ok = q < U;
+  const float wq = (p.w_q && q_ok) ? p.w_q[q] : 0.f;
+  const float* __restrict__ sq = p.sqT ? p.sqT + q0 + col : nullptr;
+  for (int i = tid; i < kWaves * Tq * kQB; i += kThreads) cnt[i] = 0;
+  // the targets: thread (col, j0 = tid / 32) takes targets j0, j0 + 8, ... of query col
+  for (int j = tid >> 5; j < Tq; j += kThreads / kQB) {
+    uint64_t key = kNoRank;
+    float s = __uint_as_float(0x7fc00000u);
+    if (q_ok) {
+      const int64_t t = targets[q * Tq + j];
+      if (t >= 0 && t < I && !(excl && ((excl[q * words + (t >> 5)] >> (t & 31)) & 1u))) {
+        s = pair_score<false, 1, 1>(p, t, q0 + col, 0, wq, sq);
+        key = rank_key(s, static_cast<uint32_t>(t));
+      }
+      if (split == 0 && target_scores) target_scores[(static_cast<int64_t>(m) * U + q) * Tq + j] = s;
+    }
+    tkey[j * kQB + col] = key;
+  }
+  __syncthreads();
+  int* mine = cnt + wave * Tq * kQB + col;
+  for (int64_t c = c_begin + wave; c < c_end; c += kWaves) {     // (c is wave-uniform)
+    const float s = pair_score<false, 1, 1>(p, c, q0 + col, h, wq, sq);
+    if (q_ok && !(excl && ((excl[q * words + (c >> 5)] >> (c & 31)) & 1u))) {
+      const uint64_t key = rank_key(s, static_cast<uint32_t>(c));
+      for (int j = h; j < Tq; j += 2) mine[j * kQB] += key > tkey[j * kQB + col];
+    }
+  }
+  __syncthreads();
+  // thread i = (query i / Tq, target i % Tq): the block's rows of part are contiguous
+  int32_t* out = part + ((static_cast<int64_t>(m) * splits + split) * U + q0) * Tq;
+  const int64_t rows = U - q0 < kQB ? U - q0 : kQB;
+  for (int i = tid; i < rows * Tq; i += kThreads) {
+    const int qq = i / Tq, j = i - qq * Tq, at = j * kQB + qq;
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) n += cnt[w * Tq * kQB + at];
+    out[i] = tkey[at] == kNoRank ? -1 : n;
+  }
+}
+
+// ranks[m][e] = the sum over the splits of part[m][split][e], -1 where the target has no rank; n = U * Tq, grid (blocks, M)
+__global__ __launch_bounds__(256) void rank_sum_k(const int32_t* __restrict__ part, int splits, int64_t n,
+                                                  int32_t* __restrict__ ranks) {
+  const int64_t m = blockIdx.y;
+  const int32_t* __restrict__ src = part + m * splits * n;
+  for (int64_t e = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; e < n; e += static_cast<int64_t>(gridDim.x) * 256) {
+    int32_t r = src[e];
+    if (r >= 0)
+      for (int s = 1; s < splits; ++s) r += src[s * n + e];
+    ranks[m * n + e] = r;
+  }
+}
+
 // one workgroup per query: entry (s, j) of the partial lists has rank j + (entries of the other lists above it)
 __global__ __launch_bounds__(256) void topk_merge_k(const uint64_t* __restrict__ part, int splits, int K,
                                                     float* __restrict__ top_score, int32_t* __restrict__ top_idx) {
@@ -675,6 +760,40 @@ GroupPlan make_group_plan(const mi_rank_member_t* members, int32_t n, int64_t U,
   return gp;
 }
 
+// mi_pair_target_ranks: make_plan's split rule — at least 64 candidates per split, about kTargetBlocks workgroups — over
+// query blocks x members (no selection lists: nothing else bounds the splits), and the workspace: the exclusion mask, the
+// splits' partial counts, the member table and the members' transposes.  pl: what side_bytes and the table need of a Plan.
+struct RanksPlan {
+  Plan pl;
+  size_t off_mask, off_part, off_table, off_sides, total;
+};
+
+bool ranks_sizes_ok(const mi_rank_member_t* members, int32_t n, int64_t U, int64_t I, int32_t Tq) {
+  return Tq >= 1 && Tq <= MI_PAIR_RANKS_MAX_TARGETS && group_sizes_ok(members, n, U, I, 1);
+}
+
+RanksPlan make_ranks_plan(const mi_rank_member_t* members, int32_t n, int64_t U, int64_t I, int32_t Tq) {
+  RanksPlan rp{};
+  Plan& pl = rp.pl;
+  pl.qblocks = mi::ceil_div(U, kQB);
+  pl.Upad = pl.qblocks * kQB;
+  int64_t s = mi::ceil_div(kTargetBlocks, pl.qblocks * n);
+  const int64_t s_min_chunk = mi::ceil_div(I, 64);
+  if (s > s_min_chunk) s = s_min_chunk;
+  if (s < 1) s = 1;
+  pl.chunk = mi::ceil_div(I, s);
+  pl.splits = static_cast<int32_t>(mi::ceil_div(I, pl.chunk));
+  pl.words = static_cast<int32_t>(mi::ceil_div(I, 32));
+  size_t o = 0;
+  rp.off_mask = o; o += align256(sizeof(uint32_t) * static_cast<size_t>(U) * pl.words);
+  rp.off_part = o; o += align256(sizeof(int32_t) * static_cast<size_t>(n) * pl.splits * U * Tq);
+  rp.off_table = o; o += align256(sizeof(GroupMember) * static_cast<size_t>(n));
+  rp.off_sides = o;
+  for (int32_t i = 0; i < n; ++i) o += side_bytes(pl, members[i].H1, members[i].E);
+  rp.total = o;
+  return rp;
+}
+
 template <bool MFMA, int NP, int NQ>
 int32_t launch_pair(const PairArgs& a, dim3 grid, size_t lds, hipStream_t st) {
   const int32_t rl = mi::raise_lds(&pair_score_topk_k<MFMA, NP, NQ>, lds, "pair_topk");
@@ -830,6 +949,91 @@ int32_t mi_pair_topk_group(const mi_rank_member_t* members, int32_t n_members, i
   topk_merge_k<<<dim3(static_cast<unsigned>(U)), dim3(256), sizeof(uint64_t) * pl.splits * k, st>>>(part, pl.splits, k,
                                                                                                     top_score, top_idx);
   MI_CHECK_LAUNCH("topk_merge_k");
+  return MI_OK;
+}
+
+size_t mi_pair_target_ranks_workspace_bytes(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, int32_t Tq) {
+  if (!ranks_sizes_ok(members, n_members, U, I, Tq)) return 0;
+  return make_ranks_plan(members, n_members, U, I, Tq).total;
+}
+
+int32_t mi_pair_target_ranks(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, const int64_t* excl_off,
+                             const int32_t* excl_idx, const int32_t* targets, int32_t Tq, int32_t* ranks, float* target_scores,
+                             void* workspace, size_t workspace_bytes, mi_stream_t stream) {
+  MI_REQUIRE(n_members >= 1, "pair_target_ranks: %d members (at least 1)", n_members);
+  if (n_members > MI_PAIR_TOPK_GROUP_MAX_MEMBERS)
+    return unsupported("pair_target_ranks: %d members (at most %d in one launch)", n_members, MI_PAIR_TOPK_GROUP_MAX_MEMBERS);
+  MI_REQUIRE(members, "pair_target_ranks: members");
+  MI_REQUIRE(Tq >= 1 && Tq <= MI_PAIR_RANKS_MAX_TARGETS, "pair_target_ranks: Tq=%d targets per query (1 to %d in one call)", Tq,
+             MI_PAIR_RANKS_MAX_TARGETS);
+  MI_REQUIRE(targets && ranks, "pair_target_ranks: targets / ranks");
+  MI_REQUIRE(!excl_off == !excl_idx, "pair_target_ranks: excl_off and excl_idx go together");
+  // every member is checked before anything is launched
+  for (int32_t i = 0; i < n_members; ++i) {
+    const mi_rank_member_t& m = members[i];
+    LayerTable lt{};
+    int maxw = 0;
+    const int32_t rc = check_model(U, I, 1, m.a_q, m.s_q, m.a_c, m.s_c, m.H1, m.E, m.dense, m.layer_off, m.widths, m.n_layers,
+                                   m.activation, true, true, lt, maxw);
+    if (rc != MI_OK) {
+      mi::member_error("pair_target_ranks", i);
+      return rc;
+    }
+    if (takes_mfma(m.n_layers, maxw))
+      return unsupported("pair_target_ranks: member %d: %d layers after layer 1 with a hidden width of %d: the kernel takes the "
+                         "VALU pair path only (fewer than two layers after layer 1, or every hidden width after layer 1 below "
+                         "%d)", i, m.n_layers, maxw, kValuW);
+  }
+  const RanksPlan rp = make_ranks_plan(members, n_members, U, I, Tq);
+  const Plan& pl = rp.pl;
+  MI_REQUIRE(workspace && workspace_bytes >= rp.total, "pair_target_ranks: workspace %zu < %zu bytes", workspace_bytes, rp.total);
+  hipStream_t st = mi::as_stream(stream);
+  char* ws = static_cast<char*>(workspace);
+  GroupMember* tab = reinterpret_cast<GroupMember*>(ws + rp.off_table);
+  uint32_t* mask = excl_off ? reinterpret_cast<uint32_t*>(ws + rp.off_mask) : nullptr;
+  int32_t* part = reinterpret_cast<int32_t*>(ws + rp.off_part);
+  auto blocks = [](int64_t n) { const int64_t b = mi::ceil_div(n, 256); return static_cast<unsigned>(b < 2048 ? b : 2048); };
+  // the member table, as mi_pair_topk_group writes it (the selection's fields of PairArgs stay zero: nothing here reads them)
+  size_t side = rp.off_sides;
+  int maxside = 0;
+  MemberChunk ch{};
+  for (int32_t i = 0; i < n_members; ++i) {
+    const mi_rank_member_t& m = members[i];
+    GroupMember& gm = ch.m[i % kTabChunk];
+    gm = GroupMember{};
+    for (int j = 0; j < m.n_layers; ++j)
+      gm.l[j] = Layer{m.layer_off[2 * j], m.layer_off[2 * j + 1], m.widths[j], m.widths[j + 1]};
+    PairArgs& a = gm.p;
+    a.aqT = m.H1 ? reinterpret_cast<float*>(ws + side) : nullptr;
+    a.sqT = m.E ? reinterpret_cast<float*>(ws + side + align256(sizeof(float) * static_cast<size_t>(m.H1) * pl.Upad)) : nullptr;
+    side += side_bytes(pl, m.H1, m.E);
+    a.a_c = m.a_c; a.s_c = m.s_c; a.w_q = m.w_q; a.w_c = m.w_c; a.dense = m.dense;
+    a.l = tab[i].l;                              // (the address of this member's layers in the workspace)
+    a.U = U; a.I = I;
+    a.Upad = static_cast<int32_t>(pl.Upad); a.H1 = m.H1; a.E = m.E; a.act = m.activation; a.n_layers = m.n_layers;
+    gm.a_q = m.a_q; gm.s_q = m.s_q;
+    if (m.H1 > maxside) maxside = m.H1;
+    if (m.E > maxside) maxside = m.E;
+    if (i % kTabChunk == kTabChunk - 1 || i + 1 == n_members) {
+      const int first = i - i % kTabChunk;
+      member_table_k<<<dim3(1), dim3(64), 0, st>>>(ch, i - first + 1, tab + first);
+    }
+  }
+  if (maxside)
+    transpose_pad_group_k<<<dim3(blocks(static_cast<int64_t>(maxside) * pl.Upad), static_cast<unsigned>(n_members), 2), dim3(256), 0,
+                            st>>>(tab, U);
+  if (mask) {
+    zero_u32_k<<<dim3(blocks(U * pl.words)), dim3(256), 0, st>>>(mask, U * pl.words);
+    excl_mask_k<<<dim3(static_cast<unsigned>(U)), dim3(256), 0, st>>>(excl_off, excl_idx, I, pl.words, mask);
+  }
+  MI_CHECK_LAUNCH("pair_target_ranks (prepare)");
+  const size_t lds = (sizeof(uint64_t) + sizeof(int) * kWaves) * kQB * static_cast<size_t>(Tq);      // at most 48 KB
+  pair_target_ranks_k<<<dim3(static_cast<unsigned>(pl.qblocks), static_cast<unsigned>(pl.splits), static_cast<unsigned>(n_members)),
+                        dim3(kThreads), lds, st>>>(tab, mask, targets, target_scores, part, U, I, pl.chunk, Tq, pl.splits, pl.words);
+  MI_CHECK_LAUNCH("pair_target_ranks_k");
+  const int64_t n = U * Tq;
+  rank_sum_k<<<dim3(blocks(n), static_cast<unsigned>(n_members)), dim3(256), 0, st>>>(part, pl.splits, n, ranks);
+  MI_CHECK_LAUNCH("rank_sum_k");
   return MI_OK;
 }
 

@@ -1389,6 +1389,51 @@ class DeepFM:
             return "a hidden layer of %d units after the first (below %d)" % (max(after), self.TOP_K_GROUP_MAX_WIDTH)
         return None
 
+    def target_ranks(self, query_ids, candidate_ids, query_fields, targets, query_x=None, candidate_x=None, exclude=None,
+                     return_scores=False, mode="auto"):
+        """The exact 0-based rank of named target candidates among ALL eligible candidates of their query, in top_k's order
+        (mi_pair_target_ranks, include/mi355x_rec.h): the position a target would take in top_k's list were k unbounded.
+        Arguments as top_k; targets: a CSR pair (offsets [U + 1], indices) or one sequence of candidate indices per query,
+        in any order, duplicates kept.  Returns ranks int32 [U, Tmax] (Tmax = the longest row), -1 for padding, for a
+        target outside [0, I) and for a target excluded for its query — plus the targets' logits float32 [U, Tmax] (NaN
+        where the rank is -1) when return_scores.
+        mode "fused": the counting launch (a group of one; ValueError naming the limit for a model outside its scope);
+        "auto": that launch inside its scope, otherwise the same integers from this model's own top_k(return_scores=True)
+        matrix by key comparisons in torch on the device."""
+        if mode not in ("auto", "fused"):
+            raise ValueError("mode must be 'auto' or 'fused'")
+        why = self._top_k_group_limit()
+        if why is None:
+            out = target_ranks_group([self], query_ids, candidate_ids, query_fields, targets, query_x, candidate_x, exclude,
+                                     return_scores)
+            return (out[0][0], out[1][0]) if return_scores else out[0]
+        if mode == "fused":
+            raise ValueError("target_ranks: mode='fused': the model has %s" % why)
+        _, U, I, _ = self._top_k_check(query_ids, candidate_ids, query_fields, 1, query_x, candidate_x)
+        tg = torch.from_numpy(dense_targets(targets, U, I)).to(self.device).long()
+        z = self.top_k(query_ids, candidate_ids, query_fields, 1, query_x, candidate_x, return_scores=True)[2]
+        # rank_key's high word as an int64 (NaN -> 0, -0 as +0); equal words are decided by the lower index
+        bits = z.view(torch.int32).long() & 0xffffffff
+        word = torch.where(bits >= 0x80000000, 0xffffffff - bits, bits + 0x80000000)
+        word = torch.where(z != z, torch.zeros_like(word), torch.where(z == 0, torch.full_like(word, 0x80000000), word))
+        ok = torch.ones(U, I, dtype=torch.bool, device=self.device)
+        if exclude is not None:
+            off, idx = self._top_k_exclusions(exclude, U, I)
+            rows = torch.repeat_interleave(torch.arange(U, device=self.device), off[1:] - off[:-1])
+            ok[rows, idx[:rows.numel()].long()] = False
+        ranks = torch.full(tuple(tg.shape), -1, dtype=torch.int32, device=self.device)
+        scores = torch.full(tuple(tg.shape), float("nan"), dtype=torch.float32, device=self.device)
+        cand = torch.arange(I, device=self.device)[None, :]
+        for j in range(tg.shape[1]):
+            t = tg[:, j]
+            tc = t.clamp(min=0)[:, None]
+            has = (t >= 0) & torch.gather(ok, 1, tc)[:, 0]
+            wt = torch.gather(word, 1, tc)
+            above = ok & ((word > wt) | ((word == wt) & (cand < tc)))
+            ranks[:, j] = torch.where(has, above.sum(1), torch.full_like(t, -1)).to(torch.int32)
+            scores[:, j] = torch.where(has, torch.gather(z, 1, tc)[:, 0], scores[:, j])
+        return (ranks, scores) if return_scores else ranks
+
     def _side_tensors(self, cat, num, ids, x, candidate):
         """One side of top_k: (a [n, H1] or None, s [n, E] or None, w [n] or None) with the model's own kernels — the
         gather (s, fm, lin and the side's concat), the numeric columns, layer 1 on the side's rows of kernel_0 (identity
@@ -2149,6 +2194,16 @@ class DeepFM:
 
 
 # ---------------------------------------------------------------------- top-K recommendation with an ensemble
+def _rank_members(engines, args):
+    """the mi_rank_member_t array of the engines and their _top_k_sides (which own the tensors it points to)"""
+    members = (_lib.RankMember * len(engines))()
+    for m, e, a in zip(members, engines, args):
+        _lib.set_ptrs(m, a_q=a["a_q"], s_q=a["s_q"], w_q=a["w_q"], a_c=a["a_c"], s_c=a["s_c"], w_c=a["w_c"], dense=e.dense,
+                      layer_off=a["layer_off"], widths=a["widths"])
+        m.H1, m.E, m.n_layers, m.activation = a["H1"], a["E"], a["n_layers"], e.act
+    return members
+
+
 def top_k_group(engines, query_ids, candidate_ids, query_fields, k, query_x=None, candidate_x=None, exclude=None,
                 return_scores=False, return_member_scores=False):
     """DeepFM.top_k for the MEAN logit of several engines over one set of feature columns (mi_pair_topk_group,
@@ -2163,11 +2218,7 @@ def top_k_group(engines, query_ids, candidate_ids, query_fields, k, query_x=None
     sides, U, I, k = lead._top_k_check(query_ids, candidate_ids, query_fields, k, query_x, candidate_x)
     excl_off, excl_idx = lead._top_k_exclusions(exclude, U, I) if exclude is not None else (None, None)
     args = [e._top_k_sides(sides) for e in engines]          # (kept alive until the launch is enqueued)
-    members = (_lib.RankMember * M)()
-    for m, e, a in zip(members, engines, args):
-        _lib.set_ptrs(m, a_q=a["a_q"], s_q=a["s_q"], w_q=a["w_q"], a_c=a["a_c"], s_c=a["s_c"], w_c=a["w_c"], dense=e.dense,
-                      layer_off=a["layer_off"], widths=a["widths"])
-        m.H1, m.E, m.n_layers, m.activation = a["H1"], a["E"], a["n_layers"], e.act
+    members = _rank_members(engines, args)
     dev, k_ = lead.device, lead.k
     top_score = torch.empty(U, k, dtype=torch.float32, device=dev)
     top_idx = torch.empty(U, k, dtype=torch.int32, device=dev)
@@ -2181,3 +2232,58 @@ def top_k_group(engines, query_ids, candidate_ids, query_fields, k, query_x=None
     if return_member_scores:
         out += (member_scores,)
     return out
+
+
+# ---------------------------------------------------------------------- exact ranks of named targets, member by member
+def dense_targets(targets, U, I):
+    """target_ranks' targets argument — a CSR pair (offsets [U + 1], indices) or one sequence of candidate indices per query,
+    order and duplicates kept — as int32 [U, Tmax] padded with -1 (Tmax = the longest row); an index outside [0, I) becomes
+    -1 too: it has no rank"""
+    if isinstance(targets, tuple) and len(targets) == 2:
+        off = np.asarray(targets[0].cpu() if isinstance(targets[0], torch.Tensor) else targets[0], np.int64)
+        idx = np.asarray(targets[1].cpu() if isinstance(targets[1], torch.Tensor) else targets[1], np.int64).reshape(-1)
+    else:
+        rows = [np.asarray([int(c) for c in r], np.int64) for r in targets]
+        if len(rows) != U:
+            raise ValueError("targets: %d rows for %d queries" % (len(rows), U))
+        off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+        idx = np.concatenate(rows + [np.zeros(0, np.int64)])
+    if off.shape != (U + 1,) or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != idx.size:
+        raise ValueError("targets: offsets must be a non-decreasing [U + 1] array from 0 to len(indices)")
+    n = np.diff(off)
+    out = np.full((U, int(n.max()) if U else 0), -1, np.int32)
+    col = np.arange(idx.size) - np.repeat(off[:-1], n)
+    out[np.repeat(np.arange(U), n), col] = np.where((idx >= 0) & (idx < I), idx, -1)
+    return out
+
+
+def target_ranks_group(engines, query_ids, candidate_ids, query_fields, targets, query_x=None, candidate_x=None, exclude=None,
+                       return_scores=False):
+    """DeepFM.target_ranks for several engines over one set of feature columns, every member by its OWN logit
+    (mi_pair_target_ranks, include/mi355x_rec.h): ranks int32 [M, U, Tmax], padded with -1, plus the targets' logits
+    float32 [M, U, Tmax] when return_scores.  The arguments are checked and the exclusions built once (member 0), the
+    per-side precompute runs once per member, then ONE scoring and counting launch for all members per 64 target columns
+    (queries with more targets are served in passes; the sides are not recomputed).  ValueError (naming the member and the
+    limit) for a member outside the kernel's scope, which is top_k_group's."""
+    engines = check_members("target_ranks_group", engines, _lib.PAIR_TOPK_GROUP_MAX_MEMBERS, DeepFM._top_k_group_limit)
+    M, lead = len(engines), engines[0]
+    sides, U, I, _ = lead._top_k_check(query_ids, candidate_ids, query_fields, 1, query_x, candidate_x)
+    excl_off, excl_idx = lead._top_k_exclusions(exclude, U, I) if exclude is not None else (None, None)
+    tg = dense_targets(targets, U, I)
+    args = [e._top_k_sides(sides) for e in engines]          # (kept alive until the launches are enqueued)
+    members = _rank_members(engines, args)
+    dev, k_ = lead.device, lead.k
+    ranks, scores = [], []
+    for lo in range(0, tg.shape[1], _lib.PAIR_RANKS_MAX_TARGETS):
+        t = torch.from_numpy(np.ascontiguousarray(tg[:, lo:lo + _lib.PAIR_RANKS_MAX_TARGETS])).to(dev)
+        Tq = t.shape[1]
+        ranks.append(torch.empty(M, U, Tq, dtype=torch.int32, device=dev))
+        scores.append(torch.empty(M, U, Tq, dtype=torch.float32, device=dev) if return_scores else None)
+        ws = lead._bytes("target_ranks_ws", k_.query("mi_pair_target_ranks_workspace_bytes", members, M, U, I, Tq))
+        k_.mi_pair_target_ranks(members, M, U, I, excl_off, excl_idx, t, Tq, ranks[-1], scores[-1], ws, ws.numel())
+    if not ranks:                                            # (no query names a target)
+        ranks, scores = [torch.empty(M, U, 0, dtype=torch.int32, device=dev)], [torch.empty(M, U, 0, device=dev)]
+    ranks = ranks[0] if len(ranks) == 1 else torch.cat(ranks, 2)
+    if not return_scores:
+        return ranks
+    return ranks, (scores[0] if len(scores) == 1 else torch.cat(scores, 2))

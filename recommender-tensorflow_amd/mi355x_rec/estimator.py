@@ -403,6 +403,16 @@ class Estimator:
         self._first_call(query_features, None, ModeKeys.PREDICT)
         return recommend_batch(query_features, candidate_features, k, exclude, self.params)
 
+    def rank_targets(self, query_features, candidate_features, targets, exclude=None):
+        """The exact 0-based rank of named target candidates among all eligible candidates of their query, in recommend's
+        order (DeepFM.target_ranks): the two feature dicts and exclude as recommend takes them, targets a CSR pair
+        (offsets, indices) or one sequence of candidate indices per query.  Returns numpy int32 [U, Tmax], -1 for padding,
+        for a target that is no candidate and for one excluded for its query."""
+        from .model import rank_targets_sides
+        self._first_call(query_features, None, ModeKeys.PREDICT)
+        store = self.params["_store"]
+        return rank_targets_sides(store["plan"], [store["engine"]], query_features, candidate_features, targets, exclude)[0]
+
 
 def train_and_evaluate(estimator, train_spec, eval_spec):
     """Local-mode tf.estimator.train_and_evaluate: train to max_steps; after every checkpoint

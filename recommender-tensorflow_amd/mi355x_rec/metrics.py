@@ -2,6 +2,8 @@
 ``head.create_estimator_spec``, trainers/deep_fm.py:118-125, and get_binary_metric_ops,
 trainers/model_utils.py:39-54).  The device side (mi_eval_accumulate) only counts; the 200-threshold
 trapezoidal AUC of tf.metrics.auc is a few hundred flops and is done here in fp64."""
+import math
+
 import numpy as np
 
 NUM_THRESHOLDS = 200
@@ -69,3 +71,42 @@ def histogram_proto(limits, counts, sums, vmin, vmax):
     lim = np.append(limits, np.finfo(np.float64).max)
     return {"min": float(vmin), "max": float(vmax), "num": int(counts.sum()), "sum": float(sums[0]), "sum_squares": float(sums[1]),
             "bucket_limit": [float(lim[b]) for b in nz], "bucket": [int(counts[b]) for b in nz]}
+
+
+def ranking_metrics_from_ranks(ranks_by_user, n_positives_by_user, ks):
+    """Ranking metrics from the exact 0-based ranks of every user's held-out positives (DeepFM.target_ranks) — no top-K
+    list, so any cutoff and the list-free metrics are available.  ranks_by_user: one row per user (an int array [U, T] or a
+    sequence of sequences) with the ranks of that user's positives, -1 for a positive without a rank (excluded, or not a
+    candidate) and for padding; n_positives_by_user [U]: how many positives the user has — a positive with rank -1 counts
+    in the denominators and never as a hit, padding does not count.  Only users with at least one positive are counted.
+    For every k in ks: hit_rate@k, recall@k, ndcg@k (binary relevance) with trainers.recommend.ranking_metrics' definitions;
+    mrr: the mean over users of 1 / (1 + best rank), 0 for a user without a ranked positive; mean_rank: the mean 0-based
+    rank over all ranked positives (0.0 when there is none); users: the number of users counted."""
+    ks = [int(k) for k in ks]
+    if any(k < 1 for k in ks):
+        raise ValueError("ranking_metrics_from_ranks: cutoffs %r (at least 1)" % (ks,))
+    rows = [np.asarray(row, np.int64).reshape(-1) for row in ranks_by_user]
+    n_pos = np.asarray(n_positives_by_user, np.int64).reshape(-1)
+    if len(rows) != len(n_pos):
+        raise ValueError("ranking_metrics_from_ranks: %d rows of ranks for %d users" % (len(rows), len(n_pos)))
+    r = np.full((len(rows), max([len(row) for row in rows] + [1])), -1, np.int64)
+    for u, row in enumerate(rows):
+        r[u, :len(row)] = row
+    r, n_pos = r[n_pos >= 1], n_pos[n_pos >= 1]              # only users with at least one positive are counted
+    ranked = r >= 0
+    if (ranked.sum(1) > n_pos).any():
+        u = int(np.flatnonzero(ranked.sum(1) > n_pos)[0])
+        raise ValueError("ranking_metrics_from_ranks: %d ranks for a user with %d positives" % (ranked[u].sum(), n_pos[u]))
+    r = np.sort(np.where(ranked, r, np.iinfo(np.int64).max), 1)             # ascending, the positives without a rank last
+    ranked = np.sort(~ranked, 1) == 0
+    gain = np.where(ranked, 1.0 / np.log2(np.where(ranked, r, 0) + 2.0), 0.0)
+    mean = lambda v: float(np.mean(v)) if len(v) else 0.0
+    out = {}
+    for k in ks:
+        top = ranked & (r < k)
+        ideal = np.concatenate([[0.0], np.cumsum(1.0 / np.log2(np.arange(min(k, int(n_pos.max()) if len(n_pos) else 0)) + 2.0))])
+        out.update({"hit_rate@%d" % k: mean(top.any(1).astype(np.float64)), "recall@%d" % k: mean(top.sum(1) / n_pos),
+                    "ndcg@%d" % k: mean(np.where(top, gain, 0.0).sum(1) / ideal[np.minimum(n_pos, k)])})
+    best = np.where(ranked[:, 0], 1.0 / (1.0 + np.where(ranked[:, 0], r[:, 0], 0)), 0.0) if len(r) else np.zeros(0)
+    out.update({"mrr": mean(best), "mean_rank": mean(r[ranked].astype(np.float64)), "users": int(len(r))})
+    return out

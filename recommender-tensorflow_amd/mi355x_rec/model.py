@@ -81,6 +81,33 @@ def recommend_sides(plan, eng, query_features, candidate_features, k, exclude):
             "indices": idx.cpu().numpy()}
 
 
+def rank_targets_sides(plan, engines, query_features, candidate_features, targets, exclude, say=None):
+    """The exact ranks of named target candidates on the two sides' raw features, for every engine by its own logit, as
+    numpy int32 [M, U, Tmax] (-1: padding, not a candidate, or excluded): ONE engine.target_ranks_group call for the engines
+    inside mi_pair_target_ranks' scope (256 a call), DeepFM.target_ranks one by one for the others — say(text) is told so.
+    Both sides' ids are transformed once.  Estimator.rank_targets, Predictor.rank_targets and FusedPopulation.rank_targets
+    end here."""
+    from .engine import target_ranks_group
+    qf = split_sides(plan, query_features, candidate_features)
+    cf = [f for f in range(len(plan.categorical) + len(plan.numeric)) if f not in qf]
+    dev = engines[0].device
+    q_ids, q_x = side_inputs(plan, qf, query_features, dev)
+    c_ids, c_x = side_inputs(plan, cf, candidate_features, dev)
+    inside = [i for i, e in enumerate(engines) if e._top_k_group_limit() is None]
+    out = [None] * len(engines)
+    for lo in range(0, len(inside), _lib.PAIR_TOPK_GROUP_MAX_MEMBERS):
+        who = inside[lo:lo + _lib.PAIR_TOPK_GROUP_MAX_MEMBERS]
+        r = target_ranks_group([engines[i] for i in who], q_ids, c_ids, qf, targets, q_x, c_x, exclude=exclude).cpu().numpy()
+        for j, i in enumerate(who):
+            out[i] = r[j]
+    for i, e in enumerate(engines):
+        if out[i] is None:
+            if say is not None:
+                say("member %d: the model has %s: ranked on its own (DeepFM.target_ranks, mode auto)" % (i, e._top_k_group_limit()))
+            out[i] = e.target_ranks(q_ids, c_ids, qf, targets, q_x, c_x, exclude=exclude).cpu().numpy()
+    return np.stack(out)
+
+
 def recommend_batch(query_features, candidate_features, k, exclude, params):
     """Estimator.recommend's body: recommend_sides on the estimator's plan and engine."""
     store = params["_store"]

@@ -224,3 +224,12 @@ class FusedPopulation:
             m["loss"] = float(np.cumsum(losses[i].astype(np.float64))[-1] / T)
             out.append(m)
         return (out, buf["logits"]) if return_logits else out
+
+    # ------------------------------------------------------------------ ranking
+    def rank_targets(self, plan, query_features, candidate_features, targets, exclude=None, say=None):
+        """Every member's exact ranks of named target candidates (Estimator.rank_targets for all members at once): numpy
+        int32 [M, U, Tmax], -1 where a target has no rank.  plan: the members' FieldPlan (they share one set of feature
+        columns).  Every row is made current first (finalize_rows: a no-op after a fused step); the members inside
+        mi_pair_target_ranks' scope are ranked in ONE launch, the others one by one (say(text) is told which)."""
+        from .model import rank_targets_sides
+        return rank_targets_sides(plan, self.engines, query_features, candidate_features, targets, exclude, say)

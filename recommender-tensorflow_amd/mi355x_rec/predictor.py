@@ -22,7 +22,7 @@ import torch
 from . import _lib
 from . import engine as _engine
 from .feature_column import FieldPlan, column_from_json
-from .model import binary_predictions, recommend_sides, side_inputs, split_sides
+from .model import binary_predictions, rank_targets_sides, recommend_sides, side_inputs, split_sides
 
 # mode="auto": the fused launch for batches up to FUSED_MAX_BATCH requests, as long as the MLP's weights — which every
 # workgroup of 32 requests streams through one CU — stay below FUSED_MAX_WEIGHT_BYTES.  Both from the table in
@@ -211,6 +211,12 @@ class Predictor:
         arrays: logits [U, k], probabilities [U, k] (the head's logistic) and indices [U, k] (-1 / -inf / 0 past the
         eligible candidates)."""
         return recommend_sides(self.plan, self.engine, query_features, candidate_features, k, exclude)
+
+    def rank_targets(self, query_features, candidate_features, targets, exclude=None):
+        """What Estimator.rank_targets does for a checkpoint, for this export: the exact 0-based rank of named target
+        candidates among all eligible candidates of their query (DeepFM.target_ranks), numpy int32 [U, Tmax], -1 where a
+        target has no rank."""
+        return rank_targets_sides(self.plan, [self.engine], query_features, candidate_features, targets, exclude)[0]
 
 
 def host_top_k(scores, k, excl_off=None, excl_idx=None):

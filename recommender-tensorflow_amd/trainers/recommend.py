@@ -6,7 +6,9 @@ are the query side, the item columns the candidate side) and writes ``user_id,ra
 Users are the distinct user_ids of --test-csv, items the distinct item_ids of --train-csv and --test-csv; each takes
 its features from its first row.  A user's training items are excluded unless --include-seen.  hit_rate@K, recall@K
 and ndcg@K over the test positives (rating >= 5, get_input_fn's cutoff; users with at least one positive) are printed
-and saved next to the CSV.
+and saved next to the CSV.  ``--metrics-at K [K ...]`` adds the same three metrics at any cutoffs (above 256 too), mrr and
+mean_rank, from the exact rank of every test positive among all eligible items (Estimator.rank_targets: one counting
+launch, no list).
 
 ``--top N`` (with ``--model deep_fm``) ranks with an ensemble instead: --job-dir is then the job directory of a
 ``trainers.sweep`` run, the sweep's N best members are loaded from their exports (EnsemblePredictor.from_sweep) and every
@@ -43,6 +45,10 @@ def make_parser(model):
                                                    "<job-dir>/recommend/top<K>_ensemble<N>.csv)")
     p.add_argument("--top", type=int, default=None, metavar="N",
                    help="rank with the ensemble of the N best members of the trainers.sweep run in --job-dir (--model deep_fm)")
+    p.add_argument("--metrics-at", type=int, nargs="+", default=None, metavar="K",
+                   help="also report hit_rate@K, recall@K and ndcg@K at these cutoffs (any K >= 1, above 256 too), mrr and "
+                        "mean_rank, from the exact rank of every test positive among all eligible items "
+                        "(Estimator.rank_targets); not with --top (default: off)")
     return p
 
 
@@ -83,6 +89,17 @@ def exclusion_csr(users, items, train):
     return off, idx
 
 
+def positive_targets(users, items, test):
+    """per user (ascending users), the candidate indices of the items it rates >= CUTOFF in the test file, ascending and
+    distinct: the targets whose ranks the exact-rank metrics are made of"""
+    pos = {int(v): i for i, v in enumerate(items)}
+    liked = {}
+    for u, it, r in zip(np.asarray(test["user_id"]), np.asarray(test["item_id"]), np.asarray(test["rating"])):
+        if r >= CUTOFF:
+            liked.setdefault(int(u), set()).add(pos[int(it)])
+    return [sorted(liked.get(int(u), ())) for u in users]
+
+
 def ranking_metrics(top_items, positives, k):
     """hit_rate@k, recall@k, ndcg@k (binary relevance) averaged over the users with at least one positive.
     top_items: user -> ranked item list; positives: user -> set of items."""
@@ -113,6 +130,12 @@ def main(argv=None):
     if getattr(args, "synthetic", None):
         args.train_csv, args.test_csv = "synthetic:%d:1" % args.synthetic, "synthetic:%d:2" % max(args.synthetic // 10, 1)
     ens = None
+    if args.metrics_at is not None:
+        if args.top is not None:
+            raise SystemExit("--metrics-at: not with --top %d: the exact-rank metrics rank by ONE model's logit; an ensemble's "
+                             "mean logit is ranked through its top-K list only (--top-k)" % args.top)
+        if min(args.metrics_at) < 1:
+            raise SystemExit("--metrics-at %s: cutoffs are at least 1" % " ".join(str(v) for v in args.metrics_at))
     if args.top is not None:
         from mi355x_rec.predictor import EnsemblePredictor
         if args.model != "deep_fm":
@@ -167,6 +190,15 @@ def main(argv=None):
         if r >= CUTOFF:
             positives.setdefault(int(u), set()).add(int(it))
     m = ranking_metrics(top, positives, k)
+    if args.metrics_at is not None:
+        from mi355x_rec.metrics import ranking_metrics_from_ranks
+        targets = positive_targets(users, items, test)
+        try:
+            ranks = est.rank_targets(qf, cf, targets, exclude=excl)
+        except ValueError as e:
+            raise SystemExit("recommend: %s" % e)
+        exact = ranking_metrics_from_ranks(ranks, [len(t) for t in targets], args.metrics_at)
+        m.update({key: v for key, v in exact.items() if key not in m})      # (the top-K list's keys keep their values)
     m_path = os.path.splitext(path)[0] + "_metrics.json"
     with open(m_path, "w") as f:
         json.dump(m, f, indent=1)

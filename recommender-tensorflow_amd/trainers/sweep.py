@@ -15,6 +15,11 @@ members are evaluated on all of it in one launch (FusedPopulation.evaluate): <jo
 evaluation — the members' learning curves — and sweep.json names every member's best point.  --final-eval fused takes the
 end-of-sweep metrics from that evaluation too, instead of one Estimator.evaluate per member.
 
+--rank-metrics K [K ...]: after the final evaluation every member is also measured as a recommender — the exact rank of
+every test user's positives among all items the user has not rated, for ALL members in one launch
+(FusedPopulation.rank_targets) — and every row of sweep.json gains "ranking" (hit_rate@K, recall@K, ndcg@K, mrr,
+mean_rank: what trainers.recommend --metrics-at reports for the member's directory); --select takes these names too.
+
 --ensemble N: after the ranking, the N best members are served as ONE model (EnsemblePredictor: their mean logit, one launch
 for all of them) over the test set; sweep.json gains "ensemble": its members and its metrics, next to the best member's.
 
@@ -23,23 +28,37 @@ trainers.deep_fm has no learning-rate flag (the reference has none): a member re
 import itertools
 import json
 import os
+import re
 import shutil
 import time
-from argparse import ArgumentParser
+from argparse import ArgumentParser, ArgumentTypeError
 
 import numpy as np
 import torch
 
 from mi355x_rec.estimator import Estimator, ModeKeys
-from mi355x_rec.metrics import metrics_from_counters
+from mi355x_rec.metrics import metrics_from_counters, ranking_metrics_from_ranks
 from mi355x_rec.predictor import EnsemblePredictor
 from mi355x_rec.population import FusedPopulation
 from trainers import _cli, deep_fm
 from trainers.conf_utils import get_exporter
-from trainers.ml_100k import get_feature_columns, get_input_fn, serving_input_fn
+from trainers.ml_100k import _read_csv, get_feature_columns, get_input_fn, serving_input_fn
 
 _KEPT = ("--train-csv", "--test-csv", "--restore", "--batch-size", "--train-steps", "--device", "--catchup", "--synthetic")
-_ASCENDING = ("loss", "average_loss")
+_ASCENDING = ("loss", "average_loss", "mean_rank")
+_EVAL_METRICS = ("auc", "accuracy", "auc_precision_recall", "loss", "average_loss")
+_RANK_AT = re.compile(r"^(hit_rate|recall|ndcg)@([1-9][0-9]*)$")
+
+
+def select_metric(name):
+    """--select: an evaluation metric, or a ranking metric of --rank-metrics (hit_rate@K, recall@K, ndcg@K, mrr, mean_rank)"""
+    if name in _EVAL_METRICS or name in ("mrr", "mean_rank") or _RANK_AT.match(name):
+        return name
+    raise ArgumentTypeError("%r is none of %s, hit_rate@K, recall@K, ndcg@K, mrr, mean_rank" % (name, ", ".join(_EVAL_METRICS)))
+
+
+def is_ranking(select):
+    return select not in _EVAL_METRICS
 
 
 def make_parser():
@@ -63,9 +82,14 @@ def make_parser():
                    help="a hidden layer specification; repeat the flag for several (default: 16 16)")
     p.add_argument("--seeds", type=int, default=1, metavar="N", help="seeds 0 .. N-1 of the variable initialisers and dropout "
                                                                      "masks (default: %(default)s)")
-    p.add_argument("--select", default="auc", choices=["auc", "accuracy", "auc_precision_recall", "loss", "average_loss"],
-                   help="the evaluation metric sweep.json is sorted by, best first (loss / average_loss: lowest first; "
-                        "default: %(default)s)")
+    p.add_argument("--select", default="auc", type=select_metric,
+                   help="the metric sweep.json is sorted by, best first: auc, accuracy, auc_precision_recall, loss, average_loss "
+                        "(loss / average_loss: lowest first), or with --rank-metrics hit_rate@K, recall@K, ndcg@K (K among "
+                        "--rank-metrics), mrr, mean_rank (lowest first) (default: %(default)s)")
+    p.add_argument("--rank-metrics", type=int, nargs="+", default=None, metavar="K",
+                   help="after the final evaluation, rank every test user's positives (rating >= 5) among all items the user "
+                        "has not rated in the training file, for ALL members in one launch, and give every row of sweep.json "
+                        "\"ranking\": hit_rate@K, recall@K, ndcg@K at these cutoffs, mrr and mean_rank (default: off)")
     p.add_argument("--eval-every", type=int, default=0, metavar="N",
                    help="evaluate every member on the whole test set every N steps and at the last step, in one launch for all "
                         "of them; one line per evaluation goes to <job-dir>/sweep_eval.jsonl and sweep.json gains best_step / "
@@ -100,6 +124,22 @@ def evaluate_ensemble(job_dir, top, test_csv, device, batch_size=4096):
     metrics = metrics_from_counters(hist.cpu().numpy(), counts.cpu().numpy(), sums.cpu().numpy())
     metrics["loss"] = metrics["average_loss"]
     return ens.sweep_members, {k: float(v) for k, v in metrics.items()}
+
+
+def rank_population(pop, plan, train_csv, test_csv, ks):
+    """Every member's ranking metrics as a recommender, what trainers.recommend --metrics-at reports for its directory:
+    users, items, exclusions and test positives as that CLI builds them, the positives' exact ranks for all members of the
+    population in ONE launch (FusedPopulation.rank_targets; a member outside that launch's scope is ranked on its own, and
+    a line says so).  Returns a list of M dicts."""
+    from trainers import recommend
+    train, _ = _read_csv(train_csv)
+    test, _ = _read_csv(test_csv)
+    users, qf, items, cf = recommend.tables(train, test)
+    targets = recommend.positive_targets(users, items, test)
+    ranks = pop.rank_targets(plan, qf, cf, targets, exclude=recommend.exclusion_csr(users, items, train),
+                             say=lambda text: print("INFO: --rank-metrics: %s" % text))
+    n_pos = [len(t) for t in targets]
+    return [ranking_metrics_from_ranks(r, n_pos, ks) for r in ranks]
 
 
 def grid(args):
@@ -259,6 +299,13 @@ def train_and_evaluate(args):
     if getattr(args, "synthetic", None):
         args.train_csv, args.test_csv = "synthetic:%d:1" % args.synthetic, "synthetic:%d:2" % max(args.synthetic // 10, 1)
     hps = grid(args)
+    rank_ks = list(getattr(args, "rank_metrics", None) or [])
+    if rank_ks and min(rank_ks) < 1:
+        raise SystemExit("--rank-metrics %s: cutoffs are at least 1" % " ".join(str(k) for k in rank_ks))
+    if is_ranking(args.select):
+        at = _RANK_AT.match(args.select)
+        if not rank_ks or (at and int(at.group(2)) not in rank_ks):
+            raise SystemExit("--select %s needs --rank-metrics%s" % (args.select, " with %s among its cutoffs" % at.group(2) if at else ""))
     if not args.restore:
         shutil.rmtree(args.job_dir, ignore_errors=True)
     config = _cli.get_run_config()
@@ -270,7 +317,9 @@ def train_and_evaluate(args):
         raise ValueError("--eval-every %d (0 = off, or a number of steps)" % eval_every)
     evaluator = None
     if eval_every or final_eval == "fused":
-        evaluator = PopulationEval(args.test_csv, args.batch_size, args.select, args.job_dir, eval_every)
+        # (the curves are made of evaluation metrics: with a ranking --select their best point is taken by auc)
+        evaluator = PopulationEval(args.test_csv, args.batch_size, "auc" if is_ranking(args.select) else args.select, args.job_dir,
+                                   eval_every)
     pop = train(members, get_input_fn(args.train_csv, batch_size=args.batch_size), args.train_steps, config, args.job_dir,
                 args.batch_size, evaluator)
     if pop is None:
@@ -292,8 +341,12 @@ def train_and_evaluate(args):
                      "flags": member_flags(args, hp), "metrics": {k: float(v) for k, v in metrics.items()}})
         if eval_every:
             rows[-1]["best_step"], rows[-1]["best_value"] = evaluator.best(i)
+    if rank_ks:
+        for row, ranking in zip(rows, rank_population(pop, members[0].params["_store"]["plan"], args.train_csv, args.test_csv, rank_ks)):
+            row["ranking"] = ranking
     sign = 1.0 if args.select in _ASCENDING else -1.0
-    rows.sort(key=lambda r: (sign * r["metrics"][args.select], r["member"]))
+    value = lambda r: r["ranking" if is_ranking(args.select) else "metrics"][args.select]
+    rows.sort(key=lambda r: (sign * value(r), r["member"]))
     doc = {"select": args.select, "members": rows}
     with open(os.path.join(args.job_dir, "sweep.json"), "w") as f:
         json.dump(doc, f, indent=1)
@@ -306,11 +359,12 @@ def train_and_evaluate(args):
         doc["ensemble"] = {"members": who, "metrics": metrics}
         with open(os.path.join(args.job_dir, "sweep.json"), "w") as f:
             json.dump(doc, f, indent=1)
+        shown = "auc" if is_ranking(args.select) else args.select      # (the ensemble is evaluated, not ranked)
         print("INFO: ensemble of the %d best members (%s): %s = %.6g, the best single member (member %d) has %.6g" % (
-            n_ens, ", ".join(str(m) for m in who), args.select, metrics[args.select], best["member"], best["metrics"][args.select]))
+            n_ens, ", ".join(str(m) for m in who), shown, metrics[shown], best["member"], best["metrics"][shown]))
     print("INFO: best of %d members by %s: member %d (%s), %s = %.6g, in %s" % (
         len(rows), args.select, best["member"], ", ".join("%s = %s" % kv for kv in sorted(best["params"].items())), args.select,
-        best["metrics"][args.select], best["dir"]))
+        value(best), best["dir"]))
     return members
 
 
