@@ -801,6 +801,35 @@ int32_t mi_pair_target_ranks(const mi_rank_member_t* members, int32_t n_members,
                              const int32_t* excl_idx, const int32_t* targets, int32_t Tq, int32_t* ranks, float* target_scores,
                              void* workspace, size_t workspace_bytes, mi_stream_t stream);
 
+/* ---- exact ranks of named candidates under an ensemble's mean logit, one launch (csrc/rank.hip) ----------------------
+ * What mi_pair_target_ranks does for every member's own score, for the MEAN score of the M members — the order
+ * mi_pair_topk_group selects by.  For query q and target t = targets[q, j]:
+ *   ranks[q, j] = #{c in [0, I), c != t, c not excluded for q : key(z(q, c), c) > key(z(q, t), t)}
+ *   z(q, c) = (((z_0 + z_1) + z_2) + ... + z_{M-1}) / (float)M     fp32, ascending member order, one rounding per
+ *   operation, IEEE division — mi_pair_topk_group's definition: z is bit for bit what that entry writes to `scores`
+ * with mi_pair_topk's order as the key (score descending, equal scores by ascending index, NaN below every number, -0 as
+ * +0): the 0-based position t would take in mi_pair_topk_group's list were k unbounded.  ranks[q, j] = -1 where t < 0
+ * (padding), t >= I or t is excluded for q.  Other targets of the query count as ordinary candidates; duplicate targets
+ * each get their own, equal, answer.  M = 1 takes the same path (z_0 / 1.0f).
+ *   members, n_members, U, I, excl_off, excl_idx, targets, Tq: as mi_pair_target_ranks (same scope: the VALU pair path;
+ *     same checks and messages, prefixed "member i:").
+ * Outputs: ranks [U, Tq] int32; target_scores [U, Tq] (optional, NULL to skip): the bits of z(q, t), the canonical quiet
+ *   NaN where the rank is -1.
+ * workspace: mi_pair_target_ranks_mean_workspace_bytes(members, n_members, U, I, Tq) (only H1 and E of a member are read;
+ *   0 for arguments out of range) — the exclusion mask, the splits' partial counts, the member table and the transposes.
+ * Launches: the member table (through the kernel arguments), one transpose launch, the exclusion mask, ONE scoring and
+ *   counting launch over (query blocks) x (candidate splits) — the members are a loop inside it: the mean needs every
+ *   member's score of a pair in one lane — and the sum of the splits' counts; no copy, no synchronisation.  The counts are
+ *   integers written plainly and added in a second launch: the result depends neither on the split count nor on timing,
+ *   and no workgroup waits for another.
+ * Refused on the host before anything is launched: what mi_pair_target_ranks refuses, with the same codes. */
+size_t mi_pair_target_ranks_mean_workspace_bytes(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I,
+                                                 int32_t Tq);
+int32_t mi_pair_target_ranks_mean(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I,
+                                  const int64_t* excl_off, const int32_t* excl_idx, const int32_t* targets, int32_t Tq,
+                                  int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes,
+                                  mi_stream_t stream);
+
 /* ---- serving: the forward of a request batch as one launch (csrc/serve.hip) ---------------------------------------
  * For B requests, what DeepFM.predict_logits followed by mi_binary_predictions computes (deep_fm.py:36-125 in PREDICT
  * mode, model_utils.py:9-20; the requests of ml_100k.py:64-88's receiver after the columns' id transforms):

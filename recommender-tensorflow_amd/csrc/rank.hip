@@ -19,6 +19,8 @@
 //   pair_target_ranks_k  grid (query blocks) x (candidate splits) x (members): the exact rank of named target candidates
 //                      by each member's own score — the targets' keys in LDS, the candidate loop above, integer counters;
 //                      rank_sum_k adds the splits' counts (mi_pair_target_ranks).
+//   pair_target_ranks_mean_k  grid (query blocks) x (candidate splits): the same count under the members' MEAN score — the
+//                      members are a loop in the lane, as in pair_score_topk_group_k (mi_pair_target_ranks_mean).
 //
 // Order: one 64-bit key per (score, candidate): the score's bits made monotone in the high word (NaN -> 0, below every
 // number; -0 as +0, and returned as +0), the complemented index in the low word, so "larger key" = higher score, then lower index.  Key 0 is
@@ -538,6 +540,82 @@ __global__ __launch_bounds__(kThreads) void pair_target_ranks_k(const GroupMembe
   }
 }
 
+// ---- exact ranks of named targets under the members' mean score (mi_pair_target_ranks_mean) -------------------------
+// The mean logit of pair (q, c) as pair_score_topk_group_k forms it: ascending member order, one rounding per operation,
+//   z = (((z_0 + z_1) + z_2) + ... + z_{M-1}) / (float)M
+// c may differ per lane (a target) or be the wave's one candidate; q_ok: the lane's query exists (qcol < U).
+__device__ __forceinline__ float mean_pair_score(const GroupMember* __restrict__ tab, int M, float fM, int64_t c, int64_t qcol,
+                                                 bool q_ok, int h) {
+  float acc = 0.f;
+  for (int m = 0; m < M; ++m) {
+    const PairArgs p = load_member(tab + m);
+    const float wq = (p.w_q && q_ok) ? p.w_q[qcol] : 0.f;
+    const float* __restrict__ sq = p.sqT ? p.sqT + qcol : nullptr;
+    const float z = pair_score<false, 1, 1>(p, c, qcol, h, wq, sq);
+    acc = m == 0 ? z : acc + z;
+  }
+  return acc / fM;
+}
+
+// pair_target_ranks_k with the members as a loop instead of a grid axis: grid (query blocks of 32) x (candidate splits),
+// tkey [Tq][kQB] and cnt [kWaves][Tq][kQB] as there, and both the targets' keys and the candidates' keys come from
+// mean_pair_score — a target's own pair gives the target's own bits and never counts itself.  Every lane scores a target
+// (candidate 0 where it has none, the result dropped): the member loop's wave-uniform reads never run under an empty
+// exec mask.  The split's counts go plainly to part [splits][U][Tq] (-1: no rank); rank_sum_k (one "member") adds them.
+__global__ __launch_bounds__(kThreads) void pair_target_ranks_mean_k(const GroupMember* __restrict__ tab, int M,
+                                                                    const uint32_t* __restrict__ excl,
+                                                                    const int32_t* __restrict__ targets,
+                                                                    float* __restrict__ target_scores, int32_t* __restrict__ part,
+                                                                    int64_t U, int64_t I, int64_t chunk, int Tq, int splits,
+                                                                    int words) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  uint64_t* tkey = reinterpret_cast<uint64_t*>(lds);             // [Tq][kQB]
+  int* cnt = reinterpret_cast<int*>(tkey + Tq * kQB);             // [kWaves][Tq][kQB]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31, h = lane >> 5;
+  const int64_t q0 = static_cast<int64_t>(blockIdx.x) * kQB;
+  const int split = blockIdx.y;
+  const int64_t c_begin = split * chunk;
+  const int64_t c_end = c_begin + chunk < I ? c_begin + chunk : I;
+  const int64_t q = q0 + col;
+  const bool q_ok = q < U;
+  const float fM = static_cast<float>(M);
+  for (int i = tid; i < kWaves * Tq * kQB; i += kThreads) cnt[i] = 0;
+  // the targets: thread (col, j0 = tid / 32) takes targets j0, j0 + 8, ... of query col
+  for (int j = tid >> 5; j < Tq; j += kThreads / kQB) {
+    int64_t t = q_ok ? targets[q * Tq + j] : -1;
+    const bool has = t >= 0 && t < I && !(excl && ((excl[q * words + (t >> 5)] >> (t & 31)) & 1u));
+    if (!has) t = 0;
+    float s = mean_pair_score(tab, M, fM, t, q, q_ok, 0);
+    uint64_t key = rank_key(s, static_cast<uint32_t>(t));
+    if (!has) {
+      s = __uint_as_float(0x7fc00000u);
+      key = kNoRank;
+    }
+    if (q_ok && split == 0 && target_scores) target_scores[q * Tq + j] = s;
+    tkey[j * kQB + col] = key;
+  }
+  __syncthreads();
+  int* mine = cnt + wave * Tq * kQB + col;
+  for (int64_t c = c_begin + wave; c < c_end; c += kWaves) {     // (c is wave-uniform)
+    const float s = mean_pair_score(tab, M, fM, c, q, q_ok, h);
+    if (q_ok && !(excl && ((excl[q * words + (c >> 5)] >> (c & 31)) & 1u))) {
+      const uint64_t key = rank_key(s, static_cast<uint32_t>(c));
+      for (int j = h; j < Tq; j += 2) mine[j * kQB] += key > tkey[j * kQB + col];
+    }
+  }
+  __syncthreads();
+  // thread i = (query i / Tq, target i % Tq): the block's rows of part are contiguous
+  int32_t* out = part + (static_cast<int64_t>(split) * U + q0) * Tq;
+  const int64_t rows = U - q0 < kQB ? U - q0 : kQB;
+  for (int i = tid; i < rows * Tq; i += kThreads) {
+    const int qq = i / Tq, j = i - qq * Tq, at = j * kQB + qq;
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) n += cnt[w * Tq * kQB + at];
+    out[i] = tkey[at] == kNoRank ? -1 : n;
+  }
+}
+
 // ranks[m][e] = the sum over the splits of part[m][split][e], -1 where the target has no rank; n = U * Tq, grid (blocks, M)
 __global__ __launch_bounds__(256) void rank_sum_k(const int32_t* __restrict__ part, int splits, int64_t n,
                                                   int32_t* __restrict__ ranks) {
@@ -660,6 +738,9 @@ struct Plan {
 
 inline size_t align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
 
+// workgroups of 256 threads for the n elements of a grid-stride kernel (at most 2048)
+inline unsigned grid_blocks(int64_t n) { const int64_t b = mi::ceil_div(n, 256); return static_cast<unsigned>(b < 2048 ? b : 2048); }
+
 Plan make_plan(int64_t U, int64_t I, int32_t k, int32_t H1, int32_t E) {
   Plan pl;
   pl.qblocks = mi::ceil_div(U, kQB);
@@ -763,6 +844,8 @@ GroupPlan make_group_plan(const mi_rank_member_t* members, int32_t n, int64_t U,
 // mi_pair_target_ranks: make_plan's split rule — at least 64 candidates per split, about kTargetBlocks workgroups — over
 // query blocks x members (no selection lists: nothing else bounds the splits), and the workspace: the exclusion mask, the
 // splits' partial counts, the member table and the members' transposes.  pl: what side_bytes and the table need of a Plan.
+// mi_pair_target_ranks_mean (mean = true): the members are a loop in the kernel, not a grid axis — the member factor drops
+// out of the split rule and of the partial counts.
 struct RanksPlan {
   Plan pl;
   size_t off_mask, off_part, off_table, off_sides, total;
@@ -772,12 +855,13 @@ bool ranks_sizes_ok(const mi_rank_member_t* members, int32_t n, int64_t U, int64
   return Tq >= 1 && Tq <= MI_PAIR_RANKS_MAX_TARGETS && group_sizes_ok(members, n, U, I, 1);
 }
 
-RanksPlan make_ranks_plan(const mi_rank_member_t* members, int32_t n, int64_t U, int64_t I, int32_t Tq) {
+RanksPlan make_ranks_plan(const mi_rank_member_t* members, int32_t n, int64_t U, int64_t I, int32_t Tq, bool mean = false) {
   RanksPlan rp{};
   Plan& pl = rp.pl;
+  const int32_t grid_members = mean ? 1 : n;
   pl.qblocks = mi::ceil_div(U, kQB);
   pl.Upad = pl.qblocks * kQB;
-  int64_t s = mi::ceil_div(kTargetBlocks, pl.qblocks * n);
+  int64_t s = mi::ceil_div(kTargetBlocks, pl.qblocks * grid_members);
   const int64_t s_min_chunk = mi::ceil_div(I, 64);
   if (s > s_min_chunk) s = s_min_chunk;
   if (s < 1) s = 1;
@@ -786,12 +870,82 @@ RanksPlan make_ranks_plan(const mi_rank_member_t* members, int32_t n, int64_t U,
   pl.words = static_cast<int32_t>(mi::ceil_div(I, 32));
   size_t o = 0;
   rp.off_mask = o; o += align256(sizeof(uint32_t) * static_cast<size_t>(U) * pl.words);
-  rp.off_part = o; o += align256(sizeof(int32_t) * static_cast<size_t>(n) * pl.splits * U * Tq);
+  rp.off_part = o; o += align256(sizeof(int32_t) * static_cast<size_t>(grid_members) * pl.splits * U * Tq);
   rp.off_table = o; o += align256(sizeof(GroupMember) * static_cast<size_t>(n));
   rp.off_sides = o;
   for (int32_t i = 0; i < n; ++i) o += side_bytes(pl, members[i].H1, members[i].E);
   rp.total = o;
   return rp;
+}
+
+// What mi_pair_target_ranks and mi_pair_target_ranks_mean (`who`, for the texts) refuse before anything is launched, in
+// their order: the member count, the per-call arguments, then every member — check_model with k = 1, and the VALU scope.
+int32_t check_ranks_call(const char* who, const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I,
+                         const int64_t* excl_off, const int32_t* excl_idx, const int32_t* targets, int32_t Tq,
+                         const int32_t* ranks) {
+  MI_REQUIRE(n_members >= 1, "%s: %d members (at least 1)", who, n_members);
+  if (n_members > MI_PAIR_TOPK_GROUP_MAX_MEMBERS)
+    return unsupported("%s: %d members (at most %d in one launch)", who, n_members, MI_PAIR_TOPK_GROUP_MAX_MEMBERS);
+  MI_REQUIRE(members, "%s: members", who);
+  MI_REQUIRE(Tq >= 1 && Tq <= MI_PAIR_RANKS_MAX_TARGETS, "%s: Tq=%d targets per query (1 to %d in one call)", who, Tq,
+             MI_PAIR_RANKS_MAX_TARGETS);
+  MI_REQUIRE(targets && ranks, "%s: targets / ranks", who);
+  MI_REQUIRE(!excl_off == !excl_idx, "%s: excl_off and excl_idx go together", who);
+  for (int32_t i = 0; i < n_members; ++i) {
+    const mi_rank_member_t& m = members[i];
+    LayerTable lt{};
+    int maxw = 0;
+    const int32_t rc = check_model(U, I, 1, m.a_q, m.s_q, m.a_c, m.s_c, m.H1, m.E, m.dense, m.layer_off, m.widths, m.n_layers,
+                                   m.activation, true, true, lt, maxw);
+    if (rc != MI_OK) {
+      mi::member_error(who, i);
+      return rc;
+    }
+    if (takes_mfma(m.n_layers, maxw))
+      return unsupported("%s: member %d: %d layers after layer 1 with a hidden width of %d: the kernel takes the "
+                         "VALU pair path only (fewer than two layers after layer 1, or every hidden width after layer 1 below "
+                         "%d)", who, i, m.n_layers, maxw, kValuW);
+  }
+  return MI_OK;
+}
+
+// The launches in front of a rank entry's scoring launch: the member table, as mi_pair_topk_group writes it (the
+// selection's fields of PairArgs stay zero: nothing here reads them), one transpose launch for all members, the mask.
+void prepare_ranks(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, const int64_t* excl_off,
+                   const int32_t* excl_idx, const RanksPlan& rp, char* ws, GroupMember* tab, uint32_t* mask, hipStream_t st) {
+  const Plan& pl = rp.pl;
+  size_t side = rp.off_sides;
+  int maxside = 0;
+  MemberChunk ch{};
+  for (int32_t i = 0; i < n_members; ++i) {
+    const mi_rank_member_t& m = members[i];
+    GroupMember& gm = ch.m[i % kTabChunk];
+    gm = GroupMember{};
+    for (int j = 0; j < m.n_layers; ++j)
+      gm.l[j] = Layer{m.layer_off[2 * j], m.layer_off[2 * j + 1], m.widths[j], m.widths[j + 1]};
+    PairArgs& a = gm.p;
+    a.aqT = m.H1 ? reinterpret_cast<float*>(ws + side) : nullptr;
+    a.sqT = m.E ? reinterpret_cast<float*>(ws + side + align256(sizeof(float) * static_cast<size_t>(m.H1) * pl.Upad)) : nullptr;
+    side += side_bytes(pl, m.H1, m.E);
+    a.a_c = m.a_c; a.s_c = m.s_c; a.w_q = m.w_q; a.w_c = m.w_c; a.dense = m.dense;
+    a.l = tab[i].l;                              // (the address of this member's layers in the workspace)
+    a.U = U; a.I = I;
+    a.Upad = static_cast<int32_t>(pl.Upad); a.H1 = m.H1; a.E = m.E; a.act = m.activation; a.n_layers = m.n_layers;
+    gm.a_q = m.a_q; gm.s_q = m.s_q;
+    if (m.H1 > maxside) maxside = m.H1;
+    if (m.E > maxside) maxside = m.E;
+    if (i % kTabChunk == kTabChunk - 1 || i + 1 == n_members) {
+      const int first = i - i % kTabChunk;
+      member_table_k<<<dim3(1), dim3(64), 0, st>>>(ch, i - first + 1, tab + first);
+    }
+  }
+  if (maxside)
+    transpose_pad_group_k<<<dim3(grid_blocks(static_cast<int64_t>(maxside) * pl.Upad), static_cast<unsigned>(n_members), 2), dim3(256), 0,
+                            st>>>(tab, U);
+  if (mask) {
+    zero_u32_k<<<dim3(grid_blocks(U * pl.words)), dim3(256), 0, st>>>(mask, U * pl.words);
+    excl_mask_k<<<dim3(static_cast<unsigned>(U)), dim3(256), 0, st>>>(excl_off, excl_idx, I, pl.words, mask);
+  }
 }
 
 template <bool MFMA, int NP, int NQ>
@@ -960,30 +1114,8 @@ size_t mi_pair_target_ranks_workspace_bytes(const mi_rank_member_t* members, int
 int32_t mi_pair_target_ranks(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, const int64_t* excl_off,
                              const int32_t* excl_idx, const int32_t* targets, int32_t Tq, int32_t* ranks, float* target_scores,
                              void* workspace, size_t workspace_bytes, mi_stream_t stream) {
-  MI_REQUIRE(n_members >= 1, "pair_target_ranks: %d members (at least 1)", n_members);
-  if (n_members > MI_PAIR_TOPK_GROUP_MAX_MEMBERS)
-    return unsupported("pair_target_ranks: %d members (at most %d in one launch)", n_members, MI_PAIR_TOPK_GROUP_MAX_MEMBERS);
-  MI_REQUIRE(members, "pair_target_ranks: members");
-  MI_REQUIRE(Tq >= 1 && Tq <= MI_PAIR_RANKS_MAX_TARGETS, "pair_target_ranks: Tq=%d targets per query (1 to %d in one call)", Tq,
-             MI_PAIR_RANKS_MAX_TARGETS);
-  MI_REQUIRE(targets && ranks, "pair_target_ranks: targets / ranks");
-  MI_REQUIRE(!excl_off == !excl_idx, "pair_target_ranks: excl_off and excl_idx go together");
-  // every member is checked before anything is launched
-  for (int32_t i = 0; i < n_members; ++i) {
-    const mi_rank_member_t& m = members[i];
-    LayerTable lt{};
-    int maxw = 0;
-    const int32_t rc = check_model(U, I, 1, m.a_q, m.s_q, m.a_c, m.s_c, m.H1, m.E, m.dense, m.layer_off, m.widths, m.n_layers,
-                                   m.activation, true, true, lt, maxw);
-    if (rc != MI_OK) {
-      mi::member_error("pair_target_ranks", i);
-      return rc;
-    }
-    if (takes_mfma(m.n_layers, maxw))
-      return unsupported("pair_target_ranks: member %d: %d layers after layer 1 with a hidden width of %d: the kernel takes the "
-                         "VALU pair path only (fewer than two layers after layer 1, or every hidden width after layer 1 below "
-                         "%d)", i, m.n_layers, maxw, kValuW);
-  }
+  const int32_t rc = check_ranks_call("pair_target_ranks", members, n_members, U, I, excl_off, excl_idx, targets, Tq, ranks);
+  if (rc != MI_OK) return rc;
   const RanksPlan rp = make_ranks_plan(members, n_members, U, I, Tq);
   const Plan& pl = rp.pl;
   MI_REQUIRE(workspace && workspace_bytes >= rp.total, "pair_target_ranks: workspace %zu < %zu bytes", workspace_bytes, rp.total);
@@ -992,47 +1124,47 @@ int32_t mi_pair_target_ranks(const mi_rank_member_t* members, int32_t n_members,
   GroupMember* tab = reinterpret_cast<GroupMember*>(ws + rp.off_table);
   uint32_t* mask = excl_off ? reinterpret_cast<uint32_t*>(ws + rp.off_mask) : nullptr;
   int32_t* part = reinterpret_cast<int32_t*>(ws + rp.off_part);
-  auto blocks = [](int64_t n) { const int64_t b = mi::ceil_div(n, 256); return static_cast<unsigned>(b < 2048 ? b : 2048); };
-  // the member table, as mi_pair_topk_group writes it (the selection's fields of PairArgs stay zero: nothing here reads them)
-  size_t side = rp.off_sides;
-  int maxside = 0;
-  MemberChunk ch{};
-  for (int32_t i = 0; i < n_members; ++i) {
-    const mi_rank_member_t& m = members[i];
-    GroupMember& gm = ch.m[i % kTabChunk];
-    gm = GroupMember{};
-    for (int j = 0; j < m.n_layers; ++j)
-      gm.l[j] = Layer{m.layer_off[2 * j], m.layer_off[2 * j + 1], m.widths[j], m.widths[j + 1]};
-    PairArgs& a = gm.p;
-    a.aqT = m.H1 ? reinterpret_cast<float*>(ws + side) : nullptr;
-    a.sqT = m.E ? reinterpret_cast<float*>(ws + side + align256(sizeof(float) * static_cast<size_t>(m.H1) * pl.Upad)) : nullptr;
-    side += side_bytes(pl, m.H1, m.E);
-    a.a_c = m.a_c; a.s_c = m.s_c; a.w_q = m.w_q; a.w_c = m.w_c; a.dense = m.dense;
-    a.l = tab[i].l;                              // (the address of this member's layers in the workspace)
-    a.U = U; a.I = I;
-    a.Upad = static_cast<int32_t>(pl.Upad); a.H1 = m.H1; a.E = m.E; a.act = m.activation; a.n_layers = m.n_layers;
-    gm.a_q = m.a_q; gm.s_q = m.s_q;
-    if (m.H1 > maxside) maxside = m.H1;
-    if (m.E > maxside) maxside = m.E;
-    if (i % kTabChunk == kTabChunk - 1 || i + 1 == n_members) {
-      const int first = i - i % kTabChunk;
-      member_table_k<<<dim3(1), dim3(64), 0, st>>>(ch, i - first + 1, tab + first);
-    }
-  }
-  if (maxside)
-    transpose_pad_group_k<<<dim3(blocks(static_cast<int64_t>(maxside) * pl.Upad), static_cast<unsigned>(n_members), 2), dim3(256), 0,
-                            st>>>(tab, U);
-  if (mask) {
-    zero_u32_k<<<dim3(blocks(U * pl.words)), dim3(256), 0, st>>>(mask, U * pl.words);
-    excl_mask_k<<<dim3(static_cast<unsigned>(U)), dim3(256), 0, st>>>(excl_off, excl_idx, I, pl.words, mask);
-  }
+  prepare_ranks(members, n_members, U, I, excl_off, excl_idx, rp, ws, tab, mask, st);
   MI_CHECK_LAUNCH("pair_target_ranks (prepare)");
   const size_t lds = (sizeof(uint64_t) + sizeof(int) * kWaves) * kQB * static_cast<size_t>(Tq);      // at most 48 KB
   pair_target_ranks_k<<<dim3(static_cast<unsigned>(pl.qblocks), static_cast<unsigned>(pl.splits), static_cast<unsigned>(n_members)),
                         dim3(kThreads), lds, st>>>(tab, mask, targets, target_scores, part, U, I, pl.chunk, Tq, pl.splits, pl.words);
   MI_CHECK_LAUNCH("pair_target_ranks_k");
   const int64_t n = U * Tq;
-  rank_sum_k<<<dim3(blocks(n), static_cast<unsigned>(n_members)), dim3(256), 0, st>>>(part, pl.splits, n, ranks);
+  rank_sum_k<<<dim3(grid_blocks(n), static_cast<unsigned>(n_members)), dim3(256), 0, st>>>(part, pl.splits, n, ranks);
+  MI_CHECK_LAUNCH("rank_sum_k");
+  return MI_OK;
+}
+
+size_t mi_pair_target_ranks_mean_workspace_bytes(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I,
+                                                 int32_t Tq) {
+  if (!ranks_sizes_ok(members, n_members, U, I, Tq)) return 0;
+  return make_ranks_plan(members, n_members, U, I, Tq, true).total;
+}
+
+int32_t mi_pair_target_ranks_mean(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I,
+                                  const int64_t* excl_off, const int32_t* excl_idx, const int32_t* targets, int32_t Tq,
+                                  int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes,
+                                  mi_stream_t stream) {
+  const int32_t rc = check_ranks_call("pair_target_ranks_mean", members, n_members, U, I, excl_off, excl_idx, targets, Tq, ranks);
+  if (rc != MI_OK) return rc;
+  const RanksPlan rp = make_ranks_plan(members, n_members, U, I, Tq, true);
+  const Plan& pl = rp.pl;
+  MI_REQUIRE(workspace && workspace_bytes >= rp.total, "pair_target_ranks_mean: workspace %zu < %zu bytes", workspace_bytes,
+             rp.total);
+  hipStream_t st = mi::as_stream(stream);
+  char* ws = static_cast<char*>(workspace);
+  GroupMember* tab = reinterpret_cast<GroupMember*>(ws + rp.off_table);
+  uint32_t* mask = excl_off ? reinterpret_cast<uint32_t*>(ws + rp.off_mask) : nullptr;
+  int32_t* part = reinterpret_cast<int32_t*>(ws + rp.off_part);
+  prepare_ranks(members, n_members, U, I, excl_off, excl_idx, rp, ws, tab, mask, st);
+  MI_CHECK_LAUNCH("pair_target_ranks_mean (prepare)");
+  const size_t lds = (sizeof(uint64_t) + sizeof(int) * kWaves) * kQB * static_cast<size_t>(Tq);      // at most 48 KB
+  pair_target_ranks_mean_k<<<dim3(static_cast<unsigned>(pl.qblocks), static_cast<unsigned>(pl.splits)), dim3(kThreads), lds, st>>>(
+      tab, n_members, mask, targets, target_scores, part, U, I, pl.chunk, Tq, pl.splits, pl.words);
+  MI_CHECK_LAUNCH("pair_target_ranks_mean_k");
+  const int64_t n = U * Tq;
+  rank_sum_k<<<dim3(grid_blocks(n), 1), dim3(256), 0, st>>>(part, pl.splits, n, ranks);
   MI_CHECK_LAUNCH("rank_sum_k");
   return MI_OK;
 }

@@ -99,7 +99,7 @@ PAIR_RANKS_MAX_TARGETS = 64        # MI_PAIR_RANKS_MAX_TARGETS
 
 
 class RankMember(C.Structure):
-    """mi_rank_member_t: one model of mi_pair_topk_group / mi_pair_target_ranks"""
+    """mi_rank_member_t: one model of mi_pair_topk_group / mi_pair_target_ranks / mi_pair_target_ranks_mean"""
     _fields_ = [("a_q", C.c_void_p), ("s_q", C.c_void_p), ("w_q", C.c_void_p), ("a_c", C.c_void_p), ("s_c", C.c_void_p),
                 ("w_c", C.c_void_p), ("dense", C.c_void_p), ("layer_off", C.c_void_p), ("widths", C.c_void_p),
                 ("H1", C.c_int32), ("E", C.c_int32), ("n_layers", C.c_int32), ("activation", C.c_int32)]
@@ -201,6 +201,8 @@ SIGNATURES = {
     "mi_pair_topk_group": (_i32, [_p, _i32, _i64, _i64, _p, _p, _i32, _p, _p, _p, _p, _p, _sz, _p]),
     "mi_pair_target_ranks_workspace_bytes": (_sz, [_p, _i32, _i64, _i64, _i32]),
     "mi_pair_target_ranks": (_i32, [_p, _i32, _i64, _i64, _p, _p, _p, _i32, _p, _p, _p, _sz, _p]),
+    "mi_pair_target_ranks_mean_workspace_bytes": (_sz, [_p, _i32, _i64, _i64, _i32]),
+    "mi_pair_target_ranks_mean": (_i32, [_p, _i32, _i64, _i64, _p, _p, _p, _i32, _p, _p, _p, _sz, _p]),
     "mi_predict_fused_workspace_bytes": (_sz, [_i64, _i32]),
     "mi_predict_fused": (_i32, [_p, _i64, _p, _i32, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32,
                                 _i32, _i32, _i64, _i64, _i64, _u64, _p, _p, _p, _p, _p, _sz, _p]),

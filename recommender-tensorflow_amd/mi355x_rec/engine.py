@@ -1412,26 +1412,8 @@ class DeepFM:
         _, U, I, _ = self._top_k_check(query_ids, candidate_ids, query_fields, 1, query_x, candidate_x)
         tg = torch.from_numpy(dense_targets(targets, U, I)).to(self.device).long()
         z = self.top_k(query_ids, candidate_ids, query_fields, 1, query_x, candidate_x, return_scores=True)[2]
-        # rank_key's high word as an int64 (NaN -> 0, -0 as +0); equal words are decided by the lower index
-        bits = z.view(torch.int32).long() & 0xffffffff
-        word = torch.where(bits >= 0x80000000, 0xffffffff - bits, bits + 0x80000000)
-        word = torch.where(z != z, torch.zeros_like(word), torch.where(z == 0, torch.full_like(word, 0x80000000), word))
-        ok = torch.ones(U, I, dtype=torch.bool, device=self.device)
-        if exclude is not None:
-            off, idx = self._top_k_exclusions(exclude, U, I)
-            rows = torch.repeat_interleave(torch.arange(U, device=self.device), off[1:] - off[:-1])
-            ok[rows, idx[:rows.numel()].long()] = False
-        ranks = torch.full(tuple(tg.shape), -1, dtype=torch.int32, device=self.device)
-        scores = torch.full(tuple(tg.shape), float("nan"), dtype=torch.float32, device=self.device)
-        cand = torch.arange(I, device=self.device)[None, :]
-        for j in range(tg.shape[1]):
-            t = tg[:, j]
-            tc = t.clamp(min=0)[:, None]
-            has = (t >= 0) & torch.gather(ok, 1, tc)[:, 0]
-            wt = torch.gather(word, 1, tc)
-            above = ok & ((word > wt) | ((word == wt) & (cand < tc)))
-            ranks[:, j] = torch.where(has, above.sum(1), torch.full_like(t, -1)).to(torch.int32)
-            scores[:, j] = torch.where(has, torch.gather(z, 1, tc)[:, 0], scores[:, j])
+        excl = self._top_k_exclusions(exclude, U, I) if exclude is not None else None
+        ranks, scores = ranks_from_scores(z, tg, excl)
         return (ranks, scores) if return_scores else ranks
 
     def _side_tensors(self, cat, num, ids, x, candidate):
@@ -2257,6 +2239,35 @@ def dense_targets(targets, U, I):
     return out
 
 
+def ranks_from_scores(z, tg, excl):
+    """mi_pair_target_ranks' rule on a score matrix, by key comparisons in torch on z's device — the fallback outside the
+    counting kernels' scope: z float32 [U, I], tg int64 [U, T] (dense_targets), excl the CSR pair of _top_k_exclusions or
+    None.  Returns (ranks int32 [U, T], -1 without a rank; the targets' scores float32 [U, T], NaN there)."""
+    U, I = z.shape
+    dev = z.device
+    # rank_key's high word as an int64 (NaN -> 0, -0 as +0); equal words are decided by the lower index
+    bits = z.view(torch.int32).long() & 0xffffffff
+    word = torch.where(bits >= 0x80000000, 0xffffffff - bits, bits + 0x80000000)
+    word = torch.where(z != z, torch.zeros_like(word), torch.where(z == 0, torch.full_like(word, 0x80000000), word))
+    ok = torch.ones(U, I, dtype=torch.bool, device=dev)
+    if excl is not None:
+        off, idx = excl
+        rows = torch.repeat_interleave(torch.arange(U, device=dev), off[1:] - off[:-1])
+        ok[rows, idx[:rows.numel()].long()] = False
+    ranks = torch.full(tuple(tg.shape), -1, dtype=torch.int32, device=dev)
+    scores = torch.full(tuple(tg.shape), float("nan"), dtype=torch.float32, device=dev)
+    cand = torch.arange(I, device=dev)[None, :]
+    for j in range(tg.shape[1]):
+        t = tg[:, j]
+        tc = t.clamp(min=0)[:, None]
+        has = (t >= 0) & torch.gather(ok, 1, tc)[:, 0]
+        wt = torch.gather(word, 1, tc)
+        above = ok & ((word > wt) | ((word == wt) & (cand < tc)))
+        ranks[:, j] = torch.where(has, above.sum(1), torch.full_like(t, -1)).to(torch.int32)
+        scores[:, j] = torch.where(has, torch.gather(z, 1, tc)[:, 0], scores[:, j])
+    return ranks, scores
+
+
 def target_ranks_group(engines, query_ids, candidate_ids, query_fields, targets, query_x=None, candidate_x=None, exclude=None,
                        return_scores=False):
     """DeepFM.target_ranks for several engines over one set of feature columns, every member by its OWN logit
@@ -2265,7 +2276,16 @@ def target_ranks_group(engines, query_ids, candidate_ids, query_fields, targets,
     per-side precompute runs once per member, then ONE scoring and counting launch for all members per 64 target columns
     (queries with more targets are served in passes; the sides are not recomputed).  ValueError (naming the member and the
     limit) for a member outside the kernel's scope, which is top_k_group's."""
-    engines = check_members("target_ranks_group", engines, _lib.PAIR_TOPK_GROUP_MAX_MEMBERS, DeepFM._top_k_group_limit)
+    return _target_ranks("target_ranks_group", "mi_pair_target_ranks", True, engines, query_ids, candidate_ids, query_fields, targets,
+                         query_x, candidate_x, exclude, return_scores)
+
+
+def _target_ranks(who, entry, per_member, engines, query_ids, candidate_ids, query_fields, targets, query_x, candidate_x, exclude,
+                  return_scores):
+    """target_ranks_group (entry mi_pair_target_ranks, per_member: outputs [M, U, Tmax]) and target_ranks_mean (entry
+    mi_pair_target_ranks_mean, outputs [U, Tmax]): the checks, the exclusions, the sides once per member, a launch per 64
+    target columns"""
+    engines = check_members(who, engines, _lib.PAIR_TOPK_GROUP_MAX_MEMBERS, DeepFM._top_k_group_limit)
     M, lead = len(engines), engines[0]
     sides, U, I, _ = lead._top_k_check(query_ids, candidate_ids, query_fields, 1, query_x, candidate_x)
     excl_off, excl_idx = lead._top_k_exclusions(exclude, U, I) if exclude is not None else (None, None)
@@ -2273,17 +2293,32 @@ def target_ranks_group(engines, query_ids, candidate_ids, query_fields, targets,
     args = [e._top_k_sides(sides) for e in engines]          # (kept alive until the launches are enqueued)
     members = _rank_members(engines, args)
     dev, k_ = lead.device, lead.k
+    shape = lambda Tq: (M, U, Tq) if per_member else (U, Tq)
     ranks, scores = [], []
     for lo in range(0, tg.shape[1], _lib.PAIR_RANKS_MAX_TARGETS):
         t = torch.from_numpy(np.ascontiguousarray(tg[:, lo:lo + _lib.PAIR_RANKS_MAX_TARGETS])).to(dev)
         Tq = t.shape[1]
-        ranks.append(torch.empty(M, U, Tq, dtype=torch.int32, device=dev))
-        scores.append(torch.empty(M, U, Tq, dtype=torch.float32, device=dev) if return_scores else None)
-        ws = lead._bytes("target_ranks_ws", k_.query("mi_pair_target_ranks_workspace_bytes", members, M, U, I, Tq))
-        k_.mi_pair_target_ranks(members, M, U, I, excl_off, excl_idx, t, Tq, ranks[-1], scores[-1], ws, ws.numel())
+        ranks.append(torch.empty(shape(Tq), dtype=torch.int32, device=dev))
+        scores.append(torch.empty(shape(Tq), dtype=torch.float32, device=dev) if return_scores else None)
+        ws = lead._bytes(who + "_ws", k_.query(entry + "_workspace_bytes", members, M, U, I, Tq))
+        getattr(k_, entry)(members, M, U, I, excl_off, excl_idx, t, Tq, ranks[-1], scores[-1], ws, ws.numel())
     if not ranks:                                            # (no query names a target)
-        ranks, scores = [torch.empty(M, U, 0, dtype=torch.int32, device=dev)], [torch.empty(M, U, 0, device=dev)]
-    ranks = ranks[0] if len(ranks) == 1 else torch.cat(ranks, 2)
+        ranks, scores = [torch.empty(shape(0), dtype=torch.int32, device=dev)], [torch.empty(shape(0), device=dev)]
+    ranks = ranks[0] if len(ranks) == 1 else torch.cat(ranks, -1)
     if not return_scores:
         return ranks
-    return ranks, (scores[0] if len(scores) == 1 else torch.cat(scores, 2))
+    return ranks, (scores[0] if len(scores) == 1 else torch.cat(scores, -1))
+
+
+# ---------------------------------------------------------------------- exact ranks of named targets under the mean logit
+def target_ranks_mean(engines, query_ids, candidate_ids, query_fields, targets, query_x=None, candidate_x=None, exclude=None,
+                      return_scores=False):
+    """DeepFM.target_ranks under the MEAN logit of several engines over one set of feature columns — the order top_k_group
+    selects by (mi_pair_target_ranks_mean, include/mi355x_rec.h): ranks int32 [U, Tmax], padded with -1, plus the targets'
+    mean logits float32 [U, Tmax] (bit for bit top_k_group's scores; NaN where the rank is -1) when return_scores.  The
+    arguments are checked and the exclusions built once (member 0), the per-side precompute runs once per member, then ONE
+    scoring and counting launch per 64 target columns (queries with more targets are served in passes; the sides are not
+    recomputed).  ValueError (naming the member and the limit) for a member outside the kernel's scope, which is
+    top_k_group's."""
+    return _target_ranks("target_ranks_mean", "mi_pair_target_ranks_mean", False, engines, query_ids, candidate_ids, query_fields,
+                         targets, query_x, candidate_x, exclude, return_scores)

@@ -305,6 +305,16 @@ def _model_columns(sig):
     return [strip(c) for c in m["categorical_columns"]], [strip(c) for c in m["numeric_columns"]]
 
 
+def _layered_mean(engines, q_ids, c_ids, qf, k, q_x, c_x):
+    """the members' mean pair score [U, I] on the device, member by member: every member's top_k(return_scores=True), a
+    torch fp32 sum in member order and a division"""
+    acc = None
+    for e in engines:
+        z = e.top_k(q_ids, c_ids, qf, k, q_x, c_x, return_scores=True)[2]
+        acc = z.clone() if acc is None else acc + z
+    return acc / torch.full_like(acc, float(len(engines)))
+
+
 class EnsemblePredictor:
     """``ensemble(features) -> dict``: the mean logit of M Predictors over the same feature columns and what the head makes
     of it — the Predictor dict (logits, logistic, probabilities, class_ids, classes); ``return_members=True`` adds
@@ -499,11 +509,7 @@ class EnsemblePredictor:
         else:
             _, U, I, k = lead._top_k_check(q_ids, c_ids, qf, k, q_x, c_x)
             off, ix = lead._top_k_exclusions(exclude, U, I) if exclude is not None else (None, None)
-            acc = None
-            for e in engines:
-                z = e.top_k(q_ids, c_ids, qf, k, q_x, c_x, return_scores=True)[2]
-                acc = z.clone() if acc is None else acc + z
-            scores = (acc / torch.full_like(acc, float(len(engines)))).cpu().numpy()
+            scores = _layered_mean(engines, q_ids, c_ids, qf, k, q_x, c_x).cpu().numpy()
             top_s, top_i = host_top_k(scores, k, None if off is None else off.cpu().numpy(),
                                       None if ix is None else ix.cpu().numpy())
             score, idx = torch.from_numpy(top_s).to(self.device), torch.from_numpy(top_i).to(self.device)
@@ -513,3 +519,40 @@ class EnsemblePredictor:
         if return_scores:
             host["scores"] = scores
         return host
+
+    def rank_targets(self, query_features, candidate_features, targets, exclude=None, mode=None, return_scores=False):
+        """Predictor.rank_targets for the ensemble: the exact 0-based rank of named target candidates among all eligible
+        candidates of their query by the MEAN logit of the members — the position a target would take in recommend's list
+        were k unbounded.  targets and exclude as DeepFM.target_ranks takes them; the two feature dicts and mode as
+        recommend takes them:
+          "fused"   one scoring and counting launch for all members per 64 target columns (engine.target_ranks_mean:
+                    mi_pair_target_ranks_mean); ValueError naming the member and the limit when a member is outside that
+                    kernel's scope;
+          "layered" the mean matrix as recommend's layered branch makes it, and the keys counted by torch comparisons on
+                    the device (engine.ranks_from_scores) — the fallback, not the hot path;
+          "auto"    fused iff every member is inside the kernel's scope.
+        Returns numpy int32 [U, Tmax], -1 where a target has no rank; return_scores adds the targets' mean logits float32
+        [U, Tmax] (NaN there)."""
+        mode = self.mode if mode is None else mode
+        if mode not in ("auto", "fused", "layered"):
+            raise ValueError("mode must be 'auto', 'fused' or 'layered'")
+        limit = self.rank_fused_limit()
+        if mode == "fused" and limit is not None:
+            raise ValueError("mode='fused': member %d: the model has %s" % limit)
+        plan, lead = self.plan, self.members[0].engine
+        qf = split_sides(plan, query_features, candidate_features)
+        cf = [f for f in range(len(plan.categorical) + len(plan.numeric)) if f not in qf]
+        q_ids, q_x = side_inputs(plan, qf, query_features, self.device)
+        c_ids, c_x = side_inputs(plan, cf, candidate_features, self.device)
+        engines = [p.engine for p in self.members]
+        if mode == "fused" or (mode == "auto" and limit is None):
+            out = _engine.target_ranks_mean(engines, q_ids, c_ids, qf, targets, q_x, c_x, exclude=exclude,
+                                            return_scores=return_scores)
+            ranks, scores = out if return_scores else (out, None)
+        else:
+            _, U, I, _ = lead._top_k_check(q_ids, c_ids, qf, 1, q_x, c_x)
+            tg = torch.from_numpy(_engine.dense_targets(targets, U, I)).to(self.device).long()
+            excl = lead._top_k_exclusions(exclude, U, I) if exclude is not None else None
+            ranks, scores = _engine.ranks_from_scores(_layered_mean(engines, q_ids, c_ids, qf, 1, q_x, c_x), tg, excl)
+        ranks = ranks.cpu().numpy()
+        return (ranks, scores.cpu().numpy()) if return_scores else ranks

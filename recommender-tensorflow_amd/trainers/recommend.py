@@ -13,7 +13,9 @@ launch, no list).
 ``--top N`` (with ``--model deep_fm``) ranks with an ensemble instead: --job-dir is then the job directory of a
 ``trainers.sweep`` run, the sweep's N best members are loaded from their exports (EnsemblePredictor.from_sweep) and every
 item is ranked by the members' mean logit, in one launch where the members allow it (EnsemblePredictor.recommend).  The
-output goes to ``<job-dir>/recommend/top<K>_ensemble<N>.csv`` with the same columns and the same ``_metrics.json``."""
+output goes to ``<job-dir>/recommend/top<K>_ensemble<N>.csv`` with the same columns and the same ``_metrics.json``.
+``--mean-metrics-at K [K ...]`` (with ``--top N``) adds what --metrics-at adds for one model, under the ensemble's mean
+logit (EnsemblePredictor.rank_targets)."""
 import csv
 import json
 import math
@@ -49,6 +51,9 @@ def make_parser(model):
                    help="also report hit_rate@K, recall@K and ndcg@K at these cutoffs (any K >= 1, above 256 too), mrr and "
                         "mean_rank, from the exact rank of every test positive among all eligible items "
                         "(Estimator.rank_targets); not with --top (default: off)")
+    p.add_argument("--mean-metrics-at", type=int, nargs="+", default=None, metavar="K",
+                   help="with --top N: what --metrics-at reports for one model, from the exact rank of every test positive "
+                        "under the ensemble's MEAN logit (EnsemblePredictor.rank_targets) (default: off)")
     return p
 
 
@@ -136,6 +141,12 @@ def main(argv=None):
                              "mean logit is ranked through its top-K list only (--top-k)" % args.top)
         if min(args.metrics_at) < 1:
             raise SystemExit("--metrics-at %s: cutoffs are at least 1" % " ".join(str(v) for v in args.metrics_at))
+    if args.mean_metrics_at is not None:
+        if args.top is None:
+            raise SystemExit("--mean-metrics-at: needs --top N: it ranks by an ensemble's mean logit; one model's exact-rank "
+                             "metrics are --metrics-at")
+        if min(args.mean_metrics_at) < 1:
+            raise SystemExit("--mean-metrics-at %s: cutoffs are at least 1" % " ".join(str(v) for v in args.mean_metrics_at))
     if args.top is not None:
         from mi355x_rec.predictor import EnsemblePredictor
         if args.model != "deep_fm":
@@ -190,14 +201,15 @@ def main(argv=None):
         if r >= CUTOFF:
             positives.setdefault(int(u), set()).add(int(it))
     m = ranking_metrics(top, positives, k)
-    if args.metrics_at is not None:
+    exact_at = args.metrics_at if ens is None else args.mean_metrics_at
+    if exact_at is not None:
         from mi355x_rec.metrics import ranking_metrics_from_ranks
         targets = positive_targets(users, items, test)
         try:
-            ranks = est.rank_targets(qf, cf, targets, exclude=excl)
+            ranks = (est if ens is None else ens).rank_targets(qf, cf, targets, exclude=excl)
         except ValueError as e:
             raise SystemExit("recommend: %s" % e)
-        exact = ranking_metrics_from_ranks(ranks, [len(t) for t in targets], args.metrics_at)
+        exact = ranking_metrics_from_ranks(ranks, [len(t) for t in targets], exact_at)
         m.update({key: v for key, v in exact.items() if key not in m})      # (the top-K list's keys keep their values)
     m_path = os.path.splitext(path)[0] + "_metrics.json"
     with open(m_path, "w") as f:

@@ -22,6 +22,8 @@ mean_rank: what trainers.recommend --metrics-at reports for the member's directo
 
 --ensemble N: after the ranking, the N best members are served as ONE model (EnsemblePredictor: their mean logit, one launch
 for all of them) over the test set; sweep.json gains "ensemble": its members and its metrics, next to the best member's.
+With --rank-metrics the ensemble is measured as a recommender too: "ensemble" gains "ranking", the members' keys under the
+ensemble's MEAN logit (EnsemblePredictor.rank_targets: what trainers.recommend --top N --mean-metrics-at reports).
 
 trainers.deep_fm has no learning-rate flag (the reference has none): a member restored through ``trainers.deep_fm
 --restore`` continues at that CLI's 0.001, a member restored through ``trainers.sweep --restore`` at its own rate."""
@@ -103,11 +105,10 @@ def make_parser():
     return p
 
 
-def evaluate_ensemble(job_dir, top, test_csv, device, batch_size=4096):
-    """The EVAL metrics of the mean of the sweep's `top` best members over the test set: EnsemblePredictor.from_sweep's
+def evaluate_ensemble(ens, test_csv, batch_size=4096):
+    """The EVAL metrics of the mean of the sweep's best members (ens: EnsemblePredictor.from_sweep) over the test set: its
     logits through mi_eval_accumulate and metrics_from_counters, as Estimator.evaluate counts one model's.  "loss" is the
     average loss (the whole set as one batch of a mean reduction)."""
-    ens = EnsemblePredictor.from_sweep(job_dir, top=top, device=device)
     dev = ens.device
     hist = torch.zeros(2 * 201, dtype=torch.int64, device=dev)
     counts = torch.zeros(8, dtype=torch.int64, device=dev)
@@ -126,20 +127,33 @@ def evaluate_ensemble(job_dir, top, test_csv, device, batch_size=4096):
     return ens.sweep_members, {k: float(v) for k, v in metrics.items()}
 
 
-def rank_population(pop, plan, train_csv, test_csv, ks):
-    """Every member's ranking metrics as a recommender, what trainers.recommend --metrics-at reports for its directory:
-    users, items, exclusions and test positives as that CLI builds them, the positives' exact ranks for all members of the
-    population in ONE launch (FusedPopulation.rank_targets; a member outside that launch's scope is ranked on its own, and
-    a line says so).  Returns a list of M dicts."""
+def rank_tables(train_csv, test_csv):
+    """The recommendation run trainers.recommend makes of the two files: (user features, item features, the test
+    positives' candidate indices per user, the users' training items as an exclusion CSR pair)"""
     from trainers import recommend
     train, _ = _read_csv(train_csv)
     test, _ = _read_csv(test_csv)
     users, qf, items, cf = recommend.tables(train, test)
-    targets = recommend.positive_targets(users, items, test)
-    ranks = pop.rank_targets(plan, qf, cf, targets, exclude=recommend.exclusion_csr(users, items, train),
-                             say=lambda text: print("INFO: --rank-metrics: %s" % text))
+    return qf, cf, recommend.positive_targets(users, items, test), recommend.exclusion_csr(users, items, train)
+
+
+def rank_population(pop, plan, train_csv, test_csv, ks):
+    """Every member's ranking metrics as a recommender, what trainers.recommend --metrics-at reports for its directory:
+    users, items, exclusions and test positives as that CLI builds them (rank_tables), the positives' exact ranks for all
+    members of the population in ONE launch (FusedPopulation.rank_targets; a member outside that launch's scope is ranked
+    on its own, and a line says so).  Returns a list of M dicts."""
+    qf, cf, targets, excl = rank_tables(train_csv, test_csv)
+    ranks = pop.rank_targets(plan, qf, cf, targets, exclude=excl, say=lambda text: print("INFO: --rank-metrics: %s" % text))
     n_pos = [len(t) for t in targets]
     return [ranking_metrics_from_ranks(r, n_pos, ks) for r in ranks]
+
+
+def rank_ensemble(ens, train_csv, test_csv, ks):
+    """rank_population for the ensemble's MEAN logit, what trainers.recommend --top N --mean-metrics-at reports: the
+    positives' exact ranks on the same tables (EnsemblePredictor.rank_targets: one launch where the members allow it).
+    Returns one dict with a member row's "ranking" keys."""
+    qf, cf, targets, excl = rank_tables(train_csv, test_csv)
+    return ranking_metrics_from_ranks(ens.rank_targets(qf, cf, targets, exclude=excl), [len(t) for t in targets], ks)
 
 
 def grid(args):
@@ -355,13 +369,19 @@ def train_and_evaluate(args):
     if n_ens:
         if n_ens < 0 or n_ens > len(rows):
             raise ValueError("--ensemble %d: the sweep has %d members" % (n_ens, len(rows)))
-        who, metrics = evaluate_ensemble(args.job_dir, n_ens, args.test_csv, args.device)
+        ens = EnsemblePredictor.from_sweep(args.job_dir, top=n_ens, device=args.device)
+        who, metrics = evaluate_ensemble(ens, args.test_csv)
         doc["ensemble"] = {"members": who, "metrics": metrics}
+        if rank_ks:
+            doc["ensemble"]["ranking"] = rank_ensemble(ens, args.train_csv, args.test_csv, rank_ks)
         with open(os.path.join(args.job_dir, "sweep.json"), "w") as f:
             json.dump(doc, f, indent=1)
-        shown = "auc" if is_ranking(args.select) else args.select      # (the ensemble is evaluated, not ranked)
+        shown = "auc" if is_ranking(args.select) else args.select      # (evaluation metrics here; a ranking --select: the line below)
         print("INFO: ensemble of the %d best members (%s): %s = %.6g, the best single member (member %d) has %.6g" % (
             n_ens, ", ".join(str(m) for m in who), shown, metrics[shown], best["member"], best["metrics"][shown]))
+        if is_ranking(args.select):
+            print("INFO: ensemble of the %d best members by its mean logit: %s = %.6g, the best single member (member %d) has %.6g" % (
+                n_ens, args.select, doc["ensemble"]["ranking"][args.select], best["member"], value(best)))
     print("INFO: best of %d members by %s: member %d (%s), %s = %.6g, in %s" % (
         len(rows), args.select, best["member"], ", ".join("%s = %s" % kv for kv in sorted(best["params"].items())), args.select,
         value(best), best["dir"]))
