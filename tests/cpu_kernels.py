@@ -44,6 +44,14 @@ def _at(ptr, n, dtype, stride=1, width=None):
     return flat.as_strided((n, width), (stride, 1)) if width else flat.as_strided((n,), (stride,))
 
 
+def _publish(vec, values):
+    """an abs-max vector (a tensor, or the address in a mi_gemm_amax_t; may be NULL) raised to max |values|: the header's
+    contract — the largest of its MI_AMAX_SLOTS entries is the value, the caller zeroes it"""
+    vec = _at(vec, _lib.AMAX_SLOTS, F32) if isinstance(vec, int) else vec
+    if vec is not None and np.size(values):
+        vec[0] = max(float(vec[0]), float(np.abs(values).max()))
+
+
 def thresholds():
     """tf.metrics.auc's 200 thresholds as mi_eval_accumulate holds them (fp32 of the fp64 values)"""
     th = np.arange(200, dtype=np.float64) / 199.0
@@ -183,6 +191,7 @@ class NumpyKernels:
             v = _np(table)[rows]                               # [B,F,E]
             if concat is not None:
                 _np(concat)[:, :F * E] = v.reshape(B, F * E)
+            _publish(amax, v)
             s = v.sum(1)
             if sumv is not None:
                 _np(sumv)[:] = s
@@ -252,7 +261,7 @@ class NumpyKernels:
 
     # ---- MLP ----------------------------------------------------------------------------------
     def mi_absmax(self, x, n, out):
-        pass          # abs-max vectors only steer the HIP kernels' fp16 scales
+        _publish(out, _np(x).reshape(-1)[:n])      # (the vectors only steer the HIP kernels' fp16 scales; tests read them)
 
     def mi_dense_fwd(self, X, ldx, W, bias, Y, ldy, M, N, K, relu, keep, seed, amax=None):
         y = _np(X)[:, :K] @ _np(W) + _np(bias)
@@ -260,6 +269,7 @@ class NumpyKernels:
         if keep < 1.0:
             y = (y / np.float32(keep)) * dropout_mask(seed, M, N, keep)
         _np(Y)[:, :N] = y
+        _publish(amax.out if amax is not None else None, y)
 
     def mi_dense_bwd_data(self, dY, lddy, W, Xact, ldxa, dX, lddx, M, N, K, keep, act=1, amax=None):
         dy = _np(dY).reshape(M, -1)[:, :N]
@@ -273,6 +283,7 @@ class NumpyKernels:
                 d = {0: np.ones_like(y), 2: y * (1 - y), 3: 1 - y * y}[int(act)]
                 g = np.where((keep < 1) & (xa == 0), 0, (g / np.float32(keep)) * d).astype(np.float32)
         _np(dX)[:, :K] = g
+        _publish(amax.out if amax is not None else None, g)
 
     def mi_dense_bwd_weight(self, X, ldx, dY, lddy, dW, db, M, N, K, ws, wsb, amax=None):
         dy = _np(dY).reshape(M, -1)[:, :N]
@@ -394,7 +405,7 @@ class NumpyKernels:
 
     def mi_dense_fwd_gathered(self, table, field_off, ids, F, E, W, bias, Y, ldy, M, N, relu, keep, seed, amax=None, ts=0):
         X = torch.from_numpy(self._concat(table, field_off, ids, F, E))
-        self.mi_dense_fwd(X, F * E, W, bias, Y, ldy, M, N, F * E, relu, keep, seed)
+        self.mi_dense_fwd(X, F * E, W, bias, Y, ldy, M, N, F * E, relu, keep, seed, amax)
 
     def mi_dense_bwd_weight_gathered(self, table, field_off, ids, F, E, dY, lddy, dW, db, M, N, ws, wsb, amax=None, ts=0):
         X = torch.from_numpy(self._concat(table, field_off, ids, F, E))

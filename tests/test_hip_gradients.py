@@ -1,5 +1,6 @@
-"""-m gpu: the gradients of ONE train step on the planes path (engine._backward_dense as the benchmark runs it) against
-the oracle's own backward in fp64.
+"""-m gpu: the gradients of ONE train step — on the planes path (engine._backward_dense as the benchmark runs it) and on the
+any-shape path every other model takes (layered_grad_check.CASES) — against the oracle's own backward in fp64.  The
+checker is tests/layered_grad_check.py, which test_layered_gradients_cpu.py runs on the numpy stand-in.
 
 What is read: every dense gradient (DeepFM.d_grad: kernels, biases, linear bias, numeric embeddings, numeric linear
 weights), the gradient of the concat (_ws["dact0"]), sumv and dlogit.  The embedding-row gradients need no comparison of
@@ -28,213 +29,20 @@ import torch
 from oracle import deepfm as O
 from oracle import optimizers as OO
 from tests.cases import _hip_engine
-from tests.util import (_compare_vars, _device_relu_masks, dev, dropout_mask, make_problem, planned_splits,
-                        row_rel_err)
+from tests.layered_grad_check import CASES, SEED, bar as _bar, check_amax_chain, dense_grads as _dense_grads, one_step
+from tests.layered_grad_check import relu_masks as _relu_masks, report as _report, rms_err as _rms_err, run_case
+from tests.layered_grad_check import top_fused as _top_fused
+from tests.util import _compare_vars, _device_relu_masks, dev, make_problem, planned_splits, row_rel_err
 
 pytestmark = pytest.mark.gpu
 
-SEED = 319                                                   # test_hip_model.CONFIG3_SAFE_SEED's problem
 VOCAB3 = [40 + 3 * i for i in range(26)]                     # config 3's 26 fields, small vocabularies
 
 
-def _rms_err(got, ref):
-    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
-    return float(np.max(np.abs(got - ref)) / (np.sqrt(np.mean(ref * ref)) + 1e-300))
-
-
-def _bar(e32):
-    return max(1e-5, 4.0 * e32)
-
-
-def _report(case, name, err, e32):
-    print("GRAD %-34s %-12s device %.2e  fp32-oracle %.2e  bar %.2e%s" % (
-        case, name, err, e32, _bar(e32), "  (second term)" if err >= 1e-5 else ""))
-
-
-def _merged(m, name, B, K):
-    out = torch.empty(B, K, device="cuda")
-    m.k.mi_merge_rows(m._pl[name].struct, B, K, out, K)
-    return out
-
-
-def _top_fused(m):
-    return getattr(m, "_top_step", None) == m.step - 1
-
-
-def _relu_masks(m, B):
-    """_device_relu_masks, and for a last hidden layer that ran inside the fused logits + head launch (its output never
-    reaches memory) the units whose gradient that launch let through: dY of that layer is dlogit * w masked, and neither
-    factor is 0 here — checked by the caller's assertion that a decision differs from the fp64 sign test only within 1e-6
-    of 0, which an unexplained zero would fail."""
-    masks = _device_relu_masks(m, B)
-    if _top_fused(m):
-        nh = len(m.hidden)
-        assert bool((m._ws["dlogit"][:B] != 0).all())
-        masks[nh - 1] = (_merged(m, "dy%dp" % (nh - 1), B, m.hidden[-1]) != 0).cpu().numpy()
-    return masks
-
-
-def _dense_grads(m):
-    """name -> device gradient, in oracle.Params.dense_list() order (kernel_0 without its zero pad rows, which must have
-    got exactly zero gradients)"""
-    g = m.d_grad
-    out = []
-    for i in range(len(m.layers)):
-        k = m.kernel(i, g)
-        if i == 0 and m.D_in < m.D:
-            assert float(k[m.D_in:].abs().max()) == 0.0
-            k = k[:m.D_in]
-        out += [("kernel_%d" % i, k.cpu().numpy()), ("bias_%d" % i, m.bias(i, g).cpu().numpy())]
-    out.append(("lin_bias", g[m.lin_bias_off:m.lin_bias_off + 1].cpu().numpy()))
-    if m.num_emb_off is not None:
-        out.append(("num_emb", m._seg(g, m.num_emb_off, (m.n_numeric, m.E)).cpu().numpy()))
-    if m.lin_num_off is not None:
-        out.append(("dw_num", g[m.lin_num_off:m.lin_num_off + m.n_numeric].cpu().numpy()))
-    return out
-
-
-def _oracle_grads(p, ids, x, y, dt, masks, drop, keep, flags, numeric, reduction):
-    q = p.astype(dt)
-    xx = None if x is None else x.astype(dt)
-    c = O.forward(q, ids, xx, *flags, dropout_masks=drop, numeric=numeric, keep_prob=keep, relu_masks=masks)
-    loss, dlogit, _, _ = O.head(c["logits"], y, reduction)
-    dense, _, _ = O.backward(q, c, dlogit, drop)
-    nh = len(q.mlp) - 1
-    # d loss / d concat as the MLP sees it (the engine's dact0): backward() folds it into the row gradients
-    d = dlogit[:, None] * q.mlp[nh][0][:, 0][None, :]
-    for i in range(nh - 1, -1, -1):
-        if drop is not None:
-            d = (d * drop[i].astype(dt)) / dt(keep)
-        d = (d * masks[i].astype(dt)) @ q.mlp[i][0].T
-    return dict(dense=dense, d_concat=d, dlogit=dlogit, sumv=c.get("sumv"), pre=c["pre"], loss=float(loss),
-                logits=c["logits"])
-
-
-def _check_masks(masks, pre64, drop):
-    """the device's relu decisions against the fp64 sign test: they may differ only on marginal units"""
-    flips = 0
-    for i, (mk, q) in enumerate(zip(masks, pre64)):
-        own = q > 0
-        if drop is not None:
-            own &= drop[i] > 0                  # (a dropped unit's stored activation is 0: its mask bit is off)
-        diff = mk != own
-        flips += int(diff.sum())
-        assert not diff.any() or float(np.abs(q[diff]).max()) < 1e-6, (i, int(diff.sum()), float(np.abs(q[diff]).max()))
-    return flips
-
-
-def _check_amax_chain(m, B):
-    """Every abs-max vector the weight gradients consume (x<i>, dy<i> of each hidden layer) against the matrix it
-    describes: same binary exponent as the true abs-max, and not below it by more than the planes' own rounding (2^-20
-    relative).  A stale, unzeroed or undersized vector fails here.  dY in fp32 where this step wrote it (need_f), as
-    planes (merged) otherwise; activations from the planes the GEMMs read."""
-    nh = len(m.hidden)
-    for i in range(nh):
-        fan, h = m.layers[i][2], m.layers[i][3]
-        x_true = float(_merged(m, "x%dp" % i, B, fan).abs().max())
-        # dact<i+1> = dY of layer i in fp32: written when the layer above is the fused tail / gemv and this layer's weight
-        # gradient reads fp32, or when the data gradient above could not write planes straight (see _backward_dense)
-        if i == nh - 1:
-            need_f = not m._wgrad_planes_ok(B, i)
-        else:
-            need_f = not (h <= 512 and m._wgrad_planes_ok(B, i))
-        if need_f:
-            dy_true = float(m._ws["dact%d" % (i + 1)][:B * h].abs().max())
-        else:
-            dy_true = float(_merged(m, "dy%dp" % i, B, h).abs().max())
-        for name, true in (("x%d" % i, x_true), ("dy%d" % i, dy_true)):
-            assert name in m._amax_idx, name
-            got = float(m._av(name).max())
-            assert true > 0 and np.isfinite(true), (name, true)
-            assert np.frexp(got)[1] == np.frexp(true)[1], (name, got, true)
-            assert got >= true * (1 - 2.0 ** -20), (name, got, true)
-
-
-def _one_step(case, vocab, E, hidden, B, nn=0, numeric="embed", dropout=0.0, flags=(True, True, True), reduction="mean",
-              prepare=None, expect_planes=True, small_rows_may_vanish=None):
-    """One train_step of an engine loaded with oracle parameters; every gradient against the fp64 oracle.  Returns the engine."""
-    if numeric == "embed":
-        p, ids, x, y = make_problem(SEED, vocab, E, hidden, B, n_numeric=nn)
-    else:
-        rng = np.random.default_rng(SEED)
-        p = O.init_params(rng, vocab, E, hidden, n_numeric=nn, dtype=np.float32, lin_scale=0.05, numeric=numeric)
-        p.lin_bias[:] = 0.1
-        for _, b in p.mlp:
-            b[:] = (rng.standard_normal(b.shape) * 0.05).astype(np.float32)
-        ids = np.stack([rng.integers(0, v, B) for v in vocab], 1).astype(np.int32)
-        ids[B // 2] = ids[0]
-        x = rng.standard_normal((B, nn)).astype(np.float32)
-        y = (rng.random(B) < 0.3).astype(np.uint8)
-    if prepare is not None:
-        y = prepare(p, ids, x, y)
-    m = _hip_engine(vocab, E, hidden, nn, gemm="f16x2", numeric=numeric, dropout=dropout, seed=7, reduction=reduction,
-                use_linear=flags[0], use_mf=flags[1], use_dnn=flags[2])
-    assert bool(m.planes) == expect_planes
-    m.load_oracle_params(p)
-    keep = 1.0 - dropout
-    drop = [dropout_mask(m._layer_seed(i), B, h, keep) for i, h in enumerate(hidden)] if dropout else None   # (step 0's seeds)
-    loss_g, logit_g = m.train_step(dev(ids), dev(y), dev(x))
-    torch.cuda.synchronize()
-    # Nothing in _apply writes d_grad unless variables are frozen (deep_numeric / wide_numeric column subsets: none here),
-    # so the gradients of the step survive it.  A buffer nobody filled must not pass: finite and non-zero.
-    assert m._frozen is None
-    assert bool(torch.isfinite(m.d_grad).all()) and float(m.d_grad.abs().max()) > 0
-    masks = _relu_masks(m, B)
-    t0 = time.perf_counter()
-    r64 = _oracle_grads(p, ids, x, y, np.float64, masks, drop, keep, flags, numeric, reduction)
-    r32 = _oracle_grads(p, ids, x, y, np.float32, masks, drop, keep, flags, numeric, reduction)
-    host_s = time.perf_counter() - t0
-    flips = _check_masks(masks, r64["pre"], drop)
-    print("GRAD %-34s B=%d  oracle fp64 + fp32 on the host: %.1f s, marginal relu decisions taken from the device: %d, "
-          "top layer fused: %s" % (case, B, host_s, flips, _top_fused(m)))
-    assert abs(loss_g.item() - r64["loss"]) <= 1e-5 * abs(r64["loss"])
-    failures = []
-
-    def hold(name, err, e32):
-        _report(case, name, err, e32)
-        if not err < _bar(e32):
-            failures.append((name, err, e32, _bar(e32)))
-    dev_dense = _dense_grads(m)
-    assert len(dev_dense) == len(r64["dense"])
-    for (name, g), g64, g32 in zip(dev_dense, r64["dense"], r32["dense"]):
-        g64 = np.asarray(g64).reshape(g.shape)
-        assert np.isfinite(g).all() and np.abs(g).max() > 0, name
-        hold(name, _rms_err(g, g64), _rms_err(np.asarray(g32).reshape(g.shape), g64))
-    D = m.D
-    dc = m._ws["dact0"][:B * D].view(B, D)
-    if m.D_in < D:
-        dc = dc[:, :m.D_in]
-    dc = dc.cpu().numpy()
-    assert np.isfinite(dc).all() and np.abs(dc).max() > 0
-    dc64 = r64["d_concat"]
-    if small_rows_may_vanish is not None:
-        # rows the documented cut-off may drop (fp64 dlogit below 2^-38 of the largest): either right or exactly zero
-        tiny = small_rows_may_vanish(r64["dlogit"])
-        gone = tiny & ~dc.any(1)
-        print("GRAD %-34s rows below 2^-38 of the largest dlogit: %d, of them zero on the device: %d" % (
-            case, int(tiny.sum()), int(gone.sum())))
-        dc, dc64, dc32 = dc[~gone], dc64[~gone], r32["d_concat"][~gone]
-    else:
-        dc32 = r32["d_concat"]
-    hold("d_concat", row_rel_err(dc, dc64), row_rel_err(dc32, dc64))
-    # An example's row of d_concat is its dlogit times a row that does not depend on it, and sigmoid(x) - y loses relative
-    # precision by cancellation wherever the two are close (in fp32 on every side): the measure above then shows the head's
-    # conditioning.  Per unit of each side's OWN dlogit the row is the chain of data gradients alone.
-    dl = m._ws["dlogit"][:B].cpu().numpy().astype(np.float64)
-    dl64, dl32 = r64["dlogit"], r32["dlogit"].astype(np.float64)
-    if small_rows_may_vanish is not None:
-        dl, dl64, dl32 = dl[~gone], dl64[~gone], dl32[~gone]
-    assert (dl != 0).all() and (dl32 != 0).all()
-    unit64 = dc64 / dl64[:, None]
-    hold("d_concat/dlogit", row_rel_err(dc / dl[:, None], unit64), row_rel_err(dc32 / dl32[:, None], unit64))
-    hold("dlogit", _rms_err(m._ws["dlogit"][:B].cpu().numpy(), r64["dlogit"]), _rms_err(r32["dlogit"], r64["dlogit"]))
-    if flags[1]:
-        hold("sumv", row_rel_err(m._ws["sumv"][:B * E].view(B, E).cpu().numpy(), r64["sumv"]),
-             row_rel_err(r32["sumv"], r64["sumv"]))
-    if m.planes:
-        _check_amax_chain(m, B)
-    assert not failures, failures
-    return m, r64
+def _one_step(case, vocab, E, hidden, B, **kw):
+    """layered_grad_check.one_step on a HIP engine (gemm "f16x2", relu unless told otherwise).  Returns (engine, fp64 reference)."""
+    r = one_step(case, _hip_engine, vocab, E, hidden, B, **kw)
+    return r.m, r.r64
 
 
 def _planes_wgrad_layers(m, B):
@@ -302,6 +110,14 @@ def test_top_hidden_layer_of_100_units_leaves_the_planes_path():
     B = 2080
     m, _ = _one_step("hidden [512, 256, 100] B=%d" % B, VOCAB3, 64, [512, 256, 100], B, expect_planes=False)
     assert _planes_wgrad_layers(m, B) == [] and "wgrad_batch_ws" not in m._ws
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])
+def test_any_shape_path_gradients(case):
+    """The models that leave the planes path (an activation other than relu, a width that is no multiple of 16, gemm "fp32" /
+    "bf16x3"): every gradient of one step, and the abs-max chain of the f16x2 weight gradients, at shapes with several row
+    tiles, column tiles and split-K slabs.  Which kernel each GEMM reaches is stated with the case and asserted there."""
+    run_case(case, _hip_engine)
 
 
 def test_wide_and_deep_raw_numeric_columns_in_the_planes():
@@ -488,5 +304,5 @@ def test_full_size_gradients():
     _report(case, "d_concat", err, e32)
     if not err < _bar(e32):
         failures.append(("d_concat", err, e32))
-    _check_amax_chain(m, B)
+    failures += check_amax_chain(m, B)
     assert not failures, failures
