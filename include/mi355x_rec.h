@@ -253,7 +253,7 @@ int32_t mi_sort_unique_rows_slots(const int32_t* rows, int64_t n, int64_t num_ro
  * (a step that was not told its next batch sorts at its head): ONE launch per radix pass and one for the compaction, the
  * tiles of a field exchanging their digit counts inside the launch (5 launches, 130 us at config 3 against 145).  1: the
  * call runs on a side stream BESIDE the step's bandwidth-bound kernels (the next batch's sort, beside this batch's Adam
- * catch-up): the round-1 form, 14 short launches that hold no resources while they wait — beside the catch-up the fused
+ * catch-up): short launches that hold no resources while they wait (9 at config 3, 113 us) — beside the catch-up the fused
  * form's resident, waiting workgroups cost the step 0.03 ms more than they save (profiles/r05_sort_and_side_streams.md). */
 size_t mi_sort_unique_fields_workspace_bytes(int64_t B, int32_t F);
 int32_t mi_sort_unique_fields(const int32_t* ids, const int64_t* field_off, int64_t B, int32_t F, int64_t max_vocab,

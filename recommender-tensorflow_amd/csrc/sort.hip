@@ -15,8 +15,14 @@
 // then head_count_k / compact_k mark the first entry of every distinct row (coalesced reads,
 // ballot ranks) and emit uniq_rows / seg_start / sorted_entry.
 // mi_sort_unique_fields: the same result for ids [B][F] of F fields whose rows are disjoint ranges — every field's
-// B local ids sorted on their own (segments of the same kernels), 20 bits instead of 25 at config 3: 3 passes of 7
-// bits, whose scattered writes come in 128-byte runs instead of 32-byte ones (193 -> 150 us).
+// B local ids sorted on their own (segments), 20 bits instead of 25 at config 3: 3 passes of 7 bits.  Two forms, same
+// outputs: beside = 0, one launch per pass whose tiles wait for each other (pass_fused_k / compact_fused_k), and the
+// short launches that run beside the catch-up, where nothing may wait — per pass hist_fields_k + scatter_runs_k, then
+// head_count_k + compact_fields_k (9 launches at config 3, 113 us alone; the 14 of hist_k / bin_scan_k / scatter_k
+// they replace: 145).  There a (key, value) travels as one 8-byte pair, pass 0 reads ids [B][F] in place, a tile
+// derives its own offsets from the raw counts (no bin_scan_k), stages its pairs in LDS in digit order and writes
+// them out in runs, and the compaction adds up the head counts before it itself (no scan_small_k):
+// profiles/sort_beside_scatter.md.
 #include "common.h"
 
 namespace {
@@ -323,18 +329,212 @@ __global__ __launch_bounds__(kBlock) void compact_k(const int32_t* __restrict__ 
   }
 }
 
-// ids [B][F] -> out [F][B] (a field's ids contiguous): 64 examples per block through LDS, both sides coalesced
 constexpr int kFieldsMax = 64;
-__global__ __launch_bounds__(kBlock) void ids_field_major_k(const int32_t* __restrict__ ids, int64_t B, int F,
-                                                            int32_t* __restrict__ out) {
-  __shared__ int32_t tile[64][kFieldsMax + 1];
-  const int64_t b0 = static_cast<int64_t>(blockIdx.x) * 64;
-  const int nb = static_cast<int>(min(static_cast<int64_t>(64), B - b0));
-  for (int i = threadIdx.x; i < nb * F; i += kBlock) tile[i / F][i % F] = ids[b0 * F + i];
+
+// ---- The short launches of mi_sort_unique_fields (beside the catch-up: no workgroup waits for another) ------------------
+// Between the passes a (key, value) is ONE 8-byte pair; pass 0 reads ids [B][F] itself (the key of field-major position
+// i = seg * B + b is ids[b * F + seg], its value the entry b * F + seg): no field-major copy of the ids is made.
+__device__ __forceinline__ int32_t fields_key(const int2* __restrict__ pairs_in, const int32_t* __restrict__ ids, int64_t i,
+                                              int seg, int64_t B, int F) {
+  return ids ? ids[(i - static_cast<int64_t>(seg) * B) * F + seg] : pairs_in[i].x;
+}
+
+// hist_k of a field's tile (B is a multiple of kTile: every position exists)
+__global__ __launch_bounds__(kBlock) void hist_fields_k(const int2* __restrict__ pairs_in, const int32_t* __restrict__ ids, int64_t B,
+                                                        int F, int shift, int nbins, int tps, int32_t* __restrict__ hist,
+                                                        int32_t* __restrict__ bin_total) {
+  __shared__ unsigned int h[kMaxBins];
+  for (int b = threadIdx.x; b < nbins; b += kBlock) h[b] = 0;
   __syncthreads();
-  for (int i = threadIdx.x; i < F * 64; i += kBlock) {
-    const int f = i >> 6, bl = i & 63;
-    if (bl < nb) out[static_cast<int64_t>(f) * B + b0 + bl] = tile[bl][f];
+  const int seg = blockIdx.x / tps, tis = blockIdx.x - seg * tps;
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile;
+  const unsigned int mask = nbins - 1;
+#pragma unroll
+  for (int r = 0; r < kItems; ++r)
+    atomicAdd(&h[(static_cast<uint32_t>(fields_key(pairs_in, ids, base + r * kBlock + threadIdx.x, seg, B, F)) >> shift) & mask], 1u);
+  __syncthreads();
+  for (int b = threadIdx.x; b < nbins; b += kBlock) {
+    const unsigned int c = h[b];
+    hist[(static_cast<int64_t>(seg) * nbins + b) * tps + tis] = static_cast<int32_t>(c);
+    if (c) atomicAdd(&bin_total[seg * nbins + b], static_cast<int32_t>(c));
+  }
+}
+
+// A tile finds its own output offsets where that read is small beside the tile's own 64 KB of pairs: per digit, the field's
+// total (exclusive scan over the digits) + the counts of the field's tiles before this one, straight from hist_k's raw
+// counts — nbins * tps ints at most (2,176 at config 3, L2-resident).  Up to kSelfOffsMaxInts = a quarter of the tile's
+// own traffic; above it bin_scan_k turns hist into offsets first, as for the other callers.
+constexpr int kSelfOffsMaxInts = 4096;
+
+// scatter_k for a field's tile, writing RUNS: the tile is first staged in LDS in digit order — stable: a key's place is
+// the tile-local start of its digit + the counts of the waves before its own + its wave's running count + its ballot rank
+// — and then written out in staged order, so consecutive lanes write consecutive slots of one bin (runs of ~32 pairs at
+// config 3: a wave's store touches a few lines, not 64).  The worst case — all 4,096 keys in one bin — is one run.
+// self_offs: hist holds the raw per-tile counts (see above), else the offsets bin_scan_k made of them.
+// keys_out != NULL (the last pass): keys and values go to two arrays, what head_count_k / compact_k read.
+// LDS: 32 KB of pairs + 8 KB of running slots: four workgroups per CU.  Before the staging the pairs' space holds the
+// waves' digit counts and the scans' scratch, after it the first wave's slots hold (global offset - tile-local start) per digit.
+template <bool IDS>
+__global__ __launch_bounds__(kBlock) void scatter_runs_k(const int2* __restrict__ pairs_in, const int32_t* __restrict__ ids, int64_t B,
+                                                         int F, int shift, int nbits, int tps, const int32_t* __restrict__ hist,
+                                                         const int32_t* __restrict__ bin_total, int self_offs,
+                                                         int2* __restrict__ pairs_out, int32_t* __restrict__ keys_out,
+                                                         int32_t* __restrict__ vals_out) {
+  __shared__ int2 staged[kTile];
+  __shared__ int32_t running[4][kMaxBins];    // per wave: the next staged slot of each digit
+  int32_t* before = reinterpret_cast<int32_t*>(staged);      // [nbins] counts of the field's earlier tiles
+  int32_t* tstart = before + kMaxBins;                       // [nbins] tile-local start of a digit
+  int32_t (*cnt)[kMaxBins] = reinterpret_cast<int32_t (*)[kMaxBins]>(tstart + kMaxBins);   // [4][nbins] per wave: digit counts
+  int32_t (*wsum)[4] = reinterpret_cast<int32_t (*)[4]>(cnt + 4);                          // [2][4] the waves' sums of the two scans
+  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+  const int nbins = 1 << nbits;
+  const int seg = blockIdx.x / tps, tis = blockIdx.x - seg * tps;
+  for (int b = t; b < 4 * kMaxBins; b += kBlock) (&cnt[0][0])[b] = 0;
+  for (int b = t; b < nbins; b += kBlock) before[b] = 0;
+  __syncthreads();
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile + w * (64 * kItems);
+  // (pass 0: the value is the entry itself, made again where it is stored — 16 registers fewer)
+  const int32_t e0 = static_cast<int32_t>((base - static_cast<int64_t>(seg) * B + lane) * F + seg);
+  int32_t key[kItems], val[IDS ? 1 : kItems];
+#pragma unroll
+  for (int r = 0; r < kItems; ++r) {
+    if (IDS) {
+      key[r] = ids[e0 + r * 64 * F];
+    } else {
+      const int2 kv = pairs_in[base + r * 64 + lane];
+      key[r] = kv.x;
+      val[r] = kv.y;
+    }
+    atomicAdd(&cnt[w][(static_cast<uint32_t>(key[r]) >> shift) & (nbins - 1)], 1);
+  }
+  const int32_t* fh = hist + static_cast<int64_t>(seg) * nbins * tps;      // the field's counts [digit][tile]
+  if (self_offs)
+    for (int i = t; i < nbins * tps; i += kBlock) {
+      const int b = i / tps;
+      if (i - b * tps < tis) atomicAdd(&before[b], fh[i]);
+    }
+  __syncthreads();
+  // two exclusive scans over the digits, thread t owning `per` consecutive digits: the tile's own counts -> tile-local
+  // starts; the field's totals -> the digit's base in the field
+  const int per = nbins > kBlock ? nbins / kBlock : 1;
+  int32_t delta[kMaxBins / kBlock];
+  {
+    int32_t tc[kMaxBins / kBlock], tot[kMaxBins / kBlock];
+    int own_c = 0, own_t = 0;
+#pragma unroll
+    for (int j = 0; j < kMaxBins / kBlock; ++j) {
+      const int b = t * per + j;
+      tc[j] = tot[j] = 0;
+      if (j < per && b < nbins) {
+        tc[j] = cnt[0][b] + cnt[1][b] + cnt[2][b] + cnt[3][b];
+        if (self_offs) tot[j] = bin_total[seg * nbins + b];
+      }
+      own_c += tc[j];
+      own_t += tot[j];
+    }
+    const int incl_c = wave_incl_scan(own_c, lane), incl_t = wave_incl_scan(own_t, lane);
+    if (lane == 63) { wsum[0][w] = incl_c; wsum[1][w] = incl_t; }
+    __syncthreads();
+    int pre_c = incl_c - own_c, pre_t = incl_t - own_t + static_cast<int>(static_cast<int64_t>(seg) * B);
+    for (int ww = 0; ww < w; ++ww) { pre_c += wsum[0][ww]; pre_t += wsum[1][ww]; }
+#pragma unroll
+    for (int j = 0; j < kMaxBins / kBlock; ++j) {
+      const int b = t * per + j;
+      delta[j] = 0;
+      if (j < per && b < nbins) {
+        const int32_t gofs = self_offs ? pre_t + before[b] : fh[static_cast<int64_t>(b) * tps + tis];
+        delta[j] = gofs - pre_c;
+        tstart[b] = pre_c;
+        pre_c += tc[j];
+        pre_t += tot[j];
+      }
+    }
+  }
+  __syncthreads();
+  // counts -> this wave's first staged slot per digit (each lane: digits lane, lane + 64, ...)
+  for (int b = lane; b < nbins; b += 64) {
+    int32_t f = tstart[b];
+    for (int ww = 0; ww < w; ++ww) f += cnt[ww][b];
+    running[w][b] = f;
+  }
+  __syncthreads();                              // the scratch is read by everyone: the staging may overwrite it
+  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  int32_t* run = running[w];
+#pragma unroll
+  for (int r = 0; r < kItems; ++r) {
+    asm volatile("" : "+v"(key[r]));            // the digit is extracted again, not carried in 16 more registers from the count above
+    const unsigned int d = (static_cast<uint32_t>(key[r]) >> shift) & (nbins - 1);
+    unsigned long long peers = ~0ull;
+    for (int b = 0; b < nbits; ++b) {
+      const unsigned long long m = __ballot((d >> b) & 1u);
+      peers &= ((d >> b) & 1u) ? m : ~m;
+    }
+    const int rank = __popcll(peers & lt_mask);
+    const int32_t dst = lds_ld(run + d) + rank;
+    __builtin_amdgcn_wave_barrier();            // every peer has read the slot before its leader moves it
+    if (rank == 0) lds_st(run + d, dst + __popcll(peers));
+    staged[dst] = make_int2(key[r], IDS ? e0 + r * 64 * F : val[r]);
+    __builtin_amdgcn_wave_barrier();
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < kMaxBins / kBlock; ++j)
+    if (j < per && t * per + j < nbins) running[0][t * per + j] = delta[j];
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < kItems; ++r) {
+    const int s = r * kBlock + t;
+    const int2 kv = staged[s];
+    const int32_t dst = running[0][(static_cast<uint32_t>(kv.x) >> shift) & (nbins - 1)] + s;
+    if (keys_out) {
+      keys_out[dst] = kv.x;
+      vals_out[dst] = kv.y;
+    } else {
+      pairs_out[dst] = kv;
+    }
+  }
+}
+
+// compact_k's tile_base / total without scan_small_k's launch: a tile adds up the head counts of the tiles before it
+// itself (up to kFoldHeadsMaxTiles ints, a quarter of the 64 KB it reads and writes anyway), the last tile writes num_uniq.
+constexpr int kFoldHeadsMaxTiles = 4096;
+__global__ __launch_bounds__(kBlock) void compact_fields_k(const int32_t* __restrict__ keys, const int32_t* __restrict__ vals, int64_t n,
+                                                           const int32_t* __restrict__ tile_heads, int32_t* __restrict__ sorted_entry,
+                                                           int32_t* __restrict__ uniq_rows, int32_t* __restrict__ seg_start,
+                                                           int32_t* __restrict__ num_uniq, int64_t seg_len,
+                                                           const int64_t* __restrict__ field_off) {
+  __shared__ int32_t red[4];
+  __shared__ int32_t wc[4];
+  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile;
+  int part = 0;
+  for (int j = t; j < static_cast<int>(blockIdx.x); j += kBlock) part += tile_heads[j];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
+  if (lane == 0) red[w] = part;
+  __syncthreads();
+  int run = red[0] + red[1] + red[2] + red[3];
+  for (int r = 0; r < kItems; ++r) {
+    const int64_t i = base + r * kBlock + t;
+    const int32_t key = keys[i];
+    const bool head = is_head(keys, i, seg_len);
+    sorted_entry[i] = vals[i];
+    const unsigned long long hb = __ballot(head);
+    __syncthreads();                       // previous round's wc consumed
+    if (lane == 0) wc[w] = __popcll(hb);
+    __syncthreads();
+    if (head) {
+      int idx = run + __popcll(hb & lt_mask);
+      for (int ww = 0; ww < w; ++ww) idx += wc[ww];
+      uniq_rows[idx] = static_cast<int32_t>(field_off[i / seg_len] + key);   // (local id -> global row)
+      seg_start[idx] = static_cast<int32_t>(i);
+    }
+    run += wc[0] + wc[1] + wc[2] + wc[3];
+  }
+  if (blockIdx.x == gridDim.x - 1 && t == 0) {
+    num_uniq[0] = run;
+    seg_start[run] = static_cast<int32_t>(n);
   }
 }
 
@@ -810,31 +1010,46 @@ int32_t mi_sort_unique_fields(const int32_t* ids, const int64_t* field_off, int6
     MI_CHECK_LAUNCH("sort_unique_fields(compact)");
     return MI_OK;
   }
+  // the short launches (hist_fields_k / scatter_runs_k / compact_fields_k above): 3 passes at config 3 = zero + 3 x (hist +
+  // scatter) + head count + compact = 9.  The two pair buffers are the key buffers and the value buffers, each pair of
+  // them contiguous; the last pass writes keys and values apart into the pair buffer it does not read.
   zero_i32(bin_total, static_cast<int64_t>(kMaxPasses) * F * kMaxBins, st);
   MI_CHECK_LAUNCH("sort_unique_fields(zero)");
-  // the ids field by field (keys = local ids); pass 0 reads them from the buffer pass 1 will overwrite
-  ids_field_major_k<<<dim3((unsigned)mi::ceil_div(B, 64)), dim3(kBlock), 0, st>>>(ids, B, F, kbuf[1]);
-  MI_CHECK_LAUNCH("sort_unique_fields(transpose)");
-  const int32_t* kin = kbuf[1];
-  const int32_t* vin = nullptr;  // pass 0: value = entry of the field-major position
+  static_assert(sizeof(int2) == 8, "pair buffers");
+  int2* pbuf[2] = {reinterpret_cast<int2*>(kbuf[0]), reinterpret_cast<int2*>(vbuf[0])};
+  const bool self_offs = static_cast<int64_t>(nbins) * tps <= kSelfOffsMaxInts;
+  const int2* pin = nullptr;       // pass 0 reads ids
+  int32_t* kout = nullptr;
+  int32_t* vout = nullptr;
   for (int p = 0; p < passes; ++p) {
-    int32_t* kout = kbuf[p & 1];
-    int32_t* vout = vbuf[p & 1];
+    const bool last = p == passes - 1;
     int32_t* bt = bin_total + static_cast<int64_t>(p) * F * kMaxBins;
-    hist_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, n, nbits * p, nbins, tps, hist, bt);
+    hist_fields_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(pin, p == 0 ? ids : nullptr, B, F, nbits * p, nbins, tps, hist, bt);
     MI_CHECK_LAUNCH("sort_unique_fields(hist)");
-    bin_scan_k<<<dim3(F * nbins), dim3(kBlock), 0, st>>>(hist, tps, nbins, bt, B);
-    MI_CHECK_LAUNCH("sort_unique_fields(scan)");
-    scatter_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, vin, n, nbits * p, nbits, tps, hist, kout, vout, p == 0 ? B : 0, F);
+    if (!self_offs) {
+      bin_scan_k<<<dim3(F * nbins), dim3(kBlock), 0, st>>>(hist, tps, nbins, bt, B);
+      MI_CHECK_LAUNCH("sort_unique_fields(scan)");
+    }
+    kout = last ? (p & 1 ? vbuf[0] : kbuf[0]) : nullptr;
+    vout = last ? (p & 1 ? vbuf[1] : kbuf[1]) : nullptr;
+    if (p == 0)
+      scatter_runs_k<true><<<dim3(ntiles), dim3(kBlock), 0, st>>>(nullptr, ids, B, F, 0, nbits, tps, hist, bt, self_offs ? 1 : 0,
+                                                                  last ? nullptr : pbuf[0], kout, vout);
+    else
+      scatter_runs_k<false><<<dim3(ntiles), dim3(kBlock), 0, st>>>(pin, nullptr, B, F, nbits * p, nbits, tps, hist, bt, self_offs ? 1 : 0,
+                                                                   last ? nullptr : pbuf[p & 1], kout, vout);
     MI_CHECK_LAUNCH("sort_unique_fields(scatter)");
-    kin = kout;
-    vin = vout;
+    pin = pbuf[p & 1];
   }
-  head_count_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, n, heads, B);
+  head_count_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kout, n, heads, B);
   MI_CHECK_LAUNCH("sort_unique_fields(heads)");
-  scan_small_k<<<dim3(1), dim3(kScanSmallBlock), 0, st>>>(heads, ntiles, total);
-  MI_CHECK_LAUNCH("sort_unique_fields(scan heads)");
-  compact_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, vin, n, heads, total, sorted_entry, uniq_rows, seg_start, num_uniq, B, field_off);
+  if (ntiles <= kFoldHeadsMaxTiles) {
+    compact_fields_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kout, vout, n, heads, sorted_entry, uniq_rows, seg_start, num_uniq, B, field_off);
+  } else {
+    scan_small_k<<<dim3(1), dim3(kScanSmallBlock), 0, st>>>(heads, ntiles, total);
+    MI_CHECK_LAUNCH("sort_unique_fields(scan heads)");
+    compact_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kout, vout, n, heads, total, sorted_entry, uniq_rows, seg_start, num_uniq, B, field_off);
+  }
   MI_CHECK_LAUNCH("sort_unique_fields(compact)");
   return MI_OK;
 }

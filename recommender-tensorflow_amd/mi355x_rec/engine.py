@@ -1633,7 +1633,7 @@ class DeepFM:
         return self._sort_unique(rows, n, self.R, tag)
 
     def _presort(self, next_ids, tag):
-        """The sort of the NEXT batch, on a side stream, enqueued right before this step's catch-up: ~14 small launches
+        """The sort of the NEXT batch, on a side stream, enqueued right before this step's catch-up: 9 short launches at config 3
         that are bound by launch latency and leave most of the chip idle (0.17 ms at config 3 alone).  Beside the catch-up
         — whose resident workgroups fill half the wave slots: the sort ends about when the catch-up does, at +35 us for it.
         (Measured alternatives, kernel timelines of tools/step_timeline.py: beside the sparse apply the apply takes 713 us

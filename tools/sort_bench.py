@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """us per call of the two sort + unique entries at config 3's size (1.7 M keys).  With MI_TUNING_LIB=1 the tools' build is
 loaded (make -C recommender-tensorflow_amd/csrc tuning) and MI_SORT_FUSED=0|1 / MI_SORT_BITS=7..10 choose the per-field form:
-   MI_TUNING_LIB=1 MI_SORT_FUSED=0 python tools/sort_bench.py fields      # round 4's 14 launches
+   MI_TUNING_LIB=1 MI_SORT_FUSED=0 python tools/sort_bench.py fields      # the short launches (what beside = 1 runs; BESIDE=1 with the shipped library)
    MI_TUNING_LIB=1 MI_SORT_BITS=7 python tools/sort_bench.py fields       # fused, 3 passes of 7 bits
    python tools/sort_bench.py fields                                      # the shipped library: fused, 2 passes of 10 bits"""
 import sys, os, torch

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Soak of the one-launch-per-pass sort (mi_sort_unique_fields, beside = 0: workgroups of a field wait for each other inside a
-launch): N calls on fresh random ids, each compared with the 14-launch form (beside = 1) bit for bit, with and without a
+launch): N calls on fresh random ids, each compared with the short-launch form (beside = 1) bit for bit, with and without a
 bandwidth-heavy copy loop on another stream taking wave slots and HBM away.  usage: python tools/sort_soak.py [N]"""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
