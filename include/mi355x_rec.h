@@ -1043,6 +1043,53 @@ int32_t mi_predict_group(const mi_serve_group_plan_t* plan, int32_t n_members, c
                          float* member_logits, int32_t* tickets, float* logits, float* logistic, float* probabilities,
                          int64_t* class_ids, mi_stream_t stream);
 
+/* ---- exact AUC and per-group AUC of a population's logits: pair counts as one launch (csrc/auc.hip) --------------------
+ * The "auc" of mi_eval_accumulate is tf.metrics.auc's trapezoid over 200 thresholds in probability: its error depends on
+ * the scale of the logits, so it is a poor yardstick BETWEEN the members of a sweep.  These entries count, for every member
+ * and every group of examples, the (positive, negative) pairs whose positive scores higher and those that tie:
+ *   AUC = (2 gt + eq) / (2 P N-), formed on the host.  Integers only; exact; independent of order, grid and timing.
+ * The count is O(P N-) per member on purpose: the entries are meant for the held-out sets of sweeps (20,000 examples are 1e8
+ * pairs a member); the large-batch path keeps the bucketed metric.
+ *
+ * Key of a logit: the 32-bit monotone image of the fp32 that mi_pair_topk's order uses (csrc/score_key.h): NaN is below
+ * every number and equal to every other NaN, -0 equals +0.
+ *
+ * Layout of one evaluation set, built by the host once and shared by all members (the kernel takes no labels):
+ *   order [N] int32 (device): a permutation of the examples, segment major, within a segment the negatives first;
+ *   seg_off [S + 1], seg_neg [S] int64 (HOST): positions [seg_off[s], seg_off[s] + seg_neg[s]) of `order` are segment s's
+ *     negatives, [seg_off[s] + seg_neg[s], seg_off[s + 1]) its positives.  The global AUC is S = 1.
+ *
+ * mi_auc_plan: cuts every segment that has both classes into work items (segment, a tile of at most 64 positives, a run
+ * of at most C negatives; a segment of one class yields none) and copies the item table into device_table
+ * (mi_auc_plan_bytes(...) bytes of device memory for the same arguments, 16-byte aligned, never 0 for a layout that is
+ * accepted; the copy has completed when the call returns).  neg_run: C (0 = the built-in choice, at most 2^24; a test seam —
+ * no count depends on it).  Refused (MI_ERR_INVALID; a short table MI_ERR_WORKSPACE; more than 2^24 items
+ * MI_ERR_UNSUPPORTED), writing neither device_table nor *plan: NULL seg_off / seg_neg / device_table / plan,
+ * n_segments < 1, seg_off not ascending from 0 to N, seg_neg[s] outside [0, its segment's size], N < 1 or N >= 2^31,
+ * neg_run out of range.  mi_auc_plan_bytes returns 0 for a layout mi_auc_plan refuses.
+ *
+ * mi_auc_pair_counts: ONE launch, grid (items, members); no copy, no synchronisation, no workspace.
+ *   logits: member m's logit of example i at logits[m * member_stride + i] (member_stride >= N);
+ *   order [N]: as above.  PRECONDITION: every entry in [0, N) — the entry cannot look at device memory;
+ *   counts [M, S, 2] int64, ZEROED BY THE CALLER: [m, s, 0] += the pairs of segment s with key_pos > key_neg,
+ *     [m, s, 1] += those with equal keys (64-bit integer atomic adds, one per wave and counter: a second call into the same
+ *     buffer adds the same numbers again).
+ * Two calls on equal input give equal bits.  No workgroup reads what another writes and none waits for another.
+ * Refused on the host before anything is launched (MI_ERR_INVALID): a plan mi_auc_plan did not write, NULL logits / order /
+ * counts, n_members outside [1, MI_AUC_MAX_MEMBERS], member_stride < N. */
+#define MI_AUC_MAX_MEMBERS 1024
+typedef struct mi_auc_plan {
+  void* device_table;
+  uint64_t magic;
+  int64_t N;
+  int32_t n_segments, n_items;
+} mi_auc_plan_t;
+size_t mi_auc_plan_bytes(const int64_t* seg_off, const int64_t* seg_neg, int32_t n_segments, int32_t neg_run);
+int32_t mi_auc_plan(const int64_t* seg_off, const int64_t* seg_neg, int32_t n_segments, int32_t neg_run, void* device_table,
+                    size_t device_table_bytes, mi_auc_plan_t* plan, mi_stream_t stream);
+int32_t mi_auc_pair_counts(const mi_auc_plan_t* plan, const float* logits, int64_t member_stride, int32_t n_members,
+                           const int32_t* order, int64_t* counts, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@
 // the empty slot.  Keys of one query are distinct, so every merge is a rank computation with one answer: the results do
 // not depend on the split count, the order in which waves append survivors, or timing.  No workgroup waits for another.
 #include "common.h"
+#include "score_key.h"
 
 namespace {
 
@@ -70,11 +71,7 @@ struct LayerTable {
 };
 
 __device__ __forceinline__ uint64_t rank_key(float s, uint32_t c) {
-  uint32_t u = __float_as_uint(s);
-  if (s != s) u = 0u;
-  else if (s == 0.f) u = 0x80000000u;
-  else u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return (static_cast<uint64_t>(u) << 32) | static_cast<uint32_t>(~c);
+  return (static_cast<uint64_t>(mi_score_key32(s)) << 32) | static_cast<uint32_t>(~c);
 }
 __device__ __forceinline__ float key_score(uint64_t key) {
   const uint32_t u = static_cast<uint32_t>(key >> 32);

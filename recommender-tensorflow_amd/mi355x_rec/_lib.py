@@ -105,6 +105,15 @@ class RankMember(C.Structure):
                 ("H1", C.c_int32), ("E", C.c_int32), ("n_layers", C.c_int32), ("activation", C.c_int32)]
 
 
+AUC_MAX_MEMBERS = 1024  # MI_AUC_MAX_MEMBERS
+
+
+class AucPlan(C.Structure):
+    """mi_auc_plan_t: what mi_auc_plan leaves on the host for mi_auc_pair_counts"""
+    _fields_ = [("device_table", C.c_void_p), ("magic", C.c_uint64), ("N", C.c_int64), ("n_segments", C.c_int32),
+                ("n_items", C.c_int32)]
+
+
 _p = C.c_void_p
 _i32, _i64, _u32, _u64, _f32, _sz = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_size_t
 _amax = C.POINTER(GemmAmax)
@@ -217,6 +226,9 @@ SIGNATURES = {
     "mi_predict_group_plan_bytes": (_sz, [_i32]),
     "mi_predict_group_plan": (_i32, [_p, _i32, _i32, _i32, _p, _p, _p, _p]),
     "mi_predict_group": (_i32, [_p, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
+    "mi_auc_plan_bytes": (_sz, [_p, _p, _i32, _i32]),
+    "mi_auc_plan": (_i32, [_p, _p, _i32, _i32, _p, _sz, _p, _p]),
+    "mi_auc_pair_counts": (_i32, [_p, _p, _i64, _i32, _p, _p, _p]),
 }
 
 _lib = None

@@ -52,6 +52,44 @@ def metrics_from_counters(hist, counts, sums):
     }
 
 
+def auc_from_pair_counts(gt, eq, n_pos, n_neg):
+    """The exact AUC of one set from mi_auc_pair_counts' two integers: of its n_pos * n_neg (positive, negative) pairs, gt
+    have the positive's score higher and eq tie (half a pair each): (2 gt + eq) / (2 n_pos n_neg), one correctly rounded
+    division of integers.  0.0 for a set with one class, as metrics_from_counters' "auc" is there."""
+    pairs = int(n_pos) * int(n_neg)
+    return (2 * int(gt) + int(eq)) / (2 * pairs) if pairs else 0.0
+
+
+def exact_auc_from_counts(counts, n_pos, n_neg):
+    """counts [1, 2] (or [2]) of the whole set as one segment -> {"auc_exact", "auc_exact_pairs"}"""
+    gt, eq = np.asarray(counts, np.int64).reshape(-1)[:2]
+    return {"auc_exact": auc_from_pair_counts(gt, eq, n_pos, n_neg), "auc_exact_pairs": int(n_pos) * int(n_neg)}
+
+
+def gauc_from_counts(counts, n_pos, n_neg):
+    """counts [S, 2], n_pos [S], n_neg [S] of S groups -> {"gauc", "gauc_groups"}: the mean of the groups' own exact AUCs
+    weighted by the groups' numbers of examples, sum_u w_u AUC_u / sum_u w_u with w_u = n_pos[u] + n_neg[u], over the groups
+    that have both classes (a group of one class has no AUC and no weight), added in fp64 in ascending group order;
+    gauc_groups: how many groups counted.  0.0 when none did.  counts [M, S, 2] (M models on the same groups): a list of
+    M such dicts."""
+    counts = np.asarray(counts, np.int64)
+    n_pos, n_neg = np.asarray(n_pos, np.int64).reshape(-1), np.asarray(n_neg, np.int64).reshape(-1)
+    if counts.ndim not in (2, 3) or counts.shape[-1] != 2 or not counts.shape[-2] == len(n_pos) == len(n_neg):
+        raise ValueError("gauc_from_counts: counts of shape %s for %d / %d group sizes" % (counts.shape, len(n_pos), len(n_neg)))
+    both = (n_pos > 0) & (n_neg > 0)
+    groups = int(both.sum())
+    c = counts.reshape(-1, len(n_pos), 2)[:, both]
+    if groups:
+        w = (n_pos + n_neg)[both].astype(np.float64)
+        auc = (2 * c[..., 0] + c[..., 1]).astype(np.float64) / (2 * n_pos * n_neg)[both].astype(np.float64)
+        num = np.cumsum(w * auc, axis=1)[:, -1]           # (one addition after the other, in group order)
+        gauc = num / np.cumsum(w)[-1]
+    else:
+        gauc = np.zeros(len(c))
+    out = [{"gauc": float(v), "gauc_groups": groups} for v in gauc]
+    return out if counts.ndim == 3 else out[0]
+
+
 def histogram_limits():
     """TensorFlow's default histogram bucket limits (core/lib/histogram/histogram.cc InitDefaultBucketsInner,
     what tf.summary.histogram of layer_summary — model_utils.py:6 — bins with): 1e-12 * 1.1^k below 1e20,

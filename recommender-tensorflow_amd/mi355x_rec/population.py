@@ -164,14 +164,16 @@ class FusedPopulation:
         return loss, logits
 
     # ------------------------------------------------------------------ evaluation
-    def evaluate(self, ids, labels, batch_size=None, return_logits=False):
+    def evaluate(self, ids, labels, batch_size=None, return_logits=False, exact=None):
         """Every member's EVAL metrics over a whole evaluation set as ONE launch (mi_eval_group) and one device-to-host copy:
         a list of M dicts with the keys of metrics.metrics_from_counters plus "loss", the fp64 mean over the fp32 losses of
         the batches of batch_size examples (tf.metrics.mean over batch losses; the last batch may be short and is reduced
         with its own 1 / n) — what Estimator.evaluate reports for the member on these batches.  ids int32 [N, F], labels uint8
         [N], on the population's device, one set for all members.  batch_size None: that of the latest train_step, else
         EVAL_BATCH.  No dropout; no member's variables, slots, step or schedule change.  return_logits: (metrics, logits
-        [M, N] device tensor)."""
+        [M, N] device tensor).  exact: an exact_auc.ExactAuc of these labels (and, for GAUC, the examples' groups): the
+        logits of this evaluation are kept and every member's dict gains auc_exact, auc_exact_pairs and, with groups, gauc,
+        gauc_groups — one more launch per layout for all members (ExactAuc.metrics).  None: none of that."""
         M, F = self.M, self.F
         if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or not ids.is_contiguous() or ids.dim() != 2 \
                 or ids.shape[1] != F:
@@ -184,6 +186,9 @@ class FusedPopulation:
             raise ValueError("FusedPopulation: labels must be a contiguous uint8 [N] tensor (N = %d)" % N)
         if ids.device.type != self.device.type or labels.device.type != self.device.type:
             raise ValueError("FusedPopulation: ids and labels must live on %s" % self.device)
+        if exact is not None and (exact.N != N or exact.device.type != self.device.type):
+            raise ValueError("FusedPopulation: exact was built for %d examples on %s, the evaluation has %d on %s" % (
+                exact.N, exact.device, N, self.device))
         B = int(batch_size) if batch_size is not None else (self._last_b or self.EVAL_BATCH)
         if B < 1:
             raise ValueError("FusedPopulation: batch_size=%d (at least 1)" % B)
@@ -191,7 +196,8 @@ class FusedPopulation:
             e.finalize_rows()                         # (a no-op after a fused step)
         plan = self._plan_for(B)
         T, n_tail = -(-N // B), N % B
-        key = (B, N, bool(return_logits))
+        with_logits = bool(return_logits) or exact is not None
+        key = (B, N, with_logits)
         buf = self._eval_buf.get(key)
         if buf is None:
             # one allocation, so that one copy brings everything home: [hist | counts] int64, partials f64, batch losses f32
@@ -204,12 +210,13 @@ class FusedPopulation:
                 raw=raw, ints=ints, hist=ints[:M * 402].view(M, 2, 201), counts=ints[M * 402:].view(M, 8),
                 partials=raw[8 * n_int:8 * (n_int + n_par)].view(torch.float64).view(M, T, 3),
                 loss=raw[8 * (n_int + n_par):].view(torch.float32).view(M, T), tail=tail,
-                logits=torch.empty(M, N, dtype=torch.float32, device=self.device) if return_logits else None)
+                logits=torch.empty(M, N, dtype=torch.float32, device=self.device) if with_logits else None)
             if len(self._eval_buf) > 4:
                 self._eval_buf.pop(next(iter(self._eval_buf)))
         buf["ints"].zero_()
         self.k.mi_eval_group(plan[1], M, ids, labels, N, buf["tail"], buf["logits"], buf["loss"], buf["hist"], buf["counts"],
                              buf["partials"], int(self.EVAL_BLOCKS))
+        extra = exact.metrics(buf["logits"]) if exact is not None else None     # (the pair counts of these logits, and their own copy)
         host = buf["raw"].cpu().numpy()
         n_int, n_par = M * 410, M * T * 3
         ints = host[:8 * n_int].view(np.int64)
@@ -222,6 +229,8 @@ class FusedPopulation:
         for i in range(M):
             m = metrics_from_counters(hist[i], counts[i], sums[i])
             m["loss"] = float(np.cumsum(losses[i].astype(np.float64))[-1] / T)
+            if extra is not None:
+                m.update(extra[i])
             out.append(m)
         return (out, buf["logits"]) if return_logits else out
 

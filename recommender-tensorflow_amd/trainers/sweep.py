@@ -25,6 +25,12 @@ for all of them) over the test set; sweep.json gains "ensemble": its members and
 With --rank-metrics the ensemble is measured as a recommender too: "ensemble" gains "ranking", the members' keys under the
 ensemble's MEAN logit (EnsemblePredictor.rank_targets: what trainers.recommend --top N --mean-metrics-at reports).
 
+--exact-auc: every evaluation of the population also COUNTS every member's correctly ranked (positive, negative) pairs on
+the logits it has anyway (mi355x_rec.exact_auc.ExactAuc: one more launch for all members) and the members' metrics gain
+"auc_exact" — free of the 200-bucket "auc"'s dependence on the scale of the logits, which between the members of a grid
+over learning rates is a bias.  --gauc-by COLUMN (user_id is the usual choice) adds "gauc", the mean of every group's own
+AUC weighted by the group's examples, and "gauc_groups".  --select takes auc_exact and gauc with the matching flag.
+
 trainers.deep_fm has no learning-rate flag (the reference has none): a member restored through ``trainers.deep_fm
 --restore`` continues at that CLI's 0.001, a member restored through ``trainers.sweep --restore`` at its own rate."""
 import itertools
@@ -39,6 +45,7 @@ import numpy as np
 import torch
 
 from mi355x_rec.estimator import Estimator, ModeKeys
+from mi355x_rec.exact_auc import ExactAuc
 from mi355x_rec.metrics import metrics_from_counters, ranking_metrics_from_ranks
 from mi355x_rec.predictor import EnsemblePredictor
 from mi355x_rec.population import FusedPopulation
@@ -49,18 +56,19 @@ from trainers.ml_100k import _read_csv, get_feature_columns, get_input_fn, servi
 _KEPT = ("--train-csv", "--test-csv", "--restore", "--batch-size", "--train-steps", "--device", "--catchup", "--synthetic")
 _ASCENDING = ("loss", "average_loss", "mean_rank")
 _EVAL_METRICS = ("auc", "accuracy", "auc_precision_recall", "loss", "average_loss")
+_EXACT_METRICS = ("auc_exact", "gauc")      # of --exact-auc / --gauc-by
 _RANK_AT = re.compile(r"^(hit_rate|recall|ndcg)@([1-9][0-9]*)$")
 
 
 def select_metric(name):
     """--select: an evaluation metric, or a ranking metric of --rank-metrics (hit_rate@K, recall@K, ndcg@K, mrr, mean_rank)"""
-    if name in _EVAL_METRICS or name in ("mrr", "mean_rank") or _RANK_AT.match(name):
+    if name in _EVAL_METRICS or name in _EXACT_METRICS or name in ("mrr", "mean_rank") or _RANK_AT.match(name):
         return name
     raise ArgumentTypeError("%r is none of %s, hit_rate@K, recall@K, ndcg@K, mrr, mean_rank" % (name, ", ".join(_EVAL_METRICS)))
 
 
 def is_ranking(select):
-    return select not in _EVAL_METRICS
+    return select not in _EVAL_METRICS and select not in _EXACT_METRICS
 
 
 def make_parser():
@@ -87,7 +95,8 @@ def make_parser():
     p.add_argument("--select", default="auc", type=select_metric,
                    help="the metric sweep.json is sorted by, best first: auc, accuracy, auc_precision_recall, loss, average_loss "
                         "(loss / average_loss: lowest first), or with --rank-metrics hit_rate@K, recall@K, ndcg@K (K among "
-                        "--rank-metrics), mrr, mean_rank (lowest first) (default: %(default)s)")
+                        "--rank-metrics), mrr, mean_rank (lowest first), or auc_exact with --exact-auc, gauc with --gauc-by "
+                        "(default: %(default)s)")
     p.add_argument("--rank-metrics", type=int, nargs="+", default=None, metavar="K",
                    help="after the final evaluation, rank every test user's positives (rating >= 5) among all items the user "
                         "has not rated in the training file, for ALL members in one launch, and give every row of sweep.json "
@@ -102,28 +111,41 @@ def make_parser():
     p.add_argument("--ensemble", type=int, default=0, metavar="N",
                    help="after the ranking, evaluate the mean of the N best members on the test set as one model and write it "
                         "to sweep.json as \"ensemble\" (default: 0 = off)")
+    p.add_argument("--exact-auc", action="store_true",
+                   help="count every member's exact AUC (the fraction of (positive, negative) pairs ranked the right way, ties "
+                        "half) on the population evaluation's logits, one launch for all members: metrics gain auc_exact "
+                        "(default: off)")
+    p.add_argument("--gauc-by", default=None, metavar="COLUMN",
+                   help="also the per-group AUC over the groups this column of the test file names by its raw values (user_id "
+                        "is the usual choice): metrics gain gauc, the groups' AUCs weighted by their examples, and gauc_groups; "
+                        "implies --exact-auc (default: off)")
     return p
 
 
-def evaluate_ensemble(ens, test_csv, batch_size=4096):
+def evaluate_ensemble(ens, test_csv, batch_size=4096, exact=None):
     """The EVAL metrics of the mean of the sweep's best members (ens: EnsemblePredictor.from_sweep) over the test set: its
     logits through mi_eval_accumulate and metrics_from_counters, as Estimator.evaluate counts one model's.  "loss" is the
-    average loss (the whole set as one batch of a mean reduction)."""
+    average loss (the whole set as one batch of a mean reduction).  exact: the sweep's ExactAuc of the test set — the
+    mean logits are counted by it too and the metrics gain its keys."""
     dev = ens.device
     hist = torch.zeros(2 * 201, dtype=torch.int64, device=dev)
     counts = torch.zeros(8, dtype=torch.int64, device=dev)
     sums = torch.zeros(4, dtype=torch.float64, device=dev)
     n = 0
+    kept = []
     for features, labels in get_input_fn(test_csv, ModeKeys.EVAL, batch_size=batch_size)():
         ids, x = ens.plan.transform(features)
         z = torch.from_numpy(np.ascontiguousarray(ens.predict_ids(ids, x)["logits"][:, 0])).to(dev)
         y = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1)).astype(np.uint8)).to(dev)
         ens.k.mi_eval_accumulate(z, y, z.numel(), hist, counts, sums)
         n += z.numel()
+        kept.append(z)
     if not n:
         raise ValueError("no evaluation data in %s" % test_csv)
     metrics = metrics_from_counters(hist.cpu().numpy(), counts.cpu().numpy(), sums.cpu().numpy())
     metrics["loss"] = metrics["average_loss"]
+    if exact is not None:
+        metrics.update(exact.metrics(torch.cat(kept))[0])
     return ens.sweep_members, {k: float(v) for k, v in metrics.items()}
 
 
@@ -210,8 +232,10 @@ class PopulationEval:
     """The held-out set on the device and the members' curves on it: every run() is one FusedPopulation.evaluate (one launch
     for all members), one line of <job-dir>/sweep_eval.jsonl and one log line."""
 
-    def __init__(self, test_csv, batch_size, select, job_dir, every=0):
+    def __init__(self, test_csv, batch_size, select, job_dir, every=0, exact_auc=False, gauc_by=None):
         self.test_csv, self.batch_size, self.select, self.job_dir, self.every = test_csv, batch_size, select, job_dir, int(every)
+        self.exact_auc, self.gauc_by = bool(exact_auc or gauc_by), gauc_by
+        self.exact = None          # the test set's ExactAuc (--exact-auc / --gauc-by), made with the data
         self.path = os.path.join(job_dir, "sweep_eval.jsonl")
         self.data = None
         self.curve = []            # (global_step, [the members' metrics]), in step order
@@ -221,22 +245,31 @@ class PopulationEval:
 
     def load(self, plan, dev):
         """the test set, read and transformed ONCE: ids int32 [N, F] and labels uint8 [N] on the device"""
-        ids, ys = [], []
+        ids, ys, groups = [], [], []
         for features, labels in get_input_fn(self.test_csv, ModeKeys.EVAL, batch_size=4096)():
             ids.append(plan.transform(features)[0])
             ys.append(np.asarray(labels).reshape(-1).astype(np.uint8))
+            if self.gauc_by:
+                if self.gauc_by not in features:
+                    raise SystemExit("--gauc-by %s: the test file has no such column (it has %s)" % (
+                        self.gauc_by, ", ".join(sorted(features))))
+                groups.append(np.asarray(features[self.gauc_by]).reshape(-1))
         if not ids:
             raise ValueError("no evaluation data in %s" % self.test_csv)
+        if self.exact_auc:
+            self.exact = ExactAuc(np.concatenate(ys), np.concatenate(groups) if self.gauc_by else None, device=dev)
         self.data = (torch.from_numpy(np.ascontiguousarray(np.concatenate(ids))).to(dev),
                      torch.from_numpy(np.ascontiguousarray(np.concatenate(ys))).to(dev))
 
     def run(self, pop, step, lead):
         """All members on the whole test set at global step `step`; returns their metrics (at most once per step)"""
-        if self.curve and self.curve[-1][0] == step:
-            return self.curve[-1][1]
+        newest = "gauc" if self.gauc_by else "auc_exact" if self.exact_auc else "auc"
+        if self.curve and self.curve[-1][0] == step and newest in self.curve[-1][1][0]:
+            return self.curve[-1][1]       # (--restore: a line of this step without the keys asked for now is measured again)
         if self.data is None:
             self.load(lead.params["_store"]["plan"], lead._engine().device)
-        metrics = [{k: float(v) for k, v in m.items()} for m in pop.evaluate(self.data[0], self.data[1], batch_size=self.batch_size)]
+        metrics = [{k: float(v) for k, v in m.items()} for m in pop.evaluate(self.data[0], self.data[1], batch_size=self.batch_size,
+                                                                                     exact=self.exact)]
         self.curve.append((step, metrics))
         os.makedirs(self.job_dir, exist_ok=True)
         with open(self.path, "a") as f:
@@ -250,7 +283,8 @@ class PopulationEval:
     def best(self, i):
         """(best_step, best_value) of member i's curve by the select metric; the earliest step among equals"""
         sign = 1.0 if self.select in _ASCENDING else -1.0
-        step, ms = min(self.curve, key=lambda rec: (sign * rec[1][i][self.select], rec[0]))
+        curve = [rec for rec in self.curve if self.select in rec[1][i]]       # (--restore: earlier lines may lack auc_exact / gauc)
+        step, ms = min(curve, key=lambda rec: (sign * rec[1][i][self.select], rec[0]))
         return step, ms[i][self.select]
 
 
@@ -320,6 +354,12 @@ def train_and_evaluate(args):
         at = _RANK_AT.match(args.select)
         if not rank_ks or (at and int(at.group(2)) not in rank_ks):
             raise SystemExit("--select %s needs --rank-metrics%s" % (args.select, " with %s among its cutoffs" % at.group(2) if at else ""))
+    gauc_by = getattr(args, "gauc_by", None)
+    exact_auc = bool(getattr(args, "exact_auc", False) or gauc_by)
+    if args.select == "auc_exact" and not exact_auc:
+        raise SystemExit("--select auc_exact needs --exact-auc")
+    if args.select == "gauc" and not gauc_by:
+        raise SystemExit("--select gauc needs --gauc-by")
     if not args.restore:
         shutil.rmtree(args.job_dir, ignore_errors=True)
     config = _cli.get_run_config()
@@ -330,10 +370,10 @@ def train_and_evaluate(args):
     if eval_every < 0:
         raise ValueError("--eval-every %d (0 = off, or a number of steps)" % eval_every)
     evaluator = None
-    if eval_every or final_eval == "fused":
+    if eval_every or final_eval == "fused" or exact_auc:
         # (the curves are made of evaluation metrics: with a ranking --select their best point is taken by auc)
         evaluator = PopulationEval(args.test_csv, args.batch_size, "auc" if is_ranking(args.select) else args.select, args.job_dir,
-                                   eval_every)
+                                   eval_every, exact_auc, gauc_by)
     pop = train(members, get_input_fn(args.train_csv, batch_size=args.batch_size), args.train_steps, config, args.job_dir,
                 args.batch_size, evaluator)
     if pop is None:
@@ -350,6 +390,8 @@ def train_and_evaluate(args):
             metrics = dict(fused[i], global_step=est.global_step)
         else:
             metrics = est.evaluate(eval_fn)
+            if exact_auc:          # (counted on the population evaluation's logits, whatever --final-eval says)
+                metrics.update({k: v for k, v in fused[i].items() if k.startswith(("auc_exact", "gauc"))})
         export = exporter.export(est, os.path.join(est.model_dir, "export"))
         rows.append({"member": i, "dir": est.model_dir, "export": export, "global_step": est.global_step, "params": hp,
                      "flags": member_flags(args, hp), "metrics": {k: float(v) for k, v in metrics.items()}})
@@ -362,6 +404,11 @@ def train_and_evaluate(args):
     value = lambda r: r["ranking" if is_ranking(args.select) else "metrics"][args.select]
     rows.sort(key=lambda r: (sign * value(r), r["member"]))
     doc = {"select": args.select, "members": rows}
+    if exact_auc:
+        gap = max(abs(r["metrics"]["auc"] - r["metrics"]["auc_exact"]) for r in rows)
+        by = lambda key: [r["member"] for r in sorted(rows, key=lambda r: (-r["metrics"][key], r["member"]))]
+        print("INFO: --exact-auc: the largest |auc - auc_exact| over the %d members is %.3g; the order of the members by auc "
+              "and by auc_exact %s" % (len(rows), gap, "DIFFERS" if by("auc") != by("auc_exact") else "is the same"))
     with open(os.path.join(args.job_dir, "sweep.json"), "w") as f:
         json.dump(doc, f, indent=1)
     best = rows[0]
@@ -370,7 +417,9 @@ def train_and_evaluate(args):
         if n_ens < 0 or n_ens > len(rows):
             raise ValueError("--ensemble %d: the sweep has %d members" % (n_ens, len(rows)))
         ens = EnsemblePredictor.from_sweep(args.job_dir, top=n_ens, device=args.device)
-        who, metrics = evaluate_ensemble(ens, args.test_csv)
+        if exact_auc and evaluator.data is None:                        # (--restore with nothing left to evaluate)
+            evaluator.load(members[0].params["_store"]["plan"], members[0]._engine().device)
+        who, metrics = evaluate_ensemble(ens, args.test_csv, exact=evaluator.exact if exact_auc else None)
         doc["ensemble"] = {"members": who, "metrics": metrics}
         if rank_ks:
             doc["ensemble"]["ranking"] = rank_ensemble(ens, args.train_csv, args.test_csv, rank_ks)
