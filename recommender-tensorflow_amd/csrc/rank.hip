@@ -16,11 +16,16 @@
 //                      sorted top-K list in LDS; a candidate that does not beat the list's K-th key is rejected by one
 //                      64-bit compare, survivors are appended and merged into the list in batches (rank merge).
 //   topk_merge_k       one workgroup per query: the splits' partial lists merged into the final [U, K].
-//   pair_target_ranks_k  grid (query blocks) x (candidate splits) x (members): the exact rank of named target candidates
-//                      by each member's own score — the targets' keys in LDS, the candidate loop above, integer counters;
-//                      rank_sum_k adds the splits' counts (mi_pair_target_ranks).
-//   pair_target_ranks_mean_k  grid (query blocks) x (candidate splits): the same count under the members' MEAN score — the
-//                      members are a loop in the lane, as in pair_score_topk_group_k (mi_pair_target_ranks_mean).
+//
+// The pair kernels are a 2 x 2 — how a pair is scored, by what is done with the score:
+//                                     keep the best K                  count the keys above named targets (count_ranks)
+//   one model's logit                 pair_score_topk_k (written out)  pair_target_ranks_k: SoloScorer, members on grid z
+//   the members' mean (MeanScorer)    pair_score_topk_group_k          pair_target_ranks_mean_k
+//                                     (select_topk)
+// A scorer answers "the score of candidate c for this lane's query"; a body owns the LDS and what is written.  The three
+// kernels that read the member table build a scorer and call a body; the mean is formed in MeanScorer alone, the counting
+// loop stands in count_ranks alone.  pair_score_topk_k states its selection itself (see there for why) and select_topk
+// restates it for the mean.  rank_sum_k adds the splits' counts of the two on the right.
 //
 // Order: one 64-bit key per (score, candidate): the score's bits made monotone in the high word (NaN -> 0, below every
 // number; -0 as +0, and returned as +0), the complemented index in the low word, so "larger key" = higher score, then lower index.  Key 0 is
@@ -49,7 +54,8 @@ struct Layer {
   int32_t fan_in, fan_out;
 };
 
-struct PairArgs {
+// one model as pair_score and the dnn_* functions read it
+struct ScoreArgs {
   const float* aqT;                     // [H1][Upad] (workspace: a_q transposed, zero columns past U)
   const float* a_c;                     // [I][H1]
   const float* sqT;                     // [E][Upad]
@@ -57,13 +63,28 @@ struct PairArgs {
   const float* w_q;                     // [U] or NULL
   const float* w_c;                     // [I] or NULL
   const float* dense;
+  const Layer* l;                       // [n_layers] (workspace; a table in the kernel arguments would be copied to
+                                        // scratch by the runtime-indexed reads)
+  int32_t Upad, H1, E, act, n_layers;
+};
+
+// what select_topk does with the scores
+struct SelectArgs {
   const uint32_t* excl;                 // [U][words] bitmask or NULL
   float* scores;                        // [U][I] or NULL
   uint64_t* part;                       // [U][splits][K]
   int64_t U, I, chunk;
-  const Layer* l;                       // [n_layers] (workspace; a table in the kernel arguments would be copied to
-                                        // scratch by the runtime-indexed reads)
-  int32_t Upad, H1, E, K, splits, words, act, n_layers;
+  int32_t K, splits, words;
+};
+
+// what count_ranks does with them
+struct RanksArgs {
+  const uint32_t* excl;                 // [U][words] bitmask or NULL
+  const int32_t* targets;               // [U][Tq]
+  float* target_scores;                 // [members on the grid][U][Tq] or NULL
+  int32_t* part;                        // [members on the grid][splits][U][Tq]
+  int64_t U, I, chunk;
+  int32_t Tq, splits, words;
 };
 
 struct LayerTable {
@@ -98,8 +119,8 @@ __device__ __forceinline__ void epilogue(f32x16 (&y)[NB], const float* __restric
 }
 
 // layer 2: the input h1 = act(a_q + a_c) is made as it is consumed, two k per MFMA step
-template <int NB>
-__device__ __forceinline__ void layer2_mfma(const PairArgs& p, const float* __restrict__ ac, int64_t qcol, int h,
+template <int NB, class Args>
+__device__ __forceinline__ void layer2_mfma(const Args& p, const float* __restrict__ ac, int64_t qcol, int h,
                                             f32x16 (&y)[NB]) {
   const int col = static_cast<int>(qcol & 31);
   const Layer L = p.l[0];
@@ -124,8 +145,8 @@ __device__ __forceinline__ void layer2_mfma(const PairArgs& p, const float* __re
 
 // a hidden layer whose input x is in registers: k-step (bi, r) takes the lane's own x[bi][r] as B and the weight row
 // of that feature as A
-template <int NI, int NO>
-__device__ __forceinline__ void layer_mfma(const PairArgs& p, const Layer L, const f32x16 (&x)[NI], f32x16 (&y)[NO],
+template <int NI, int NO, class Args>
+__device__ __forceinline__ void layer_mfma(const Args& p, const Layer L, const f32x16 (&x)[NI], f32x16 (&y)[NO],
                                            int col, int h) {
   const float* __restrict__ W = p.dense + L.w_off;
   const int K = L.fan_in, N = L.fan_out;
@@ -150,8 +171,8 @@ __device__ __forceinline__ void layer_mfma(const PairArgs& p, const Layer L, con
   epilogue<NO>(y, p.dense + L.b_off, N, p.act, h);
 }
 
-template <int NB>
-__device__ __forceinline__ float logits_mfma(const PairArgs& p, const Layer L, const f32x16 (&x)[NB], int h) {
+template <int NB, class Args>
+__device__ __forceinline__ float logits_mfma(const Args& p, const Layer L, const f32x16 (&x)[NB], int h) {
   const float* __restrict__ W = p.dense + L.w_off;
   float s = 0.f;
 #pragma unroll
@@ -167,8 +188,8 @@ __device__ __forceinline__ float logits_mfma(const PairArgs& p, const Layer L, c
 }
 
 // the outputs of layers 2, 4, ... live in y (NP tiles of 32 features), those of layers 3, 5, ... in x (NQ tiles)
-template <int NP, int NQ>
-__device__ __forceinline__ float dnn_mfma(const PairArgs& p, const float* __restrict__ ac, int64_t qcol, int h) {
+template <int NP, int NQ, class Args>
+__device__ __forceinline__ float dnn_mfma(const Args& p, const float* __restrict__ ac, int64_t qcol, int h) {
   const int col = static_cast<int>(qcol & 31);
   f32x16 y[NP], x[NQ];
   layer2_mfma<NP>(p, ac, qcol, h, y);
@@ -191,7 +212,8 @@ __device__ __forceinline__ void epilogue_valu(float (&y)[kValuW], const float* _
   for (int j = 0; j < kValuW; ++j) y[j] = j < N ? mi_act(act, y[j] + bias[j]) : 0.f;
 }
 
-__device__ __forceinline__ void layer_valu(const PairArgs& p, const Layer L, const float (&x)[kValuW], float (&y)[kValuW]) {
+template <class Args>
+__device__ __forceinline__ void layer_valu(const Args& p, const Layer L, const float (&x)[kValuW], float (&y)[kValuW]) {
   const float* __restrict__ W = p.dense + L.w_off;
   const int K = L.fan_in, N = L.fan_out;
 #pragma unroll
@@ -205,7 +227,8 @@ __device__ __forceinline__ void layer_valu(const PairArgs& p, const Layer L, con
   epilogue_valu(y, p.dense + L.b_off, N, p.act);
 }
 
-__device__ __forceinline__ float logits_valu(const PairArgs& p, const Layer L, const float (&x)[kValuW]) {
+template <class Args>
+__device__ __forceinline__ float logits_valu(const Args& p, const Layer L, const float (&x)[kValuW]) {
   const float* __restrict__ W = p.dense + L.w_off;
   float s = 0.f;
 #pragma unroll
@@ -214,7 +237,8 @@ __device__ __forceinline__ float logits_valu(const PairArgs& p, const Layer L, c
   return s + p.dense[L.b_off];
 }
 
-__device__ __forceinline__ float dnn_valu(const PairArgs& p, const float* __restrict__ ac, int64_t qcol) {
+template <class Args>
+__device__ __forceinline__ float dnn_valu(const Args& p, const float* __restrict__ ac, int64_t qcol) {
   const int H1 = p.H1;
   const float* __restrict__ aq = p.aqT + qcol;
   if (p.n_layers == 0) return aq[0] + ac[0];                      // no hidden layer: layer 1 is the logits layer
@@ -254,10 +278,10 @@ __device__ __forceinline__ float dnn_valu(const PairArgs& p, const float* __rest
 // ---- the score of one pair -------------------------------------------------------------------------------------------
 // logit(q, c) of the model p for candidate c and the lane's query column qcol: the DNN on act(a_q + a_c), the E-wide dot of
 // the two embedding sums, and the head's order ((w_q + w_c) + dot) + dnn.  wq / sq: the lane's w_q and its column of sqT
-// (NULL without the FM term).  Both pair kernels call this: a group member's score is its own kernel's, bit for bit
+// (NULL without the FM term).  Every scorer calls this: a group member's score is its own kernel's, bit for bit
 // (every product is an explicit fmaf and no multiply feeds an add, so there is nothing for the compiler to contract).
-template <bool MFMA, int NP, int NQ>
-__device__ __forceinline__ float pair_score(const PairArgs& p, int64_t c, int64_t qcol, int h, float wq,
+template <bool MFMA, int NP, int NQ, class Args>
+__device__ __forceinline__ float pair_score(const Args& p, int64_t c, int64_t qcol, int h, float wq,
                                             const float* __restrict__ sq) {
   float dnn = 0.f;
   if (p.H1 > 0) {
@@ -320,6 +344,219 @@ __device__ __forceinline__ void merge_survivors(uint64_t* list, const uint64_t* 
   }
 }
 
+// ---- the pair kernels' grid ------------------------------------------------------------------------------------------
+// Block x: 32 queries, one per lane of a half wave (the halves h are the MFMA's two k steps; on the VALU path lanes 32..63
+// repeat lanes 0..31).  Block y: a split, candidates [c_begin, c_end), every wave scoring ONE candidate at a time.
+struct Place {
+  int tid, wave, lane, col, h, split;
+  int64_t q0, q, c_begin, c_end;
+  bool q_ok;                            // the lane's query exists
+};
+
+__device__ __forceinline__ Place place(int64_t U, int64_t I, int64_t chunk) {
+  Place at;
+  at.tid = threadIdx.x; at.wave = at.tid >> 6; at.lane = at.tid & 63; at.col = at.lane & 31; at.h = at.lane >> 5;
+  at.split = blockIdx.y;
+  at.q0 = static_cast<int64_t>(blockIdx.x) * kQB;
+  at.q = at.q0 + at.col;
+  at.c_begin = at.split * chunk;
+  at.c_end = at.c_begin + chunk < I ? at.c_begin + chunk : I;
+  at.q_ok = at.q < U;
+  return at;
+}
+
+// is candidate c on query q's exclusion list (excl [U][words] bits, or NULL)?
+__device__ __forceinline__ bool excluded(const uint32_t* __restrict__ excl, int words, int64_t q, int64_t c) {
+  return excl && ((excl[q * words + (c >> 5)] >> (c & 31)) & 1u);
+}
+
+// ---- the scorers: "the score of candidate c for this lane's query" ---------------------------------------------------
+// One member of the table, on the VALU path: its arguments, the lane's w_q and its column of sqT fetched once.
+struct SoloScorer {
+  const ScoreArgs& p;
+  const int64_t qcol;
+  const float wq;
+  const float* __restrict__ const sq;
+  __device__ __forceinline__ SoloScorer(const ScoreArgs& p, const Place& at)
+      : p(p), qcol(at.q), wq((p.w_q && at.q_ok) ? p.w_q[at.q] : 0.f), sq(p.sqT ? p.sqT + at.q : nullptr) {}
+  // c: the wave's one candidate, or a candidate per lane (a target: a_c, s_c and w_c become per-lane loads)
+  __device__ __forceinline__ float operator()(int64_t c, int h) const { return pair_score<false, 1, 1>(p, c, qcol, h, wq, sq); }
+};
+
+// A member of a group as the kernels see it, in device memory (workspace): its scoring arguments (s.l points at l below,
+// s.aqT / s.sqT at the member's transposes in the workspace) and the caller's query-side tensors the transposes are made from.
+struct GroupMember {
+  ScoreArgs s;
+  const float* a_q;                     // [U][H1]
+  const float* s_q;                     // [U][E]
+  Layer l[kMaxLayers];
+};
+
+// A member's scoring arguments from the table, word by word and every word made wave-uniform (readfirstlane): the loop
+// bounds, the activation and the pointers stay in scalar registers, as pair_score_topk_k holds its kernel arguments.  A
+// pointer is put together from its two words AS A GLOBAL ONE: a pointer read from memory is a generic pointer to the
+// compiler, and it treats what a generic (flat) load returns as divergent — the layer table's widths, every loop bound.
+struct MemberWords {
+  const uint32_t* __restrict__ w;
+  __device__ __forceinline__ uint32_t u32(size_t off) const { return __builtin_amdgcn_readfirstlane(w[off / 4]); }
+  template <class T>
+  __device__ __forceinline__ const T* ptr(size_t off) const {
+    const uint64_t v = u32(off) | (static_cast<uint64_t>(u32(off + 4)) << 32);
+    return (const T*)(const __attribute__((address_space(1))) T*)v;
+  }
+};
+
+__device__ __forceinline__ ScoreArgs load_member(const GroupMember* __restrict__ gm) {
+  const MemberWords m{reinterpret_cast<const uint32_t*>(&gm->s)};
+  ScoreArgs p;
+  p.aqT = m.ptr<float>(offsetof(ScoreArgs, aqT)); p.a_c = m.ptr<float>(offsetof(ScoreArgs, a_c));
+  p.sqT = m.ptr<float>(offsetof(ScoreArgs, sqT)); p.s_c = m.ptr<float>(offsetof(ScoreArgs, s_c));
+  p.w_q = m.ptr<float>(offsetof(ScoreArgs, w_q)); p.w_c = m.ptr<float>(offsetof(ScoreArgs, w_c));
+  p.dense = m.ptr<float>(offsetof(ScoreArgs, dense)); p.l = m.ptr<Layer>(offsetof(ScoreArgs, l));
+  p.Upad = static_cast<int32_t>(m.u32(offsetof(ScoreArgs, Upad))); p.H1 = static_cast<int32_t>(m.u32(offsetof(ScoreArgs, H1)));
+  p.E = static_cast<int32_t>(m.u32(offsetof(ScoreArgs, E))); p.act = static_cast<int32_t>(m.u32(offsetof(ScoreArgs, act)));
+  p.n_layers = static_cast<int32_t>(m.u32(offsetof(ScoreArgs, n_layers)));
+  return p;
+}
+
+// The members' mean logit
+//   z = (((z_0 + z_1) + z_2) + ... + z_{M-1}) / (float)M    ascending member order, one rounding per operation
+// (mi_predict_group's definition), z_m = member m's own score on the VALU path (the entries refuse a member whose own call
+// would take the MFMA path): a group of one scores as the solo kernel does, bit for bit.  The member table is read from
+// device memory with wave-uniform addresses; nothing of it lives in LDS.  member_scores [M][U][I] or NULL takes every z_m.
+struct MeanScorer {
+  const GroupMember* __restrict__ tab;
+  int M;
+  const Place& at;
+  float* __restrict__ member_scores;
+  int64_t U, I;
+  __device__ __forceinline__ float operator()(int64_t c, int h) const {
+    float acc = 0.f;
+    for (int m = 0; m < M; ++m) {
+      const ScoreArgs p = load_member(tab + m);
+      const float z = SoloScorer(p, at)(c, h);
+      if (member_scores && h == 0 && at.q_ok) member_scores[(static_cast<int64_t>(m) * U + at.q) * I + c] = z;
+      acc = m == 0 ? z : acc + z;
+    }
+    return acc / static_cast<float>(M);
+  }
+};
+
+// ---- keep the best K ---------------------------------------------------------------------------------------------------
+// Every query's sorted list and its survivor slots live in LDS; the split's lists go to part [U][splits][K].  The loop is
+// pair_score_topk_k's, over a scorer.
+template <class Scorer>
+__device__ __forceinline__ void select_topk(const Scorer& score, const SelectArgs& a, const Place& at) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int K = a.K, tid = at.tid, col = at.col;
+  uint64_t* list = reinterpret_cast<uint64_t*>(lds);             // [kQB][K], descending, 0 = empty
+  uint64_t* surv = list + kQB * K;                                // [kQB][kSurv]
+  int* nsurv = reinterpret_cast<int*>(surv + kQB * kSurv);        // [kQB]
+  for (int i = tid; i < kQB * K; i += kThreads) list[i] = 0;
+  if (tid < kQB) nsurv[tid] = 0;
+  __syncthreads();
+  for (int64_t base = at.c_begin; base < at.c_end; base += kWaves) {
+    const int64_t c = base + at.wave;
+    if (c < at.c_end) {                                           // (wave-uniform)
+      const float s = score(c, at.h);
+      if (at.h == 0 && at.q_ok) {
+        if (a.scores) a.scores[at.q * a.I + c] = s;
+        if (!excluded(a.excl, a.words, at.q, c)) {
+          const uint64_t key = rank_key(s, static_cast<uint32_t>(c));
+          if (key > list[col * K + K - 1]) {
+            const int slot = atomicAdd(&nsurv[col], 1);
+            surv[col * kSurv + slot] = key;
+          }
+        }
+      }
+    }
+    // (__syncthreads_or evaluates its argument BEFORE its barrier: the counts are read only after every wave's appends of
+    // this round are in — a stale count could skip a merge the next round's appends need, and overflow the slots)
+    __syncthreads();
+    if (__syncthreads_or(tid < kQB && nsurv[tid] > kSurv - kWaves)) merge_survivors(list, surv, nsurv, K, at.wave, at.lane);
+  }
+  __syncthreads();
+  if (__syncthreads_or(tid < kQB && nsurv[tid] > 0)) merge_survivors(list, surv, nsurv, K, at.wave, at.lane);
+  for (int i = tid; i < kQB * K; i += kThreads) {
+    const int qq = i / K;
+    if (at.q0 + qq < a.U) a.part[((at.q0 + qq) * a.splits + at.split) * K + (i - qq * K)] = list[i];
+  }
+}
+
+// ---- count the keys above named targets --------------------------------------------------------------------------------
+// A workgroup first scores its 32 queries' targets (the candidate differs per lane) and keeps their keys in LDS, then runs
+// the candidate loop over its chunk and counts, per target of the query, whether the candidate's key is larger.  Keys of one
+// query are distinct and a target's own pair scores to the target's own bits, so the count never includes the target.
+//   tkey [Tq][kQB]          the targets' keys; ~0 (above every key) where the target has no rank
+//   cnt  [kWaves][Tq][kQB]  one set of counters per wave: lane (col, h) alone adds to targets j = h, h + 2, ... of query
+//                           col in its wave's set, so the adds are plain LDS read-modify-writes — no atomics, no barrier in
+//                           the candidate loop, and the idle half of the VALU path's wave does half of the compares
+// The split's counts go plainly to part [m][splits][U][Tq] (-1: no rank; m: the scorer's place among the members on the
+// grid, 0 where they are a loop in the scorer); rank_sum_k adds the splits.  Integers only: the result depends neither on
+// the split count nor on timing, and no workgroup waits for another.
+constexpr uint64_t kNoRank = ~static_cast<uint64_t>(0);
+
+template <class Scorer>
+__device__ __forceinline__ void count_ranks(const Scorer& score, const RanksArgs& a, const Place& at, int m) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int Tq = a.Tq, tid = at.tid, col = at.col;
+  uint64_t* tkey = reinterpret_cast<uint64_t*>(lds);             // [Tq][kQB]
+  int* cnt = reinterpret_cast<int*>(tkey + Tq * kQB);             // [kWaves][Tq][kQB]
+  for (int i = tid; i < kWaves * Tq * kQB; i += kThreads) cnt[i] = 0;
+  // the targets: thread (col, j0 = tid / 32) takes targets j0, j0 + 8, ... of query col.  Every lane scores one (candidate 0
+  // where it has none, the result dropped — never stored, and q_ok guards w_q): a mean scorer's wave-uniform reads of the
+  // member table never run under an empty exec mask.
+  for (int j = tid >> 5; j < Tq; j += kThreads / kQB) {
+    int64_t t = at.q_ok ? a.targets[at.q * Tq + j] : -1;
+    const bool has = t >= 0 && t < a.I && !excluded(a.excl, a.words, at.q, t);
+    if (!has) t = 0;
+    float s = score(t, 0);
+    uint64_t key = rank_key(s, static_cast<uint32_t>(t));
+    if (!has) {
+      s = __uint_as_float(0x7fc00000u);
+      key = kNoRank;
+    }
+    if (at.q_ok && at.split == 0 && a.target_scores) a.target_scores[(static_cast<int64_t>(m) * a.U + at.q) * Tq + j] = s;
+    tkey[j * kQB + col] = key;
+  }
+  __syncthreads();
+  int* mine = cnt + at.wave * Tq * kQB + col;
+  for (int64_t c = at.c_begin + at.wave; c < at.c_end; c += kWaves) {     // (c is wave-uniform)
+    const float s = score(c, at.h);
+    if (at.q_ok && !excluded(a.excl, a.words, at.q, c)) {
+      const uint64_t key = rank_key(s, static_cast<uint32_t>(c));
+      for (int j = at.h; j < Tq; j += 2) mine[j * kQB] += key > tkey[j * kQB + col];
+    }
+  }
+  __syncthreads();
+  // thread i = (query i / Tq, target i % Tq): the block's rows of part are contiguous
+  int32_t* out = a.part + ((static_cast<int64_t>(m) * a.splits + at.split) * a.U + at.q0) * Tq;
+  const int64_t rows = a.U - at.q0 < kQB ? a.U - at.q0 : kQB;
+  for (int i = tid; i < rows * Tq; i += kThreads) {
+    const int qq = i / Tq, j = i - qq * Tq, slot = j * kQB + qq;
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) n += cnt[w * Tq * kQB + slot];
+    out[i] = tkey[slot] == kNoRank ? -1 : n;
+  }
+}
+
+// ---- the kernels -----------------------------------------------------------------------------------------------------
+// pair_score_topk_k keeps its own statement of the selection, over its own by-value argument struct (every word wave-uniform,
+// in scalar registers; the scoring functions read the fields they name from it as they do from a ScoreArgs).  The MFMA
+// instances sit at the register ceiling and the kernel is the most used of the four: built as select_topk over a scorer it ran
+// 0.3 to 1.7 % slower in every variant measured (profiles/rank_one_body.md), so the loop below and select_topk's are kept equal
+// by hand.  A change to the survivor protocol is made in both.
+struct PairArgs {
+  const float *aqT, *a_c, *sqT, *s_c, *w_q, *w_c, *dense;
+  const uint32_t* excl;
+  float* scores;
+  uint64_t* part;
+  int64_t U, I, chunk;
+  const Layer* l;
+  int32_t Upad, H1, E, K, splits, words, act, n_layers;
+};
+
 template <bool MFMA, int NP, int NQ>
 __global__ __launch_bounds__(kThreads) void pair_score_topk_k(const PairArgs p) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -355,9 +592,7 @@ __global__ __launch_bounds__(kThreads) void pair_score_topk_k(const PairArgs p) 
         }
       }
     }
-    // (__syncthreads_or evaluates its argument BEFORE its barrier: the counts are read only after every wave's appends of
-    // this round are in — a stale count could skip a merge the next round's appends need, and overflow the slots)
-    __syncthreads();
+    __syncthreads();                                              // (the protocol: select_topk)
     if (__syncthreads_or(tid < kQB && nsurv[tid] > kSurv - kWaves)) merge_survivors(list, surv, nsurv, K, wave, lane);
   }
   __syncthreads();
@@ -368,249 +603,33 @@ __global__ __launch_bounds__(kThreads) void pair_score_topk_k(const PairArgs p) 
   }
 }
 
-// ---- an ensemble: M models, one selection (mi_pair_topk_group) ------------------------------------------------------
-// A member of the group as the kernels see it, in device memory (workspace): the scoring arguments of its own
-// pair_score_topk_k (p.l points at l below, p.aqT / p.sqT at the member's transposes in the workspace) and the caller's
-// query-side tensors the transposes are made from.
-struct GroupMember {
-  PairArgs p;
-  const float* a_q;                     // [U][H1]
-  const float* s_q;                     // [U][E]
-  Layer l[kMaxLayers];
-};
-
-// A member's scoring arguments from the table, word by word and every word made wave-uniform (readfirstlane): the loop
-// bounds, the activation and the pointers stay in scalar registers, as pair_score_topk_k holds its kernel arguments.  A
-// pointer is put together from its two words AS A GLOBAL ONE: a pointer read from memory is a generic pointer to the
-// compiler, and it treats what a generic (flat) load returns as divergent — the layer table's widths, every loop bound.
-struct MemberWords {
-  const uint32_t* __restrict__ w;
-  __device__ __forceinline__ uint32_t u32(size_t off) const { return __builtin_amdgcn_readfirstlane(w[off / 4]); }
-  template <class T>
-  __device__ __forceinline__ const T* ptr(size_t off) const {
-    const uint64_t v = u32(off) | (static_cast<uint64_t>(u32(off + 4)) << 32);
-    return (const T*)(const __attribute__((address_space(1))) T*)v;
-  }
-};
-
-__device__ __forceinline__ PairArgs load_member(const GroupMember* __restrict__ gm) {
-  const MemberWords m{reinterpret_cast<const uint32_t*>(&gm->p)};
-  PairArgs p{};                                  // (the fields pair_score reads; the selection's are the group's)
-  p.aqT = m.ptr<float>(offsetof(PairArgs, aqT)); p.a_c = m.ptr<float>(offsetof(PairArgs, a_c));
-  p.sqT = m.ptr<float>(offsetof(PairArgs, sqT)); p.s_c = m.ptr<float>(offsetof(PairArgs, s_c));
-  p.w_q = m.ptr<float>(offsetof(PairArgs, w_q)); p.w_c = m.ptr<float>(offsetof(PairArgs, w_c));
-  p.dense = m.ptr<float>(offsetof(PairArgs, dense)); p.l = m.ptr<Layer>(offsetof(PairArgs, l));
-  p.Upad = static_cast<int32_t>(m.u32(offsetof(PairArgs, Upad))); p.H1 = static_cast<int32_t>(m.u32(offsetof(PairArgs, H1)));
-  p.E = static_cast<int32_t>(m.u32(offsetof(PairArgs, E))); p.act = static_cast<int32_t>(m.u32(offsetof(PairArgs, act)));
-  p.n_layers = static_cast<int32_t>(m.u32(offsetof(PairArgs, n_layers)));
-  return p;
+// The kernels that read the member table take their body's arguments one by one, as __restrict__ pointers, and fill its struct
+// themselves.  By value a SelectArgs leaves 36 unused bytes of private memory per lane reserved, and a RanksArgs loses the promise
+// that the kernel's stores leave a member's weights alone: they become vector loads, the rank entries 13-17 % slower (measured).
+__global__ __launch_bounds__(kThreads) void pair_score_topk_group_k(
+    const GroupMember* __restrict__ tab, int M, const uint32_t* __restrict__ excl, float* __restrict__ scores,
+    float* __restrict__ member_scores, uint64_t* __restrict__ part, int64_t U, int64_t I, int64_t chunk, int K, int splits, int words) {
+  const SelectArgs a{excl, scores, part, U, I, chunk, K, splits, words};
+  const Place at = place(a.U, a.I, a.chunk);
+  select_topk(MeanScorer{tab, M, at, member_scores, a.U, a.I}, a, at);
 }
 
-// The grid, the LDS lists and the selection of pair_score_topk_k; what enters the selection is the mean logit
-//   z = (((z_0 + z_1) + z_2) + ... + z_{M-1}) / (float)M    ascending member order, one rounding per operation
-// (mi_predict_group's definition), z_m = pair_score on member m's arguments (the VALU path: mi_pair_topk_group refuses a
-// member whose own call would take the MFMA path).  The member table is read from device memory with wave-uniform
-// addresses; nothing of it lives in LDS.
-__global__ __launch_bounds__(kThreads) void pair_score_topk_group_k(const GroupMember* __restrict__ tab, int M,
-                                                                   const uint32_t* __restrict__ excl, float* __restrict__ scores,
-                                                                   float* __restrict__ member_scores, uint64_t* __restrict__ part,
-                                                                   int64_t U, int64_t I, int64_t chunk, int K, int splits,
-                                                                   int words) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  uint64_t* list = reinterpret_cast<uint64_t*>(lds);             // [kQB][K], descending, 0 = empty
-  uint64_t* surv = list + kQB * K;                                // [kQB][kSurv]
-  int* nsurv = reinterpret_cast<int*>(surv + kQB * kSurv);        // [kQB]
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31, h = lane >> 5;
-  const int64_t q0 = static_cast<int64_t>(blockIdx.x) * kQB;
-  const int split = blockIdx.y;
-  const int64_t c_begin = split * chunk;
-  const int64_t c_end = c_begin + chunk < I ? c_begin + chunk : I;
-  for (int i = tid; i < kQB * K; i += kThreads) list[i] = 0;
-  if (tid < kQB) nsurv[tid] = 0;
-  __syncthreads();
-  const int64_t q = q0 + col;
-  const bool q_ok = q < U;
-  const float fM = static_cast<float>(M);
-  for (int64_t base = c_begin; base < c_end; base += kWaves) {
-    const int64_t c = base + wave;
-    if (c < c_end) {                                              // (wave-uniform)
-      float acc = 0.f;
-      for (int m = 0; m < M; ++m) {
-        const PairArgs p = load_member(tab + m);
-        const float wq = (p.w_q && q_ok) ? p.w_q[q] : 0.f;
-        const float* __restrict__ sq = p.sqT ? p.sqT + q0 + col : nullptr;
-        const float z = pair_score<false, 1, 1>(p, c, q0 + col, h, wq, sq);
-        if (member_scores && h == 0 && q_ok) member_scores[(static_cast<int64_t>(m) * U + q) * I + c] = z;
-        acc = m == 0 ? z : acc + z;
-      }
-      const float s = acc / fM;
-      if (h == 0 && q_ok) {
-        if (scores) scores[q * I + c] = s;
-        const bool excluded = excl && ((excl[q * words + (c >> 5)] >> (c & 31)) & 1u);
-        if (!excluded) {
-          const uint64_t key = rank_key(s, static_cast<uint32_t>(c));
-          if (key > list[col * K + K - 1]) {
-            const int slot = atomicAdd(&nsurv[col], 1);
-            surv[col * kSurv + slot] = key;
-          }
-        }
-      }
-    }
-    // (as in pair_score_topk_k: the counts are read only after every wave's appends of this round are in)
-    __syncthreads();
-    if (__syncthreads_or(tid < kQB && nsurv[tid] > kSurv - kWaves)) merge_survivors(list, surv, nsurv, K, wave, lane);
-  }
-  __syncthreads();
-  if (__syncthreads_or(tid < kQB && nsurv[tid] > 0)) merge_survivors(list, surv, nsurv, K, wave, lane);
-  for (int i = tid; i < kQB * K; i += kThreads) {
-    const int qq = i / K;
-    if (q0 + qq < U) part[((q0 + qq) * splits + split) * K + (i - qq * K)] = list[i];
-  }
+// grid z: the members, every one for itself
+__global__ __launch_bounds__(kThreads) void pair_target_ranks_k(
+    const GroupMember* __restrict__ tab, const uint32_t* __restrict__ excl, const int32_t* __restrict__ targets,
+    float* __restrict__ target_scores, int32_t* __restrict__ part, int64_t U, int64_t I, int64_t chunk, int Tq, int splits, int words) {
+  const RanksArgs a{excl, targets, target_scores, part, U, I, chunk, Tq, splits, words};
+  const Place at = place(a.U, a.I, a.chunk);
+  const ScoreArgs p = load_member(tab + blockIdx.z);
+  count_ranks(SoloScorer(p, at), a, at, blockIdx.z);
 }
 
-// ---- exact ranks of named targets, every member for itself (mi_pair_target_ranks) ----------------------------------
-// Grid (query blocks of 32) x (candidate splits) x (members).  A workgroup first scores its 32 queries' targets with its
-// member's pair_score (the candidate differs per lane: a_c, s_c and w_c become per-lane loads) and keeps their keys in LDS,
-// then runs pair_score_topk_k's candidate loop over its chunk — a wave scores ONE candidate against the 32 queries — and
-// counts, per target of the query, whether the candidate's key is larger.  Keys of one query are distinct and a target's
-// own pair scores to the target's own bits, so the count never includes the target.
-//   tkey [Tq][kQB]          the targets' keys; ~0 (above every key) where the target has no rank
-//   cnt  [kWaves][Tq][kQB]  one set of counters per wave: lane (col, h) alone adds to targets j = h, h + 2, ... of query
-//                           col in its wave's set, so the adds are plain LDS read-modify-writes — no atomics, no barrier in
-//                           the candidate loop, and the idle half of the VALU path's wave does half of the compares
-// The split's counts go plainly to part [M][splits][U][Tq] (-1: no rank); rank_sum_k adds the splits.  Integers only: the
-// result depends neither on the split count nor on timing, and no workgroup waits for another.
-constexpr uint64_t kNoRank = ~static_cast<uint64_t>(0);
-
-__global__ __launch_bounds__(kThreads) void pair_target_ranks_k(const GroupMember* __restrict__ tab,
-                                                               const uint32_t* __restrict__ excl,
-                                                               const int32_t* __restrict__ targets,
-                                                               float* __restrict__ target_scores, int32_t* __restrict__ part,
-                                                               int64_t U, int64_t I, int64_t chunk, int Tq, int splits, int words) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  uint64_t* tkey = reinterpret_cast<uint64_t*>(lds);             // [Tq][kQB]
-  int* cnt = reinterpret_cast<int*>(tkey + Tq * kQB);             // [kWaves][Tq][kQB]
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31, h = lane >> 5;
-  const int64_t q0 = static_cast<int64_t>(blockIdx.x) * kQB;
-  const int split = blockIdx.y, m = blockIdx.z;
-  const int64_t c_begin = split * chunk;
-  const int64_t c_end = c_begin + chunk < I ? c_begin + chunk : I;
-  const PairArgs p = load_member(tab + m);
-  const int64_t q = q0 + col;
-  const bool q_ok = q < U;
-  const float wq = (p.w_q && q_ok) ? p.w_q[q] : 0.f;
-  const float* __restrict__ sq = p.sqT ? p.sqT + q0 + col : nullptr;
-  for (int i = tid; i < kWaves * Tq * kQB; i += kThreads) cnt[i] = 0;
-  // the targets: thread (col, j0 = tid / 32) takes targets j0, j0 + 8, ... of query col
-  for (int j = tid >> 5; j < Tq; j += kThreads / kQB) {
-    uint64_t key = kNoRank;
-    float s = __uint_as_float(0x7fc00000u);
-    if (q_ok) {
-      const int64_t t = targets[q * Tq + j];
-      if (t >= 0 && t < I && !(excl && ((excl[q * words + (t >> 5)] >> (t & 31)) & 1u))) {
-        s = pair_score<false, 1, 1>(p, t, q0 + col, 0, wq, sq);
-        key = rank_key(s, static_cast<uint32_t>(t));
-      }
-      if (split == 0 && target_scores) target_scores[(static_cast<int64_t>(m) * U + q) * Tq + j] = s;
-    }
-    tkey[j * kQB + col] = key;
-  }
-  __syncthreads();
-  int* mine = cnt + wave * Tq * kQB + col;
-  for (int64_t c = c_begin + wave; c < c_end; c += kWaves) {     // (c is wave-uniform)
-    const float s = pair_score<false, 1, 1>(p, c, q0 + col, h, wq, sq);
-    if (q_ok && !(excl && ((excl[q * words + (c >> 5)] >> (c & 31)) & 1u))) {
-      const uint64_t key = rank_key(s, static_cast<uint32_t>(c));
-      for (int j = h; j < Tq; j += 2) mine[j * kQB] += key > tkey[j * kQB + col];
-    }
-  }
-  __syncthreads();
-  // thread i = (query i / Tq, target i % Tq): the block's rows of part are contiguous
-  int32_t* out = part + ((static_cast<int64_t>(m) * splits + split) * U + q0) * Tq;
-  const int64_t rows = U - q0 < kQB ? U - q0 : kQB;
-  for (int i = tid; i < rows * Tq; i += kThreads) {
-    const int qq = i / Tq, j = i - qq * Tq, at = j * kQB + qq;
-    int n = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) n += cnt[w * Tq * kQB + at];
-    out[i] = tkey[at] == kNoRank ? -1 : n;
-  }
-}
-
-// ---- exact ranks of named targets under the members' mean score (mi_pair_target_ranks_mean) -------------------------
-// The mean logit of pair (q, c) as pair_score_topk_group_k forms it: ascending member order, one rounding per operation,
-//   z = (((z_0 + z_1) + z_2) + ... + z_{M-1}) / (float)M
-// c may differ per lane (a target) or be the wave's one candidate; q_ok: the lane's query exists (qcol < U).
-__device__ __forceinline__ float mean_pair_score(const GroupMember* __restrict__ tab, int M, float fM, int64_t c, int64_t qcol,
-                                                 bool q_ok, int h) {
-  float acc = 0.f;
-  for (int m = 0; m < M; ++m) {
-    const PairArgs p = load_member(tab + m);
-    const float wq = (p.w_q && q_ok) ? p.w_q[qcol] : 0.f;
-    const float* __restrict__ sq = p.sqT ? p.sqT + qcol : nullptr;
-    const float z = pair_score<false, 1, 1>(p, c, qcol, h, wq, sq);
-    acc = m == 0 ? z : acc + z;
-  }
-  return acc / fM;
-}
-
-// pair_target_ranks_k with the members as a loop instead of a grid axis: grid (query blocks of 32) x (candidate splits),
-// tkey [Tq][kQB] and cnt [kWaves][Tq][kQB] as there, and both the targets' keys and the candidates' keys come from
-// mean_pair_score — a target's own pair gives the target's own bits and never counts itself.  Every lane scores a target
-// (candidate 0 where it has none, the result dropped): the member loop's wave-uniform reads never run under an empty
-// exec mask.  The split's counts go plainly to part [splits][U][Tq] (-1: no rank); rank_sum_k (one "member") adds them.
-__global__ __launch_bounds__(kThreads) void pair_target_ranks_mean_k(const GroupMember* __restrict__ tab, int M,
-                                                                    const uint32_t* __restrict__ excl,
-                                                                    const int32_t* __restrict__ targets,
-                                                                    float* __restrict__ target_scores, int32_t* __restrict__ part,
-                                                                    int64_t U, int64_t I, int64_t chunk, int Tq, int splits,
-                                                                    int words) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  uint64_t* tkey = reinterpret_cast<uint64_t*>(lds);             // [Tq][kQB]
-  int* cnt = reinterpret_cast<int*>(tkey + Tq * kQB);             // [kWaves][Tq][kQB]
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31, h = lane >> 5;
-  const int64_t q0 = static_cast<int64_t>(blockIdx.x) * kQB;
-  const int split = blockIdx.y;
-  const int64_t c_begin = split * chunk;
-  const int64_t c_end = c_begin + chunk < I ? c_begin + chunk : I;
-  const int64_t q = q0 + col;
-  const bool q_ok = q < U;
-  const float fM = static_cast<float>(M);
-  for (int i = tid; i < kWaves * Tq * kQB; i += kThreads) cnt[i] = 0;
-  // the targets: thread (col, j0 = tid / 32) takes targets j0, j0 + 8, ... of query col
-  for (int j = tid >> 5; j < Tq; j += kThreads / kQB) {
-    int64_t t = q_ok ? targets[q * Tq + j] : -1;
-    const bool has = t >= 0 && t < I && !(excl && ((excl[q * words + (t >> 5)] >> (t & 31)) & 1u));
-    if (!has) t = 0;
-    float s = mean_pair_score(tab, M, fM, t, q, q_ok, 0);
-    uint64_t key = rank_key(s, static_cast<uint32_t>(t));
-    if (!has) {
-      s = __uint_as_float(0x7fc00000u);
-      key = kNoRank;
-    }
-    if (q_ok && split == 0 && target_scores) target_scores[q * Tq + j] = s;
-    tkey[j * kQB + col] = key;
-  }
-  __syncthreads();
-  int* mine = cnt + wave * Tq * kQB + col;
-  for (int64_t c = c_begin + wave; c < c_end; c += kWaves) {     // (c is wave-uniform)
-    const float s = mean_pair_score(tab, M, fM, c, q, q_ok, h);
-    if (q_ok && !(excl && ((excl[q * words + (c >> 5)] >> (c & 31)) & 1u))) {
-      const uint64_t key = rank_key(s, static_cast<uint32_t>(c));
-      for (int j = h; j < Tq; j += 2) mine[j * kQB] += key > tkey[j * kQB + col];
-    }
-  }
-  __syncthreads();
-  // thread i = (query i / Tq, target i % Tq): the block's rows of part are contiguous
-  int32_t* out = part + (static_cast<int64_t>(split) * U + q0) * Tq;
-  const int64_t rows = U - q0 < kQB ? U - q0 : kQB;
-  for (int i = tid; i < rows * Tq; i += kThreads) {
-    const int qq = i / Tq, j = i - qq * Tq, at = j * kQB + qq;
-    int n = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) n += cnt[w * Tq * kQB + at];
-    out[i] = tkey[at] == kNoRank ? -1 : n;
-  }
+__global__ __launch_bounds__(kThreads) void pair_target_ranks_mean_k(
+    const GroupMember* __restrict__ tab, int M, const uint32_t* __restrict__ excl, const int32_t* __restrict__ targets,
+    float* __restrict__ target_scores, int32_t* __restrict__ part, int64_t U, int64_t I, int64_t chunk, int Tq, int splits, int words) {
+  const RanksArgs a{excl, targets, target_scores, part, U, I, chunk, Tq, splits, words};
+  const Place at = place(a.U, a.I, a.chunk);
+  count_ranks(MeanScorer{tab, M, at, nullptr, a.U, a.I}, a, at, 0);
 }
 
 // ranks[m][e] = the sum over the splits of part[m][split][e], -1 where the target has no rank; n = U * Tq, grid (blocks, M)
@@ -698,8 +717,8 @@ __global__ __launch_bounds__(256) void excl_mask_k(const int64_t* __restrict__ o
   }
 }
 
-// The group's member table reaches the workspace through the kernel arguments, kTabChunk members a launch (compile-time
-// indices: see PairArgs::l) — no host-to-device copy, so the call neither synchronises nor needs pinned memory.
+// The member table reaches the workspace through the kernel arguments, kTabChunk members a launch (compile-time
+// indices: see ScoreArgs::l) — no host-to-device copy, so the call neither synchronises nor needs pinned memory.
 constexpr int kTabChunk = 8;
 struct MemberChunk {
   GroupMember m[kTabChunk];
@@ -717,9 +736,9 @@ __global__ __launch_bounds__(256) void transpose_pad_group_k(const GroupMember* 
   const GroupMember& gm = tab[blockIdx.y];
   const bool a = blockIdx.z == 0;
   const float* __restrict__ src = a ? gm.a_q : gm.s_q;
-  float* __restrict__ dst = const_cast<float*>(a ? gm.p.aqT : gm.p.sqT);
+  float* __restrict__ dst = const_cast<float*>(a ? gm.s.aqT : gm.s.sqT);
   if (!dst) return;
-  const int W = a ? gm.p.H1 : gm.p.E, Upad = gm.p.Upad;
+  const int W = a ? gm.s.H1 : gm.s.E, Upad = gm.s.Upad;
   const int64_t n = static_cast<int64_t>(W) * Upad;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * 256) {
     const int64_t k = i / Upad, q = i - k * Upad;
@@ -727,36 +746,47 @@ __global__ __launch_bounds__(256) void transpose_pad_group_k(const GroupMember* 
   }
 }
 
-struct Plan {
-  int64_t Upad, qblocks, chunk;
-  int32_t splits, words;
-  size_t off_layers, off_aq, off_sq, off_mask, off_part, total;
-};
-
 inline size_t align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
 
 // workgroups of 256 threads for the n elements of a grid-stride kernel (at most 2048)
 inline unsigned grid_blocks(int64_t n) { const int64_t b = mi::ceil_div(n, 256); return static_cast<unsigned>(b < 2048 ? b : 2048); }
 
-Plan make_plan(int64_t U, int64_t I, int32_t k, int32_t H1, int32_t E) {
-  Plan pl;
-  pl.qblocks = mi::ceil_div(U, kQB);
-  pl.Upad = pl.qblocks * kQB;
-  int64_t s = mi::ceil_div(kTargetBlocks, pl.qblocks);
-  const int64_t s_lds = kMergeLds / (8 * static_cast<int64_t>(k));
-  const int64_t s_min_chunk = mi::ceil_div(I, 64);                 // at least 64 candidates per split
-  if (s > s_lds) s = s_lds;
+// The pair kernels' grid for U queries and I candidates.  The split rule: about kTargetBlocks workgroups over query blocks x
+// the members on the grid, at least 64 candidates per split, and at most cap splits (what the final merge's LDS holds).
+struct Split {
+  int64_t Upad, qblocks, chunk;
+  int32_t splits, words;
+};
+
+Split make_split(int64_t U, int64_t I, int64_t grid_members, int64_t cap = INT64_MAX) {
+  Split sp;
+  sp.qblocks = mi::ceil_div(U, kQB);
+  sp.Upad = sp.qblocks * kQB;
+  int64_t s = mi::ceil_div(kTargetBlocks, sp.qblocks * grid_members);
+  const int64_t s_min_chunk = mi::ceil_div(I, 64);
+  if (s > cap) s = cap;
   if (s > s_min_chunk) s = s_min_chunk;
   if (s < 1) s = 1;
-  pl.chunk = mi::ceil_div(I, s);
-  pl.splits = static_cast<int32_t>(mi::ceil_div(I, pl.chunk));
-  pl.words = static_cast<int32_t>(mi::ceil_div(I, 32));
+  sp.chunk = mi::ceil_div(I, s);
+  sp.splits = static_cast<int32_t>(mi::ceil_div(I, sp.chunk));
+  sp.words = static_cast<int32_t>(mi::ceil_div(I, 32));
+  return sp;
+}
+
+struct Plan {
+  Split sp;
+  size_t off_layers, off_aq, off_sq, off_mask, off_part, total;
+};
+
+Plan make_plan(int64_t U, int64_t I, int32_t k, int32_t H1, int32_t E) {
+  Plan pl;
+  pl.sp = make_split(U, I, 1, kMergeLds / (8 * static_cast<int64_t>(k)));
   size_t o = 0;
   pl.off_layers = o; o += align256(sizeof(Layer) * kMaxLayers);
-  pl.off_aq = o; o += align256(sizeof(float) * static_cast<size_t>(H1) * pl.Upad);
-  pl.off_sq = o; o += align256(sizeof(float) * static_cast<size_t>(E) * pl.Upad);
-  pl.off_mask = o; o += align256(sizeof(uint32_t) * static_cast<size_t>(U) * pl.words);
-  pl.off_part = o; o += align256(sizeof(uint64_t) * static_cast<size_t>(U) * pl.splits * k);
+  pl.off_aq = o; o += align256(sizeof(float) * static_cast<size_t>(H1) * pl.sp.Upad);
+  pl.off_sq = o; o += align256(sizeof(float) * static_cast<size_t>(E) * pl.sp.Upad);
+  pl.off_mask = o; o += align256(sizeof(uint32_t) * static_cast<size_t>(U) * pl.sp.words);
+  pl.off_part = o; o += align256(sizeof(uint64_t) * static_cast<size_t>(U) * pl.sp.splits * k);
   pl.total = o;
   return pl;
 }
@@ -807,17 +837,36 @@ inline bool takes_mfma(int n_layers, int maxw) { return n_layers >= 2 && maxw >=
 
 using mi::unsupported;
 
-// What the group shares (query blocks, splits, exclusion mask, partial lists: make_plan with no per-model tensors) and
-// where the member table and the members' transposes lie in the workspace.
-constexpr size_t kMaxGroupLds = 160 * 1024;      // the dynamic LDS a launch can be raised to on gfx950
+// ---- a group of members (mi_pair_topk_group and the two rank entries) ------------------------------------------------
+// What every group entry (`who`, for the texts) refuses first, in this order: the member count, then the table itself.
+int32_t check_member_count(const char* who, const mi_rank_member_t* members, int32_t n_members) {
+  MI_REQUIRE(n_members >= 1, "%s: %d members (at least 1)", who, n_members);
+  if (n_members > MI_PAIR_TOPK_GROUP_MAX_MEMBERS)
+    return unsupported("%s: %d members (at most %d in one launch)", who, n_members, MI_PAIR_TOPK_GROUP_MAX_MEMBERS);
+  MI_REQUIRE(members, "%s: members", who);
+  return MI_OK;
+}
 
-struct GroupPlan {
-  Plan pl;
-  size_t off_table, off_sides, total;
-};
-
-inline size_t side_bytes(const Plan& pl, int32_t H1, int32_t E) {
-  return align256(sizeof(float) * static_cast<size_t>(H1) * pl.Upad) + align256(sizeof(float) * static_cast<size_t>(E) * pl.Upad);
+// Every member is checked before anything is launched: check_model (the entry has checked the per-call arguments), and the
+// mean scorer's and the rank kernels' VALU scope.  kernel: the entry's word for what scores, "the group kernel" / "the kernel".
+int32_t check_members(const char* who, const char* kernel, const mi_rank_member_t* members, int32_t n_members, int64_t U,
+                      int64_t I, int32_t k) {
+  for (int32_t i = 0; i < n_members; ++i) {
+    const mi_rank_member_t& m = members[i];
+    LayerTable lt{};
+    int maxw = 0;
+    const int32_t rc = check_model(U, I, k, m.a_q, m.s_q, m.a_c, m.s_c, m.H1, m.E, m.dense, m.layer_off, m.widths, m.n_layers,
+                                   m.activation, true, true, lt, maxw);
+    if (rc != MI_OK) {
+      mi::member_error(who, i);
+      return rc;
+    }
+    if (takes_mfma(m.n_layers, maxw))
+      return unsupported("%s: member %d: %d layers after layer 1 with a hidden width of %d: %s takes the VALU pair path only "
+                         "(fewer than two layers after layer 1, or every hidden width after layer 1 below %d)", who, i,
+                         m.n_layers, maxw, kernel, kValuW);
+  }
+  return MI_OK;
 }
 
 bool group_sizes_ok(const mi_rank_member_t* members, int32_t n, int64_t U, int64_t I, int32_t k) {
@@ -827,91 +876,34 @@ bool group_sizes_ok(const mi_rank_member_t* members, int32_t n, int64_t U, int64
   return true;
 }
 
-GroupPlan make_group_plan(const mi_rank_member_t* members, int32_t n, int64_t U, int64_t I, int32_t k) {
-  GroupPlan gp;
-  gp.pl = make_plan(U, I, k, 0, 0);
-  size_t o = gp.pl.total;
-  gp.off_table = o; o += align256(sizeof(GroupMember) * static_cast<size_t>(n));
-  gp.off_sides = o;
-  for (int32_t i = 0; i < n; ++i) o += side_bytes(gp.pl, members[i].H1, members[i].E);
-  gp.total = o;
-  return gp;
-}
-
-// mi_pair_target_ranks: make_plan's split rule — at least 64 candidates per split, about kTargetBlocks workgroups — over
-// query blocks x members (no selection lists: nothing else bounds the splits), and the workspace: the exclusion mask, the
-// splits' partial counts, the member table and the members' transposes.  pl: what side_bytes and the table need of a Plan.
-// mi_pair_target_ranks_mean (mean = true): the members are a loop in the kernel, not a grid axis — the member factor drops
-// out of the split rule and of the partial counts.
-struct RanksPlan {
-  Plan pl;
-  size_t off_mask, off_part, off_table, off_sides, total;
+// The member table in the workspace, and behind it every member's transposes aqT [H1][Upad] and sqT [E][Upad].
+struct TablePlace {
+  size_t off_table, off_sides;
 };
 
-bool ranks_sizes_ok(const mi_rank_member_t* members, int32_t n, int64_t U, int64_t I, int32_t Tq) {
-  return Tq >= 1 && Tq <= MI_PAIR_RANKS_MAX_TARGETS && group_sizes_ok(members, n, U, I, 1);
+// The workspace keeps 352 bytes per member for the table — what a GroupMember took while it carried the selection's
+// arguments as well — so every offset behind the table and every *_workspace_bytes answer is what callers have been given.
+// (56 bytes a member lie unused: the slot can shrink to sizeof(GroupMember) with the next ABI version.)
+constexpr size_t kTableSlot = 352;
+static_assert(sizeof(GroupMember) <= kTableSlot, "the member table outgrew its place in the workspace");
+
+inline size_t side_bytes(int64_t Upad, int32_t H1, int32_t E) {
+  return align256(sizeof(float) * static_cast<size_t>(H1) * Upad) + align256(sizeof(float) * static_cast<size_t>(E) * Upad);
 }
 
-RanksPlan make_ranks_plan(const mi_rank_member_t* members, int32_t n, int64_t U, int64_t I, int32_t Tq, bool mean = false) {
-  RanksPlan rp{};
-  Plan& pl = rp.pl;
-  const int32_t grid_members = mean ? 1 : n;
-  pl.qblocks = mi::ceil_div(U, kQB);
-  pl.Upad = pl.qblocks * kQB;
-  int64_t s = mi::ceil_div(kTargetBlocks, pl.qblocks * grid_members);
-  const int64_t s_min_chunk = mi::ceil_div(I, 64);
-  if (s > s_min_chunk) s = s_min_chunk;
-  if (s < 1) s = 1;
-  pl.chunk = mi::ceil_div(I, s);
-  pl.splits = static_cast<int32_t>(mi::ceil_div(I, pl.chunk));
-  pl.words = static_cast<int32_t>(mi::ceil_div(I, 32));
-  size_t o = 0;
-  rp.off_mask = o; o += align256(sizeof(uint32_t) * static_cast<size_t>(U) * pl.words);
-  rp.off_part = o; o += align256(sizeof(int32_t) * static_cast<size_t>(grid_members) * pl.splits * U * Tq);
-  rp.off_table = o; o += align256(sizeof(GroupMember) * static_cast<size_t>(n));
-  rp.off_sides = o;
-  for (int32_t i = 0; i < n; ++i) o += side_bytes(pl, members[i].H1, members[i].E);
-  rp.total = o;
-  return rp;
+TablePlace place_table(const mi_rank_member_t* members, int32_t n, int64_t Upad, size_t& o) {
+  TablePlace tp;
+  tp.off_table = o; o += align256(kTableSlot * static_cast<size_t>(n));
+  tp.off_sides = o;
+  for (int32_t i = 0; i < n; ++i) o += side_bytes(Upad, members[i].H1, members[i].E);
+  return tp;
 }
 
-// What mi_pair_target_ranks and mi_pair_target_ranks_mean (`who`, for the texts) refuse before anything is launched, in
-// their order: the member count, the per-call arguments, then every member — check_model with k = 1, and the VALU scope.
-int32_t check_ranks_call(const char* who, const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I,
-                         const int64_t* excl_off, const int32_t* excl_idx, const int32_t* targets, int32_t Tq,
-                         const int32_t* ranks) {
-  MI_REQUIRE(n_members >= 1, "%s: %d members (at least 1)", who, n_members);
-  if (n_members > MI_PAIR_TOPK_GROUP_MAX_MEMBERS)
-    return unsupported("%s: %d members (at most %d in one launch)", who, n_members, MI_PAIR_TOPK_GROUP_MAX_MEMBERS);
-  MI_REQUIRE(members, "%s: members", who);
-  MI_REQUIRE(Tq >= 1 && Tq <= MI_PAIR_RANKS_MAX_TARGETS, "%s: Tq=%d targets per query (1 to %d in one call)", who, Tq,
-             MI_PAIR_RANKS_MAX_TARGETS);
-  MI_REQUIRE(targets && ranks, "%s: targets / ranks", who);
-  MI_REQUIRE(!excl_off == !excl_idx, "%s: excl_off and excl_idx go together", who);
-  for (int32_t i = 0; i < n_members; ++i) {
-    const mi_rank_member_t& m = members[i];
-    LayerTable lt{};
-    int maxw = 0;
-    const int32_t rc = check_model(U, I, 1, m.a_q, m.s_q, m.a_c, m.s_c, m.H1, m.E, m.dense, m.layer_off, m.widths, m.n_layers,
-                                   m.activation, true, true, lt, maxw);
-    if (rc != MI_OK) {
-      mi::member_error(who, i);
-      return rc;
-    }
-    if (takes_mfma(m.n_layers, maxw))
-      return unsupported("%s: member %d: %d layers after layer 1 with a hidden width of %d: the kernel takes the "
-                         "VALU pair path only (fewer than two layers after layer 1, or every hidden width after layer 1 below "
-                         "%d)", who, i, m.n_layers, maxw, kValuW);
-  }
-  return MI_OK;
-}
-
-// The launches in front of a rank entry's scoring launch: the member table, as mi_pair_topk_group writes it (the
-// selection's fields of PairArgs stay zero: nothing here reads them), one transpose launch for all members, the mask.
-void prepare_ranks(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, const int64_t* excl_off,
-                   const int32_t* excl_idx, const RanksPlan& rp, char* ws, GroupMember* tab, uint32_t* mask, hipStream_t st) {
-  const Plan& pl = rp.pl;
-  size_t side = rp.off_sides;
+// Writes the table, kTabChunk members a launch, and transposes every member's query side in one more launch.
+GroupMember* write_member_table(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t Upad, char* ws,
+                                const TablePlace& tp, hipStream_t st) {
+  GroupMember* tab = reinterpret_cast<GroupMember*>(ws + tp.off_table);
+  size_t side = tp.off_sides;
   int maxside = 0;
   MemberChunk ch{};
   for (int32_t i = 0; i < n_members; ++i) {
@@ -920,14 +912,13 @@ void prepare_ranks(const mi_rank_member_t* members, int32_t n_members, int64_t U
     gm = GroupMember{};
     for (int j = 0; j < m.n_layers; ++j)
       gm.l[j] = Layer{m.layer_off[2 * j], m.layer_off[2 * j + 1], m.widths[j], m.widths[j + 1]};
-    PairArgs& a = gm.p;
+    ScoreArgs& a = gm.s;
     a.aqT = m.H1 ? reinterpret_cast<float*>(ws + side) : nullptr;
-    a.sqT = m.E ? reinterpret_cast<float*>(ws + side + align256(sizeof(float) * static_cast<size_t>(m.H1) * pl.Upad)) : nullptr;
-    side += side_bytes(pl, m.H1, m.E);
+    a.sqT = m.E ? reinterpret_cast<float*>(ws + side + align256(sizeof(float) * static_cast<size_t>(m.H1) * Upad)) : nullptr;
+    side += side_bytes(Upad, m.H1, m.E);
     a.a_c = m.a_c; a.s_c = m.s_c; a.w_q = m.w_q; a.w_c = m.w_c; a.dense = m.dense;
     a.l = tab[i].l;                              // (the address of this member's layers in the workspace)
-    a.U = U; a.I = I;
-    a.Upad = static_cast<int32_t>(pl.Upad); a.H1 = m.H1; a.E = m.E; a.act = m.activation; a.n_layers = m.n_layers;
+    a.Upad = static_cast<int32_t>(Upad); a.H1 = m.H1; a.E = m.E; a.act = m.activation; a.n_layers = m.n_layers;
     gm.a_q = m.a_q; gm.s_q = m.s_q;
     if (m.H1 > maxside) maxside = m.H1;
     if (m.E > maxside) maxside = m.E;
@@ -937,19 +928,126 @@ void prepare_ranks(const mi_rank_member_t* members, int32_t n_members, int64_t U
     }
   }
   if (maxside)
-    transpose_pad_group_k<<<dim3(grid_blocks(static_cast<int64_t>(maxside) * pl.Upad), static_cast<unsigned>(n_members), 2), dim3(256), 0,
+    transpose_pad_group_k<<<dim3(grid_blocks(static_cast<int64_t>(maxside) * Upad), static_cast<unsigned>(n_members), 2), dim3(256), 0,
                             st>>>(tab, U);
-  if (mask) {
-    zero_u32_k<<<dim3(grid_blocks(U * pl.words)), dim3(256), 0, st>>>(mask, U * pl.words);
-    excl_mask_k<<<dim3(static_cast<unsigned>(U)), dim3(256), 0, st>>>(excl_off, excl_idx, I, pl.words, mask);
-  }
+  return tab;
 }
+
+// the exclusion lists as the bit mask the kernels test (nothing to do without lists: mask is NULL)
+void prepare_mask(const int64_t* excl_off, const int32_t* excl_idx, int64_t U, int64_t I, int32_t words, uint32_t* mask,
+                  hipStream_t st) {
+  if (!mask) return;
+  zero_u32_k<<<dim3(grid_blocks(U * words)), dim3(256), 0, st>>>(mask, U * words);
+  excl_mask_k<<<dim3(static_cast<unsigned>(U)), dim3(256), 0, st>>>(excl_off, excl_idx, I, words, mask);
+}
+
+// ---- top-K: the selection's LDS, its launch for one model, and the final merge ---------------------------------------
+inline size_t select_lds(int32_t k) { return sizeof(uint64_t) * kQB * (k + kSurv) + sizeof(int) * kQB; }
 
 template <bool MFMA, int NP, int NQ>
 int32_t launch_pair(const PairArgs& a, dim3 grid, size_t lds, hipStream_t st) {
   const int32_t rl = mi::raise_lds(&pair_score_topk_k<MFMA, NP, NQ>, lds, "pair_topk");
   if (rl != MI_OK) return rl;
   pair_score_topk_k<MFMA, NP, NQ><<<grid, dim3(kThreads), lds, st>>>(a);
+  return MI_OK;
+}
+
+int32_t finish_topk(const uint64_t* part, int64_t U, int32_t splits, int32_t k, float* top_score, int32_t* top_idx,
+                    hipStream_t st) {
+  topk_merge_k<<<dim3(static_cast<unsigned>(U)), dim3(256), sizeof(uint64_t) * splits * k, st>>>(part, splits, k, top_score,
+                                                                                                 top_idx);
+  MI_CHECK_LAUNCH("topk_merge_k");
+  return MI_OK;
+}
+
+// What the group shares (query blocks, splits, exclusion mask, partial lists: make_plan with no per-model tensors) and
+// where the member table and the members' transposes lie in the workspace.
+constexpr size_t kMaxGroupLds = 160 * 1024;      // the dynamic LDS a launch can be raised to on gfx950
+
+struct GroupPlan {
+  Plan pl;
+  TablePlace tp;
+  size_t total;
+};
+
+GroupPlan make_group_plan(const mi_rank_member_t* members, int32_t n, int64_t U, int64_t I, int32_t k) {
+  GroupPlan gp;
+  gp.pl = make_plan(U, I, k, 0, 0);
+  size_t o = gp.pl.total;
+  gp.tp = place_table(members, n, gp.pl.sp.Upad, o);
+  gp.total = o;
+  return gp;
+}
+
+// ---- target ranks: every member for itself (the members on grid z), or under the members' mean (a loop in the scorer) --
+struct RanksKind {
+  bool mean;
+  const char *who, *prepare, *kernel;           // the entry's name in its texts
+};
+constexpr RanksKind kEachMember{false, "pair_target_ranks", "pair_target_ranks (prepare)", "pair_target_ranks_k"};
+constexpr RanksKind kMembersMean{true, "pair_target_ranks_mean", "pair_target_ranks_mean (prepare)", "pair_target_ranks_mean_k"};
+
+// No selection lists: nothing but the split rule bounds the splits.  The workspace: the exclusion mask, the splits' partial
+// counts (one set per member on the grid), the member table and the members' transposes.
+struct RanksPlan {
+  Split sp;
+  int32_t grid_members;
+  size_t off_mask, off_part, total;
+  TablePlace tp;
+};
+
+RanksPlan make_ranks_plan(const RanksKind& kind, const mi_rank_member_t* members, int32_t n, int64_t U, int64_t I, int32_t Tq) {
+  RanksPlan rp;
+  rp.grid_members = kind.mean ? 1 : n;
+  rp.sp = make_split(U, I, rp.grid_members);
+  size_t o = 0;
+  rp.off_mask = o; o += align256(sizeof(uint32_t) * static_cast<size_t>(U) * rp.sp.words);
+  rp.off_part = o; o += align256(sizeof(int32_t) * static_cast<size_t>(rp.grid_members) * rp.sp.splits * U * Tq);
+  rp.tp = place_table(members, n, rp.sp.Upad, o);
+  rp.total = o;
+  return rp;
+}
+
+size_t target_ranks_bytes(const RanksKind& kind, const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I,
+                          int32_t Tq) {
+  if (Tq < 1 || Tq > MI_PAIR_RANKS_MAX_TARGETS || !group_sizes_ok(members, n_members, U, I, 1)) return 0;
+  return make_ranks_plan(kind, members, n_members, U, I, Tq).total;
+}
+
+int32_t target_ranks_call(const RanksKind& kind, const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I,
+                          const int64_t* excl_off, const int32_t* excl_idx, const int32_t* targets, int32_t Tq, int32_t* ranks,
+                          float* target_scores, void* workspace, size_t workspace_bytes, mi_stream_t stream) {
+  const char* who = kind.who;
+  int32_t rc = check_member_count(who, members, n_members);
+  if (rc != MI_OK) return rc;
+  MI_REQUIRE(Tq >= 1 && Tq <= MI_PAIR_RANKS_MAX_TARGETS, "%s: Tq=%d targets per query (1 to %d in one call)", who, Tq,
+             MI_PAIR_RANKS_MAX_TARGETS);
+  MI_REQUIRE(targets && ranks, "%s: targets / ranks", who);
+  MI_REQUIRE(!excl_off == !excl_idx, "%s: excl_off and excl_idx go together", who);
+  rc = check_members(who, "the kernel", members, n_members, U, I, 1);
+  if (rc != MI_OK) return rc;
+  const RanksPlan rp = make_ranks_plan(kind, members, n_members, U, I, Tq);
+  const Split& sp = rp.sp;
+  MI_REQUIRE(workspace && workspace_bytes >= rp.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, rp.total);
+  hipStream_t st = mi::as_stream(stream);
+  char* ws = static_cast<char*>(workspace);
+  uint32_t* mask = excl_off ? reinterpret_cast<uint32_t*>(ws + rp.off_mask) : nullptr;
+  const GroupMember* tab = write_member_table(members, n_members, U, sp.Upad, ws, rp.tp, st);
+  prepare_mask(excl_off, excl_idx, U, I, sp.words, mask, st);
+  MI_CHECK_LAUNCH(kind.prepare);
+  int32_t* part = reinterpret_cast<int32_t*>(ws + rp.off_part);
+  const size_t lds = (sizeof(uint64_t) + sizeof(int) * kWaves) * kQB * static_cast<size_t>(Tq);      // at most 48 KB
+  const dim3 grid(static_cast<unsigned>(sp.qblocks), static_cast<unsigned>(sp.splits), static_cast<unsigned>(rp.grid_members));
+  if (kind.mean)
+    pair_target_ranks_mean_k<<<grid, dim3(kThreads), lds, st>>>(tab, n_members, mask, targets, target_scores, part, U, I, sp.chunk,
+                                                                Tq, sp.splits, sp.words);
+  else
+    pair_target_ranks_k<<<grid, dim3(kThreads), lds, st>>>(tab, mask, targets, target_scores, part, U, I, sp.chunk, Tq, sp.splits,
+                                                           sp.words);
+  MI_CHECK_LAUNCH(kind.kernel);
+  const int64_t n = U * Tq;
+  rank_sum_k<<<dim3(grid_blocks(n), static_cast<unsigned>(rp.grid_members)), dim3(256), 0, st>>>(part, sp.splits, n, ranks);
+  MI_CHECK_LAUNCH("rank_sum_k");
   return MI_OK;
 }
 
@@ -968,38 +1066,30 @@ int32_t mi_pair_topk(const float* a_q, const float* s_q, const float* w_q, int64
                      int32_t activation, const int64_t* excl_off, const int32_t* excl_idx, int32_t k,
                      float* top_score, int32_t* top_idx, float* scores, void* workspace, size_t workspace_bytes,
                      mi_stream_t stream) {
-  PairArgs a{};
   LayerTable lt{};
   int maxw = 0;
   const int32_t rc = check_model(U, I, k, a_q, s_q, a_c, s_c, H1, E, dense, layer_off, widths, n_layers, activation,
                                  top_score && top_idx, !excl_off == !excl_idx, lt, maxw);
   if (rc != MI_OK) return rc;
-  a.n_layers = n_layers;
   const Plan pl = make_plan(U, I, k, H1, E);
+  const Split& sp = pl.sp;
   MI_REQUIRE(workspace && workspace_bytes >= pl.total, "pair_topk: workspace %zu < %zu bytes", workspace_bytes, pl.total);
   hipStream_t st = mi::as_stream(stream);
   char* ws = static_cast<char*>(workspace);
   float* aqT = H1 ? reinterpret_cast<float*>(ws + pl.off_aq) : nullptr;
   float* sqT = E ? reinterpret_cast<float*>(ws + pl.off_sq) : nullptr;
   uint32_t* mask = excl_off ? reinterpret_cast<uint32_t*>(ws + pl.off_mask) : nullptr;
-  uint64_t* part = reinterpret_cast<uint64_t*>(ws + pl.off_part);
-  auto blocks = [](int64_t n) { const int64_t b = mi::ceil_div(n, 256); return static_cast<unsigned>(b < 2048 ? b : 2048); };
   Layer* layers = reinterpret_cast<Layer*>(ws + pl.off_layers);
   if (n_layers) layer_table_k<<<dim3(1), dim3(64), 0, st>>>(lt, n_layers, layers);
-  if (aqT) transpose_pad_k<<<dim3(blocks(static_cast<int64_t>(H1) * pl.Upad)), dim3(256), 0, st>>>(a_q, U, H1, (int)pl.Upad, aqT);
-  if (sqT) transpose_pad_k<<<dim3(blocks(static_cast<int64_t>(E) * pl.Upad)), dim3(256), 0, st>>>(s_q, U, E, (int)pl.Upad, sqT);
-  if (mask) {
-    zero_u32_k<<<dim3(blocks(U * pl.words)), dim3(256), 0, st>>>(mask, U * pl.words);
-    excl_mask_k<<<dim3(static_cast<unsigned>(U)), dim3(256), 0, st>>>(excl_off, excl_idx, I, pl.words, mask);
-  }
+  if (aqT) transpose_pad_k<<<dim3(grid_blocks(static_cast<int64_t>(H1) * sp.Upad)), dim3(256), 0, st>>>(a_q, U, H1, (int)sp.Upad, aqT);
+  if (sqT) transpose_pad_k<<<dim3(grid_blocks(static_cast<int64_t>(E) * sp.Upad)), dim3(256), 0, st>>>(s_q, U, E, (int)sp.Upad, sqT);
+  prepare_mask(excl_off, excl_idx, U, I, sp.words, mask, st);
   MI_CHECK_LAUNCH("pair_topk (prepare)");
-  a.aqT = aqT; a.a_c = a_c; a.sqT = sqT; a.s_c = s_c; a.w_q = w_q; a.w_c = w_c; a.dense = dense;
-  a.excl = mask; a.scores = scores; a.part = part; a.l = layers;
-  a.U = U; a.I = I; a.chunk = pl.chunk;
-  a.Upad = static_cast<int32_t>(pl.Upad); a.H1 = H1; a.E = E; a.K = k; a.splits = pl.splits; a.words = pl.words;
-  a.act = activation;
-  const size_t lds = sizeof(uint64_t) * kQB * (k + kSurv) + sizeof(int) * kQB;
-  const dim3 grid(static_cast<unsigned>(pl.qblocks), static_cast<unsigned>(pl.splits));
+  uint64_t* part = reinterpret_cast<uint64_t*>(ws + pl.off_part);
+  const PairArgs a{aqT, a_c, sqT, s_c, w_q, w_c, dense, mask, scores, part, U, I, sp.chunk, layers,
+                   static_cast<int32_t>(sp.Upad), H1, E, k, sp.splits, sp.words, activation, n_layers};
+  const size_t lds = select_lds(k);
+  const dim3 grid(static_cast<unsigned>(sp.qblocks), static_cast<unsigned>(sp.splits));
   int32_t rl;
   if (takes_mfma(n_layers, maxw)) {
     if (maxw <= 32) rl = launch_pair<true, 1, 1>(a, grid, lds, st);
@@ -1011,10 +1101,7 @@ int32_t mi_pair_topk(const float* a_q, const float* s_q, const float* w_q, int64
   }
   if (rl != MI_OK) return rl;
   MI_CHECK_LAUNCH("pair_score_topk_k");
-  topk_merge_k<<<dim3(static_cast<unsigned>(U)), dim3(256), sizeof(uint64_t) * pl.splits * k, st>>>(part, pl.splits, k,
-                                                                                                    top_score, top_idx);
-  MI_CHECK_LAUNCH("topk_merge_k");
-  return MI_OK;
+  return finish_topk(part, U, sp.splits, k, top_score, top_idx, st);
 }
 
 size_t mi_pair_topk_group_workspace_bytes(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, int32_t k) {
@@ -1025,145 +1112,55 @@ size_t mi_pair_topk_group_workspace_bytes(const mi_rank_member_t* members, int32
 int32_t mi_pair_topk_group(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, const int64_t* excl_off,
                            const int32_t* excl_idx, int32_t k, float* top_score, int32_t* top_idx, float* scores,
                            float* member_scores, void* workspace, size_t workspace_bytes, mi_stream_t stream) {
-  MI_REQUIRE(n_members >= 1, "pair_topk_group: %d members (at least 1)", n_members);
-  if (n_members > MI_PAIR_TOPK_GROUP_MAX_MEMBERS)
-    return unsupported("pair_topk_group: %d members (at most %d in one launch)", n_members, MI_PAIR_TOPK_GROUP_MAX_MEMBERS);
-  MI_REQUIRE(members, "pair_topk_group: members");
+  const char* who = "pair_topk_group";
+  int32_t rc = check_member_count(who, members, n_members);
+  if (rc != MI_OK) return rc;
   MI_REQUIRE(top_score && top_idx, "pair_topk_group: top_score / top_idx");
   MI_REQUIRE(!excl_off == !excl_idx, "pair_topk_group: excl_off and excl_idx go together");
-  // every member is checked before anything is launched
-  for (int32_t i = 0; i < n_members; ++i) {
-    const mi_rank_member_t& m = members[i];
-    LayerTable lt{};
-    int maxw = 0;
-    const int32_t rc = check_model(U, I, k, m.a_q, m.s_q, m.a_c, m.s_c, m.H1, m.E, m.dense, m.layer_off, m.widths, m.n_layers,
-                                   m.activation, true, true, lt, maxw);
-    if (rc != MI_OK) {
-      mi::member_error("pair_topk_group", i);
-      return rc;
-    }
-    if (takes_mfma(m.n_layers, maxw))
-      return unsupported("pair_topk_group: member %d: %d layers after layer 1 with a hidden width of %d: the group kernel takes "
-                         "the VALU pair path only (fewer than two layers after layer 1, or every hidden width after layer 1 "
-                         "below %d)", i, m.n_layers, maxw, kValuW);
-  }
+  rc = check_members(who, "the group kernel", members, n_members, U, I, k);
+  if (rc != MI_OK) return rc;
   const GroupPlan gp = make_group_plan(members, n_members, U, I, k);
-  const Plan& pl = gp.pl;
+  const Split& sp = gp.pl.sp;
   MI_REQUIRE(workspace && workspace_bytes >= gp.total, "pair_topk_group: workspace %zu < %zu bytes", workspace_bytes, gp.total);
-  const size_t lds = sizeof(uint64_t) * kQB * (k + kSurv) + sizeof(int) * kQB;    // (the lists; no member data lives in LDS)
+  const size_t lds = select_lds(k);                                               // (the lists; no member data lives in LDS)
   if (lds > kMaxGroupLds) return unsupported("pair_topk_group: %zu bytes of LDS for k=%d (at most %zu)", lds, k, kMaxGroupLds);
-  const int32_t rl = mi::raise_lds(&pair_score_topk_group_k, lds, "pair_topk_group");
+  const int32_t rl = mi::raise_lds(&pair_score_topk_group_k, lds, who);
   if (rl != MI_OK) return rl;
   hipStream_t st = mi::as_stream(stream);
   char* ws = static_cast<char*>(workspace);
-  GroupMember* tab = reinterpret_cast<GroupMember*>(ws + gp.off_table);
-  uint32_t* mask = excl_off ? reinterpret_cast<uint32_t*>(ws + pl.off_mask) : nullptr;
-  uint64_t* part = reinterpret_cast<uint64_t*>(ws + pl.off_part);
-  auto blocks = [](int64_t n) { const int64_t b = mi::ceil_div(n, 256); return static_cast<unsigned>(b < 2048 ? b : 2048); };
-  size_t side = gp.off_sides;
-  int maxside = 0;
-  MemberChunk ch{};
-  for (int32_t i = 0; i < n_members; ++i) {
-    const mi_rank_member_t& m = members[i];
-    GroupMember& gm = ch.m[i % kTabChunk];
-    gm = GroupMember{};
-    for (int j = 0; j < m.n_layers; ++j)
-      gm.l[j] = Layer{m.layer_off[2 * j], m.layer_off[2 * j + 1], m.widths[j], m.widths[j + 1]};
-    float* aqT = m.H1 ? reinterpret_cast<float*>(ws + side) : nullptr;
-    float* sqT = m.E ? reinterpret_cast<float*>(ws + side + align256(sizeof(float) * static_cast<size_t>(m.H1) * pl.Upad)) : nullptr;
-    side += side_bytes(pl, m.H1, m.E);
-    PairArgs& a = gm.p;
-    a.aqT = aqT; a.a_c = m.a_c; a.sqT = sqT; a.s_c = m.s_c; a.w_q = m.w_q; a.w_c = m.w_c; a.dense = m.dense;
-    a.l = tab[i].l;                              // (the address of this member's layers in the workspace)
-    a.U = U; a.I = I; a.chunk = pl.chunk;
-    a.Upad = static_cast<int32_t>(pl.Upad); a.H1 = m.H1; a.E = m.E; a.K = k; a.splits = pl.splits; a.words = pl.words;
-    a.act = m.activation; a.n_layers = m.n_layers;
-    gm.a_q = m.a_q; gm.s_q = m.s_q;
-    if (m.H1 > maxside) maxside = m.H1;
-    if (m.E > maxside) maxside = m.E;
-    if (i % kTabChunk == kTabChunk - 1 || i + 1 == n_members) {
-      const int first = i - i % kTabChunk;
-      member_table_k<<<dim3(1), dim3(64), 0, st>>>(ch, i - first + 1, tab + first);
-    }
-  }
-  if (maxside)
-    transpose_pad_group_k<<<dim3(blocks(static_cast<int64_t>(maxside) * pl.Upad), static_cast<unsigned>(n_members), 2), dim3(256), 0,
-                            st>>>(tab, U);
-  if (mask) {
-    zero_u32_k<<<dim3(blocks(U * pl.words)), dim3(256), 0, st>>>(mask, U * pl.words);
-    excl_mask_k<<<dim3(static_cast<unsigned>(U)), dim3(256), 0, st>>>(excl_off, excl_idx, I, pl.words, mask);
-  }
+  uint32_t* mask = excl_off ? reinterpret_cast<uint32_t*>(ws + gp.pl.off_mask) : nullptr;
+  const GroupMember* tab = write_member_table(members, n_members, U, sp.Upad, ws, gp.tp, st);
+  prepare_mask(excl_off, excl_idx, U, I, sp.words, mask, st);
   MI_CHECK_LAUNCH("pair_topk_group (prepare)");
-  pair_score_topk_group_k<<<dim3(static_cast<unsigned>(pl.qblocks), static_cast<unsigned>(pl.splits)), dim3(kThreads), lds, st>>>(
-      tab, n_members, mask, scores, member_scores, part, U, I, pl.chunk, k, pl.splits, pl.words);
+  uint64_t* part = reinterpret_cast<uint64_t*>(ws + gp.pl.off_part);
+  pair_score_topk_group_k<<<dim3(static_cast<unsigned>(sp.qblocks), static_cast<unsigned>(sp.splits)), dim3(kThreads), lds, st>>>(
+      tab, n_members, mask, scores, member_scores, part, U, I, sp.chunk, k, sp.splits, sp.words);
   MI_CHECK_LAUNCH("pair_score_topk_group_k");
-  topk_merge_k<<<dim3(static_cast<unsigned>(U)), dim3(256), sizeof(uint64_t) * pl.splits * k, st>>>(part, pl.splits, k,
-                                                                                                    top_score, top_idx);
-  MI_CHECK_LAUNCH("topk_merge_k");
-  return MI_OK;
+  return finish_topk(part, U, sp.splits, k, top_score, top_idx, st);
 }
 
 size_t mi_pair_target_ranks_workspace_bytes(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, int32_t Tq) {
-  if (!ranks_sizes_ok(members, n_members, U, I, Tq)) return 0;
-  return make_ranks_plan(members, n_members, U, I, Tq).total;
+  return target_ranks_bytes(kEachMember, members, n_members, U, I, Tq);
 }
 
 int32_t mi_pair_target_ranks(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I, const int64_t* excl_off,
                              const int32_t* excl_idx, const int32_t* targets, int32_t Tq, int32_t* ranks, float* target_scores,
                              void* workspace, size_t workspace_bytes, mi_stream_t stream) {
-  const int32_t rc = check_ranks_call("pair_target_ranks", members, n_members, U, I, excl_off, excl_idx, targets, Tq, ranks);
-  if (rc != MI_OK) return rc;
-  const RanksPlan rp = make_ranks_plan(members, n_members, U, I, Tq);
-  const Plan& pl = rp.pl;
-  MI_REQUIRE(workspace && workspace_bytes >= rp.total, "pair_target_ranks: workspace %zu < %zu bytes", workspace_bytes, rp.total);
-  hipStream_t st = mi::as_stream(stream);
-  char* ws = static_cast<char*>(workspace);
-  GroupMember* tab = reinterpret_cast<GroupMember*>(ws + rp.off_table);
-  uint32_t* mask = excl_off ? reinterpret_cast<uint32_t*>(ws + rp.off_mask) : nullptr;
-  int32_t* part = reinterpret_cast<int32_t*>(ws + rp.off_part);
-  prepare_ranks(members, n_members, U, I, excl_off, excl_idx, rp, ws, tab, mask, st);
-  MI_CHECK_LAUNCH("pair_target_ranks (prepare)");
-  const size_t lds = (sizeof(uint64_t) + sizeof(int) * kWaves) * kQB * static_cast<size_t>(Tq);      // at most 48 KB
-  pair_target_ranks_k<<<dim3(static_cast<unsigned>(pl.qblocks), static_cast<unsigned>(pl.splits), static_cast<unsigned>(n_members)),
-                        dim3(kThreads), lds, st>>>(tab, mask, targets, target_scores, part, U, I, pl.chunk, Tq, pl.splits, pl.words);
-  MI_CHECK_LAUNCH("pair_target_ranks_k");
-  const int64_t n = U * Tq;
-  rank_sum_k<<<dim3(grid_blocks(n), static_cast<unsigned>(n_members)), dim3(256), 0, st>>>(part, pl.splits, n, ranks);
-  MI_CHECK_LAUNCH("rank_sum_k");
-  return MI_OK;
+  return target_ranks_call(kEachMember, members, n_members, U, I, excl_off, excl_idx, targets, Tq, ranks, target_scores,
+                           workspace, workspace_bytes, stream);
 }
 
 size_t mi_pair_target_ranks_mean_workspace_bytes(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I,
                                                  int32_t Tq) {
-  if (!ranks_sizes_ok(members, n_members, U, I, Tq)) return 0;
-  return make_ranks_plan(members, n_members, U, I, Tq, true).total;
+  return target_ranks_bytes(kMembersMean, members, n_members, U, I, Tq);
 }
 
 int32_t mi_pair_target_ranks_mean(const mi_rank_member_t* members, int32_t n_members, int64_t U, int64_t I,
                                   const int64_t* excl_off, const int32_t* excl_idx, const int32_t* targets, int32_t Tq,
                                   int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes,
                                   mi_stream_t stream) {
-  const int32_t rc = check_ranks_call("pair_target_ranks_mean", members, n_members, U, I, excl_off, excl_idx, targets, Tq, ranks);
-  if (rc != MI_OK) return rc;
-  const RanksPlan rp = make_ranks_plan(members, n_members, U, I, Tq, true);
-  const Plan& pl = rp.pl;
-  MI_REQUIRE(workspace && workspace_bytes >= rp.total, "pair_target_ranks_mean: workspace %zu < %zu bytes", workspace_bytes,
-             rp.total);
-  hipStream_t st = mi::as_stream(stream);
-  char* ws = static_cast<char*>(workspace);
-  GroupMember* tab = reinterpret_cast<GroupMember*>(ws + rp.off_table);
-  uint32_t* mask = excl_off ? reinterpret_cast<uint32_t*>(ws + rp.off_mask) : nullptr;
-  int32_t* part = reinterpret_cast<int32_t*>(ws + rp.off_part);
-  prepare_ranks(members, n_members, U, I, excl_off, excl_idx, rp, ws, tab, mask, st);
-  MI_CHECK_LAUNCH("pair_target_ranks_mean (prepare)");
-  const size_t lds = (sizeof(uint64_t) + sizeof(int) * kWaves) * kQB * static_cast<size_t>(Tq);      // at most 48 KB
-  pair_target_ranks_mean_k<<<dim3(static_cast<unsigned>(pl.qblocks), static_cast<unsigned>(pl.splits)), dim3(kThreads), lds, st>>>(
-      tab, n_members, mask, targets, target_scores, part, U, I, pl.chunk, Tq, pl.splits, pl.words);
-  MI_CHECK_LAUNCH("pair_target_ranks_mean_k");
-  const int64_t n = U * Tq;
-  rank_sum_k<<<dim3(grid_blocks(n), 1), dim3(256), 0, st>>>(part, pl.splits, n, ranks);
-  MI_CHECK_LAUNCH("rank_sum_k");
-  return MI_OK;
+  return target_ranks_call(kMembersMean, members, n_members, U, I, excl_off, excl_idx, targets, Tq, ranks, target_scores,
+                           workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -148,6 +148,30 @@ def test_one_member_is_that_members_top_k(mixed):
     assert torch.equal(sc1.view(torch.int32), sc2.view(torch.int32)) and torch.equal(sc1.view(torch.int32), ms[0].view(torch.int32))
 
 
+def test_nine_members_cross_the_member_tables_chunk(mixed):
+    """the member table reaches the workspace 8 members a launch: 9 members take two; U = 37 (a partial second block),
+    I = 131 (a ragged last split), k = 10"""
+    engines = [m for m, _ in mixed] + [_engine(40 + i, *MIXED[i % 3])[0] for i in range(6)]
+    rng = np.random.default_rng(14)
+    U, I, k = 37, 131, 10
+    qid, cid = _ids(rng, U, I)
+    excl = [sorted(set(rng.integers(0, I, 4).tolist())) for _ in range(U)]
+    top_s, top_i, scores, member_scores = engine.top_k_group(engines, dev(qid), dev(cid), Q5, k, exclude=excl, return_scores=True,
+                                                             return_member_scores=True)
+    # the last member, from the table's second launch, scores as it does alone
+    own = engines[8].top_k(dev(qid), dev(cid), Q5, k, return_scores=True)[2]
+    assert torch.equal(member_scores[8].view(torch.int32), own.view(torch.int32))
+    z = member_scores.cpu()
+    acc = z[0]
+    for i in range(1, 9):
+        acc = acc + z[i]
+    mean = (acc / torch.full_like(acc, 9.0)).numpy()
+    assert np.array_equal(scores.cpu().numpy().view(np.uint32), mean.view(np.uint32))
+    s_ref, i_ref = host_topk(mean, k, excl)
+    assert np.array_equal(top_i.cpu().numpy(), i_ref)
+    assert np.array_equal(top_s.cpu().numpy().view(np.uint32), s_ref.view(np.uint32))
+
+
 def _raw_members(engines, qid, cid):
     """the mi_rank_member_t array engine.top_k_group would pass, and what keeps its tensors alive"""
     sides, U, I, _ = engines[0]._top_k_check(dev(qid), dev(cid), Q5, 10, None, None)

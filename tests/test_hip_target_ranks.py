@@ -157,6 +157,28 @@ def test_many_splits_with_an_analytic_answer():
     assert np.array_equal(ranks[0], want) and np.array_equal(ranks[1], want)
 
 
+def test_nine_members_cross_the_member_tables_chunk(mixed):
+    """the member table reaches the workspace 8 members a launch: 9 members take two; U = 37 (a partial second block),
+    I = 131 (a ragged last split), 3 targets per query, one of them -1 and one excluded"""
+    engines = mixed + [_engine(40 + i, *MIXED[i % 3]) for i in range(6)]
+    rng = np.random.default_rng(14)
+    U, I = 37, 131
+    qid, cid = _ids(rng, U, I)
+    targets = [[int(t[0]), -1, int(t[1])] for t in (rng.choice(I, 2, replace=False) for _ in range(U))]
+    excl = [sorted(set(rng.integers(0, I, 4).tolist()) - {targets[u][0]} | {targets[u][2]}) for u in range(U)]
+    ranks, scores = engine.target_ranks_group(engines, dev(qid), dev(cid), Q5, targets, exclude=excl, return_scores=True)
+    ranks, scores = ranks.cpu().numpy(), scores.cpu().numpy()
+    assert ranks.shape == (9, U, 3) and (ranks[:, :, 0] >= 0).all() and (ranks[:, :, 1:] == -1).all()
+    # the last member, from the table's second launch, ranks as it does alone and as the rule says on its own scores
+    alone, s1 = engines[8].target_ranks(dev(qid), dev(cid), Q5, targets, exclude=excl, return_scores=True, mode="fused")
+    assert np.array_equal(ranks[8], alone.cpu().numpy())
+    assert np.array_equal(scores[8, :, 0].view(np.uint32), s1.cpu().numpy()[:, 0].view(np.uint32))
+    z = _own_scores(engines[8], qid, cid)
+    assert np.array_equal(ranks[8], oracle_ranks(z, targets, excl))
+    assert np.array_equal(scores[8, :, 0].view(np.uint32), z[np.arange(U), [t[0] for t in targets]].view(np.uint32))
+    assert np.isnan(scores[8, :, 1:]).all()
+
+
 def _raw_members(engines, qid, cid):
     """the mi_rank_member_t array engine.target_ranks_group would pass, and what keeps its tensors alive"""
     sides, U, I, _ = engines[0]._top_k_check(dev(qid), dev(cid), Q5, 1, None, None)

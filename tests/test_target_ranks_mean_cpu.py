@@ -1,7 +1,7 @@
 """CPU: the host side of exact target ranks under an ensemble's MEAN logit — engine.target_ranks_mean (ragged targets, passes
 of 64 columns, what it does once per call), EnsemblePredictor.rank_targets (its modes and refusals), trainers.sweep
 --ensemble N --rank-metrics and trainers.recommend --top N --mean-metrics-at.  mi_pair_target_ranks_mean is stood in by a
-numpy restatement of its definition in include/mi355x_rec.h (tests.rank_mean_kernels.RankMeanKernels: the mean in fp32 in
+numpy restatement of its definition in include/mi355x_rec.h (tests.rank_kernels.RankKernels: the mean in fp32 in
 member order, the rank counted, not read off a sorted list); the real kernel is tested in test_hip_target_ranks_mean.py.  The
 binding and the library's host-side refusals are checked against the real library."""
 import json
@@ -14,8 +14,7 @@ from mi355x_rec import _lib, engine
 from mi355x_rec.engine import DeepFM
 from mi355x_rec.predictor import EnsemblePredictor, Predictor
 from tests.cases import _sweep_args
-from tests.rank_kernels import oracle_ranks
-from tests.rank_mean_kernels import RankMeanKernels, rank_mean_kernels  # noqa: F401  (rank_mean_kernels: a fixture)
+from tests.rank_kernels import RankKernels, oracle_ranks, rank_kernels  # noqa: F401  (rank_kernels: a fixture)
 from tests.util import _header_decls, _train_deep_fm_export, make_problem
 from trainers import ml_100k, recommend
 
@@ -24,7 +23,7 @@ QF, CF = [1, 4], [0, 2, 3, 5]
 
 
 def _model(seed, E, hidden, **kw):
-    m = DeepFM(VOCAB, embedding_size=E, hidden_units=hidden, device="cpu", _kernels=RankMeanKernels(), **kw)
+    m = DeepFM(VOCAB, embedding_size=E, hidden_units=hidden, device="cpu", _kernels=RankKernels(), **kw)
     p, _, _, _ = make_problem(seed, VOCAB, E, hidden, 4, use_dnn=kw.get("use_dnn", True))
     m.load_oracle_params(p)
     return m
@@ -110,7 +109,7 @@ def exports(tmp_path_factory):
     """three small trained deep_fm exports: two inside the kernel's scope, one ([64, 64]) outside it"""
     root = str(tmp_path_factory.mktemp("rankmean"))
     with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(engine, "HipKernels", RankMeanKernels)
+        mp.setattr(engine, "HipKernels", RankKernels)
         return [_train_deep_fm_export(root, "a", ["--embedding-size", "4", "--hidden-units", "8", "8"]),
                 _train_deep_fm_export(root, "b", ["--embedding-size", "8", "--hidden-units", "8"]),
                 _train_deep_fm_export(root, "c", ["--embedding-size", "4", "--hidden-units", "64", "64"])]
@@ -124,7 +123,7 @@ def sides():
     return qf, cf, recommend.positive_targets(users, items, test), recommend.exclusion_csr(users, items, train), len(items)
 
 
-def test_ensemble_rank_targets_fused_and_layered_give_equal_integers(rank_mean_kernels, exports, sides):
+def test_ensemble_rank_targets_fused_and_layered_give_equal_integers(rank_kernels, exports, sides):
     qf, cf, targets, excl, I = sides
     ens = EnsemblePredictor([Predictor.from_export(d, device="cpu") for d in exports[:2]])
     k = ens.k
@@ -157,13 +156,13 @@ def test_ensemble_rank_targets_fused_and_layered_give_equal_integers(rank_mean_k
         ens.rank_targets(qf, cf, targets, mode="eager")
 
 
-def test_sweep_ranks_its_ensemble_as_recommend_does(rank_mean_kernels, tmp_path, capsys, monkeypatch):
+def test_sweep_ranks_its_ensemble_as_recommend_does(rank_kernels, tmp_path, capsys, monkeypatch):
     from trainers import sweep
     real = EnsemblePredictor.from_sweep.__func__
 
     def registered(cls, *a, **kw):                       # (the stand-in of mi_predict_group finds a member's engine by register())
         ens = real(cls, *a, **kw)
-        RankMeanKernels.register([p.engine for p in ens.members])
+        RankKernels.register([p.engine for p in ens.members])
         return ens
     monkeypatch.setattr(EnsemblePredictor, "from_sweep", classmethod(registered))
     job = tmp_path / "job"
