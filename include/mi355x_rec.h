@@ -654,7 +654,7 @@ int32_t mi_dense_bwd_weight_planes_batch(const mi_wgrad_job_t* jobs, int32_t n_j
  *   d_logit[b]  = (sigmoid(x) - y) * loss_scale
  *   d_logit_sum[0] = sum_b d_logit[b]   (= gradient of the linear_model bias; fixed-order sum)
  * labels: uint8 0/1 (ml_100k.py:48 rating >= cutoff).  d_logit / d_logit_sum / loss_out may be NULL
- * (eval / predict).  workspace: mi_head_workspace_bytes(B). */
+ * (eval / predict).  workspace: mi_head_workspace_bytes(B).  Inputs are finite: an infinite or NaN term has no contract. */
 size_t mi_head_workspace_bytes(int64_t B);
 int32_t mi_sigmoid_ce_head(const float* lin, const float* lin_bias, const float* fm,
                            const float* dnn, const uint8_t* labels, int64_t B, float loss_scale,
@@ -665,7 +665,7 @@ int32_t mi_sigmoid_ce_head(const float* lin, const float* lin_bias, const float*
  * binary_classification_head) and get_binary_losses' unreduced loss (model_utils.py:23-36).
  *   logistic[b] = sigmoid(x)   probabilities[b] = {1 - p, p}   class_ids[b] = p > 0.5   (int64, as TF's)
  *   unreduced_loss[b] = max(x,0) - x*y + log1p(exp(-|x|))      (needs labels)
- * Any output may be NULL. */
+ * Any output may be NULL.  Inputs are finite: an infinite or NaN logit has no contract. */
 int32_t mi_binary_predictions(const float* logits, const uint8_t* labels, int64_t B, float* logistic,
                               float* probabilities, int64_t* class_ids, float* unreduced_loss, mi_stream_t stream);
 
@@ -693,7 +693,8 @@ int32_t mi_layer_histogram(const float* x, int64_t n, const double* limits, int3
  *   hist   [2*201] int64: hist[y*201+k] = examples with label y whose sigmoid exceeds exactly k of
  *          tf.metrics.auc's 200 ascending thresholds; tp[j] = sum_{k>j} hist[1][k] etc. on the host
  *   counts [8] int64: n, n_pos, n_pred_pos, n_correct, tp@.5, fp@.5, fn@.5, (unused)
- *   sums   [4] f64 : sum(loss_b), sum(sigmoid), sum(label), (unused) */
+ *   sums   [4] f64 : sum(loss_b), sum(sigmoid), sum(label), (unused)
+ * Inputs are finite: an infinite or NaN logit has no contract. */
 int32_t mi_eval_accumulate(const float* logits, const uint8_t* labels, int64_t B,
                            int64_t* hist /*[2*201]*/, int64_t* counts /*[8]*/,
                            double* sums /*[4]*/, mi_stream_t stream);

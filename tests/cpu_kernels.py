@@ -59,12 +59,18 @@ def thresholds():
     return th.astype(F32)
 
 
+def sigmoid32(z):
+    """mi_sigmoid_stable restated in numpy fp32: e = exp(-|z|); 1 / (1 + e) for z >= 0, e / (1 + e) below"""
+    z = np.asarray(z, F32)
+    e = np.exp(-np.abs(z)).astype(F32)
+    return np.where(z >= 0, F32(1) / (F32(1) + e), e / (F32(1) + e)).astype(F32)
+
+
 def counters(z, y):
     """mi_eval_accumulate restated: (hist [2, 201], counts [8], sums [3]) of fp32 logits z and labels y"""
     z = np.asarray(z, F32)
     y = np.asarray(y).astype(np.int64)
-    e = np.exp(-np.abs(z)).astype(F32)
-    p = np.where(z >= 0, F32(1) / (F32(1) + e), e / (F32(1) + e)).astype(F32)
+    p = sigmoid32(z)
     k = np.searchsorted(thresholds(), p, side="left")                    # #{j : th[j] < p}
     hist = np.zeros((2, 201), np.int64)
     np.add.at(hist, (y, k), 1)
