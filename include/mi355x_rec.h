@@ -323,7 +323,13 @@ int32_t mi_dense_apply(float* param, float* slot0, float* slot1, const float* gr
                        const mi_opt_hparams* hp, mi_stream_t stream);
 
 /* Sparse apply on the U distinct rows found by mi_sort_unique_rows: segment-sums the entry
- * gradients in ascending entry order (== TF's unsorted_segment_sum order on CPU), then applies
+ * gradients in ascending entry order (== TF's unsorted_segment_sum order on CPU) for every segment of at most 48
+ * entries; a longer segment of c entries is cut into G slices of ceil(c / G) consecutive entries, each summed in
+ * ascending order, and the slice sums are added in slice order (a fixed order: results are reproducible; it differs
+ * from the one-pass order in fp32 association only).  G = 256 / LPR with LPR = the smallest power of two >= E / 4, and
+ * G = 256 in a call without the table (lin_w alone) — here, in mi_sparse_apply_fused and in mi_entry_grads_segsum
+ * (there: without out_rows).  tests/sparse_cases.py restates both orders; tests/test_hip_sparse_sums.py holds the
+ * entries to them bit for bit and to fp64 within (c + 3) 2^-24 sum |terms|.  Then applies
  * the optimizer's sparse rule to table row r (width E) and, when lin_w != NULL, to lin_w[r]
  * (width 1) with d_lin.  For Adam the rule is TF's dense-equivalent one: see mi_sparse_catchup.
  * last_step[r] is set to step.  slot arrays mirror the parameter arrays' shapes. */

@@ -210,7 +210,8 @@ __global__ __launch_bounds__(kBlock) void sparse_apply_k(ApplyArgs a, Hp h, cons
   float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
   float gl = 0.f;
   float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (a.table && lane_on) w = ld4(a.table + r * a.ts + 4 * l);
+  // (STORE without the FM term: w is not used, and a.table is then no table at all but out_rows — whose row u need not exist)
+  if (a.table && lane_on && (!STORE || fg.dlf)) w = ld4(a.table + r * a.ts + 4 * l);
   RowState q;
   if constexpr (!STORE) q = load_row_state(a, h, r, l, lane_on);
   seg_accumulate<FUSED>(a, fg, s_beg, s_end, l, lane_on, w, g, gl);
@@ -222,7 +223,8 @@ __global__ __launch_bounds__(kBlock) void sparse_apply_k(ApplyArgs a, Hp h, cons
 // j, j + grid, j + 2 grid, ... of kRun consecutive rows (hot rows have neighbouring ids: the stride spreads them), collects
 // the long ones, and for each splits the segment into kBlock/LPR contiguous slices, one per lane
 // group, summed in order; the slice sums are then added in slice order.  A fixed order, so results
-// are reproducible; it differs from the one-pass order only in fp32 association.
+// are reproducible; it differs from the one-pass order only in fp32 association.  (A launch without the
+// table — the wide part alone, out_lin alone — runs with LPR = 1: 256 slices whatever E is.)
 template <int LPR, bool FUSED, bool STORE = false>
 __global__ __launch_bounds__(kBlock) void sparse_apply_long_k(ApplyArgs a, Hp h, const FusedGrad fg) {
   if (a.st) { a.step = a.st->step; h.lr_t = a.st->lr_t; }
@@ -263,7 +265,7 @@ __global__ __launch_bounds__(kBlock) void sparse_apply_long_k(ApplyArgs a, Hp h,
       float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
       float gl = 0.f;
       float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (a.table && lane_on) w = ld4(a.table + r * a.ts + 4 * l);
+      if (a.table && lane_on && (!STORE || fg.dlf)) w = ld4(a.table + r * a.ts + 4 * l);
       seg_accumulate<FUSED>(a, fg, k0, k1, l, lane_on, w, g, gl);
       part[t] = g;
       if (l == 0) part_l[grp] = gl;
@@ -1130,7 +1132,7 @@ int32_t mi_entry_grads_segsum(const float* rows, const int32_t* seg_start, const
   const FusedGrad fg{d_concat, ld_dconcat, sumv, d_logit_fm, d_logit_lin, F, b0};
   ApplyArgs a{};
   a.table = out_rows ? const_cast<float*>(rows) : nullptr;     // read only: w of d fm / d v = sumv - w
-  if (out_rows && !rows) a.table = out_rows;                    // (no FM term: w is never read; any valid pointer turns the row part on)
+  if (out_rows && !rows) a.table = out_rows;                    // (no FM term: w is never loaded; any non-null pointer turns the row part on)
   a.lin_w = out_lin;                                            // (non-null turns the linear part on; never read)
   a.seg_start = seg_start; a.sorted_entry = sorted_entry;
   // request u is written at row u - out_row0 of the out buffers (the kernels index by u: the bases are moved back; only
