@@ -1056,7 +1056,8 @@ int32_t mi_predict_group(const mi_serve_group_plan_t* plan, int32_t n_members, c
  * and every group of examples, the (positive, negative) pairs whose positive scores higher and those that tie:
  *   AUC = (2 gt + eq) / (2 P N-), formed on the host.  Integers only; exact; independent of order, grid and timing.
  * The count is O(P N-) per member on purpose: the entries are meant for the held-out sets of sweeps (20,000 examples are 1e8
- * pairs a member); the large-batch path keeps the bucketed metric.
+ * pairs a member); an evaluation of any size, the large-batch path's among them, gets the same integers from
+ * mi_auc_sorted_counts below, which sorts instead.
  *
  * Key of a logit: the 32-bit monotone image of the fp32 that mi_pair_topk's order uses (csrc/score_key.h): NaN is below
  * every number and equal to every other NaN, -0 equals +0.
@@ -1096,6 +1097,35 @@ int32_t mi_auc_plan(const int64_t* seg_off, const int64_t* seg_neg, int32_t n_se
                     size_t device_table_bytes, mi_auc_plan_t* plan, mi_stream_t stream);
 int32_t mi_auc_pair_counts(const mi_auc_plan_t* plan, const float* logits, int64_t member_stride, int32_t n_members,
                            const int32_t* order, int64_t* counts, mi_stream_t stream);
+
+/* ---- the same counts at any evaluation size: sort the examples, count the tie runs (csrc/auc_sort.hip) -------------------
+ * mi_auc_sorted_counts gives exactly mi_auc_pair_counts' integers in O(N log N) per member, from labels and groups that lie
+ * on the device in the examples' own order: no `order`, no plan, no host layout — what an evaluation loop that meets its
+ * data batch by batch can provide.
+ *   logits: member m's logit of example i at logits[m * member_stride + i] (member_stride >= N);
+ *   labels [N] uint8 (device): positive when non-zero;
+ *   groups [N] int32 (device), or NULL with n_groups = 1 (the global AUC): example i's group in [0, n_groups).  An example
+ *     whose group lies outside that range is IGNORED (the kernels check: it never causes a write outside counts);
+ *   counts [M, S, 2] int64 (S = n_groups), ZEROED BY THE CALLER: [m, s, 0] += the (positive, negative) pairs of group s
+ *     with key_pos > key_neg, [m, s, 1] += those with equal keys — the key of csrc/score_key.h, as above (64-bit integer
+ *     atomic adds, summed inside a workgroup first: one add per counter, tile of 4,096 sorted examples and group in it;
+ *     a second call into the same buffer adds the same numbers again);
+ *   workspace: mi_auc_sorted_workspace_bytes(N, n_groups) bytes of device memory, 16-byte aligned (0 for arguments the
+ *     entry refuses: N < 1, N >= 2^31, n_groups < 1).  The members are taken one after another on the stream inside the
+ *     call and reuse it in stream order.
+ * Per member: every example becomes one 64-bit word group : key : label; a stable LSD radix sort of the words over the
+ * 33 + ceil(log2 S) bits in use (digits of at most 9 bits: 4 passes for the global AUC; three short launches per pass);
+ * then for every tie run r of a group (equal group and key) with P_r positives and N_r negatives, gt += P_r x (the
+ * group's negatives in earlier runs), eq += P_r x N_r, by head flags and segmented scans (three launches).
+ * Two calls on equal input give equal bits, whatever the tile count.  No workgroup reads what another writes inside a
+ * launch and none waits for another; no library but HIP.
+ * Refused on the host before anything is launched, writing nothing — MI_ERR_INVALID: NULL logits / labels / counts /
+ * workspace, N < 1 or N >= 2^31, n_groups < 1, groups == NULL with n_groups != 1, n_members outside
+ * [1, MI_AUC_MAX_MEMBERS], member_stride < N, a workspace that is not 16-byte aligned; MI_ERR_WORKSPACE: a short workspace. */
+size_t mi_auc_sorted_workspace_bytes(int64_t N, int32_t n_groups);
+int32_t mi_auc_sorted_counts(const float* logits, int64_t member_stride, int32_t n_members, const uint8_t* labels,
+                             const int32_t* groups, int32_t n_groups, int64_t N, int64_t* counts, void* workspace,
+                             size_t workspace_bytes, mi_stream_t stream);
 
 #ifdef __cplusplus
 }

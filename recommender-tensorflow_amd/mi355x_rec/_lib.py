@@ -229,6 +229,8 @@ SIGNATURES = {
     "mi_auc_plan_bytes": (_sz, [_p, _p, _i32, _i32]),
     "mi_auc_plan": (_i32, [_p, _p, _i32, _i32, _p, _sz, _p, _p]),
     "mi_auc_pair_counts": (_i32, [_p, _p, _i64, _i32, _p, _p, _p]),
+    "mi_auc_sorted_workspace_bytes": (_sz, [_i64, _i32]),
+    "mi_auc_sorted_counts": (_i32, [_p, _i64, _i32, _p, _p, _i32, _i64, _p, _p, _sz, _p]),
 }
 
 _lib = None

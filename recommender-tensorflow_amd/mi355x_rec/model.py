@@ -206,14 +206,32 @@ def run_batch(features, labels, mode, params, make_engine):
         if store["counters"] is None:
             store["counters"] = _EvalCounters(dev)
         ctr = store["counters"]
-        if store.pop("metrics_reset", False):
+        fresh = store.pop("metrics_reset", False)
+        if fresh:
             ctr.reset()
         eng.k.mi_eval_accumulate(logits, y, ids.shape[0], ctr.hist, ctr.counts, ctr.sums)
         ctr.batch_losses.append(loss.clone())
+        # params["exact_auc"] / params["gauc_by"] (a raw feature key, the per-group AUC's groups; implies exact_auc): the
+        # evaluation's logits are also kept and, in result(), sorted and counted — auc_exact, auc_exact_pairs, gauc,
+        # gauc_groups beside the bucketed "auc".  On N ranks every rank evaluates the same batches: no collective.
+        gauc_by = params.get("gauc_by")
+        exact = None
+        if params.get("exact_auc") or gauc_by:
+            exact = store.get("exact_auc")
+            if exact is None:
+                from .exact_auc import StreamingExactAuc
+                exact = store["exact_auc"] = StreamingExactAuc(dev, eng.k)
+            if fresh:
+                exact.reset()
+            if gauc_by and gauc_by not in features:
+                raise ValueError("gauc_by=%r: the batch has no such feature (it has %s)" % (gauc_by, ", ".join(sorted(features))))
+            exact.add(logits, y, np.asarray(features[gauc_by]).reshape(-1) if gauc_by else None)
 
         def result():
             out = metrics_from_counters(ctr.hist.cpu().numpy(), ctr.counts.cpu().numpy(), ctr.sums.cpu().numpy())
             out["loss"] = float(torch.stack(ctr.batch_losses).mean())     # tf.metrics.mean over batch losses
+            if exact is not None:
+                out.update(exact.metrics())
             return out
         store["metrics_result"] = result
         return EstimatorSpec(mode, predictions=binary_predictions(logits, eng.k), loss=loss, eval_metric_ops=result)

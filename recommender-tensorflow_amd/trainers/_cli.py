@@ -39,6 +39,13 @@ _COMMON = [
                             "for bit, ~8 %% slower at large vocabularies (default: %(default)s — the mode bench.py's headline is timed in)")),
     ("--synthetic", dict(type=int, default=None, metavar="N", help="train on N generated MovieLens-shaped examples (and evaluate on "
                                                                    "N/10) instead of --train-csv / --test-csv")),
+    ("--exact-auc", dict(action="store_true", help="every evaluation also sorts its logits on the device and counts the exact AUC — "
+                                                   "the fraction of (positive, negative) pairs ranked the right way, ties half: "
+                                                   "metrics gain auc_exact and auc_exact_pairs beside the 200-bucket auc (default: off)")),
+    ("--gauc-by", dict(default=None, metavar="COLUMN", help="also the per-group AUC over the groups this column of the test data names by "
+                                                            "its raw values (user_id is the usual choice): metrics gain gauc, the groups' "
+                                                            "AUCs weighted by their examples, and gauc_groups; implies --exact-auc "
+                                                            "(default: off)")),
 ]
 _OPTIONAL = {
     "hidden_units": ("--hidden-units", dict(type=int, nargs="+", default=[16, 16],
@@ -116,6 +123,15 @@ def run(args, make_estimator):
     estimator.params["hip_graph"] = getattr(args, "hip_graph", "auto")
     estimator.params["catchup"] = getattr(args, "catchup", "bounded")
     estimator.params["fused_step"] = getattr(args, "fused_step", "off")
+    gauc_by = getattr(args, "gauc_by", None)
+    if getattr(args, "exact_auc", False) or gauc_by:
+        estimator.params["exact_auc"] = True
+    if gauc_by:
+        estimator.params["gauc_by"] = gauc_by          # (implies exact_auc, as in trainers.sweep)
+        for features, _ in get_input_fn(args.test_csv, ModeKeys.EVAL, batch_size=args.batch_size)():
+            if gauc_by not in features:                # refused before the training, not at its first evaluation
+                raise SystemExit("--gauc-by %s: the test file has no such column (it has %s)" % (gauc_by, ", ".join(sorted(features))))
+            break
     train_spec = get_train_spec(get_input_fn(args.train_csv, batch_size=args.batch_size, seed=rank if world > 1 else None),
                                 args.train_steps)
     eval_spec = get_eval_spec(get_input_fn(args.test_csv, ModeKeys.EVAL, batch_size=args.batch_size),

@@ -5,7 +5,9 @@ the same defaults (:13-26) and raises the same two ValueErrors (:31-34); instead
 graph it binds (once) an ``mi355x_rec.engine.DeepFM`` — linear + FM + DNN logits summed, sigmoid
 cross-entropy head with the mean reduction of tf.contrib's binary_classification_head — and runs
 the batch on it.  Divergence kept on purpose: ``--exclude-linear/-mf/-dnn``
-work here, whereas trailing commas at :135-137 make them no-ops in the reference."""
+work here, whereas trailing commas at :135-137 make them no-ops in the reference.  Beyond the
+reference, like every trainer of ``_cli``: ``--exact-auc`` / ``--gauc-by COLUMN`` add the exact AUC
+and the per-group AUC of every evaluation (params ``exact_auc`` / ``gauc_by``) beside ``auc``."""
 from mi355x_rec.engine import DeepFM
 from mi355x_rec.estimator import Estimator
 from mi355x_rec.model import run_batch

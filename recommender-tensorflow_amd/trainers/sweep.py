@@ -30,6 +30,8 @@ the logits it has anyway (mi355x_rec.exact_auc.ExactAuc: one more launch for all
 "auc_exact" — free of the 200-bucket "auc"'s dependence on the scale of the logits, which between the members of a grid
 over learning rates is a bias.  --gauc-by COLUMN (user_id is the usual choice) adds "gauc", the mean of every group's own
 AUC weighted by the group's examples, and "gauc_groups".  --select takes auc_exact and gauc with the matching flag.
+--auc-method sorted counts the same integers by sorting every member's logits on the device (mi_auc_sorted_counts) instead
+of comparing every pair: the way for test sets of millions of examples.
 
 trainers.deep_fm has no learning-rate flag (the reference has none): a member restored through ``trainers.deep_fm
 --restore`` continues at that CLI's 0.001, a member restored through ``trainers.sweep --restore`` at its own rate."""
@@ -119,6 +121,10 @@ def make_parser():
                    help="also the per-group AUC over the groups this column of the test file names by its raw values (user_id "
                         "is the usual choice): metrics gain gauc, the groups' AUCs weighted by their examples, and gauc_groups; "
                         "implies --exact-auc (default: off)")
+    p.add_argument("--auc-method", default="pairs", choices=["pairs", "sorted"],
+                   help="how --exact-auc / --gauc-by count (the same integers): pairs compares every (positive, negative) pair of "
+                        "a test set laid out once, sorted sorts every member's logits on the device — the way for test sets of "
+                        "millions (default: %(default)s)")
     return p
 
 
@@ -232,9 +238,9 @@ class PopulationEval:
     """The held-out set on the device and the members' curves on it: every run() is one FusedPopulation.evaluate (one launch
     for all members), one line of <job-dir>/sweep_eval.jsonl and one log line."""
 
-    def __init__(self, test_csv, batch_size, select, job_dir, every=0, exact_auc=False, gauc_by=None):
+    def __init__(self, test_csv, batch_size, select, job_dir, every=0, exact_auc=False, gauc_by=None, auc_method="pairs"):
         self.test_csv, self.batch_size, self.select, self.job_dir, self.every = test_csv, batch_size, select, job_dir, int(every)
-        self.exact_auc, self.gauc_by = bool(exact_auc or gauc_by), gauc_by
+        self.exact_auc, self.gauc_by, self.auc_method = bool(exact_auc or gauc_by), gauc_by, auc_method
         self.exact = None          # the test set's ExactAuc (--exact-auc / --gauc-by), made with the data
         self.path = os.path.join(job_dir, "sweep_eval.jsonl")
         self.data = None
@@ -257,7 +263,8 @@ class PopulationEval:
         if not ids:
             raise ValueError("no evaluation data in %s" % self.test_csv)
         if self.exact_auc:
-            self.exact = ExactAuc(np.concatenate(ys), np.concatenate(groups) if self.gauc_by else None, device=dev)
+            self.exact = ExactAuc(np.concatenate(ys), np.concatenate(groups) if self.gauc_by else None, device=dev,
+                                  method=self.auc_method)
         self.data = (torch.from_numpy(np.ascontiguousarray(np.concatenate(ids))).to(dev),
                      torch.from_numpy(np.ascontiguousarray(np.concatenate(ys))).to(dev))
 
@@ -373,7 +380,7 @@ def train_and_evaluate(args):
     if eval_every or final_eval == "fused" or exact_auc:
         # (the curves are made of evaluation metrics: with a ranking --select their best point is taken by auc)
         evaluator = PopulationEval(args.test_csv, args.batch_size, "auc" if is_ranking(args.select) else args.select, args.job_dir,
-                                   eval_every, exact_auc, gauc_by)
+                                   eval_every, exact_auc, gauc_by, getattr(args, "auc_method", "pairs"))
     pop = train(members, get_input_fn(args.train_csv, batch_size=args.batch_size), args.train_steps, config, args.job_dir,
                 args.batch_size, evaluator)
     if pop is None:
