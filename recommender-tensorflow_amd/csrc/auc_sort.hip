@@ -8,11 +8,13 @@
 // example whose group lies outside [0, S) becomes (group 0, kNoKey, label 1): no score has that key, so it is a run of its
 // own at the end of group 0, and the count takes it for neither class — nothing downstream ever sees a group >= S.
 //
-// Per member, per pass of the stable LSD radix sort (digits of up to 9 bits over the 33 + ceil(log2 S) bits in use; the
-// int32-keyed model is sort.hip's hist_k / bin_scan_k / scatter_k):
+// This file owns the word format, the sort's three kernels and entry, and the count.  The histogram, the scans, the ballot
+// ranks and the running slots of the sort are radix.h's, shared with sort.hip's int32 sorts.
+//
+// Per member, per pass of the stable LSD radix sort (digits of up to 9 bits over the 33 + ceil(log2 S) bits in use):
 //   word_hist_k     per-tile digit histogram (LDS atomics) -> hist[digit][tile]; pass 0 makes the words on the way
 //   digit_scan_k    one workgroup per digit: exclusive scan of its row over the tiles, the row's sum -> bin_total[digit]
-//   word_scatter_k  a tile adds up the lower digits' totals itself (512 ints), then the stable scatter of scatter_k
+//   word_scatter_k  a tile adds up the lower digits' totals itself (512 ints), then the stable scatter by ballot ranks
 // No global atomic, so nothing to zero.  Then the count, by head flags and segmented scans (DESIGN.md §19 says why not
 // by binary search): with neg(i) = 1 for a negative,
 //   eq(i) = the negatives of i's run before i, gt(i) = the negatives of i's group before i, minus eq(i)
@@ -24,16 +26,23 @@
 //                       by the thread that holds the group's last example of the tile.  S = 1: two atomics per tile.
 // No workgroup waits for another, and none reads what another writes inside a launch.  Integer adds commute: the counts
 // do not depend on the digit width, the tile count or timing.
-#include "common.h"
+#include "radix.h"
 #include "score_key.h"
 
 namespace {
 
+// The tile of this file: the count's kernels hold 16 words per thread, and the workspace and every launch are sized by it.
+// The sort's tiles are the same ones (one ntiles for both), so it has to be radix.h's.
 constexpr int kBlock = 256;
 constexpr int kItems = 16;                 // words per thread per tile
 constexpr int kTile = kBlock * kItems;     // 4096
-constexpr int kMaxBits = 9;
-constexpr int kMaxBins = 1 << kMaxBits;    // 512
+static_assert(kBlock == radix::kBlock && kItems == radix::kItems && kTile == radix::kTile, "the sort and the count share tiles");
+
+// what the sort takes from radix.h
+using radix::kWaves; using radix::kMaxBits; using radix::kMaxBins; using radix::digit_of; using radix::tile_digit_hist;
+using radix::block_excl_scan_chunked; using radix::digit_excl_scan; using radix::wave_first_slots; using radix::ranked_scatter;
+using radix::align_up; using radix::Digits; using radix::plan_digits; using radix::bits_for;
+
 constexpr uint32_t kNoKey = 0xffffffffu;   // the image of no score (score_key.h)
 
 // the examples as the caller holds them: one member's logits, the labels, the groups (NULL: all in group 0)
@@ -49,147 +58,58 @@ __device__ __forceinline__ uint64_t make_word(const Source& s, int64_t i) {
   if (static_cast<uint32_t>(g) >= static_cast<uint32_t>(s.S)) return (static_cast<uint64_t>(kNoKey) << 1) | 1u;
   return (static_cast<uint64_t>(g) << 33) | (static_cast<uint64_t>(mi_score_key32(s.z[i])) << 1) | (s.y[i] ? 1u : 0u);
 }
+// the key source of a tile (radix.h): pass 0 makes the words from the examples (RAW), the later passes read them
 template <bool RAW>
-__device__ __forceinline__ uint64_t load_word(const uint64_t* __restrict__ words, const Source& s, int64_t i) {
-  return RAW ? make_word(s, i) : words[i];
-}
+struct WordKeys {
+  const uint64_t* __restrict__ words;
+  Source src;
+  __device__ __forceinline__ uint64_t at(int64_t i) const { return RAW ? make_word(src, i) : words[i]; }
+};
 
 // ---- the sort ------------------------------------------------------------------------------------------------------------
+// (no totals by atomics here: digit_scan_k has every row's sum anyway)
 template <bool RAW>
 __global__ __launch_bounds__(kBlock) void word_hist_k(const uint64_t* __restrict__ words, Source src, int64_t n, int shift, int nbins,
                                                       int ntiles, int32_t* __restrict__ hist) {
-  __shared__ unsigned int h[kMaxBins];
-  for (int b = threadIdx.x; b < nbins; b += kBlock) h[b] = 0;
-  __syncthreads();
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile;
-  const unsigned int mask = nbins - 1;
-#pragma unroll
-  for (int r = 0; r < kItems; ++r) {
-    const int64_t i = base + r * kBlock + threadIdx.x;
-    if (i < n) atomicAdd(&h[static_cast<unsigned int>(load_word<RAW>(words, src, i) >> shift) & mask], 1u);
-  }
-  __syncthreads();
-  for (int b = threadIdx.x; b < nbins; b += kBlock) hist[static_cast<int64_t>(b) * ntiles + blockIdx.x] = static_cast<int32_t>(h[b]);
-}
-
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int u = __shfl_up(v, off, 64);
-    if (lane >= off) v += u;
-  }
-  return v;
+  tile_digit_hist(WordKeys<RAW>{words, src}, n, shift, nbins, ntiles, hist, nullptr);
 }
 
 // block b: hist[b, 0..ntiles) -> its exclusive scan (a tile's offset inside digit b), the row's sum -> bin_total[b]
 __global__ __launch_bounds__(kBlock) void digit_scan_k(int32_t* __restrict__ hist, int ntiles, int32_t* __restrict__ bin_total) {
-  __shared__ int32_t wsum[4];
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   int32_t* row = hist + static_cast<int64_t>(blockIdx.x) * ntiles;
-  int carry = 0;
-  for (int c0 = 0; c0 < ntiles; c0 += kBlock) {
-    const int i = c0 + t;
-    const int v = (i < ntiles) ? row[i] : 0;
-    const int incl = wave_incl_scan(v, lane);
-    __syncthreads();                     // previous chunk's wsum fully consumed
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int pre = carry;
-    for (int ww = 0; ww < w; ++ww) pre += wsum[ww];
-    if (i < ntiles) row[i] = pre + incl - v;
-    carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  }
-  if (t == 0) bin_total[blockIdx.x] = carry;
+  const int total = block_excl_scan_chunked<kBlock>(ntiles, 0, [&](int i) { return row[i]; }, [&](int i, int excl, int) { row[i] = excl; });
+  if (threadIdx.x == 0) bin_total[blockIdx.x] = total;
 }
 
-// scatter_k of sort.hip for 64-bit words without values: wave w owns words [w * 1024, (w + 1) * 1024) of the tile (round r:
-// 64 consecutive words); the waves count their digits, every wave derives its own running slots — the digit's base (the sum
-// of the lower digits' totals, scanned here) + the tile's offset inside the digit + the counts of the waves before it — and
-// scatters its 16 rounds alone, lanes finding their equal-digit peers with ballots.
+// The stable scatter of a tile of words (no values): the waves count their digits, every wave derives its own running
+// slots — the digit's base (the sum of the lower digits' totals, scanned here) + the tile's offset inside the digit + the
+// counts of the waves before it — and scatters its 16 rounds alone, lanes finding their equal-digit peers with ballots.
 template <bool RAW>
 __global__ __launch_bounds__(kBlock) void word_scatter_k(const uint64_t* __restrict__ words, Source src, int64_t n, int shift, int nbits,
                                                          int ntiles, const int32_t* __restrict__ offs,
                                                          const int32_t* __restrict__ bin_total, uint64_t* __restrict__ out) {
-  __shared__ int32_t running[4][kMaxBins];    // per wave: digit counts, then the next output slot of each digit
-  __shared__ int32_t dbase[kMaxBins];         // first slot of a digit in the whole array
-  __shared__ int32_t wsum[4];
+  __shared__ int32_t running[kWaves][kMaxBins];    // per wave: digit counts, then the next output slot of each digit
+  __shared__ int32_t dbase[kMaxBins];              // first slot of a digit in the whole array
+  __shared__ int32_t wsum[kWaves];
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const int nbins = 1 << nbits;
-  for (int b = t; b < 4 * kMaxBins; b += kBlock) (&running[0][0])[b] = 0;
+  for (int b = t; b < kWaves * kMaxBins; b += kBlock) (&running[0][0])[b] = 0;
   __syncthreads();
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile + w * (64 * kItems);
+  const WordKeys<RAW> keys{words, src};
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile + w * (64 * kItems) + lane;
   uint64_t key[kItems];
 #pragma unroll
   for (int r = 0; r < kItems; ++r) {
-    const int64_t i = base + r * 64 + lane;
+    const int64_t i = base + r * 64;
     const bool valid = i < n;
-    key[r] = valid ? load_word<RAW>(words, src, i) : 0;
-    if (valid) atomicAdd(&running[w][static_cast<unsigned int>(key[r] >> shift) & (nbins - 1)], 1);
+    key[r] = valid ? keys.at(i) : 0;
+    if (valid) atomicAdd(&running[w][digit_of(key[r], shift, nbins - 1)], 1);
   }
-  // exclusive scan of the digits' totals: thread t owns `per` consecutive digits
-  const int per = nbins > kBlock ? nbins / kBlock : 1;
-  int32_t tot[kMaxBins / kBlock];
-  int own = 0;
-#pragma unroll
-  for (int j = 0; j < kMaxBins / kBlock; ++j) {
-    const int b = t * per + j;
-    tot[j] = (j < per && b < nbins) ? bin_total[b] : 0;
-    own += tot[j];
-  }
-  const int incl = wave_incl_scan(own, lane);
-  if (lane == 63) wsum[w] = incl;
+  digit_excl_scan<1>(
+      nbins, wsum, [&](int b, int (&c)[1]) { c[0] = bin_total[b]; }, [&](int b, int, const int (&pre)[1]) { dbase[b] = pre[0]; });
   __syncthreads();
-  int pre = incl - own;
-  for (int ww = 0; ww < w; ++ww) pre += wsum[ww];
-#pragma unroll
-  for (int j = 0; j < kMaxBins / kBlock; ++j) {
-    const int b = t * per + j;
-    if (j < per && b < nbins) dbase[b] = pre;
-    pre += tot[j];
-  }
-  __syncthreads();
-  // counts -> this wave's first slot per digit (each lane: digits lane, lane + 64, ...)
-  int32_t first[kMaxBins / 64];
-#pragma unroll
-  for (int q = 0; q < kMaxBins / 64; ++q) {
-    const int b = q * 64 + lane;
-    int32_t f = 0;
-    if (b < nbins) {
-      f = dbase[b] + offs[static_cast<int64_t>(b) * ntiles + blockIdx.x];
-      for (int ww = 0; ww < w; ++ww) f += running[ww][b];
-    }
-    first[q] = f;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < kMaxBins / 64; ++q)
-    if (q * 64 + lane < nbins) running[w][q * 64 + lane] = first[q];
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  // (a wave's private LDS words, read / written where other lanes of the SAME wave write / read them in between: wavefront-
-  // scope atomics on the LDS array itself, as in sort.hip)
-  __attribute__((address_space(3))) int32_t* run = (__attribute__((address_space(3))) int32_t*)(running[w]);
-#pragma unroll
-  for (int r = 0; r < kItems; ++r) {
-    const bool valid = base + r * 64 + lane < n;
-    const unsigned int d = static_cast<unsigned int>(key[r] >> shift) & (nbins - 1);
-    // peers = lanes of this wave holding a valid word with the same digit
-    unsigned long long peers = __ballot(valid);
-    for (int b = 0; b < nbits; ++b) {
-      const unsigned long long m = __ballot((d >> b) & 1u);
-      peers &= ((d >> b) & 1u) ? m : ~m;
-    }
-    const int rank = __popcll(peers & lt_mask);
-    int32_t dst = 0;
-    if (valid) dst = __hip_atomic_load(run + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) + rank;
-    __builtin_amdgcn_wave_barrier();            // every peer has read the slot before its leader moves it
-    if (valid) {
-      if (rank == 0) __hip_atomic_store(run + d, dst + __popcll(peers), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-      out[dst] = key[r];
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
+  wave_first_slots(running, running, nbins, [&](int b) { return dbase[b] + offs[static_cast<int64_t>(b) * ntiles + blockIdx.x]; });
+  ranked_scatter<true>(key, shift, nbits, running[w], base, n, [&](int32_t dst, int r) { out[dst] = key[r]; });
 }
 
 // ---- the count -----------------------------------------------------------------------------------------------------------
@@ -342,8 +262,6 @@ __global__ __launch_bounds__(kBlock) void tile_carry_k(const int4* __restrict__ 
   }
 }
 
-int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-
 struct Layout {
   int64_t ntiles, wordsA, wordsB, hist, bin_total, summary, carry, bytes;
 };
@@ -398,13 +316,8 @@ int32_t mi_auc_sorted_counts(const float* logits, int64_t member_stride, int32_t
   const int ntiles = static_cast<int>(L.ntiles);
 
   // the bits in use: label, key, and the group's ceil(log2 S); digits of equal width, at most 9 bits (S = 1: 4 passes of 9)
-  int bits = 33;
-  while (bits < 64 && (static_cast<int64_t>(1) << (bits - 33)) < n_groups) ++bits;
-  int max_bits = mi::env_int("MI_AUC_SORT_BITS", kMaxBits);
-  max_bits = max_bits < 1 ? 1 : (max_bits > kMaxBits ? kMaxBits : max_bits);
-  const int passes = (bits + max_bits - 1) / max_bits;
-  const int nbits = (bits + passes - 1) / passes;
-  const int nbins = 1 << nbits;
+  const Digits D = plan_digits(33 + bits_for(n_groups, 31), mi::env_int("MI_AUC_SORT_BITS", kMaxBits));
+  const int passes = D.passes, nbits = D.nbits, nbins = 1 << nbits;
 
   for (int32_t m = 0; m < n_members; ++m) {
     const Source src{logits + static_cast<int64_t>(m) * member_stride, labels, groups, n_groups};

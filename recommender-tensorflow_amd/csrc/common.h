@@ -28,7 +28,8 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Tuning switches (MI_PL_TILE, MI_WGRAD_PL, MI_WGRAD_MIN_KSTEPS, MI_CATCHUP_BLOCKS, MI_SORT_FUSED, MI_SORT_BITS, MI_SORT_NAP, MI_AUC_SORT_BITS): read from the
+// Tuning switches (MI_PL_TILE, MI_WGRAD_PL, MI_WGRAD_MIN_KSTEPS, MI_CATCHUP_BLOCKS, MI_SORT_FUSED, MI_SORT_BITS = the digit
+// width of the fused per-field sort, 1..9, built-in 7; MI_SORT_NAP, MI_AUC_SORT_BITS = 1..9, built-in 9): read from the
 // environment ONLY in the tools' build of the library (`make tuning` -> tools/probe/libmi355x_rec_tuning.so, -DMI_TUNING; the
 // tools/*_bench.py scripts load that file).  The shipped libmi355x_rec.so has no environment switch: env_int is the
 // built-in value.  Every switch tunes or chooses between shipped paths: a variant that lost its A/B is deleted, not kept

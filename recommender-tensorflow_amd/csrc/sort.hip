@@ -6,13 +6,17 @@
 // Integer work, bit exact: equal rows keep their entry order, so the later segment sum adds
 // duplicates in ascending example order like TF's CPU kernel.
 //
-// Digits of up to 9 bits (26 M rows = 25 bits -> 3 passes).  Per pass:
+// This file owns the int32 key + value sorts: their kernels (what a tile reads, where its offsets come from, where a ranked
+// key goes), their workspace and their entries.  How a tile counts its digits, scans, ranks its keys with ballots and
+// compacts the row heads is written once, in radix.h, for these and for auc_sort.hip's 64-bit words.
+//
+// mi_sort_unique_rows: digits of up to 9 bits (26 M rows = 25 bits -> 3 passes).  Per pass:
 //   hist_k      per-tile digit histogram (LDS atomics) + per-digit totals (global integer atomics)
 //   bin_scan_k  one workgroup per digit: base = sum of the lower digits' totals, then an
 //               exclusive scan of that digit's per-tile counts (wave shuffles, carried in chunks)
 //   scatter_k   stable scatter: lanes find their equal-digit peers in the wave with ballots; a wave owns
 //               a contiguous quarter of the tile and keeps its own running slot per digit in LDS
-// then head_count_k / compact_k mark the first entry of every distinct row (coalesced reads,
+// then head_count_k / scan_small_k / compact_k mark the first entry of every distinct row (coalesced reads,
 // ballot ranks) and emit uniq_rows / seg_start / sorted_entry.
 // mi_sort_unique_fields: the same result for ids [B][F] of F fields whose rows are disjoint ranges — every field's
 // B local ids sorted on their own (segments), 20 bits instead of 25 at config 3: 3 passes of 7 bits.  Two forms, same
@@ -23,18 +27,13 @@
 // derives its own offsets from the raw counts (no bin_scan_k), stages its pairs in LDS in digit order and writes
 // them out in runs, and the compaction adds up the head counts before it itself (no scan_small_k):
 // profiles/sort_beside_scatter.md.
-#include "common.h"
+#include "radix.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kItems = 16;                 // keys per thread per tile
-constexpr int kTile = kBlock * kItems;     // 4096
-constexpr int kMaxBits = 9;
-constexpr int kMaxBins = 1 << kMaxBits;    // 512
+using namespace radix;
+
 constexpr int kMaxPasses = 4;
-constexpr int kFusedMaxBits = 10;          // digit width limit of the fused per-field passes (pass_fused_k)
-constexpr int kFusedMaxBins = 1 << kFusedMaxBits;
 constexpr int kFusedMaxTps = 256;          // tiles per field up to which a field's tiles wait for each other inside one launch
 
 // (our own kernel instead of hipMemsetAsync: a plain kernel node when the step is captured into a hipGraph — a
@@ -53,27 +52,13 @@ inline void zero_i32(int32_t* p, int64_t n, hipStream_t st) {
 __global__ __launch_bounds__(kBlock) void hist_k(const int32_t* __restrict__ keys, int64_t n, int shift,
                                                  int nbins, int tps, int32_t* __restrict__ hist,
                                                  int32_t* __restrict__ bin_total) {
-  __shared__ unsigned int h[kMaxBins];
-  for (int b = threadIdx.x; b < nbins; b += kBlock) h[b] = 0;
-  __syncthreads();
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile;
-  const unsigned int mask = nbins - 1;
-#pragma unroll
-  for (int r = 0; r < kItems; ++r) {
-    const int64_t i = base + r * kBlock + threadIdx.x;
-    if (i < n) atomicAdd(&h[(static_cast<uint32_t>(keys[i]) >> shift) & mask], 1u);
-  }
-  __syncthreads();
-  const int seg = blockIdx.x / tps, tis = blockIdx.x - seg * tps;
-  for (int b = threadIdx.x; b < nbins; b += kBlock) {
-    const unsigned int c = h[b];
-    hist[(static_cast<int64_t>(seg) * nbins + b) * tps + tis] = static_cast<int32_t>(c);
-    if (c) atomicAdd(&bin_total[seg * nbins + b], static_cast<int32_t>(c));
-  }
+  tile_digit_hist(ArrayKeys{keys}, n, shift, nbins, tps, hist, bin_total);
 }
 
 // hist_k of the catch-up's staleness key, computed on the way (the key of mi_catchup_gap_keys: steps to replay,
-// clamped to 62; 63 for the slots past num_uniq) and kept for the scatter
+// clamped to 62; 63 for the slots past num_uniq) and kept for the scatter.  (Not tile_digit_hist: the 16 keys are two
+// dependent loads each, all issued before the first store, and the 64 bins are one per thread of a wave.  The kernel on the
+// shared body was neither built nor timed.)
 __global__ __launch_bounds__(kBlock) void gap_hist_k(const int32_t* __restrict__ uniq_rows, const int32_t* __restrict__ num_uniq,
                                                      const int32_t* __restrict__ last_step, int64_t n, int step_to, int st,
                                                      const mi_step_state_t* __restrict__ ss, int32_t* __restrict__ keys,
@@ -107,58 +92,22 @@ __global__ __launch_bounds__(kBlock) void gap_hist_k(const int32_t* __restrict__
   }
 }
 
-// a wave's private LDS word, read / written where other lanes of the SAME wave write / read it in between
-__device__ __forceinline__ int32_t lds_ld(int32_t* p) {
-  return __hip_atomic_load((__attribute__((address_space(3))) int32_t*)(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-__device__ __forceinline__ void lds_st(int32_t* p, int32_t v) {
-  __hip_atomic_store((__attribute__((address_space(3))) int32_t*)(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int u = __shfl_up(v, off, 64);
-    if (lane >= off) v += u;
-  }
-  return v;
-}
-
 // block (seg, b): hist[seg, b, 0..tps) -> global offsets (exclusive scan + base of digit b inside segment seg,
 // which starts at seg * seg_len)
 __global__ __launch_bounds__(kBlock) void bin_scan_k(int32_t* __restrict__ hist, int ntiles, int nbins,
                                                      const int32_t* __restrict__ bin_total, int64_t seg_len) {
-  __shared__ int32_t red[4];
-  __shared__ int32_t wsum[4];
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+  __shared__ int32_t red[kWaves];
   const int seg = blockIdx.x / nbins, b = blockIdx.x - seg * nbins;
   bin_total += seg * nbins;
   int part = 0;
-  for (int j = t; j < b; j += kBlock) part += bin_total[j];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
-  if (lane == 0) red[w] = part;
-  __syncthreads();
-  int carry = red[0] + red[1] + red[2] + red[3] + static_cast<int>(seg * seg_len);
+  for (int j = threadIdx.x; j < b; j += kBlock) part += bin_total[j];
+  const int base = block_sum(part, red) + static_cast<int>(seg * seg_len);
   int32_t* row = hist + (static_cast<int64_t>(seg) * nbins + b) * ntiles;
-  for (int c0 = 0; c0 < ntiles; c0 += kBlock) {
-    const int i = c0 + t;
-    const int v = (i < ntiles) ? row[i] : 0;
-    const int incl = wave_incl_scan(v, lane);
-    __syncthreads();                     // previous chunk's wsum fully consumed
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int pre = carry;
-    for (int ww = 0; ww < w; ++ww) pre += wsum[ww];
-    if (i < ntiles) row[i] = pre + incl - v;
-    carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  }
+  block_excl_scan_chunked<kBlock>(ntiles, base, [&](int i) { return row[i]; }, [&](int i, int excl, int) { row[i] = excl; });
 }
 
-// Wave w of a tile owns its keys [w * 1024, (w + 1) * 1024) (round r: 64 consecutive keys), so the tile order
-// is wave order, then round order, then lane order.  Two block barriers in total: the waves first count
-// their digits (private LDS histograms), every wave then derives its own running offsets
-// (tile offset of the digit + the counts of the waves before it) and scatters its 16 rounds alone.
+// Two block barriers in total: the waves first count their digits (private LDS histograms), every wave then derives its
+// own running offsets (tile offset of the digit + the counts of the waves before it) and scatters its 16 rounds alone.
 // (vals_in == NULL: the value of position i is i — or, with fm_B > 0, the entry b * fm_F + f of the field-major
 // position i = f * fm_B + b.)
 __global__ __launch_bounds__(kBlock) void scatter_k(const int32_t* __restrict__ keys_in,
@@ -167,89 +116,36 @@ __global__ __launch_bounds__(kBlock) void scatter_k(const int32_t* __restrict__ 
                                                     const int32_t* __restrict__ offs,
                                                     int32_t* __restrict__ keys_out,
                                                     int32_t* __restrict__ vals_out, int64_t fm_B = 0, int fm_F = 0) {
-  __shared__ int32_t running[4][kMaxBins];    // per wave: next output slot of each digit
+  __shared__ int32_t running[kWaves][kMaxBins];    // per wave: digit counts, then the next output slot of each digit
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const int nbins = 1 << nbits;
   const int seg = blockIdx.x / tps, tis = blockIdx.x - seg * tps;
-  for (int b = t; b < 4 * kMaxBins; b += kBlock) (&running[0][0])[b] = 0;
+  for (int b = t; b < kWaves * kMaxBins; b += kBlock) (&running[0][0])[b] = 0;
   __syncthreads();
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile + w * (64 * kItems);
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile + w * (64 * kItems) + lane;
   int32_t key[kItems], val[kItems];
 #pragma unroll
   for (int r = 0; r < kItems; ++r) {
-    const int64_t i = base + r * 64 + lane;
+    const int64_t i = base + r * 64;
     const bool valid = i < n;
     key[r] = valid ? keys_in[i] : 0;
     val[r] = valid ? (vals_in ? vals_in[i] : (fm_B ? static_cast<int32_t>((i % fm_B) * fm_F + i / fm_B) : static_cast<int32_t>(i))) : 0;
-    if (valid) atomicAdd(&running[w][(static_cast<uint32_t>(key[r]) >> shift) & (nbins - 1)], 1);
+    if (valid) atomicAdd(&running[w][digit_of(key[r], shift, nbins - 1)], 1);
   }
   __syncthreads();
-  // counts -> this wave's first slot per digit (each lane: digits lane, lane + 64, ...)
-  int32_t first[kMaxBins / 64];
-#pragma unroll
-  for (int q = 0; q < kMaxBins / 64; ++q) {
-    const int b = q * 64 + lane;
-    int32_t f = 0;
-    if (b < nbins) {
-      f = offs[(static_cast<int64_t>(seg) * nbins + b) * tps + tis];
-      for (int ww = 0; ww < w; ++ww) f += running[ww][b];
-    }
-    first[q] = f;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < kMaxBins / 64; ++q)
-    if (q * 64 + lane < nbins) running[w][q * 64 + lane] = first[q];
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  // (the running slots through wavefront-scope atomics on the LDS array itself: a volatile POINTER to it loses the address
-  // space and compiles to flat loads / stores with sc0 sc1)
-  int32_t* run = running[w];
-#pragma unroll
-  for (int r = 0; r < kItems; ++r) {
-    const bool valid = base + r * 64 + lane < n;
-    const unsigned int d = (static_cast<uint32_t>(key[r]) >> shift) & (nbins - 1);
-    // peers = lanes of this wave holding a valid key with the same digit
-    unsigned long long peers = __ballot(valid);
-    for (int b = 0; b < nbits; ++b) {
-      const unsigned long long m = __ballot((d >> b) & 1u);
-      peers &= ((d >> b) & 1u) ? m : ~m;
-    }
-    const int rank = __popcll(peers & lt_mask);
-    int32_t dst = 0;
-    if (valid) dst = lds_ld(run + d) + rank;
-    __builtin_amdgcn_wave_barrier();            // every peer has read the slot before its leader moves it
-    if (valid) {
-      if (rank == 0) lds_st(run + d, dst + __popcll(peers));
-      keys_out[dst] = key[r];
-      vals_out[dst] = val[r];
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
-// (seg_len > 0: positions that start a segment — a field — start a row whatever the keys say)
-__device__ __forceinline__ bool is_head(const int32_t* __restrict__ keys, int64_t i, int64_t seg_len) {
-  return i == 0 || keys[i] != keys[i - 1] || (seg_len > 0 && i % seg_len == 0);
+  wave_first_slots(running, running, nbins, [&](int b) { return offs[(static_cast<int64_t>(seg) * nbins + b) * tps + tis]; });
+  ranked_scatter<true>(key, shift, nbits, running[w], base, n, [&](int32_t dst, int r) {
+    keys_out[dst] = key[r];
+    vals_out[dst] = val[r];
+  });
 }
 
 // heads[tile] = number of positions in the tile that start a new row
 __global__ __launch_bounds__(kBlock) void head_count_k(const int32_t* __restrict__ keys, int64_t n,
                                                        int32_t* __restrict__ tile_heads, int64_t seg_len = 0) {
-  __shared__ int32_t red[4];
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile;
-  int c = 0;
-#pragma unroll
-  for (int r = 0; r < kItems; ++r) {
-    const int64_t i = base + r * kBlock + threadIdx.x;
-    if (i < n && is_head(keys, i, seg_len)) ++c;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) tile_heads[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  __shared__ int32_t red[kWaves];
+  const int c = count_heads(keys, n, seg_len, red);
+  if (threadIdx.x == 0) tile_heads[blockIdx.x] = c;
 }
 
 // exclusive scan of `count` int32 values by ONE block (count = number of tiles: small).  256 threads, not 1,024: a
@@ -257,89 +153,37 @@ __global__ __launch_bounds__(kBlock) void head_count_k(const int32_t* __restrict
 // the resident catch-up workgroups it waited for that for 0.17 ms on average (0.5 ms at worst: rocprofv3 trace of the
 // row-sharded step, profiles/r05_sharded_one_rank.md) — for 5 us of work.
 constexpr int kScanSmallBlock = 256;
-__global__ __launch_bounds__(kScanSmallBlock) void scan_small_k(int32_t* __restrict__ data, int64_t count,
-                                                                int32_t* __restrict__ total_out) {
-  constexpr int NW = kScanSmallBlock / 64;
-  __shared__ int32_t wsum[NW];
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
-  int carry = 0;
-  for (int64_t c0 = 0; c0 < count; c0 += kScanSmallBlock) {
-    const int64_t i = c0 + t;
-    const int v = (i < count) ? data[i] : 0;
-    const int incl = wave_incl_scan(v, lane);
-    __syncthreads();
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int pre = carry, tot = 0;
-#pragma unroll
-    for (int ww = 0; ww < NW; ++ww) {
-      if (ww < w) pre += wsum[ww];
-      tot += wsum[ww];
-    }
-    if (i < count) data[i] = pre + incl - v;
-    carry += tot;
-  }
-  if (total_out && t == 0) total_out[0] = carry;
+__global__ __launch_bounds__(kScanSmallBlock) void scan_small_k(int32_t* __restrict__ data, int64_t count) {
+  block_excl_scan_chunked<kScanSmallBlock>(count, 0, [&](int64_t i) { return data[i]; }, [&](int64_t i, int excl, int) { data[i] = excl; });
 }
 
+// tile_base = the heads of the tiles before each (scan_small_k of head_count_k's counts)
 __global__ __launch_bounds__(kBlock) void compact_k(const int32_t* __restrict__ keys,
                                                     const int32_t* __restrict__ vals, int64_t n,
                                                     const int32_t* __restrict__ tile_base,
-                                                    const int32_t* __restrict__ total,
                                                     int32_t* __restrict__ sorted_entry,
                                                     int32_t* __restrict__ uniq_rows,
                                                     int32_t* __restrict__ seg_start,
                                                     int32_t* __restrict__ num_uniq, int64_t seg_len = 0,
                                                     const int64_t* __restrict__ field_off = nullptr,
                                                     int32_t* __restrict__ slot_of_entry = nullptr) {
-  __shared__ int32_t wc[4];
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile;
-  int run = tile_base[blockIdx.x];
-  for (int r = 0; r < kItems; ++r) {
-    const int64_t i = base + r * kBlock + t;
-    const bool valid = i < n;
-    int32_t key = 0;
-    bool head = false;
-    if (valid) {
-      key = keys[i];
-      head = is_head(keys, i, seg_len);
-      sorted_entry[i] = vals[i];
-    }
-    const unsigned long long hb = __ballot(head);
-    __syncthreads();                       // previous round's wc consumed
-    if (lane == 0) wc[w] = __popcll(hb);
-    __syncthreads();
-    int idx = run + __popcll(hb & lt_mask);
-    for (int ww = 0; ww < w; ++ww) idx += wc[ww];
-    if (head) {
-      uniq_rows[idx] = seg_len > 0 ? static_cast<int32_t>(field_off[i / seg_len] + key) : key;   // (local id -> global row)
-      seg_start[idx] = static_cast<int32_t>(i);
-    }
-    // (the segment a position belongs to: the heads up to and including its own, minus one — what mi_segment_slots finds by
-    // binary search, 112 us at 1.7 M entries, for the price of one scattered 4-byte store here)
-    if (slot_of_entry && valid) slot_of_entry[vals[i]] = head ? idx : idx - 1;
-    run += wc[0] + wc[1] + wc[2] + wc[3];
-  }
-  if (blockIdx.x == 0 && t == 0) {
-    const int32_t U = total[0];
-    num_uniq[0] = U;
-    seg_start[U] = static_cast<int32_t>(n);
-  }
+  compact_tile<true>(keys, vals, n, tile_base[blockIdx.x], sorted_entry, uniq_rows, seg_start, num_uniq, seg_len, field_off, slot_of_entry);
 }
 
 constexpr int kFieldsMax = 64;
 
 // ---- The short launches of mi_sort_unique_fields (beside the catch-up: no workgroup waits for another) ------------------
-// Between the passes a (key, value) is ONE 8-byte pair; pass 0 reads ids [B][F] itself (the key of field-major position
-// i = seg * B + b is ids[b * F + seg], its value the entry b * F + seg): no field-major copy of the ids is made.
+// Between the passes a (key, value) is ONE 8-byte pair; pass 0 reads ids [B][F] in place: the key of field-major position
+// i = seg * B + b is ids[b * F + seg], its value the entry b * F + seg, so no field-major copy of the ids is made.
 __device__ __forceinline__ int32_t fields_key(const int2* __restrict__ pairs_in, const int32_t* __restrict__ ids, int64_t i,
                                               int seg, int64_t B, int F) {
   return ids ? ids[(i - static_cast<int64_t>(seg) * B) * F + seg] : pairs_in[i].x;
 }
 
-// hist_k of a field's tile (B is a multiple of kTile: every position exists)
+// hist_k of a field's tile (B is a multiple of kTile: every position exists).  Written out, not on radix.h's
+// tile_digit_hist: on it, with a key source that took the segment, the kernel ran 7.70 to 7.74 us against 7.60 to 7.68
+// for this text (three earlier forms of the source: 7.72 to 7.88), above its own run-to-run range of 0.08 us
+// (profiles/sort_one_body.md).
 __global__ __launch_bounds__(kBlock) void hist_fields_k(const int2* __restrict__ pairs_in, const int32_t* __restrict__ ids, int64_t B,
                                                         int F, int shift, int nbins, int tps, int32_t* __restrict__ hist,
                                                         int32_t* __restrict__ bin_total) {
@@ -351,7 +195,7 @@ __global__ __launch_bounds__(kBlock) void hist_fields_k(const int2* __restrict__
   const unsigned int mask = nbins - 1;
 #pragma unroll
   for (int r = 0; r < kItems; ++r)
-    atomicAdd(&h[(static_cast<uint32_t>(fields_key(pairs_in, ids, base + r * kBlock + threadIdx.x, seg, B, F)) >> shift) & mask], 1u);
+    atomicAdd(&h[digit_of(fields_key(pairs_in, ids, base + r * kBlock + threadIdx.x, seg, B, F), shift, mask)], 1u);
   __syncthreads();
   for (int b = threadIdx.x; b < nbins; b += kBlock) {
     const unsigned int c = h[b];
@@ -381,15 +225,15 @@ __global__ __launch_bounds__(kBlock) void scatter_runs_k(const int2* __restrict_
                                                          int2* __restrict__ pairs_out, int32_t* __restrict__ keys_out,
                                                          int32_t* __restrict__ vals_out) {
   __shared__ int2 staged[kTile];
-  __shared__ int32_t running[4][kMaxBins];    // per wave: the next staged slot of each digit
+  __shared__ int32_t running[kWaves][kMaxBins];    // per wave: the next staged slot of each digit
   int32_t* before = reinterpret_cast<int32_t*>(staged);      // [nbins] counts of the field's earlier tiles
   int32_t* tstart = before + kMaxBins;                       // [nbins] tile-local start of a digit
   int32_t (*cnt)[kMaxBins] = reinterpret_cast<int32_t (*)[kMaxBins]>(tstart + kMaxBins);   // [4][nbins] per wave: digit counts
-  int32_t (*wsum)[4] = reinterpret_cast<int32_t (*)[4]>(cnt + 4);                          // [2][4] the waves' sums of the two scans
+  int32_t* wsum = &cnt[kWaves][0];                                                         // [2][4] the waves' sums of the two scans
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const int nbins = 1 << nbits;
   const int seg = blockIdx.x / tps, tis = blockIdx.x - seg * tps;
-  for (int b = t; b < 4 * kMaxBins; b += kBlock) (&cnt[0][0])[b] = 0;
+  for (int b = t; b < kWaves * kMaxBins; b += kBlock) (&cnt[0][0])[b] = 0;
   for (int b = t; b < nbins; b += kBlock) before[b] = 0;
   __syncthreads();
   const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile + w * (64 * kItems);
@@ -405,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void scatter_runs_k(const int2* __restrict_
       key[r] = kv.x;
       val[r] = kv.y;
     }
-    atomicAdd(&cnt[w][(static_cast<uint32_t>(key[r]) >> shift) & (nbins - 1)], 1);
+    atomicAdd(&cnt[w][digit_of(key[r], shift, nbins - 1)], 1);
   }
   const int32_t* fh = hist + static_cast<int64_t>(seg) * nbins * tps;      // the field's counts [digit][tile]
   if (self_offs)
@@ -414,68 +258,34 @@ __global__ __launch_bounds__(kBlock) void scatter_runs_k(const int2* __restrict_
       if (i - b * tps < tis) atomicAdd(&before[b], fh[i]);
     }
   __syncthreads();
-  // two exclusive scans over the digits, thread t owning `per` consecutive digits: the tile's own counts -> tile-local
-  // starts; the field's totals -> the digit's base in the field
-  const int per = nbins > kBlock ? nbins / kBlock : 1;
-  int32_t delta[kMaxBins / kBlock];
-  {
-    int32_t tc[kMaxBins / kBlock], tot[kMaxBins / kBlock];
-    int own_c = 0, own_t = 0;
-#pragma unroll
-    for (int j = 0; j < kMaxBins / kBlock; ++j) {
-      const int b = t * per + j;
-      tc[j] = tot[j] = 0;
-      if (j < per && b < nbins) {
-        tc[j] = cnt[0][b] + cnt[1][b] + cnt[2][b] + cnt[3][b];
-        if (self_offs) tot[j] = bin_total[seg * nbins + b];
-      }
-      own_c += tc[j];
-      own_t += tot[j];
-    }
-    const int incl_c = wave_incl_scan(own_c, lane), incl_t = wave_incl_scan(own_t, lane);
-    if (lane == 63) { wsum[0][w] = incl_c; wsum[1][w] = incl_t; }
-    __syncthreads();
-    int pre_c = incl_c - own_c, pre_t = incl_t - own_t + static_cast<int>(static_cast<int64_t>(seg) * B);
-    for (int ww = 0; ww < w; ++ww) { pre_c += wsum[0][ww]; pre_t += wsum[1][ww]; }
-#pragma unroll
-    for (int j = 0; j < kMaxBins / kBlock; ++j) {
-      const int b = t * per + j;
-      delta[j] = 0;
-      if (j < per && b < nbins) {
-        const int32_t gofs = self_offs ? pre_t + before[b] : fh[static_cast<int64_t>(b) * tps + tis];
-        delta[j] = gofs - pre_c;
-        tstart[b] = pre_c;
-        pre_c += tc[j];
-        pre_t += tot[j];
-      }
-    }
-  }
+  // two exclusive scans over the digits: the tile's own counts -> tile-local starts; the field's totals -> the digit's base
+  // in the field (which starts at seg * B)
+  const int per = digits_per_thread(nbins);
+  int32_t delta[kMaxBins / kBlock] = {};
+  digit_excl_scan<2>(
+      nbins, wsum,
+      [&](int b, int (&c)[2]) {
+        c[0] = cnt[0][b] + cnt[1][b] + cnt[2][b] + cnt[3][b];
+        if (self_offs) c[1] = bin_total[seg * nbins + b];
+      },
+      [&](int b, int j, const int (&pre)[2]) {
+        const int32_t gofs = self_offs ? pre[1] + static_cast<int>(static_cast<int64_t>(seg) * B) + before[b] : fh[static_cast<int64_t>(b) * tps + tis];
+        delta[j] = gofs - pre[0];
+        tstart[b] = pre[0];
+      });
   __syncthreads();
-  // counts -> this wave's first staged slot per digit (each lane: digits lane, lane + 64, ...)
+  // counts -> this wave's first staged slot per digit.  (radix.h's wave_first_slots written out as a loop: counts and slots
+  // are two arrays here, so nothing is held in registers across a barrier; with the shared body, unrolled over the 8 x 64
+  // digits, the kernel was 28 % longer and ran 21.75 us instead of 21.58 (pass 0: 24.27 instead of 24.07) in a kernel
+  // trace of tools/sort_bench.py fields, parent and change alternating three times, the parent's own range 0.08.)
   for (int b = lane; b < nbins; b += 64) {
     int32_t f = tstart[b];
     for (int ww = 0; ww < w; ++ww) f += cnt[ww][b];
     running[w][b] = f;
   }
   __syncthreads();                              // the scratch is read by everyone: the staging may overwrite it
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  int32_t* run = running[w];
-#pragma unroll
-  for (int r = 0; r < kItems; ++r) {
-    asm volatile("" : "+v"(key[r]));            // the digit is extracted again, not carried in 16 more registers from the count above
-    const unsigned int d = (static_cast<uint32_t>(key[r]) >> shift) & (nbins - 1);
-    unsigned long long peers = ~0ull;
-    for (int b = 0; b < nbits; ++b) {
-      const unsigned long long m = __ballot((d >> b) & 1u);
-      peers &= ((d >> b) & 1u) ? m : ~m;
-    }
-    const int rank = __popcll(peers & lt_mask);
-    const int32_t dst = lds_ld(run + d) + rank;
-    __builtin_amdgcn_wave_barrier();            // every peer has read the slot before its leader moves it
-    if (rank == 0) lds_st(run + d, dst + __popcll(peers));
-    staged[dst] = make_int2(key[r], IDS ? e0 + r * 64 * F : val[r]);
-    __builtin_amdgcn_wave_barrier();
-  }
+  ranked_scatter<false, true>(key, shift, nbits, running[w], 0, 0,
+                              [&](int32_t dst, int r) { staged[dst] = make_int2(key[r], IDS ? e0 + r * 64 * F : val[r]); });
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < kMaxBins / kBlock; ++j)
@@ -485,7 +295,7 @@ __global__ __launch_bounds__(kBlock) void scatter_runs_k(const int2* __restrict_
   for (int r = 0; r < kItems; ++r) {
     const int s = r * kBlock + t;
     const int2 kv = staged[s];
-    const int32_t dst = running[0][(static_cast<uint32_t>(kv.x) >> shift) & (nbins - 1)] + s;
+    const int32_t dst = running[0][digit_of(kv.x, shift, nbins - 1)] + s;
     if (keys_out) {
       keys_out[dst] = kv.x;
       vals_out[dst] = kv.y;
@@ -495,47 +305,18 @@ __global__ __launch_bounds__(kBlock) void scatter_runs_k(const int2* __restrict_
   }
 }
 
-// compact_k's tile_base / total without scan_small_k's launch: a tile adds up the head counts of the tiles before it
-// itself (up to kFoldHeadsMaxTiles ints, a quarter of the 64 KB it reads and writes anyway), the last tile writes num_uniq.
+// compact_k without scan_small_k's launch: a tile adds up the head counts of the tiles before it itself (up to
+// kFoldHeadsMaxTiles ints, a quarter of the 64 KB it reads and writes anyway).
 constexpr int kFoldHeadsMaxTiles = 4096;
 __global__ __launch_bounds__(kBlock) void compact_fields_k(const int32_t* __restrict__ keys, const int32_t* __restrict__ vals, int64_t n,
                                                            const int32_t* __restrict__ tile_heads, int32_t* __restrict__ sorted_entry,
                                                            int32_t* __restrict__ uniq_rows, int32_t* __restrict__ seg_start,
                                                            int32_t* __restrict__ num_uniq, int64_t seg_len,
                                                            const int64_t* __restrict__ field_off) {
-  __shared__ int32_t red[4];
-  __shared__ int32_t wc[4];
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile;
+  __shared__ int32_t red[kWaves];
   int part = 0;
-  for (int j = t; j < static_cast<int>(blockIdx.x); j += kBlock) part += tile_heads[j];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
-  if (lane == 0) red[w] = part;
-  __syncthreads();
-  int run = red[0] + red[1] + red[2] + red[3];
-  for (int r = 0; r < kItems; ++r) {
-    const int64_t i = base + r * kBlock + t;
-    const int32_t key = keys[i];
-    const bool head = is_head(keys, i, seg_len);
-    sorted_entry[i] = vals[i];
-    const unsigned long long hb = __ballot(head);
-    __syncthreads();                       // previous round's wc consumed
-    if (lane == 0) wc[w] = __popcll(hb);
-    __syncthreads();
-    if (head) {
-      int idx = run + __popcll(hb & lt_mask);
-      for (int ww = 0; ww < w; ++ww) idx += wc[ww];
-      uniq_rows[idx] = static_cast<int32_t>(field_off[i / seg_len] + key);   // (local id -> global row)
-      seg_start[idx] = static_cast<int32_t>(i);
-    }
-    run += wc[0] + wc[1] + wc[2] + wc[3];
-  }
-  if (blockIdx.x == gridDim.x - 1 && t == 0) {
-    num_uniq[0] = run;
-    seg_start[run] = static_cast<int32_t>(n);
-  }
+  for (int j = threadIdx.x; j < static_cast<int>(blockIdx.x); j += kBlock) part += tile_heads[j];
+  compact_tile<false>(keys, vals, n, block_sum(part, red), sorted_entry, uniq_rows, seg_start, num_uniq, seg_len, field_off, nullptr);
 }
 
 
@@ -552,20 +333,19 @@ __device__ __forceinline__ int32_t ld_agent(const int32_t* p) { return __hip_ato
 constexpr int kSpinMax = 1 << 22;          // x s_sleep 8 (~0.25 us): about a second
 
 // pass 0 reads ids [B][F] itself (key = the local id of (b, seg), value = the entry b * F + seg): no field-major copy
-template <int MAXBINS>
 __global__ __launch_bounds__(kBlock) void pass_fused_k(const int32_t* __restrict__ keys_in, const int32_t* __restrict__ vals_in,
                                                        const int32_t* __restrict__ ids, int64_t B, int F, int shift, int nbits,
                                                        int tps, int32_t* __restrict__ thist, int32_t* __restrict__ ready,
                                                        int32_t* __restrict__ err, int32_t* __restrict__ keys_out,
                                                        int32_t* __restrict__ vals_out, int nap) {
-  __shared__ int32_t running[4][MAXBINS];     // per wave: digit counts, then the next output slot of each digit
-  __shared__ int32_t offsT[MAXBINS];          // this tile's first slot per digit
-  __shared__ int32_t totS[MAXBINS];           // the field's total per digit
-  __shared__ int32_t wsum[4];
+  __shared__ int32_t running[kWaves][kMaxBins];    // per wave: digit counts, then the next output slot of each digit
+  __shared__ int32_t offsT[kMaxBins];              // this tile's first slot per digit
+  __shared__ int32_t totS[kMaxBins];               // the field's total per digit
+  __shared__ int32_t wsum[kWaves];
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const int nbins = 1 << nbits;
   const int seg = blockIdx.x / tps, tis = blockIdx.x - seg * tps;
-  for (int b = t; b < 4 * MAXBINS; b += kBlock) (&running[0][0])[b] = 0;
+  for (int b = t; b < kWaves * kMaxBins; b += kBlock) (&running[0][0])[b] = 0;
   __syncthreads();
   const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile + w * (64 * kItems);
   int32_t key[kItems], val[kItems];
@@ -580,7 +360,7 @@ __global__ __launch_bounds__(kBlock) void pass_fused_k(const int32_t* __restrict
       key[r] = keys_in[i];
       val[r] = vals_in[i];
     }
-    atomicAdd(&running[w][(static_cast<uint32_t>(key[r]) >> shift) & (nbins - 1)], 1);
+    atomicAdd(&running[w][digit_of(key[r], shift, nbins - 1)], 1);
   }
   __syncthreads();
   for (int b = t; b < nbins; b += kBlock)
@@ -618,61 +398,16 @@ __global__ __launch_bounds__(kBlock) void pass_fused_k(const int32_t* __restrict
     offsT[b] = before;
   }
   __syncthreads();
-  // exclusive scan of the totals over the digits: thread t owns `per` consecutive digits
-  {
-    const int per = nbins > kBlock ? nbins / kBlock : 1;
-    int own = 0;
-    if (t * per < nbins)
-      for (int j = 0; j < per; ++j) own += totS[t * per + j];
-    const int incl = wave_incl_scan(own, lane);
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int pre = incl - own + static_cast<int>(static_cast<int64_t>(seg) * B);
-    for (int ww = 0; ww < w; ++ww) pre += wsum[ww];
-    if (t * per < nbins)
-      for (int j = 0; j < per; ++j) {
-        const int b = t * per + j;
-        const int c = totS[b];
-        offsT[b] += pre;
-        pre += c;
-      }
-  }
+  // the digit's base in the field (which starts at seg * B): the exclusive scan of the totals over the digits
+  digit_excl_scan<1>(
+      nbins, wsum, [&](int b, int (&c)[1]) { c[0] = totS[b]; },
+      [&](int b, int, const int (&pre)[1]) { offsT[b] += pre[0] + static_cast<int>(static_cast<int64_t>(seg) * B); });
   __syncthreads();
-  int32_t first[MAXBINS / 64];
-#pragma unroll
-  for (int q = 0; q < MAXBINS / 64; ++q) {
-    const int b = q * 64 + lane;
-    int32_t f = 0;
-    if (b < nbins) {
-      f = offsT[b];
-      for (int ww = 0; ww < w; ++ww) f += running[ww][b];
-    }
-    first[q] = f;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < MAXBINS / 64; ++q)
-    if (q * 64 + lane < nbins) running[w][q * 64 + lane] = first[q];
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  int32_t* run = running[w];
-#pragma unroll
-  for (int r = 0; r < kItems; ++r) {
-    const unsigned int d = (static_cast<uint32_t>(key[r]) >> shift) & (nbins - 1);
-    unsigned long long peers = ~0ull;
-    for (int b = 0; b < nbits; ++b) {
-      const unsigned long long m = __ballot((d >> b) & 1u);
-      peers &= ((d >> b) & 1u) ? m : ~m;
-    }
-    const int rank = __popcll(peers & lt_mask);
-    const int32_t dst = lds_ld(run + d) + rank;
-    __builtin_amdgcn_wave_barrier();            // every peer has read the slot before its leader moves it
-    if (rank == 0) lds_st(run + d, dst + __popcll(peers));
+  wave_first_slots(running, running, nbins, [&](int b) { return offsT[b]; });
+  ranked_scatter<false>(key, shift, nbits, running[w], 0, 0, [&](int32_t dst, int r) {
     keys_out[dst] = key[r];
     vals_out[dst] = val[r];
-    __builtin_amdgcn_wave_barrier();
-  }
+  });
 }
 
 // head_count_k + scan_small_k + compact_k as one launch: a tile publishes its number of row heads (+ 1: 0 = not there yet)
@@ -682,25 +417,11 @@ __global__ __launch_bounds__(kBlock) void compact_fused_k(const int32_t* __restr
                                                           int32_t* __restrict__ sorted_entry, int32_t* __restrict__ uniq_rows,
                                                           int32_t* __restrict__ seg_start, int32_t* __restrict__ num_uniq,
                                                           int64_t seg_len, const int64_t* __restrict__ field_off) {
-  __shared__ int32_t red[4];
-  __shared__ int32_t wc[4];
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * kTile;
-  int c = 0;
-#pragma unroll
-  for (int r = 0; r < kItems; ++r) {
-    const int64_t i = base + r * kBlock + t;
-    if (i < n && is_head(keys, i, seg_len)) ++c;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-  if (lane == 0) red[w] = c;
-  __syncthreads();
-  const int mine = red[0] + red[1] + red[2] + red[3];
-  if (t == 0) st_agent(hcf + blockIdx.x, mine + 1);
+  __shared__ int32_t red[kWaves];
+  const int mine = count_heads(keys, n, seg_len, red);
+  if (threadIdx.x == 0) st_agent(hcf + blockIdx.x, mine + 1);
   int part = 0;
-  for (int j = t; j < static_cast<int>(blockIdx.x); j += kBlock) {
+  for (int j = threadIdx.x; j < static_cast<int>(blockIdx.x); j += kBlock) {
     int v, spins = 0;
     while ((v = ld_agent(hcf + j)) == 0) {
       __builtin_amdgcn_s_sleep(8);
@@ -708,44 +429,17 @@ __global__ __launch_bounds__(kBlock) void compact_fused_k(const int32_t* __restr
     }
     part += v - 1;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
   __syncthreads();                         // red[] read by everyone
-  if (lane == 0) red[w] = part;
-  __syncthreads();
-  int run = red[0] + red[1] + red[2] + red[3];
-  for (int r = 0; r < kItems; ++r) {
-    const int64_t i = base + r * kBlock + t;
-    const bool valid = i < n;
-    int32_t key = 0;
-    bool head = false;
-    if (valid) {
-      key = keys[i];
-      head = is_head(keys, i, seg_len);
-      sorted_entry[i] = vals[i];
-    }
-    const unsigned long long hb = __ballot(head);
-    __syncthreads();                       // previous round's wc consumed
-    if (lane == 0) wc[w] = __popcll(hb);
-    __syncthreads();
-    if (head) {
-      int idx = run + __popcll(hb & lt_mask);
-      for (int ww = 0; ww < w; ++ww) idx += wc[ww];
-      uniq_rows[idx] = seg_len > 0 ? static_cast<int32_t>(field_off[i / seg_len] + key) : key;   // (local id -> global row)
-      seg_start[idx] = static_cast<int32_t>(i);
-    }
-    run += wc[0] + wc[1] + wc[2] + wc[3];
-  }
-  if (blockIdx.x == gridDim.x - 1 && t == 0) {
-    num_uniq[0] = run;
-    seg_start[run] = static_cast<int32_t>(n);
-  }
+  compact_tile<true>(keys, vals, n, block_sum(part, red), sorted_entry, uniq_rows, seg_start, num_uniq, seg_len, field_off, nullptr);
 }
 
-int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-
+// The workspace: two key and two value buffers (the per-field short launches use each pair of them as one pair buffer),
+// hist, the tiles' head counts, bin_total per pass (and field), the fused passes' sync words.
+// kReservedBytes: unused.  The region held the rows sort's total, which the last tile of the compaction knows itself; it stays
+// so that mi_sort_unique_workspace_bytes and mi_sort_unique_fields_workspace_bytes return what callers already allocate.
+constexpr int64_t kReservedBytes = 256;
 struct Layout {
-  int64_t ntiles, keysA, keysB, valsA, valsB, hist, heads, bin_total, total, sync, sync_words, bytes;
+  int64_t ntiles, keysA, keysB, valsA, valsB, hist, heads, bin_total, sync, sync_words, bytes;
 };
 
 Layout layout_for(int64_t n, int nseg = 1) {
@@ -757,16 +451,33 @@ Layout layout_for(int64_t n, int nseg = 1) {
   L.keysB = o; o += nb;
   L.valsA = o; o += nb;
   L.valsB = o; o += nb;
-  L.hist = o; o += align_up(L.ntiles * (nseg > 1 ? kFusedMaxBins : kMaxBins) * 4, 256);
+  L.hist = o; o += align_up(L.ntiles * kMaxBins * 4, 256);
   L.heads = o; o += align_up(L.ntiles * 4, 256);
   L.bin_total = o; o += static_cast<int64_t>(kMaxPasses) * (nseg > 1 ? nseg : 1) * kMaxBins * 4;
-  L.total = o; o += 256;
+  o += kReservedBytes;
   // the fused passes' sync words (mi_sort_unique_fields): [pass][field] arrival counters, one published head count per
   // tile, one error word — zeroed by the entry's first launch
   L.sync_words = static_cast<int64_t>(kMaxPasses) * (nseg > 1 ? nseg : 1) + L.ntiles + 1;
   L.sync = o; o += align_up(L.sync_words * 4, 256);
   L.bytes = o;
   return L;
+}
+
+struct Buffers {
+  int32_t *kbuf[2], *vbuf[2], *hist, *heads, *bin_total, *sync;
+  int ntiles;
+};
+Buffers carve(void* workspace, const Layout& L) {
+  char* ws = static_cast<char*>(workspace);
+  auto at = [&](int64_t o) { return reinterpret_cast<int32_t*>(ws + o); };
+  return Buffers{{at(L.keysA), at(L.keysB)}, {at(L.valsA), at(L.valsB)}, at(L.hist), at(L.heads), at(L.bin_total), at(L.sync),
+                 static_cast<int>(L.ntiles)};
+}
+
+// the digits of an int32 key below `count`
+Digits plan_rows(int64_t count, int max_bits) {
+  const int bits = bits_for(count, 31);
+  return plan_digits(bits > 1 ? bits : 1, max_bits);
 }
 
 }  // namespace
@@ -782,7 +493,6 @@ __global__ __launch_bounds__(kBlock) void sort_small_k(const int32_t* __restrict
   // last.  (The first version ranked every key against every other: 87 us of the 280-us B = 32 step.)
   __shared__ unsigned long long a[kSmallN];
   __shared__ int32_t sk[kSmallN], head[kSmallN];
-  __shared__ int32_t wsum[4];
   const int t = threadIdx.x;
   int np2 = 64;
   while (np2 < n) np2 <<= 1;
@@ -807,24 +517,16 @@ __global__ __launch_bounds__(kBlock) void sort_small_k(const int32_t* __restrict
   if (!uniq_rows) return;
   __syncthreads();
   // head flags -> exclusive scan (4 passes of 256) -> compaction
-  int carry = 0;
-  for (int c0 = 0; c0 < n; c0 += kBlock) {
-    const int i = c0 + t;
-    const int v = (i < n && (i == 0 || sk[i] != sk[i - 1])) ? 1 : 0;
-    const int incl = wave_incl_scan(v, t & 63);
-    __syncthreads();
-    if ((t & 63) == 63) wsum[t >> 6] = incl;
-    __syncthreads();
-    int pre = carry;
-    for (int w = 0; w < (t >> 6); ++w) pre += wsum[w];
-    if (i < n) head[i] = v ? pre + incl - 1 : -1;
-    if (slot_of_entry && i < n) slot_of_entry[a[i] & 1023u] = pre + incl - 1;      // (heads up to and including i, minus one)
-    carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  }
+  const int U = block_excl_scan_chunked<kBlock>(
+      n, 0, [&](int i) { return (i == 0 || sk[i] != sk[i - 1]) ? 1 : 0; },
+      [&](int i, int excl, int v) {
+        head[i] = v ? excl : -1;
+        if (slot_of_entry) slot_of_entry[a[i] & 1023u] = excl + v - 1;      // (heads up to and including i, minus one)
+      });
   __syncthreads();
   for (int i = t; i < n; i += kBlock)
     if (head[i] >= 0) { uniq_rows[head[i]] = sk[i]; seg_start[head[i]] = i; }
-  if (t == 0) { seg_start[carry] = n; *num_uniq = carry; }
+  if (t == 0) { seg_start[U] = n; *num_uniq = U; }
 }
 }  // namespace
 
@@ -854,44 +556,34 @@ static int32_t sort_unique_rows_impl(const int32_t* rows, int64_t n, int64_t num
     MI_CHECK_LAUNCH("sort_unique_rows(small)");
     return MI_OK;
   }
-  char* ws = static_cast<char*>(workspace);
-  int32_t* kbuf[2] = {reinterpret_cast<int32_t*>(ws + L.keysA), reinterpret_cast<int32_t*>(ws + L.keysB)};
-  int32_t* vbuf[2] = {reinterpret_cast<int32_t*>(ws + L.valsA), reinterpret_cast<int32_t*>(ws + L.valsB)};
-  int32_t* hist = reinterpret_cast<int32_t*>(ws + L.hist);
-  int32_t* heads = reinterpret_cast<int32_t*>(ws + L.heads);
-  int32_t* bin_total = reinterpret_cast<int32_t*>(ws + L.bin_total);
-  int32_t* total = reinterpret_cast<int32_t*>(ws + L.total);
-  const int ntiles = static_cast<int>(L.ntiles);
+  const Buffers W = carve(workspace, L);
+  const int ntiles = W.ntiles;
+  const Digits D = plan_rows(num_rows_total, kMaxBits);
+  const int nbins = 1 << D.nbits;
 
-  int bits = 1;
-  while (bits < 31 && (static_cast<int64_t>(1) << bits) < num_rows_total) ++bits;
-  const int passes = (bits + kMaxBits - 1) / kMaxBits;
-  const int nbits = (bits + passes - 1) / passes;   // digit width, <= 9
-  const int nbins = 1 << nbits;
-
-  zero_i32(bin_total, kMaxPasses * kMaxBins, st);
+  zero_i32(W.bin_total, kMaxPasses * kMaxBins, st);
   MI_CHECK_LAUNCH("sort_unique_rows(zero)");
   const int32_t* kin = rows;
   const int32_t* vin = nullptr;  // pass 0: value = position
-  for (int p = 0; p < passes; ++p) {
-    int32_t* kout = kbuf[p & 1];
-    int32_t* vout = (perm_only && p == passes - 1) ? sorted_entry : vbuf[p & 1];
-    int32_t* bt = bin_total + p * kMaxBins;
-    hist_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, n, nbits * p, nbins, ntiles, hist, bt);
+  for (int p = 0; p < D.passes; ++p) {
+    int32_t* kout = W.kbuf[p & 1];
+    int32_t* vout = (perm_only && p == D.passes - 1) ? sorted_entry : W.vbuf[p & 1];
+    int32_t* bt = W.bin_total + p * kMaxBins;
+    hist_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, n, D.nbits * p, nbins, ntiles, W.hist, bt);
     MI_CHECK_LAUNCH("sort_unique_rows(hist)");
-    bin_scan_k<<<dim3(nbins), dim3(kBlock), 0, st>>>(hist, ntiles, nbins, bt, 0);
+    bin_scan_k<<<dim3(nbins), dim3(kBlock), 0, st>>>(W.hist, ntiles, nbins, bt, 0);
     MI_CHECK_LAUNCH("sort_unique_rows(scan)");
-    scatter_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, vin, n, nbits * p, nbits, ntiles, hist, kout, vout);
+    scatter_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, vin, n, D.nbits * p, D.nbits, ntiles, W.hist, kout, vout);
     MI_CHECK_LAUNCH("sort_unique_rows(scatter)");
     kin = kout;
     vin = vout;
   }
   if (perm_only) return MI_OK;
-  head_count_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, n, heads);
+  head_count_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, n, W.heads);
   MI_CHECK_LAUNCH("sort_unique_rows(heads)");
-  scan_small_k<<<dim3(1), dim3(kScanSmallBlock), 0, st>>>(heads, ntiles, total);
+  scan_small_k<<<dim3(1), dim3(kScanSmallBlock), 0, st>>>(W.heads, ntiles);
   MI_CHECK_LAUNCH("sort_unique_rows(scan heads)");
-  compact_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, vin, n, heads, total, sorted_entry, uniq_rows, seg_start, num_uniq, 0, nullptr,
+  compact_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, vin, n, W.heads, sorted_entry, uniq_rows, seg_start, num_uniq, 0, nullptr,
                                                    slot_of_entry);
   MI_CHECK_LAUNCH("sort_unique_rows(compact)");
   return MI_OK;
@@ -924,20 +616,18 @@ int32_t mi_catchup_rows_by_gap(const int32_t* uniq_rows, const int32_t* num_uniq
     return MI_ERR_WORKSPACE;
   }
   hipStream_t st = mi::as_stream(stream);
-  char* ws = static_cast<char*>(workspace);
-  int32_t* keys = reinterpret_cast<int32_t*>(ws + L.keysA);
-  int32_t* keys_sorted = reinterpret_cast<int32_t*>(ws + L.keysB);
-  int32_t* hist = reinterpret_cast<int32_t*>(ws + L.hist);
-  int32_t* bin_total = reinterpret_cast<int32_t*>(ws + L.bin_total);
-  const int ntiles = static_cast<int>(L.ntiles);
-  zero_i32(bin_total, 64, st);
+  const Buffers W = carve(workspace, L);
+  int32_t* keys = W.kbuf[0];
+  int32_t* keys_sorted = W.kbuf[1];
+  const int ntiles = W.ntiles;
+  zero_i32(W.bin_total, 64, st);
   MI_CHECK_LAUNCH("catchup_rows_by_gap(zero)");
   gap_hist_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(uniq_rows, num_uniq, last_step, n_max, step_to, lin_stride, mi::step_state(),
-                                                    keys, ntiles, hist, bin_total);
+                                                    keys, ntiles, W.hist, W.bin_total);
   MI_CHECK_LAUNCH("catchup_rows_by_gap(keys + hist)");
-  bin_scan_k<<<dim3(64), dim3(kBlock), 0, st>>>(hist, ntiles, 64, bin_total, 0);
+  bin_scan_k<<<dim3(64), dim3(kBlock), 0, st>>>(W.hist, ntiles, 64, W.bin_total, 0);
   MI_CHECK_LAUNCH("catchup_rows_by_gap(scan)");
-  scatter_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(keys, uniq_rows, n_max, 0, 6, ntiles, hist, keys_sorted, rows_out);
+  scatter_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(keys, uniq_rows, n_max, 0, 6, ntiles, W.hist, keys_sorted, rows_out);
   MI_CHECK_LAUNCH("catchup_rows_by_gap(scatter)");
   return MI_OK;
 }
@@ -962,46 +652,27 @@ int32_t mi_sort_unique_fields(const int32_t* ids, const int64_t* field_off, int6
     return MI_ERR_WORKSPACE;
   }
   hipStream_t st = mi::as_stream(stream);
-  char* ws = static_cast<char*>(workspace);
-  int32_t* kbuf[2] = {reinterpret_cast<int32_t*>(ws + L.keysA), reinterpret_cast<int32_t*>(ws + L.keysB)};
-  int32_t* vbuf[2] = {reinterpret_cast<int32_t*>(ws + L.valsA), reinterpret_cast<int32_t*>(ws + L.valsB)};
-  int32_t* hist = reinterpret_cast<int32_t*>(ws + L.hist);
-  int32_t* heads = reinterpret_cast<int32_t*>(ws + L.heads);
-  int32_t* bin_total = reinterpret_cast<int32_t*>(ws + L.bin_total);
-  int32_t* total = reinterpret_cast<int32_t*>(ws + L.total);
-  const int ntiles = static_cast<int>(L.ntiles), tps = static_cast<int>(B / kTile);
-
-  int bits = 1;
-  while (bits < 31 && (static_cast<int64_t>(1) << bits) < max_vocab) ++bits;
-  const int passes = (bits + kMaxBits - 1) / kMaxBits;
-  const int nbits = (bits + passes - 1) / passes;   // digit width, <= 9
-  const int nbins = 1 << nbits;
+  const Buffers W = carve(workspace, L);
+  const int ntiles = W.ntiles, tps = static_cast<int>(B / kTile);
 
   if (tps <= kFusedMaxTps && !beside && mi::env_int("MI_SORT_FUSED", 1) != 0) {
     // one launch per pass + one for the compaction (pass_fused_k / compact_fused_k above).  Digits of 7 bits: 20-bit ids = 3
     // passes, 130 us at config 3 against 149 for 2 passes of 10 bits (1,024 bins per 4,096-key tile scatter 16-byte runs)
-    const int fbits = mi::env_int("MI_SORT_BITS", 7) < kFusedMaxBits ? mi::env_int("MI_SORT_BITS", 7) : kFusedMaxBits;
-    const int fpasses = (bits + fbits - 1) / fbits;
-    const int fnb = (bits + fpasses - 1) / fpasses;
-    MI_REQUIRE(fpasses <= kMaxPasses, "sort_unique_fields: %d passes", fpasses);
-    int32_t* sync = reinterpret_cast<int32_t*>(ws + L.sync);
-    int32_t* ready = sync;                                   // [pass][field]
-    int32_t* hcf = sync + static_cast<int64_t>(kMaxPasses) * F;  // [tile]
+    const Digits D = plan_rows(max_vocab, mi::env_int("MI_SORT_BITS", 7));
+    MI_REQUIRE(D.passes <= kMaxPasses, "sort_unique_fields: %d passes", D.passes);
+    int32_t* ready = W.sync;                                       // [pass][field]
+    int32_t* hcf = W.sync + static_cast<int64_t>(kMaxPasses) * F;  // [tile]
     int32_t* err = hcf + ntiles;
-    zero_i32(sync, L.sync_words, st);
+    zero_i32(W.sync, L.sync_words, st);
     MI_CHECK_LAUNCH("sort_unique_fields(zero)");
     const int32_t* kin = nullptr;
     const int32_t* vin = nullptr;
     const int nap = mi::env_int("MI_SORT_NAP", 1);
-    for (int p = 0; p < fpasses; ++p) {
-      int32_t* kout = kbuf[p & 1];
-      int32_t* vout = vbuf[p & 1];
-      if (fnb > 9)
-        pass_fused_k<kFusedMaxBins><<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, vin, p == 0 ? ids : nullptr, B, F, fnb * p, fnb, tps, hist,
-                                                                          ready + static_cast<int64_t>(p) * F, err, kout, vout, nap);
-      else
-        pass_fused_k<kMaxBins><<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, vin, p == 0 ? ids : nullptr, B, F, fnb * p, fnb, tps, hist,
-                                                                      ready + static_cast<int64_t>(p) * F, err, kout, vout, nap);
+    for (int p = 0; p < D.passes; ++p) {
+      int32_t* kout = W.kbuf[p & 1];
+      int32_t* vout = W.vbuf[p & 1];
+      pass_fused_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kin, vin, p == 0 ? ids : nullptr, B, F, D.nbits * p, D.nbits, tps, W.hist,
+                                                          ready + static_cast<int64_t>(p) * F, err, kout, vout, nap);
       MI_CHECK_LAUNCH("sort_unique_fields(pass)");
       kin = kout;
       vin = vout;
@@ -1013,42 +684,44 @@ int32_t mi_sort_unique_fields(const int32_t* ids, const int64_t* field_off, int6
   // the short launches (hist_fields_k / scatter_runs_k / compact_fields_k above): 3 passes at config 3 = zero + 3 x (hist +
   // scatter) + head count + compact = 9.  The two pair buffers are the key buffers and the value buffers, each pair of
   // them contiguous; the last pass writes keys and values apart into the pair buffer it does not read.
-  zero_i32(bin_total, static_cast<int64_t>(kMaxPasses) * F * kMaxBins, st);
+  const Digits D = plan_rows(max_vocab, kMaxBits);
+  const int nbins = 1 << D.nbits;
+  zero_i32(W.bin_total, static_cast<int64_t>(kMaxPasses) * F * kMaxBins, st);
   MI_CHECK_LAUNCH("sort_unique_fields(zero)");
   static_assert(sizeof(int2) == 8, "pair buffers");
-  int2* pbuf[2] = {reinterpret_cast<int2*>(kbuf[0]), reinterpret_cast<int2*>(vbuf[0])};
+  int2* pbuf[2] = {reinterpret_cast<int2*>(W.kbuf[0]), reinterpret_cast<int2*>(W.vbuf[0])};
   const bool self_offs = static_cast<int64_t>(nbins) * tps <= kSelfOffsMaxInts;
   const int2* pin = nullptr;       // pass 0 reads ids
   int32_t* kout = nullptr;
   int32_t* vout = nullptr;
-  for (int p = 0; p < passes; ++p) {
-    const bool last = p == passes - 1;
-    int32_t* bt = bin_total + static_cast<int64_t>(p) * F * kMaxBins;
-    hist_fields_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(pin, p == 0 ? ids : nullptr, B, F, nbits * p, nbins, tps, hist, bt);
+  for (int p = 0; p < D.passes; ++p) {
+    const bool last = p == D.passes - 1;
+    int32_t* bt = W.bin_total + static_cast<int64_t>(p) * F * kMaxBins;
+    hist_fields_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(pin, p == 0 ? ids : nullptr, B, F, D.nbits * p, nbins, tps, W.hist, bt);
     MI_CHECK_LAUNCH("sort_unique_fields(hist)");
     if (!self_offs) {
-      bin_scan_k<<<dim3(F * nbins), dim3(kBlock), 0, st>>>(hist, tps, nbins, bt, B);
+      bin_scan_k<<<dim3(F * nbins), dim3(kBlock), 0, st>>>(W.hist, tps, nbins, bt, B);
       MI_CHECK_LAUNCH("sort_unique_fields(scan)");
     }
-    kout = last ? (p & 1 ? vbuf[0] : kbuf[0]) : nullptr;
-    vout = last ? (p & 1 ? vbuf[1] : kbuf[1]) : nullptr;
+    kout = last ? (p & 1 ? W.vbuf[0] : W.kbuf[0]) : nullptr;
+    vout = last ? (p & 1 ? W.vbuf[1] : W.kbuf[1]) : nullptr;
     if (p == 0)
-      scatter_runs_k<true><<<dim3(ntiles), dim3(kBlock), 0, st>>>(nullptr, ids, B, F, 0, nbits, tps, hist, bt, self_offs ? 1 : 0,
+      scatter_runs_k<true><<<dim3(ntiles), dim3(kBlock), 0, st>>>(nullptr, ids, B, F, 0, D.nbits, tps, W.hist, bt, self_offs ? 1 : 0,
                                                                   last ? nullptr : pbuf[0], kout, vout);
     else
-      scatter_runs_k<false><<<dim3(ntiles), dim3(kBlock), 0, st>>>(pin, nullptr, B, F, nbits * p, nbits, tps, hist, bt, self_offs ? 1 : 0,
+      scatter_runs_k<false><<<dim3(ntiles), dim3(kBlock), 0, st>>>(pin, nullptr, B, F, D.nbits * p, D.nbits, tps, W.hist, bt, self_offs ? 1 : 0,
                                                                    last ? nullptr : pbuf[p & 1], kout, vout);
     MI_CHECK_LAUNCH("sort_unique_fields(scatter)");
     pin = pbuf[p & 1];
   }
-  head_count_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kout, n, heads, B);
+  head_count_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kout, n, W.heads, B);
   MI_CHECK_LAUNCH("sort_unique_fields(heads)");
   if (ntiles <= kFoldHeadsMaxTiles) {
-    compact_fields_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kout, vout, n, heads, sorted_entry, uniq_rows, seg_start, num_uniq, B, field_off);
+    compact_fields_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kout, vout, n, W.heads, sorted_entry, uniq_rows, seg_start, num_uniq, B, field_off);
   } else {
-    scan_small_k<<<dim3(1), dim3(kScanSmallBlock), 0, st>>>(heads, ntiles, total);
+    scan_small_k<<<dim3(1), dim3(kScanSmallBlock), 0, st>>>(W.heads, ntiles);
     MI_CHECK_LAUNCH("sort_unique_fields(scan heads)");
-    compact_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kout, vout, n, heads, total, sorted_entry, uniq_rows, seg_start, num_uniq, B, field_off);
+    compact_k<<<dim3(ntiles), dim3(kBlock), 0, st>>>(kout, vout, n, W.heads, sorted_entry, uniq_rows, seg_start, num_uniq, B, field_off);
   }
   MI_CHECK_LAUNCH("sort_unique_fields(compact)");
   return MI_OK;

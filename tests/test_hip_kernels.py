@@ -829,6 +829,25 @@ def test_sort_unique_rows(lib, n, R):
     assert np.array_equal(sg.cpu().numpy()[:U + 1], np.r_[starts, n].astype(np.int32))
 
 
+@pytest.mark.parametrize("n,R", [(100, 7), (4097, 300), (70000, 26_000_000)])
+def test_sort_unique_rows_without_uniq_rows_is_the_permutation_alone(lib, n, R):
+    """uniq_rows = NULL: only the stable sort permutation — the last pass writes straight into sorted_entry — and nothing
+    else is written.  One workgroup; one pass with a partial tile; three passes."""
+    rng = np.random.default_rng(n + R)
+    rows = rng.integers(0, R, n).astype(np.int32)
+    rows[n // 2:n // 2 + 5] = rows[0]
+    r = dev(rows)
+    se = torch.full((n + 128,), -7, dtype=torch.int32, device="cuda")
+    sg = torch.full((n + 1,), -7, dtype=torch.int32, device="cuda")
+    nu = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+    ws = torch.empty(lib.mi_sort_unique_workspace_bytes(n) + 256, dtype=torch.uint8, device="cuda")
+    _chk(lib.mi_sort_unique_rows(_p(r), n, R, _p(se[64:]), None, _p(sg), _p(nu), _p(ws), ws.numel(), _st()))
+    assert np.array_equal(se[64:64 + n].cpu().numpy(), np.argsort(rows, kind="stable").astype(np.int32))
+    assert bool((se[:64] == -7).all()) and bool((se[64 + n:] == -7).all())
+    assert bool((sg == -7).all()) and int(nu.item()) == -7
+    assert torch.equal(r, dev(rows))
+
+
 @pytest.mark.parametrize("n,R", [(1, 10), (100, 7), (1000, 3), (5000, 300), (70000, 4106), (300000, 26_000_000), (4097, 65536)])
 def test_sort_unique_rows_slots_equals_sort_then_segment_slots(lib, n, R):
     """mi_sort_unique_rows_slots = mi_sort_unique_rows + mi_segment_slots (the entry the row-sharded step's routing used until

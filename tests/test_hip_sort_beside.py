@@ -90,3 +90,26 @@ def test_sort_unique_fields_beside_is_the_stable_sort_per_field(lib, B, F, kind,
     for a, b in zip(got[:3], other[:3]):
         assert np.array_equal(a, b)
     assert torch.equal(d_ids, dev(ids))                    # the ids are read in place, never written
+
+
+def test_sort_unique_fields_where_bin_scan_makes_the_offsets(lib):
+    """nbins x tiles per field above 4,096: the short launches no longer derive a tile's offsets from the raw counts —
+    bin_scan_k turns hist into offsets per (field, digit), with segments and seg_len = B, and scatter_runs_k reads them.
+    The smallest such shape: B = 9 tiles, vocabulary 200,000 = 18 bits = 2 passes of 9 -> 512 x 9 = 4,608 ints.  Both
+    fields uniform, then the second given a single id; both forms, against the host reference."""
+    B, F, V = 36_864, 2, 200_000
+    rng = np.random.default_rng(36_864)
+    ids = _ids("uniform", B, [V, V], rng)
+    off = np.array([0, V], np.int64)
+    d_off = dev(off)
+    for single in (False, True):
+        if single:
+            ids[:, 1] = 123_456
+        d_ids = dev(ids)
+        ref_se, ref_uq, ref_sg = _host(ids, off)
+        for beside in (0, 1):
+            se, uq, sg, U = _run(lib, d_ids, d_off, B, F, V, beside)
+            assert U == len(ref_uq)
+            assert np.array_equal(se, ref_se)
+            assert np.array_equal(uq, ref_uq) and np.array_equal(sg, ref_sg)
+        assert torch.equal(d_ids, dev(ids))

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """us per call of the two sort + unique entries at config 3's size (1.7 M keys).  With MI_TUNING_LIB=1 the tools' build is
-loaded (make -C recommender-tensorflow_amd/csrc tuning) and MI_SORT_FUSED=0|1 / MI_SORT_BITS=7..10 choose the per-field form:
+loaded (make -C recommender-tensorflow_amd/csrc tuning) and MI_SORT_FUSED=0|1 / MI_SORT_BITS=7..9 choose the per-field form:
    MI_TUNING_LIB=1 MI_SORT_FUSED=0 python tools/sort_bench.py fields      # the short launches (what beside = 1 runs; BESIDE=1 with the shipped library)
-   MI_TUNING_LIB=1 MI_SORT_BITS=7 python tools/sort_bench.py fields       # fused, 3 passes of 7 bits
-   python tools/sort_bench.py fields                                      # the shipped library: fused, 2 passes of 10 bits"""
+   MI_TUNING_LIB=1 MI_SORT_BITS=9 python tools/sort_bench.py fields       # fused, digits of at most 9 bits (20-bit ids: still 3 passes of 7; 18-bit ids: 2 of 9)
+   python tools/sort_bench.py fields                                      # the shipped library: fused (BESIDE=0), digits of at most 7 bits: 3 passes of 7 at 1 M ids"""
 import sys, os, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "recommender-tensorflow_amd"))
