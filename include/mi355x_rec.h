@@ -967,6 +967,71 @@ int32_t mi_train_group_step(const mi_fused_group_plan_t* plan, int32_t n_members
                             const uint8_t* labels, int64_t labels_member_stride, int64_t B, int32_t step, float* logits,
                             float* loss, int32_t sweep_blocks, mi_stream_t stream);
 
+/* ---- the one-launch step under any of the five optimizers, two rules and the canned estimators' columns ------------------
+ * What trainers/linear.py, deep.py and linear_deep.py train (LinearClassifier: Ftrl; DNNClassifier: Adagrad;
+ * DNNLinearCombinedClassifier: Ftrl on TF's "linear" scope, Adagrad on its "dnn" scope) and what model_utils.get_optimizer
+ * offers model_fn (Adagrad, Adam, Ftrl, RMSProp, SGD), as the ONE launch of mi_train_step_fused: the same device code.
+ *
+ * mi_fused_model_t: mi_fused_member_t's fields with the same meaning, and
+ *   two_rules / hp_wide: 0 = every variable follows hp (hp_wide is ignored); 1 = the WIDE part — the lin_w records and the
+ *     wide bias at lin_bias_off — follows hp_wide, everything else hp (needs use_linear);
+ *   dw_m / dw_v [n_dense]: with two_rules the wide part's dense slots, indexed like dense (the bias's at lin_bias_off);
+ *   lr_table_wide / lr_table_wide_len: hp_wide's Adam schedule (plans only), as lr_table is hp's;
+ *   wide_fields: bit f set = categorical field f has a linear weight (mi_predict_fused's meaning).  The wide sum, the wide
+ *     gradient and the wide record's update skip the other fields; such a field's wide record is never written.
+ * Slots: Adam, Ftrl and RMSProp keep two, Adagrad slot 0 only (t_m / l_m / d_m / dw_m), SGD none.  A slot the rule does not
+ *   keep is neither read nor written, whatever its pointer (pass NULL); a slot it keeps must be there.  The record strides
+ *   are the caller's: table_stride >= E floats for table records, lin_stride for wide records.
+ * The sweep: only records under Adam are walked — a sweep workgroup gives an untouched row one replay step on each of its
+ *   records whose rule is Adam, with that rule's own lr_t, and stamps it.  Under the other four rules untouched rows are
+ *   neither read nor written (TensorFlow's sparse applies of those optimizers touch the batch's rows only).  With no part
+ *   under Adam no sweep workgroup is launched (grid (1); in a group a member without Adam returns from its sweep
+ *   workgroups at once), last_step may be NULL and no stamp is written; with one it must be there and ends == step on
+ *   every row.
+ * Embedding columns narrower than E (the canned estimators' per-column dimensions) need nothing here: their padding and the
+ *   matching rows of kernel_0 are zero, their gradients are products with those zeros, and every rule leaves them zero.
+ * Limits and results otherwise as for mi_train_step_fused; refused in addition (MI_ERR_INVALID, nothing launched or
+ * written): an optimizer kind outside the five, a missing slot, last_step NULL with a part under Adam, two_rules without
+ * use_linear, a wide_fields bit at or above F, Ftrl with lr_power != -0.5.
+ *
+ * mi_train_step_model: one step of one model; hp.lr_t and hp_wide.lr_t are the caller's (lr_table* and seed_base unused),
+ *   seed as in mi_train_step_fused.  mi_train_group_plan_models: mi_train_group_plan for such models — a schedule table is
+ *   required exactly for a rule that is Adam — writing the same plan, which mi_train_group_step and mi_eval_group take;
+ *   step <= every table's last index.  Both share mi_train_step_fused's planning: a model that entry accepts gets its bits. */
+typedef struct mi_fused_model {
+  float* table; float* t_m; float* t_v;
+  int64_t table_stride;
+  float* lin_w; float* l_m; float* l_v;
+  int32_t* last_step;
+  int64_t R;
+  float* dense; float* d_m; float* d_v;
+  int64_t n_dense;
+  const int64_t* layer_off;
+  const int32_t* widths;
+  int64_t lin_bias_off;
+  const float* lr_table;
+  int64_t lr_table_len;
+  uint64_t seed_base;
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t lin_stride, E, n_layers, activation, use_linear, use_fm, use_dnn;
+  float keep_prob, scale;
+  mi_opt_hparams hp;
+  int32_t two_rules;
+  mi_opt_hparams hp_wide;
+  float* dw_m; float* dw_v;
+  const float* lr_table_wide;
+  int64_t lr_table_wide_len;
+  uint64_t wide_fields;
+} mi_fused_model_t;
+
+int32_t mi_train_step_model(const mi_fused_model_t* model, const int64_t* field_off, const int32_t* ids, const uint8_t* labels,
+                            int64_t B, int32_t F, uint64_t seed, int32_t step, float* logits, float* loss, int32_t sweep_blocks,
+                            mi_stream_t stream);
+int32_t mi_train_group_plan_models(const mi_fused_model_t* models, int32_t n_members, int64_t B, int32_t F,
+                                   const int64_t* field_off, void* device_table, size_t device_table_bytes,
+                                   mi_fused_group_plan_t* plan, mi_stream_t stream);
+
 /* ---- evaluating a population of small models: a whole evaluation set, for every member, as one launch ------------------
  * What Estimator.evaluate does for one model (the EVAL branch of trainers/deep_fm.py:118-125 and model_utils.py:39-54) for
  * the M members of a plan mi_train_group_plan wrote: the forward of mi_train_step_fused — the same device code — WITHOUT

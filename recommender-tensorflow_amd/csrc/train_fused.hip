@@ -1,7 +1,9 @@
 // Training small models: one whole optimizer.minimize(loss) of a DeepFM — gather, wide part, FM term, MLP forward with
 // dropout, sigmoid-CE head, full backward, dense Adam and TF's dense-equivalent sparse Adam — as ONE launch
 // (mi_train_step_fused, include/mi355x_rec.h).  Replaces, for a model whose state fits the chip's caches, what
-// trainers/deep_fm.py:36-125 and model_utils.py:57-72 have TensorFlow execute per step.
+// trainers/deep_fm.py:36-125 and model_utils.py:57-72 have TensorFlow execute per step.  mi_train_step_model is the same
+// launch under any of the five optimizers of optim_rules.h, with a second rule for the wide part (trainers/linear_deep.py:
+// 32-39), slots a rule does not keep left out, and the wide part on a subset of the columns (struct Args below).
 //
 //   train_fused_k    block 0 = the BATCH workgroup, blocks 1 .. G-1 = SWEEP workgroups.
 //     batch   everything that depends on the loss, phases separated by workgroup barriers:
@@ -18,7 +20,9 @@
 //                   dense_rule on every dense variable with the gradient of phase 3
 //     sweep   each workgroup owns a slice of the R rows, builds the batch's touched set itself (a bitmap of R bits in
 //             LDS, from ids) and gives every row of its slice that is NOT touched one step of TF Adam's whole-table
-//             sweep (replay_step of optim_rules.h), table record and wide record, stamp = step.
+//             sweep (replay_step of optim_rules.h), table record and wide record, stamp = step.  Only records under
+//             Adam are swept, each with its own rule's lr_t; with no part under Adam there is no sweep workgroup (in a
+//             group: such a member's return at once) and untouched rows are neither read nor written.
 //   Touched and untouched rows are disjoint and the dense variables belong to block 0: no workgroup reads what another
 //   writes in this launch and none waits for another — no flags, no grid barrier, no float atomics to global memory.
 //   Results do not depend on G.
@@ -64,6 +68,10 @@ struct Layer {
   int32_t out_off, pad;                 // the layer's output [B][fan_out] in LDS (float offset)
 };
 
+// Two rules: hp is the rule of the table records and the MLP's variables (slots tm / tv, dm / dv), hpw the rule of the WIDE
+// part — the lin_w records (lm / lv) and the wide bias at lin_bias_off (dwm / dwv, indexed like dense).  With one optimizer
+// the plan sets hpw = hp and dwm / dwv = dm / dv.  A slot pointer is NULL where the rule keeps no such slot (Adagrad: slot 1;
+// SGD: both): that slot is neither loaded nor stored.  last_step is NULL when neither rule is Adam (no stamps, no sweep).
 struct Args {
   float* table; float* tm; float* tv;   // or NULL (no FM term and no DNN)
   float* lin_w; float* lm; float* lv;   // or NULL (no wide part)
@@ -72,6 +80,8 @@ struct Args {
   const int32_t* ids;
   const uint8_t* labels;
   float* dense; float* dm; float* dv;
+  float* dwm; float* dwv;
+  uint64_t wide_mask;                   // bit f set: field f has a wide weight (mi_predict_fused's wide_fields)
   float* gdense;                        // workspace: the dense gradient, indexed like dense
   float* dcat_ws;                       // workspace: d_concat [B][F E] when LDS has no room for it, else NULL
   float* logits; float* loss;
@@ -80,9 +90,15 @@ struct Args {
   int32_t B, F, E, ls, act, n_layers, use_linear, use_fm, step;
   int32_t o_sumv, o_tq, o_lin, o_dl, o_dcat;   // float offsets in LDS (the rows [B F] int32 lead)
   float keep, scale;
-  Hp hp;
+  Hp hp, hpw;
   Layer l[kMaxLayers];
 };
+
+// a slot that may be absent: 0 stands in for the value no rule reads, and nothing is stored
+__device__ __forceinline__ float ld_slot(const float* s, int64_t o) { return s ? s[o] : 0.f; }
+__device__ __forceinline__ void st_slot(float* s, int64_t o, float v) { if (s) s[o] = v; }
+__device__ __forceinline__ float4 ld4_slot(const float* s, int64_t o) { return s ? ld4(s + o) : make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ void st4_slot(float* s, int64_t o, float4 v) { if (s) st4(s + o, v); }
 
 __device__ __forceinline__ int32_t row_of(const Args& p, int i) {
   const int f = i % p.F;
@@ -93,6 +109,9 @@ __device__ __forceinline__ int32_t row_of(const Args& p, int i) {
 
 // ---- sweep workgroups ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void sweep_block(const Args& p, uint32_t* __restrict__ bm) {
+  // the records under Adam: TF Adam's sparse apply walks the whole variable; the other four rules touch the batch's rows only
+  const bool t_adam = p.table && p.hp.kind == MI_OPT_ADAM, l_adam = p.lin_w && p.hpw.kind == MI_OPT_ADAM;
+  if (!t_adam && !l_adam) return;                       // (a member of a group without an Adam part: its rows stay as they are)
   const int tid = threadIdx.x;
   const int words = static_cast<int>((p.R + 31) >> 5);
   for (int i = tid; i < words; i += kThreads) bm[i] = 0u;
@@ -103,13 +122,14 @@ __device__ __forceinline__ void sweep_block(const Args& p, uint32_t* __restrict_
     atomicOr(&bm[r >> 5], 1u << (r & 31));
   }
   __syncthreads();
-  const int cpf = p.table ? p.E / 4 : 1;
+  const int cpf = t_adam ? p.E / 4 : 1;
   const int64_t G = static_cast<int64_t>(gridDim.x) - 1;
   const int64_t per = (p.R + G - 1) / G;
   const int64_t lo = (static_cast<int64_t>(blockIdx.x) - 1) * per;
   const int64_t hi = lo + per < p.R ? lo + per : p.R;
   const int64_t items = hi > lo ? (hi - lo) * cpf : 0;
   const float b1 = p.hp.beta1, b2 = p.hp.beta2, eps = p.hp.eps, lr_t = p.hp.lr_t;
+  const float wb1 = p.hpw.beta1, wb2 = p.hpw.beta2, weps = p.hpw.eps, wlr_t = p.hpw.lr_t;      // (each part its own schedule)
   for (int64_t i0 = tid; i0 < items; i0 += static_cast<int64_t>(kThreads) * kRowsInFlight) {
     float4 w[kRowsInFlight], m[kRowsInFlight], v[kRowsInFlight];
     float lw[kRowsInFlight], lm[kRowsInFlight], lv[kRowsInFlight];
@@ -125,11 +145,11 @@ __device__ __forceinline__ void sweep_block(const Args& p, uint32_t* __restrict_
       on[u] = on[u] && !((bm[r[u] >> 5] >> (r[u] & 31)) & 1u);
       w[u] = m[u] = v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
       lw[u] = lm[u] = lv[u] = 0.f;
-      if (on[u] && p.table) {
+      if (on[u] && t_adam) {
         const int64_t o = r[u] * p.ts + 4 * c[u];
         w[u] = ld4(p.table + o); m[u] = ld4(p.tm + o); v[u] = ld4(p.tv + o);
       }
-      if (on[u] && c[u] == 0 && p.lin_w) {
+      if (on[u] && c[u] == 0 && l_adam) {
         const int64_t o = r[u] * p.ls;
         lw[u] = p.lin_w[o]; lm[u] = p.lm[o]; lv[u] = p.lv[o];
       }
@@ -137,7 +157,7 @@ __device__ __forceinline__ void sweep_block(const Args& p, uint32_t* __restrict_
 #pragma unroll
     for (int u = 0; u < kRowsInFlight; ++u) {
       if (!on[u]) continue;
-      if (p.table) {
+      if (t_adam) {
         const int64_t o = r[u] * p.ts + 4 * c[u];
         replay_step(w[u].x, m[u].x, v[u].x, lr_t, b1, b2, eps);
         replay_step(w[u].y, m[u].y, v[u].y, lr_t, b1, b2, eps);
@@ -147,8 +167,8 @@ __device__ __forceinline__ void sweep_block(const Args& p, uint32_t* __restrict_
       }
       if (c[u] == 0) {
         const int64_t o = r[u] * p.ls;
-        if (p.lin_w) {
-          replay_step(lw[u], lm[u], lv[u], lr_t, b1, b2, eps);
+        if (l_adam) {
+          replay_step(lw[u], lm[u], lv[u], wlr_t, wb1, wb2, weps);
           p.lin_w[o] = lw[u]; p.lm[o] = lm[u]; p.lv[o] = lv[u];
         }
         p.last_step[o] = p.step;
@@ -208,7 +228,8 @@ __device__ __forceinline__ float forward_block(const Args& p, char* lds, const L
       } else if (i < nE + nL) {
         const int b = i - nE;
         float acc = 0.f;
-        for (int f = 0; f < F; ++f) acc = acc + p.lin_w[static_cast<int64_t>(rows[b * F + f]) * p.ls];
+        for (int f = 0; f < F; ++f)
+          if ((p.wide_mask >> f) & 1u) acc = acc + p.lin_w[static_cast<int64_t>(rows[b * F + f]) * p.ls];
         zlin[b] = acc;
       } else {
         const int j = i - nE - nL, b = j / w1, n = j - b * w1;
@@ -383,21 +404,21 @@ __device__ __forceinline__ void batch_block(const Args& p, char* lds, const Laye
       }
       if (!leader) continue;
       if (p.table) {
-        float4 m = ld4(p.tm + o), v = ld4(p.tv + o);
+        float4 m = ld4_slot(p.tm, o), v = ld4_slot(p.tv, o);
         sparse_rule(p.hp, w.x, m.x, v.x, g.x);
         sparse_rule(p.hp, w.y, m.y, v.y, g.y);
         sparse_rule(p.hp, w.z, m.z, v.z, g.z);
         sparse_rule(p.hp, w.w, m.w, v.w, g.w);
-        st4(p.table + o, w); st4(p.tm + o, m); st4(p.tv + o, v);
+        st4(p.table + o, w); st4_slot(p.tm, o, m); st4_slot(p.tv, o, v);
       }
       if (c == 0) {
         const int64_t ol = static_cast<int64_t>(r) * p.ls;
-        if (p.lin_w) {
-          float lw = p.lin_w[ol], m = p.lm[ol], v = p.lv[ol];
-          sparse_rule(p.hp, lw, m, v, gl);
-          p.lin_w[ol] = lw; p.lm[ol] = m; p.lv[ol] = v;
+        if (p.lin_w && ((p.wide_mask >> f) & 1u)) {               // (a field without a wide weight: its record stays as it is)
+          float lw = p.lin_w[ol], m = ld_slot(p.lm, ol), v = ld_slot(p.lv, ol);
+          sparse_rule(p.hpw, lw, m, v, gl);
+          p.lin_w[ol] = lw; st_slot(p.lm, ol, m); st_slot(p.lv, ol, v);
         }
-        p.last_step[ol] = p.step;
+        if (p.last_step) p.last_step[ol] = p.step;
       }
     }
   }
@@ -407,18 +428,18 @@ __device__ __forceinline__ void batch_block(const Args& p, char* lds, const Laye
     const int kn = ly.fan_in * ly.fan_out;
     for (int i = tid; i < kn + ly.fan_out; i += kThreads) {
       const int64_t o = i < kn ? ly.w_off + i : ly.b_off + (i - kn);
-      float w = p.dense[o], m = p.dm[o], v = p.dv[o];
+      float w = p.dense[o], m = ld_slot(p.dm, o), v = ld_slot(p.dv, o);
       dense_rule(p.hp, w, m, v, p.gdense[o]);
-      p.dense[o] = w; p.dm[o] = m; p.dv[o] = v;
+      p.dense[o] = w; st_slot(p.dm, o, m); st_slot(p.dv, o, v);
     }
   }
   if (p.use_linear && tid == 0) {
     float g = red[1][0];
     for (int w = 1; w < nw; ++w) g = g + red[1][w];
     const int64_t o = p.lin_bias_off;
-    float w = p.dense[o], m = p.dm[o], v = p.dv[o];
-    dense_rule(p.hp, w, m, v, g);
-    p.dense[o] = w; p.dm[o] = m; p.dv[o] = v;
+    float w = p.dense[o], m = ld_slot(p.dwm, o), v = ld_slot(p.dwv, o);
+    dense_rule(p.hpw, w, m, v, g);                                 // (the wide part's rule and its own dense slots)
+    p.dense[o] = w; st_slot(p.dwm, o, m); st_slot(p.dwv, o, v);
   }
 }
 
@@ -439,12 +460,14 @@ __global__ __launch_bounds__(kThreads) void train_fused_k(const Args p) {
 }
 
 // one member of a population: its Args as mi_train_group_plan validated them (ids / labels / logits / loss / step / seed /
-// hp.lr_t are filled in by the kernel), its Adam schedule table and the step-free part of its dropout seed
+// hp.lr_t / hpw.lr_t are filled in by the kernel), the Adam schedule table of each rule (NULL: the rule is not Adam; with
+// one rule both name the same table) and the step-free part of its dropout seed
 struct Member {
   Args a;
   const float* lr_table;                // lr_t of step s at [s], lr_len entries
+  const float* lr_table_w;              // the wide part's, lr_len_w entries
   uint64_t seed_base;
-  int64_t lr_len;
+  int64_t lr_len, lr_len_w;
 };
 
 __global__ __launch_bounds__(kThreads) void train_fused_group_k(const Member* __restrict__ members, const int32_t* __restrict__ ids,
@@ -460,13 +483,14 @@ __global__ __launch_bounds__(kThreads) void train_fused_group_k(const Member* __
   mi_copy_words<kThreads>(&sp, &me->a);
   __syncthreads();
   if (threadIdx.x == 0) {
-    const int64_t s = step < me->lr_len ? step : me->lr_len - 1;           // (mi_train_group_step checked it: stay inside)
+    // (mi_train_group_step checked the step against every table: stay inside)
+    if (me->lr_table) sp.hp.lr_t = me->lr_table[step < me->lr_len ? step : me->lr_len - 1];
+    if (me->lr_table_w) sp.hpw.lr_t = me->lr_table_w[step < me->lr_len_w ? step : me->lr_len_w - 1];
     sp.ids = ids + y * ids_stride;
     sp.labels = labels + y * labels_stride;
     sp.logits = logits + static_cast<int64_t>(y) * sp.B;
     sp.loss = loss + y;
     sp.step = step;
-    sp.hp.lr_t = me->lr_table[s];
     sp.seed = me->seed_base + static_cast<uint64_t>(step) * 1000003ull;    // engine._layer_seed(0) of this step
   }
   if (threadIdx.x < kMaxLayers) layers[threadIdx.x] = sp.l[threadIdx.x];
@@ -565,16 +589,43 @@ size_t workspace_bytes_of(int64_t B, int32_t F, int32_t E, int64_t n_dense) {
   return sizeof(float) * static_cast<size_t>(align4(n_dense) + align4(B * F * E));
 }
 
+// slots a rule keeps: Adam, Ftrl and RMSProp two, Adagrad slot 0 only, SGD none
+int slots_of(int kind) { return kind == MI_OPT_SGD ? 0 : (kind == MI_OPT_ADAGRAD ? 1 : 2); }
+
+// what the Adam-only entries (mi_train_step_fused, mi_train_group_plan) describe, as the general description: one rule,
+// every field in the wide part
+mi_fused_model_t model_of(const mi_fused_member_t& m, int32_t F) {
+  mi_fused_model_t g{};
+  g.table = m.table; g.t_m = m.t_m; g.t_v = m.t_v; g.table_stride = m.table_stride;
+  g.lin_w = m.lin_w; g.l_m = m.l_m; g.l_v = m.l_v; g.last_step = m.last_step; g.R = m.R;
+  g.dense = m.dense; g.d_m = m.d_m; g.d_v = m.d_v; g.n_dense = m.n_dense;
+  g.layer_off = m.layer_off; g.widths = m.widths; g.lin_bias_off = m.lin_bias_off;
+  g.lr_table = m.lr_table; g.lr_table_len = m.lr_table_len; g.seed_base = m.seed_base;
+  g.workspace = m.workspace; g.workspace_bytes = m.workspace_bytes;
+  g.lin_stride = m.lin_stride; g.E = m.E; g.n_layers = m.n_layers; g.activation = m.activation;
+  g.use_linear = m.use_linear; g.use_fm = m.use_fm; g.use_dnn = m.use_dnn;
+  g.keep_prob = m.keep_prob; g.scale = m.scale; g.hp = m.hp;
+  g.wide_fields = (F >= 1 && F < 64) ? (uint64_t(1) << F) - 1 : ~uint64_t(0);
+  return g;
+}
+
 // The checks of one model, in mi_train_step_fused's order, and its Args (everything but ids / labels / logits / loss / step /
 // seed / lr_t, which the caller fills in; have_batch / have_outputs: the caller holds those pointers — a plan has none yet),
-// the dynamic LDS of its workgroups and the built-in number of sweep workgroups.  Writes nothing but `a`.  (m's lr_table,
-// lr_table_len and seed_base belong to the group plan.)
-int32_t plan_model(const mi_fused_member_t& m, const int64_t* field_off, int64_t B, int32_t F, int32_t step, bool have_batch,
+// the dynamic LDS of its workgroups and the built-in number of sweep workgroups (0: no part is under Adam, nothing to
+// sweep).  Writes nothing but `a`.  (m's lr_table*, lr_table*_len and seed_base belong to the group plan.)
+int32_t plan_model(const mi_fused_model_t& m, const int64_t* field_off, int64_t B, int32_t F, int32_t step, bool have_batch,
                    bool have_outputs, int32_t sweep_blocks, Args& a, size_t& lds_out, int& blocks_out) {
   const int64_t R = m.R, n_dense = m.n_dense;
   const int32_t n_layers = m.n_layers;
   const int32_t* widths = m.widths;
-  if (m.hp.kind != MI_OPT_ADAM) return unsupported("train_step_fused: optimizer kind %d (Adam only)", m.hp.kind);
+  const bool two = m.two_rules != 0;
+  const mi_opt_hparams& hw = two ? m.hp_wide : m.hp;
+  for (const mi_opt_hparams* h : {&m.hp, &hw}) {
+    MI_REQUIRE(h->kind >= MI_OPT_ADAM && h->kind <= MI_OPT_SGD, "train_step_fused: optimizer kind %d (0 to 4)", h->kind);
+    MI_REQUIRE(h->kind != MI_OPT_FTRL || h->lr_power == -0.5f,
+               "train_step_fused: Ftrl learning_rate_power %f unsupported (TF default -0.5 only)", h->lr_power);
+  }
+  MI_REQUIRE(!two || m.use_linear, "train_step_fused: two_rules without the wide part (use_linear = 0)");
   MI_REQUIRE(m.use_linear || m.use_fm || m.use_dnn, "train_step_fused: no part of the model is switched on");
   MI_REQUIRE(m.activation >= 0 && m.activation <= 3, "train_step_fused: activation %d", m.activation);
   MI_REQUIRE(step >= 1, "train_step_fused: step=%d (the global step after this call, 1-based)", step);
@@ -590,15 +641,23 @@ int32_t plan_model(const mi_fused_member_t& m, const int64_t* field_off, int64_t
   if (R < 1 || R > kMaxRows) return unsupported("train_step_fused: R=%lld table rows (1 to %lld)", (long long)R, (long long)kMaxRows);
   if (sweep_blocks < 0 || sweep_blocks > kMaxSweepBlocks)
     return unsupported("train_step_fused: sweep_blocks=%d (0 = the built-in choice, at most %d)", sweep_blocks, kMaxSweepBlocks);
-  MI_REQUIRE(field_off && have_batch && m.last_step, "train_step_fused: field_off / ids / labels / last_step");
+  const int nt = slots_of(m.hp.kind), nw = slots_of(hw.kind);      // slots of the table / MLP rule and of the wide rule
+  const bool adam = (emb && m.hp.kind == MI_OPT_ADAM) || (m.use_linear && hw.kind == MI_OPT_ADAM);
+  MI_REQUIRE(field_off && have_batch && (m.last_step || !adam), "train_step_fused: field_off / ids / labels / last_step");
   MI_REQUIRE(have_outputs, "train_step_fused: logits / loss");
-  MI_REQUIRE(!emb || (m.table && m.t_m && m.t_v && mi::aligned16(m.table) && mi::aligned16(m.t_m) && mi::aligned16(m.t_v)),
+  float* const t_m = nt >= 1 ? m.t_m : nullptr;
+  float* const t_v = nt >= 2 ? m.t_v : nullptr;
+  MI_REQUIRE(!emb || (m.table && (nt < 1 || t_m) && (nt < 2 || t_v) && mi::aligned16(m.table) && mi::aligned16(t_m) &&
+                      mi::aligned16(t_v)),
              "train_step_fused: table / t_m / t_v (16-byte aligned)");
+  MI_REQUIRE(!m.use_linear || F > 63 || (m.wide_fields >> F) == 0,
+             "train_step_fused: wide_fields names a field at or above F=%d", F);
   MI_REQUIRE(m.table_stride == 0 || (m.table_stride >= E && (m.table_stride & 3) == 0),
              "train_step_fused: table_stride=%lld (0 = E, else >= E and a multiple of 4)", (long long)m.table_stride);
   MI_REQUIRE(m.lin_stride >= 1, "train_step_fused: lin_stride=%d", m.lin_stride);
-  MI_REQUIRE(!m.use_linear || (m.lin_w && m.l_m && m.l_v), "train_step_fused: lin_w / l_m / l_v");
-  MI_REQUIRE(m.dense && m.d_m && m.d_v && n_dense >= 1, "train_step_fused: dense / d_m / d_v / n_dense");
+  MI_REQUIRE(!m.use_linear || (m.lin_w && (nw < 1 || m.l_m) && (nw < 2 || m.l_v)), "train_step_fused: lin_w / l_m / l_v");
+  MI_REQUIRE(m.dense && (nt < 1 || m.d_m) && (nt < 2 || m.d_v) && n_dense >= 1, "train_step_fused: dense / d_m / d_v / n_dense");
+  MI_REQUIRE(!two || ((nw < 1 || m.dw_m) && (nw < 2 || m.dw_v)), "train_step_fused: dw_m / dw_v (the wide rule's dense slots)");
   MI_REQUIRE(!m.use_linear || (m.lin_bias_off >= 0 && m.lin_bias_off < n_dense), "train_step_fused: lin_bias_off");
   MI_REQUIRE(m.use_dnn ? n_layers >= 1 : n_layers == 0, "train_step_fused: %d layers (a DNN has at least its logits layer)", n_layers);
   if (n_layers > kMaxLayers)
@@ -643,18 +702,22 @@ int32_t plan_model(const mi_fused_member_t& m, const int64_t* field_off, int64_t
   const size_t bitmap = sizeof(uint32_t) * static_cast<size_t>((R + 31) / 32);
   if (bitmap > lds) lds = bitmap;
 
-  a.table = emb ? m.table : nullptr; a.tm = emb ? m.t_m : nullptr; a.tv = emb ? m.t_v : nullptr;
-  a.lin_w = m.use_linear ? m.lin_w : nullptr; a.lm = m.use_linear ? m.l_m : nullptr; a.lv = m.use_linear ? m.l_v : nullptr;
-  a.last_step = m.last_step; a.field_off = field_off;
-  a.dense = m.dense; a.dm = m.d_m; a.dv = m.d_v;
+  // (a slot the rule does not keep: NULL, whatever the caller passed)
+  a.table = emb ? m.table : nullptr; a.tm = emb ? t_m : nullptr; a.tv = emb ? t_v : nullptr;
+  a.lin_w = m.use_linear ? m.lin_w : nullptr;
+  a.lm = (m.use_linear && nw >= 1) ? m.l_m : nullptr; a.lv = (m.use_linear && nw >= 2) ? m.l_v : nullptr;
+  a.last_step = adam ? m.last_step : nullptr; a.field_off = field_off;
+  a.dense = m.dense; a.dm = nt >= 1 ? m.d_m : nullptr; a.dv = nt >= 2 ? m.d_v : nullptr;
+  a.dwm = nw >= 1 ? (two ? m.dw_m : m.d_m) : nullptr; a.dwv = nw >= 2 ? (two ? m.dw_v : m.d_v) : nullptr;
+  a.wide_mask = m.use_linear ? m.wide_fields : 0;
   a.ts = m.table_stride ? m.table_stride : E; a.R = R; a.lin_bias_off = m.lin_bias_off;
   a.B = iB; a.F = F; a.E = E; a.ls = m.lin_stride; a.act = m.activation; a.n_layers = n_layers;
   a.use_linear = m.use_linear != 0; a.use_fm = m.use_fm != 0;
-  a.keep = m.keep_prob; a.scale = m.scale; a.hp = make_hp(&m.hp);
+  a.keep = m.keep_prob; a.scale = m.scale; a.hp = make_hp(&m.hp); a.hpw = make_hp(&hw);
 
-  const int64_t items = R * (emb ? E / 4 : 1);
+  const int64_t items = R * ((emb && m.hp.kind == MI_OPT_ADAM) ? E / 4 : 1);
   const int64_t want = mi::ceil_div(items, static_cast<int64_t>(kThreads) * kRowsInFlight);
-  blocks_out = sweep_blocks ? sweep_blocks : static_cast<int>(want < 1 ? 1 : (want > 128 ? 128 : want));
+  blocks_out = !adam ? 0 : (sweep_blocks ? sweep_blocks : static_cast<int>(want < 1 ? 1 : (want > 128 ? 128 : want)));
   lds_out = lds;
   return MI_OK;
 }
@@ -662,6 +725,99 @@ int32_t plan_model(const mi_fused_member_t& m, const int64_t* field_off, int64_t
 constexpr uint64_t kPlanMagic = 0x6d695f67726f7570ull;   // "mi_group"
 constexpr int kGroupGridBlocks = 1 << 16;                // the built-in sweep_blocks keeps (1 + G) M at or below this
 constexpr int kEvalResident = 4 * 256;                   // workgroups of one evaluation launch (the built-in choice)
+
+// one step of one model: mi_train_step_fused and mi_train_step_model behind their own checks
+int32_t step_one(const mi_fused_model_t& m, const int64_t* field_off, const int32_t* ids, const uint8_t* labels, int64_t B,
+                 int32_t F, uint64_t seed, int32_t step, float* logits, float* loss, int32_t sweep_blocks, mi_stream_t stream) {
+  Args a;
+  size_t lds = 0;
+  int blocks = 0;
+  const int32_t rc = plan_model(m, field_off, B, F, step, ids && labels, logits && loss, sweep_blocks, a, lds, blocks);
+  if (rc != MI_OK) return rc;
+  a.ids = ids; a.labels = labels; a.logits = logits; a.loss = loss; a.seed = seed; a.step = step;
+  const int32_t rl = mi::raise_lds(&train_fused_k, lds, "train_step_fused");
+  if (rl != MI_OK) return rl;
+  train_fused_k<<<dim3(1 + blocks), dim3(kThreads), lds, mi::as_stream(stream)>>>(a);       // (no Adam part: the batch workgroup alone)
+  MI_CHECK_LAUNCH("train_step_fused");
+  return MI_OK;
+}
+
+// mi_train_group_plan (adam_only: its members, behind that entry's refusal) and mi_train_group_plan_models: model(i) is
+// member i's description
+template <typename Get>
+int32_t plan_group(Get model, bool adam_only, int32_t n_members, int64_t B, int32_t F, const int64_t* field_off, void* device_table,
+                   size_t device_table_bytes, mi_fused_group_plan_t* plan, mi_stream_t stream) {
+  MI_REQUIRE(plan, "train_group_plan: plan");
+  MI_REQUIRE(n_members >= 1, "train_group_plan: %d members (at least 1)", n_members);
+  if (n_members > MI_FUSED_GROUP_MAX_MEMBERS)
+    return unsupported("train_group_plan: %d members (at most %d in one launch)", n_members, MI_FUSED_GROUP_MAX_MEMBERS);
+  const size_t need = mi_train_group_plan_bytes(n_members);
+  if (!device_table || device_table_bytes < need) {
+    mi::set_error("train_group_plan: device table of %zu bytes, %zu needed", device_table_bytes, need);
+    return MI_ERR_WORKSPACE;
+  }
+  MI_REQUIRE(mi::aligned16(device_table), "train_group_plan: device_table (16-byte aligned)");
+  struct Owned { const void* p; int32_t member; };
+  constexpr int kOwned = 13;
+  const std::unique_ptr<Member[]> tab(new (std::nothrow) Member[n_members]);
+  const std::unique_ptr<Owned[]> owned(new (std::nothrow) Owned[kOwned * static_cast<size_t>(n_members)]);
+  MI_REQUIRE(tab && owned, "train_group_plan: out of host memory");
+  size_t n_owned = 0, lds = 0;
+  int blocks = 0;
+  int64_t max_step = INT32_MAX;
+  for (int32_t i = 0; i < n_members; ++i) {
+    const mi_fused_model_t m = model(i);
+    size_t lds_i = 0;
+    int blocks_i = 0;
+    int32_t rc = MI_OK;
+    if (adam_only && m.hp.kind != MI_OPT_ADAM) rc = unsupported("train_step_fused: optimizer kind %d (Adam only)", m.hp.kind);
+    if (rc == MI_OK) rc = plan_model(m, field_off, B, F, 1, true, true, 0, tab[i].a, lds_i, blocks_i);
+    // a schedule table exactly for a rule that is Adam (with one rule the wide part reads hp's)
+    const bool t_adam = m.hp.kind == MI_OPT_ADAM, w_adam = m.two_rules && m.hp_wide.kind == MI_OPT_ADAM;
+    if (rc == MI_OK && t_adam && (!m.lr_table || m.lr_table_len < 2)) {
+      mi::set_error("train_step_fused: lr_table of %lld entries (lr_t of step s at [s], s >= 1)", (long long)m.lr_table_len);
+      rc = MI_ERR_INVALID;
+    }
+    if (rc == MI_OK && w_adam && (!m.lr_table_wide || m.lr_table_wide_len < 2)) {
+      mi::set_error("train_step_fused: lr_table_wide of %lld entries (lr_t of step s at [s], s >= 1)", (long long)m.lr_table_wide_len);
+      rc = MI_ERR_INVALID;
+    }
+    if (rc != MI_OK) {
+      mi::member_error("train_group_plan", i);
+      return rc;
+    }
+    tab[i].lr_table = t_adam ? m.lr_table : nullptr; tab[i].lr_len = t_adam ? m.lr_table_len : 0;
+    tab[i].lr_table_w = m.two_rules ? (w_adam ? m.lr_table_wide : nullptr) : tab[i].lr_table;
+    tab[i].lr_len_w = m.two_rules ? (w_adam ? m.lr_table_wide_len : 0) : tab[i].lr_len;
+    tab[i].seed_base = m.seed_base;
+    if (lds_i > lds) lds = lds_i;
+    if (blocks_i > blocks) blocks = blocks_i;
+    if (t_adam && m.lr_table_len - 1 < max_step) max_step = m.lr_table_len - 1;
+    if (w_adam && m.lr_table_wide_len - 1 < max_step) max_step = m.lr_table_wide_len - 1;
+    const Args& a = tab[i].a;
+    const void* own[kOwned] = {a.table, a.tm, a.tv, a.lin_w, a.lm, a.lv, a.last_step, a.dense, a.dm, a.dv,
+                               m.two_rules ? a.dwm : nullptr, m.two_rules ? a.dwv : nullptr, m.workspace};
+    for (const void* p : own)
+      if (p) owned[n_owned++] = Owned{p, i};
+  }
+  // two members (or two roles of one member) on the same memory: every pointer above is written by its member's workgroups
+  qsort(owned.get(), n_owned, sizeof(Owned), [](const void* x, const void* y) {
+    const Owned* a = static_cast<const Owned*>(x);
+    const Owned* b = static_cast<const Owned*>(y);
+    return a->p < b->p ? -1 : (a->p > b->p ? 1 : (a->member < b->member ? -1 : (a->member > b->member ? 1 : 0)));
+  });
+  for (size_t j = 1; j < n_owned; ++j)
+    MI_REQUIRE(owned[j].p != owned[j - 1].p,
+               "train_group_plan: member %d and member %d share a state or workspace pointer (%p): members are independent",
+               owned[j - 1].member, owned[j].member, owned[j].p);
+  const int32_t rc = mi::upload_table(device_table, tab.get(), need, stream, "train_group_plan");
+  if (rc != MI_OK) return rc;
+  while (blocks > 1 && static_cast<int64_t>(1 + blocks) * n_members > kGroupGridBlocks) --blocks;
+  plan->device_table = device_table; plan->n_members = n_members; plan->B = static_cast<int32_t>(B); plan->F = F;
+  plan->lds_bytes = static_cast<uint32_t>(lds); plan->sweep_blocks = blocks; plan->max_step = static_cast<int32_t>(max_step);
+  plan->magic = kPlanMagic;
+  return MI_OK;
+}
 
 }  // namespace
 
@@ -689,17 +845,15 @@ int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_
   m.use_linear = use_linear; m.use_fm = use_fm; m.use_dnn = use_dnn; m.lin_bias_off = lin_bias_off;
   m.keep_prob = keep_prob; m.scale = scale; m.hp = *hp;
   m.workspace = workspace; m.workspace_bytes = workspace_bytes;
-  Args a;
-  size_t lds = 0;
-  int blocks = 0;
-  const int32_t rc = plan_model(m, field_off, B, F, step, ids && labels, logits && loss, sweep_blocks, a, lds, blocks);
-  if (rc != MI_OK) return rc;
-  a.ids = ids; a.labels = labels; a.logits = logits; a.loss = loss; a.seed = seed; a.step = step;
-  const int32_t rl = mi::raise_lds(&train_fused_k, lds, "train_step_fused");
-  if (rl != MI_OK) return rl;
-  train_fused_k<<<dim3(1 + blocks), dim3(kThreads), lds, mi::as_stream(stream)>>>(a);
-  MI_CHECK_LAUNCH("train_step_fused");
-  return MI_OK;
+  if (hp->kind != MI_OPT_ADAM) return unsupported("train_step_fused: optimizer kind %d (Adam only)", hp->kind);
+  return step_one(model_of(m, F), field_off, ids, labels, B, F, seed, step, logits, loss, sweep_blocks, stream);
+}
+
+int32_t mi_train_step_model(const mi_fused_model_t* model, const int64_t* field_off, const int32_t* ids, const uint8_t* labels,
+                            int64_t B, int32_t F, uint64_t seed, int32_t step, float* logits, float* loss, int32_t sweep_blocks,
+                            mi_stream_t stream) {
+  MI_REQUIRE(model, "train_step_fused: model");
+  return step_one(*model, field_off, ids, labels, B, F, seed, step, logits, loss, sweep_blocks, stream);
 }
 
 size_t mi_train_group_plan_bytes(int32_t n_members) {
@@ -713,58 +867,20 @@ int32_t mi_train_group_plan(const mi_fused_member_t* members, int32_t n_members,
   if (n_members > MI_FUSED_GROUP_MAX_MEMBERS)
     return unsupported("train_group_plan: %d members (at most %d in one launch)", n_members, MI_FUSED_GROUP_MAX_MEMBERS);
   MI_REQUIRE(members, "train_group_plan: members");
-  const size_t need = mi_train_group_plan_bytes(n_members);
-  if (!device_table || device_table_bytes < need) {
-    mi::set_error("train_group_plan: device table of %zu bytes, %zu needed", device_table_bytes, need);
-    return MI_ERR_WORKSPACE;
-  }
-  MI_REQUIRE(mi::aligned16(device_table), "train_group_plan: device_table (16-byte aligned)");
-  struct Owned { const void* p; int32_t member; };
-  const std::unique_ptr<Member[]> tab(new (std::nothrow) Member[n_members]);
-  const std::unique_ptr<Owned[]> owned(new (std::nothrow) Owned[11 * static_cast<size_t>(n_members)]);
-  MI_REQUIRE(tab && owned, "train_group_plan: out of host memory");
-  size_t n_owned = 0, lds = 0;
-  int blocks = 1;
-  int64_t max_step = INT32_MAX;
-  for (int32_t i = 0; i < n_members; ++i) {
-    const mi_fused_member_t& m = members[i];
-    size_t lds_i = 0;
-    int blocks_i = 0;
-    int32_t rc = plan_model(m, field_off, B, F, 1, true, true, 0, tab[i].a, lds_i, blocks_i);
-    if (rc == MI_OK && (!m.lr_table || m.lr_table_len < 2)) {
-      mi::set_error("train_step_fused: lr_table of %lld entries (lr_t of step s at [s], s >= 1)", (long long)m.lr_table_len);
-      rc = MI_ERR_INVALID;
-    }
-    if (rc != MI_OK) {
-      mi::member_error("train_group_plan", i);
-      return rc;
-    }
-    tab[i].lr_table = m.lr_table; tab[i].seed_base = m.seed_base; tab[i].lr_len = m.lr_table_len;
-    if (lds_i > lds) lds = lds_i;
-    if (blocks_i > blocks) blocks = blocks_i;
-    if (m.lr_table_len - 1 < max_step) max_step = m.lr_table_len - 1;
-    const void* own[11] = {tab[i].a.table, tab[i].a.tm, tab[i].a.tv, tab[i].a.lin_w, tab[i].a.lm, tab[i].a.lv, m.last_step,
-                           m.dense, m.d_m, m.d_v, m.workspace};
-    for (const void* p : own)
-      if (p) owned[n_owned++] = Owned{p, i};
-  }
-  // two members (or two roles of one member) on the same memory: every pointer above is written by its member's workgroups
-  qsort(owned.get(), n_owned, sizeof(Owned), [](const void* x, const void* y) {
-    const Owned* a = static_cast<const Owned*>(x);
-    const Owned* b = static_cast<const Owned*>(y);
-    return a->p < b->p ? -1 : (a->p > b->p ? 1 : (a->member < b->member ? -1 : (a->member > b->member ? 1 : 0)));
-  });
-  for (size_t j = 1; j < n_owned; ++j)
-    MI_REQUIRE(owned[j].p != owned[j - 1].p,
-               "train_group_plan: member %d and member %d share a state or workspace pointer (%p): members are independent",
-               owned[j - 1].member, owned[j].member, owned[j].p);
-  const int32_t rc = mi::upload_table(device_table, tab.get(), need, stream, "train_group_plan");
-  if (rc != MI_OK) return rc;
-  while (blocks > 1 && static_cast<int64_t>(1 + blocks) * n_members > kGroupGridBlocks) --blocks;
-  plan->device_table = device_table; plan->n_members = n_members; plan->B = static_cast<int32_t>(B); plan->F = F;
-  plan->lds_bytes = static_cast<uint32_t>(lds); plan->sweep_blocks = blocks; plan->max_step = static_cast<int32_t>(max_step);
-  plan->magic = kPlanMagic;
-  return MI_OK;
+  return plan_group([&](int32_t i) { return model_of(members[i], F); }, true, n_members, B, F, field_off, device_table,
+                    device_table_bytes, plan, stream);
+}
+
+int32_t mi_train_group_plan_models(const mi_fused_model_t* models, int32_t n_members, int64_t B, int32_t F,
+                                   const int64_t* field_off, void* device_table, size_t device_table_bytes,
+                                   mi_fused_group_plan_t* plan, mi_stream_t stream) {
+  MI_REQUIRE(plan, "train_group_plan: plan");
+  MI_REQUIRE(n_members >= 1, "train_group_plan: %d members (at least 1)", n_members);
+  if (n_members > MI_FUSED_GROUP_MAX_MEMBERS)
+    return unsupported("train_group_plan: %d members (at most %d in one launch)", n_members, MI_FUSED_GROUP_MAX_MEMBERS);
+  MI_REQUIRE(models, "train_group_plan: models");
+  return plan_group([&](int32_t i) { return models[i]; }, false, n_members, B, F, field_off, device_table, device_table_bytes,
+                    plan, stream);
 }
 
 int32_t mi_train_group_step(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids, int64_t ids_member_stride,
@@ -784,8 +900,9 @@ int32_t mi_train_group_step(const mi_fused_group_plan_t* plan, int32_t n_members
              (long long)labels_member_stride, (long long)B);
   if (sweep_blocks < 0 || sweep_blocks > kMaxSweepBlocks)
     return unsupported("train_group_step: sweep_blocks=%d (0 = the built-in choice, at most %d)", sweep_blocks, kMaxSweepBlocks);
-  const int blocks = sweep_blocks ? sweep_blocks : plan->sweep_blocks;
-  MI_REQUIRE(blocks >= 1 && blocks <= kMaxSweepBlocks && plan->lds_bytes <= kMaxLds, "train_group_step: plan (damaged)");
+  // (a plan without any part under Adam has no sweep: the batch workgroups alone, whatever sweep_blocks says)
+  const int blocks = plan->sweep_blocks == 0 ? 0 : (sweep_blocks ? sweep_blocks : plan->sweep_blocks);
+  MI_REQUIRE(blocks >= 0 && blocks <= kMaxSweepBlocks && plan->lds_bytes <= kMaxLds, "train_group_step: plan (damaged)");
   const int32_t rl = mi::raise_lds(&train_fused_group_k, plan->lds_bytes, "train_group_step");
   if (rl != MI_OK) return rl;
   train_fused_group_k<<<dim3(1 + blocks, n_members), dim3(kThreads), plan->lds_bytes, mi::as_stream(stream)>>>(

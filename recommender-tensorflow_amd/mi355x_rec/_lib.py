@@ -70,6 +70,14 @@ class FusedMember(C.Structure):
                 ("keep_prob", C.c_float), ("scale", C.c_float), ("hp", OptHparams)]
 
 
+class FusedModel(C.Structure):
+    """mi_fused_model_t: one model of mi_train_step_model / mi_train_group_plan_models — mi_fused_member_t's fields, then the
+    wide part's own rule, its dense slots and schedule, and the wide columns' mask"""
+    _fields_ = FusedMember._fields_ + [
+        ("two_rules", C.c_int32), ("hp_wide", OptHparams), ("dw_m", C.c_void_p), ("dw_v", C.c_void_p),
+        ("lr_table_wide", C.c_void_p), ("lr_table_wide_len", C.c_int64), ("wide_fields", C.c_uint64)]
+
+
 class FusedGroupPlan(C.Structure):
     """mi_fused_group_plan_t: what mi_train_group_plan leaves on the host for mi_train_group_step"""
     _fields_ = [("device_table", C.c_void_p), ("magic", C.c_uint64), ("n_members", C.c_int32), ("B", C.c_int32),
@@ -221,6 +229,8 @@ SIGNATURES = {
                                    _p, _p, _i32, _p, _sz, _p]),
     "mi_train_group_plan_bytes": (_sz, [_i32]),
     "mi_train_group_plan": (_i32, [_p, _i32, _i64, _i32, _p, _p, _sz, _p, _p]),
+    "mi_train_step_model": (_i32, [_p, _p, _p, _p, _i64, _i32, _u64, _i32, _p, _p, _i32, _p]),
+    "mi_train_group_plan_models": (_i32, [_p, _i32, _i64, _i32, _p, _p, _sz, _p, _p]),
     "mi_train_group_step": (_i32, [_p, _i32, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _i32, _p]),
     "mi_eval_group": (_i32, [_p, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _i32, _p]),
     "mi_predict_group_plan_bytes": (_sz, [_i32]),

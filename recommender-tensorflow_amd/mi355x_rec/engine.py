@@ -86,6 +86,7 @@ class HipKernels:
     """
 
     supports_planes = True        # the pre-split 16-bit operand path of the MLP (csrc/gemm_pl.hip)
+    supports_fused_rules = True   # the one-launch step under any optimizer, two rules, wide_fields (mi_train_step_model)
 
     def __init__(self):
         self.lib = _lib.load()
@@ -1200,12 +1201,14 @@ class DeepFM:
         """What keeps mi_train_step_fused from running a batch of B examples on this model, as text, or None."""
         if self.shard is not None:
             return "row-sharded tables (the fused step runs on one GPU)"
-        if self.opt.name != "Adam" or self.lin_opt is not None:
+        # (kernels without mi_train_step_model — a stand-in that restates mi_train_step_fused alone: that entry's scope)
+        rules = getattr(self.k, "supports_fused_rules", False)
+        if not rules and (self.opt.name != "Adam" or self.lin_opt is not None):
             return "optimizer %s%s (Adam for every variable, one schedule)" % (
                 self.opt.name, "" if self.lin_opt is None else " with linear_optimizer %s" % self.lin_opt.name)
         if self.n_numeric:
             return "%d numeric columns (categorical columns only)" % self.n_numeric
-        if self.field_dims is not None or self.wide_fields is not None:
+        if not rules and (self.field_dims is not None or self.wide_fields is not None):
             return "field_dims / wide_fields (the canned estimators' columns)"
         if not 1 <= self.F <= self.FUSED_STEP_LIMIT_FIELDS:
             return "%d categorical fields (1 to %d)" % (self.F, self.FUSED_STEP_LIMIT_FIELDS)
@@ -1240,14 +1243,45 @@ class DeepFM:
         """Bytes of per-row state the all-rows sweep of a fused step walks: table records + wide records."""
         return self.R * (self.ts * 4 * (self.table is not None) + 16 * (self.lin_state is not None))
 
+    def _fused_step_plain(self):
+        """Is this a model of mi_train_step_fused's own scope: Adam on every variable, one schedule, every column in both parts?"""
+        return self.opt.name == "Adam" and self.lin_opt is None and self.field_dims is None and self.wide_fields is None
+
+    def fused_model(self, B, workspace, lr_t=0.0, lin_lr_t=0.0):
+        """This model as a mi_fused_model_t for batches of B (mi_train_step_model, mi_train_group_plan_models): the struct and
+        the host tensors it points to, which the caller keeps alive with it.  The schedule tables and seed_base are the
+        population's to fill in."""
+        layer_off, widths = self._layer_tabs[0]
+        m = _lib.FusedModel()
+        _lib.set_ptrs(m, table=self.table, t_m=self.t_s0, t_v=self.t_s1, lin_w=self.lin_w, l_m=self.l_s0, l_v=self.l_s1,
+                      last_step=self.last_step, dense=self.dense, d_m=self.d_s0, d_v=self.d_s1, layer_off=layer_off,
+                      widths=widths, workspace=workspace)
+        m.table_stride, m.lin_stride, m.R, m.E, m.n_dense = self.ts, self.ls, self.R, self.E, self.P
+        m.n_layers, m.activation = len(self.layers), self.act
+        m.use_linear, m.use_fm, m.use_dnn = int(self.use_linear), int(self.use_mf), int(self.use_dnn)
+        m.lin_bias_off = self.lin_bias_off
+        m.keep_prob = float(1.0 - self.dropout if self.dropout > 0 else 1.0)
+        m.scale = float(np.float32(1.0 / B)) if self.reduction == "mean" else 1.0
+        m.hp = self.opt.hparams(lr_t)
+        m.workspace_bytes = workspace.numel()
+        if self.lin_opt is not None and self.use_linear:
+            m.two_rules = 1
+            m.hp_wide = self.lin_opt.hparams(lin_lr_t)
+            _lib.set_ptrs(m, dw_m=self.dl_s0, dw_v=self.dl_s1)
+        m.wide_fields = sum(1 << f for f in range(self.F) if self.wide_fields is None or self.wide_fields[f])
+        return m, (layer_off, widths, workspace)
+
     def fused_step_auto(self, B):
-        """Is the fused step the faster choice for this model and batch size (the measured thresholds above)?"""
-        return (self.fused_step_ok(B) and B <= self.FUSED_STEP_MAX_BATCH and self.state_bytes() <= self.FUSED_STEP_MAX_STATE_BYTES
+        """Is the fused step the faster choice for this model and batch size (the measured thresholds above)?  (Measured for
+        mi_train_step_fused's own scope only: the models mi_train_step_model adds stay with the replay until a table says
+        otherwise — profiles/fused_step_rules.md.)"""
+        return (self._fused_step_plain() and self.fused_step_ok(B) and B <= self.FUSED_STEP_MAX_BATCH and self.state_bytes() <= self.FUSED_STEP_MAX_STATE_BYTES
                 and 4 * self.dnn_end <= self.FUSED_STEP_MAX_WEIGHT_BYTES)
 
     def fused_train_step(self, ids, labels):
-        """One optimizer.minimize(loss) as ONE launch (mi_train_step_fused): returns (loss [1], logits [B]) device tensors,
-        no host sync.  The same step as train_step — same dropout masks, same Adam schedule — with TF's whole-table Adam
+        """One optimizer.minimize(loss) as ONE launch (mi_train_step_fused; mi_train_step_model for any other optimizer, a
+        linear_optimizer, field_dims or wide_fields): returns (loss [1], logits [B]) device tensors,
+        no host sync.  The same step as train_step — same dropout masks, same Adam schedule(s) — with TF's whole-table Adam
         sweep done literally: after it every row is current (no catch-up is owed).  May follow and be followed by
         train_step / graph_train_step / loss / predict_fused / top_k / state_dict in any order."""
         B = int(ids.shape[0])
@@ -1270,6 +1304,15 @@ class DeepFM:
                                torch.empty(B, dtype=torch.float32, device=self.device))
         ws, loss, logits = bufs
         step = self.step + 1
+        if not self._fused_step_plain():
+            lr_t = self.sched.lr_t(step) if self.sched else 0.0
+            lin_lr_t = self.lin_sched.lr_t(step) if self.lin_sched else 0.0
+            model, _ = self.fused_model(B, ws, lr_t, lin_lr_t)
+            k.mi_train_step_model(model, self.field_off, ids, labels, B, self.F, self._layer_seed(0), step, logits, loss,
+                                  int(self.FUSED_STEP_SWEEP_BLOCKS))
+            self.step = step
+            self._final_step = step
+            return loss, logits
         hp = self.opt.hparams(self.sched.lr_t(step))
         scale = np.float32(1.0 / B) if self.reduction == "mean" else np.float32(1.0)
         keep = 1.0 - self.dropout if self.dropout > 0 else 1.0

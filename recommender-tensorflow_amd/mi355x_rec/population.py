@@ -70,6 +70,18 @@ class FusedPopulation:
         E = e.E if e.use_emb else 4
         nbytes = int(self.k.query("mi_train_step_fused_workspace_bytes", B, e.F, E, e.P))
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=e.device)
+        if not e._fused_step_plain():
+            # any other optimizer, a linear_optimizer, field_dims / wide_fields: the general description
+            m, held = e.fused_model(B, ws)
+            keep_alive += list(held)
+            for sched, tab, n in ((e.sched, "lr_table", "lr_table_len"),
+                                  (e.lin_sched if m.two_rules else None, "lr_table_wide", "lr_table_wide_len")):
+                if sched is not None:
+                    keep_alive.append(sched.table)
+                    _lib.set_ptrs(m, **{tab: sched.table})
+                    setattr(m, n, int(sched.table.numel()))
+            m.seed_base = (e.seed * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)
+            return m
         keep_alive += [layer_off, widths, ws, e.sched.table]
         m = _lib.FusedMember()
         _lib.set_ptrs(m, table=e.table, t_m=e.t_s0, t_v=e.t_s1, lin_w=e.lin_w, l_m=e.l_s0, l_v=e.l_s1, last_step=e.last_step,
@@ -87,14 +99,38 @@ class FusedPopulation:
         m.workspace_bytes = ws.numel()
         return m
 
+    @staticmethod
+    def _scheds(e):
+        """the Adam schedules member e steps by (none under the other optimizers; two with two different Adams)"""
+        out = [s for s in (e.sched, e.lin_sched) if s is not None]
+        return out[:1] if len(out) == 2 and out[0] is out[1] else out
+
+    def _gens(self):
+        return [[s.gen for s in self._scheds(e)] for e in self.engines]
+
     def _build(self, B):
         keep_alive = []
-        members = (_lib.FusedMember * self.M)(*[self._describe(e, B, keep_alive) for e in self.engines])
         nbytes = int(self.k.query("mi_train_group_plan_bytes", self.M))
         table = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
         plan = _lib.FusedGroupPlan()
-        self.k.mi_train_group_plan(members, self.M, B, self.F, self.engines[0].field_off, table, table.numel(), plan)
-        self._plans[B] = (B, plan, table, [e.sched.gen for e in self.engines], keep_alive)
+        if all(e._fused_step_plain() for e in self.engines):
+            members = (_lib.FusedMember * self.M)(*[self._describe(e, B, keep_alive) for e in self.engines])
+            self.k.mi_train_group_plan(members, self.M, B, self.F, self.engines[0].field_off, table, table.numel(), plan)
+        else:
+            # (a member of mi_train_step_fused's own scope among them: the same description with one rule and every field wide)
+            descs = []
+            for e in self.engines:
+                d = self._describe(e, B, keep_alive)
+                if isinstance(d, _lib.FusedMember):
+                    g = _lib.FusedModel()
+                    for name, _ in _lib.FusedMember._fields_:
+                        setattr(g, name, getattr(d, name))
+                    g.wide_fields = (1 << e.F) - 1
+                    d = g
+                descs.append(d)
+            members = (_lib.FusedModel * self.M)(*descs)
+            self.k.mi_train_group_plan_models(members, self.M, B, self.F, self.engines[0].field_off, table, table.numel(), plan)
+        self._plans[B] = (B, plan, table, self._gens(), keep_alive)
         return self._plans[B]
 
     def _check_limits(self, B):
@@ -109,7 +145,7 @@ class FusedPopulation:
         plan = self._plans.get(B)
         if plan is None:
             self._check_limits(B)
-        if plan is None or any(e.sched.gen != g for e, g in zip(self.engines, plan[3])):
+        if plan is None or self._gens() != plan[3]:
             plan = self._build(B)
         return plan
 
@@ -143,8 +179,9 @@ class FusedPopulation:
         if step >= self._table_len or any(e._final_step != e.step for e in engines):
             for e in engines:
                 e.finalize_rows()                     # (a no-op after a fused step)
-                e.sched.lr_t(step)                    # (extends the member's table when the run outgrows it: gen changes)
-            self._table_len = min(len(e.sched.host) for e in engines)
+                for s in self._scheds(e):
+                    s.lr_t(step)                      # (extends the member's table when the run outgrows it: gen changes)
+            self._table_len = min([len(s.host) for e in engines for s in self._scheds(e)] or [1 << 62])
         plan = self._plan_for(B)
         self._last_b = B
         if out is None:

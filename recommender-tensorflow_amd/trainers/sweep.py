@@ -33,8 +33,14 @@ AUC weighted by the group's examples, and "gauc_groups".  --select takes auc_exa
 --auc-method sorted counts the same integers by sorting every member's logits on the device (mi_auc_sorted_counts) instead
 of comparing every pair: the way for test sets of millions of examples.
 
-trainers.deep_fm has no learning-rate flag (the reference has none): a member restored through ``trainers.deep_fm
---restore`` continues at that CLI's 0.001, a member restored through ``trainers.sweep --restore`` at its own rate."""
+--optimizer NAME [NAME ...]: model_fn's params["optimizer"] joins the grid — any of model_utils.get_optimizer's Adagrad,
+Adam, Ftrl, RMSProp and SGD; the members of one population may differ in it (the one-launch step applies each member's own
+rule).  Without the flag every member trains under Adam and its hyper-parameters carry no "optimizer" key.
+
+trainers.deep_fm has neither a learning-rate nor an optimizer flag (the reference has none): a member restored through
+``trainers.deep_fm --restore`` continues at that CLI's 0.001 and under ITS optimizer, Adam (whose slots are not the ones an
+Adagrad, Ftrl, RMSProp or SGD member saved); a member restored through ``trainers.sweep --restore`` with the flags it was
+made with continues at its own rate under its own optimizer."""
 import itertools
 import json
 import os
@@ -53,6 +59,7 @@ from mi355x_rec.predictor import EnsemblePredictor
 from mi355x_rec.population import FusedPopulation
 from trainers import _cli, deep_fm
 from trainers.conf_utils import get_exporter
+from trainers.model_utils import _OPTIMIZERS
 from trainers.ml_100k import _read_csv, get_feature_columns, get_input_fn, serving_input_fn
 
 _KEPT = ("--train-csv", "--test-csv", "--restore", "--batch-size", "--train-steps", "--device", "--catchup", "--synthetic")
@@ -88,6 +95,9 @@ def make_parser():
         flag, kw = _cli._OPTIONAL[name]
         p.add_argument(flag, **kw)
     p.add_argument("--learning-rate", type=float, nargs="+", default=[0.001], help="Adam learning rates (default: %(default)s)")
+    p.add_argument("--optimizer", nargs="+", default=None, choices=sorted(_OPTIMIZERS), metavar="NAME",
+                   help="optimizers of the grid, model_fn's params[\"optimizer\"]: " + ", ".join(sorted(_OPTIMIZERS)) +
+                        "; --learning-rate is then that optimizer's (default: Adam only)")
     p.add_argument("--dropout", type=float, nargs="+", default=[0.1], help="dropout rates (default: %(default)s)")
     p.add_argument("--embedding-size", type=int, nargs="+", default=[4], help="embedding sizes (default: %(default)s)")
     p.add_argument("--hidden-units", type=int, nargs="+", action="append", default=None,
@@ -191,6 +201,11 @@ def grid(args):
         raise ValueError("--seeds %d (at least 1)" % args.seeds)
     out = [dict(embedding_size=E, hidden_units=list(h), dropout=d, learning_rate=lr, seed=s)
            for E, h, d, lr, s in itertools.product(args.embedding_size, specs, args.dropout, args.learning_rate, range(args.seeds))]
+    names = getattr(args, "optimizer", None)
+    if names:                                     # (the key exists only with the flag: the default grid's dicts stay as they were)
+        out = [dict(embedding_size=E, hidden_units=list(h), dropout=d, learning_rate=lr, optimizer=o, seed=s)
+               for E, h, d, lr, o, s in itertools.product(args.embedding_size, specs, args.dropout, args.learning_rate, names,
+                                                          range(args.seeds))]
     if len(out) > FusedPopulation.MAX_MEMBERS:
         raise ValueError("the grid has %d members (at most %d train in one launch): split the sweep" % (
             len(out), FusedPopulation.MAX_MEMBERS))
@@ -225,7 +240,8 @@ def build(members, features, labels, batch_size):
         est._first_call(features, labels, ModeKeys.TRAIN)
         why = est._engine()._fused_step_limit(batch_size)
         if why is not None:
-            hp = {k: est.params[k] for k in ("embedding_size", "hidden_units", "dropout", "learning_rate", "seed")}
+            hp = {k: est.params[k] for k in ("embedding_size", "hidden_units", "dropout", "learning_rate", "optimizer", "seed")
+                  if k in est.params}
             raise ValueError("member %d (%s): the model has %s; a sweep trains models inside the fused step's scope" % (i, hp, why))
     steps = [est.global_step for est in members]
     if len(set(steps)) > 1:

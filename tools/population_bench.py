@@ -5,7 +5,8 @@
     B  M launches, one per model          a Python loop of M DeepFM.fused_train_step calls on M engines
 
 for the reference's default configuration (trainers.deep_fm: E=4, hidden [16,16], B=32, the 26 MovieLens fields, dropout
-0.1) at M = 1 .. 256, and one row with mixed members (half default, half E 16 [64, 64, 32]) at M = 16.
+0.1) at M = 1 .. 256, one row with mixed members (half default, half E 16 [64, 64, 32]) at M = 16, and one row of 16 default
+models under mixed optimizers (Adam, Adagrad, Ftrl on the wide part + Adagrad, RMSProp, SGD in turn: mi_train_group_plan_models).
 
 Protocol (tools/small_step_bench.py): both paths in ONE process on engines with identical initial
 state; every path walks the same ring of ROTATE different batches; a block is STEPS consecutive steps of one path between
@@ -34,10 +35,16 @@ VOCAB = [2] * 19 + [1000, 2000, 50, 1000, 7, 8, 3]
 DEFAULT, LARGE = (4, [16, 16]), (16, [64, 64, 32])
 
 
+RULES = [dict(optimizer=OptimizerSpec("Adam", 0.001)), dict(optimizer=OptimizerSpec("Adagrad", 0.05)),
+         dict(optimizer=OptimizerSpec("Adagrad", 0.05), linear_optimizer=OptimizerSpec("Ftrl", 0.2)),
+         dict(optimizer=OptimizerSpec("RMSProp", 0.001)), dict(optimizer=OptimizerSpec("SGD", 0.05))]
+
+
 def engines(shapes):
     out = []
-    for i, (E, hidden) in enumerate(shapes):
-        m = DeepFM(VOCAB, embedding_size=E, hidden_units=hidden, dropout=0.1, optimizer=OptimizerSpec("Adam", 0.001), seed=i)
+    for i, (E, hidden, *kw) in enumerate(shapes):
+        kw = kw[0] if kw else dict(optimizer=OptimizerSpec("Adam", 0.001))
+        m = DeepFM(VOCAB, embedding_size=E, hidden_units=hidden, dropout=0.1, seed=i, **kw)
         g = torch.Generator(device="cuda")
         g.manual_seed(i)
         m.init_variables(g, lin_scale=1e-3)
@@ -62,6 +69,7 @@ def main():
     cases = [("default", [DEFAULT] * M) for M in args.members]
     if not args.only_a:
         cases.append(("mixed: half default, half E 16 [64, 64, 32]", [DEFAULT, LARGE] * 8))
+        cases.append(("mixed optimizers: default model, five rules in turn", [DEFAULT + (RULES[i % 5],) for i in range(16)]))
     cells = []
     for name, shapes in cases:
         M = len(shapes)

@@ -14,6 +14,8 @@ synchronisations, timed on the host clock (the host's cost is part of what a use
 alternate; per path the median and the 10th / 90th percentile over BLOCKS blocks are reported.
 
     python tools/small_step_bench.py [--json FILE] [--blocks N] [--steps N]
+    python tools/small_step_bench.py --rules ...     the legs of profiles/fused_step_rules.md instead: B = 32, the three canned
+                                                     CLIs' default models and the default DeepFM under Adagrad, Ftrl, RMSProp, SGD
 """
 import argparse
 import json
@@ -23,6 +25,8 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "recommender-tensorflow_amd"))
+import math
+
 import numpy as np
 import torch
 from mi355x_rec.engine import DeepFM, OptimizerSpec
@@ -45,10 +49,23 @@ CASES = [
 ]
 
 
-def engines(voc, E, hidden, n):
+_FTRL = OptimizerSpec("Ftrl", min(0.2, 1.0 / math.sqrt(26)))        # trainers/linear.py:30
+# --rules: name, vocab, E, hidden, batch sizes, engine arguments (mi_train_step_model's models: DESIGN section 11)
+RULE_CASES = [
+    ("trainers.linear (Ftrl)", vocab(), 4, [], (32,), dict(use_mf=False, use_dnn=False, optimizer=_FTRL, reduction="sum", dropout=0.0)),
+    ("trainers.deep (Adagrad)", vocab(), 4, [16, 16], (32,),
+     dict(use_linear=False, use_mf=False, optimizer=OptimizerSpec("Adagrad", 0.05), reduction="sum")),
+    ("trainers.linear_deep (Ftrl + Adagrad)", vocab(), 4, [16, 16], (32,),
+     dict(use_mf=False, optimizer=OptimizerSpec("Adagrad", 0.05), linear_optimizer=_FTRL, reduction="sum")),
+] + [("default DeepFM, %s" % name, vocab(), 4, [16, 16], (32,), dict(optimizer=OptimizerSpec(name, lr)))
+     for name, lr in (("Adagrad", 0.05), ("Ftrl", 0.05), ("RMSProp", 0.001), ("SGD", 0.05))]
+
+
+def engines(voc, E, hidden, n, **kw):
     out = []
+    kw = dict(dict(dropout=0.1, optimizer=OptimizerSpec("Adam", 0.001)), **kw)
     for _ in range(n):
-        m = DeepFM(voc, embedding_size=E, hidden_units=hidden, dropout=0.1, optimizer=OptimizerSpec("Adam", 0.001))
+        m = DeepFM(voc, embedding_size=E, hidden_units=hidden, **kw)
         g = torch.Generator(device="cuda")
         g.manual_seed(0)
         m.init_variables(g, lin_scale=1e-3)
@@ -61,11 +78,12 @@ def main():
     ap.add_argument("--json", default=None, help="also write every cell to this file")
     ap.add_argument("--blocks", type=int, default=7)
     ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--rules", action="store_true", help="the legs of profiles/fused_step_rules.md instead of the Adam cases")
     args = ap.parse_args()
     cells = []
-    for name, voc, E, hidden, batches in CASES:
+    for name, voc, E, hidden, batches, *kw in (RULE_CASES if args.rules else CASES):
         for B in batches:
-            eager, graph, fused = engines(voc, E, hidden, 3)
+            eager, graph, fused = engines(voc, E, hidden, 3, **(kw[0] if kw else {}))
             g = torch.Generator(device="cuda")
             g.manual_seed(1)
             ring = []
