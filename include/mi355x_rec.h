@@ -1192,6 +1192,73 @@ int32_t mi_auc_sorted_counts(const float* logits, int64_t member_stride, int32_t
                              const int32_t* groups, int32_t n_groups, int64_t N, int64_t* counts, void* workspace,
                              size_t workspace_bytes, mi_stream_t stream);
 
+/* ---- (a1) categorical id transforms on the device: raw feature columns to row ids in one launch (csrc/ids.hip) ----------
+ * The device form of the host entries above (the column constructors of trainers/ml_100k.py:19-35):
+ * F raw columns of B values become ids int32 [B, ld] (ld >= F; columns F..ld-1 and rows past B are not touched) in the
+ * plan's field order.  Integer work only; every id equals what the matching host definition gives.
+ *
+ * mi_ids_column_t describes one column.  The table of F descriptors lies in HOST memory and travels in the kernel's
+ * arguments: the entry makes no allocation, no copy and no synchronisation, and can be captured in a graph.
+ *   MI_IDS_HASH_I64 / _I32   values int64 / int32 [B]: Fingerprint64 of the value's decimal ASCII ('-' for negatives, as
+ *                            "%lld" prints them) mod num_buckets — mi_hash_bucket_i64;
+ *   MI_IDS_HASH_BYTES        values uint8 (the strings, back to back), offsets int64 [B + 1]: Fingerprint64 of
+ *                            values[offsets[i] : offsets[i+1]] mod num_buckets — mi_hash_bucket_bytes.  Any length;
+ *   MI_IDS_BUCKETIZE_F32     values float [B], table = n_table boundaries (float, device), table_host = the same
+ *                            boundaries in host memory (the entry cannot look at device memory: it checks these): the
+ *                            number of boundaries <= x, NaN -> 0 — mi_bucketize_f32;
+ *   MI_IDS_VOCAB_BYTES       values / offsets as MI_IDS_HASH_BYTES, table = the vocabulary table of n_table entries (below):
+ *                            the entry's list index; a value not in the list gives n_table + Fingerprint64 % num_oov, or
+ *                            default_value when num_oov == 0;
+ *   MI_IDS_IDENTITY_I64/_I32 values int64 / int32 [B]: the value itself, or default_value when it is outside
+ *                            [0, num_buckets).
+ * The vocabulary table, built by the host once per plan, is ONE block of device memory, 8-byte aligned, n = n_table:
+ *   uint64 fingerprint[n]   the entries' Fingerprint64, ascending;
+ *   int64  start[n + 1]     entry j's bytes are text[start[j] : start[j+1]];
+ *   int32  index[n]         entry j's position in the vocabulary list (followed by 4 bytes of padding when n is odd);
+ *   uint8  text[]           the entries' bytes in the fingerprints' order.
+ * A value is looked up by a binary search on its fingerprint, then a comparison of the bytes of every entry that carries
+ * that fingerprint (a fingerprint match alone is not the contract), then the index.
+ * PRECONDITION of the two bytes kinds: wherever 0 <= offsets[i] <= offsets[i+1], offsets[i+1] is at most the length of
+ * `values` — the entry cannot look at device memory.  No byte outside a string's own range is read.
+ *
+ * A BAD value is one whose id would be < 0 or >= num_buckets (a vocabulary miss with default -1, an identity value out of
+ * range whose default_value is out of range too — -1 stands for "no default" —, offsets[i+1] < offsets[i] or
+ * offsets[i] < 0).  No id outside [0, num_buckets) is ever stored: for a bad value of column f the kernel stores id 0, adds 1
+ * to status[2 f] and takes the maximum of 2^31 - 1 - i into status[2 f + 1], i the example's index: in a status the caller
+ * ZEROED, 2^31 - 1 - status[2 f + 1] is the lowest bad example of column f where status[2 f] > 0.  status: int32 [F, 2]
+ * (device); integer atomics, so the result does not depend on order.  Two calls on equal input give equal bits.  No
+ * workgroup reads what another writes and none waits for another.  The mod is exact for every 64-bit fingerprint and
+ * every num_buckets in [1, 2^31 - 1].
+ * Refused on the host before anything is launched, ids and status untouched, the message naming the column's index
+ * (MI_ERR_INVALID): NULL columns / ids / status, F outside [1, MI_IDS_MAX_COLUMNS], B outside [1, 2^31 - 1], ld < F, an
+ * unknown kind, NULL values, NULL offsets of a bytes kind, num_buckets outside [1, 2^31 - 1], n_table < 0, NULL table or
+ * table_host with n_table > 0, boundaries that are not strictly increasing or more than num_buckets - 1 of them, a
+ * vocabulary of n_table < 1 entries or with n_table + num_oov > num_buckets, num_oov < 0.
+ *
+ * mi_fingerprint64_device: out[i] = Fingerprint64(bytes[offsets[i] : offsets[i+1]]) for i < n, raw, uint64 [n] (device).
+ * A range with offsets[i+1] < offsets[i] or offsets[i] < 0 counts as the empty string.  One launch; refused
+ * (MI_ERR_INVALID): n outside [1, 2^31 - 1], NULL offsets / out. */
+#define MI_IDS_MAX_COLUMNS 64
+enum mi_ids_kind {
+  MI_IDS_HASH_I64 = 0,
+  MI_IDS_HASH_I32 = 1,
+  MI_IDS_HASH_BYTES = 2,
+  MI_IDS_BUCKETIZE_F32 = 3,
+  MI_IDS_VOCAB_BYTES = 4,
+  MI_IDS_IDENTITY_I64 = 5,
+  MI_IDS_IDENTITY_I32 = 6
+};
+typedef struct mi_ids_column {
+  const void* values;
+  const int64_t* offsets;
+  const void* table;
+  const float* table_host;
+  int32_t kind, num_buckets, n_table, num_oov, default_value, reserved;
+} mi_ids_column_t;
+int32_t mi_ids_transform(const mi_ids_column_t* columns, int32_t F, int64_t B, int32_t* ids, int64_t ld, int32_t* status,
+                         mi_stream_t stream);
+int32_t mi_fingerprint64_device(const uint8_t* bytes, const int64_t* offsets, int64_t n, uint64_t* out, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

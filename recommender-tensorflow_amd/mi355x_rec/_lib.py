@@ -122,6 +122,18 @@ class AucPlan(C.Structure):
                 ("n_items", C.c_int32)]
 
 
+IDS_MAX_COLUMNS = 64  # MI_IDS_MAX_COLUMNS
+# enum mi_ids_kind
+IDS_HASH_I64, IDS_HASH_I32, IDS_HASH_BYTES, IDS_BUCKETIZE_F32, IDS_VOCAB_BYTES, IDS_IDENTITY_I64, IDS_IDENTITY_I32 = range(7)
+
+
+class IdsColumn(C.Structure):
+    """mi_ids_column_t: one raw feature column of mi_ids_transform"""
+    _fields_ = [("values", C.c_void_p), ("offsets", C.c_void_p), ("table", C.c_void_p), ("table_host", C.c_void_p),
+                ("kind", C.c_int32), ("num_buckets", C.c_int32), ("n_table", C.c_int32), ("num_oov", C.c_int32),
+                ("default_value", C.c_int32), ("reserved", C.c_int32)]
+
+
 _p = C.c_void_p
 _i32, _i64, _u32, _u64, _f32, _sz = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_size_t
 _amax = C.POINTER(GemmAmax)
@@ -241,6 +253,8 @@ SIGNATURES = {
     "mi_auc_pair_counts": (_i32, [_p, _p, _i64, _i32, _p, _p, _p]),
     "mi_auc_sorted_workspace_bytes": (_sz, [_i64, _i32]),
     "mi_auc_sorted_counts": (_i32, [_p, _i64, _i32, _p, _p, _i32, _i64, _p, _p, _sz, _p]),
+    "mi_ids_transform": (_i32, [_p, _i32, _i64, _p, _i64, _p, _p]),
+    "mi_fingerprint64_device": (_i32, [_p, _p, _i64, _p, _p]),
 }
 
 _lib = None

@@ -28,6 +28,37 @@ class _Categorical:
         self.name = name or key
 
 
+def encode_strings(v):
+    """A column of n strings as (blob bytes, offsets int64 [n + 1]): value i is blob[offsets[i]:offsets[i + 1]], the
+    utf-8 of str(value) (bytes values as they are) — what Fingerprint64 is taken of, on the host and on the device."""
+    n = len(v)
+    arr = np.asarray(v)
+    blob = offs = None
+    # the whole column at once: numpy encodes ASCII strings into a fixed-width byte matrix at C speed; the
+    # padding is cut out with one boolean index.  Anything that path would change takes the per-element path
+    # below (the bytes mean the same in either case: utf-8 of str(value)): non-ASCII text (the encode raises),
+    # values that are neither str nor bytes (len() raises), trailing NULs, which a fixed-width array drops
+    # (the total length then differs from Python's).
+    if n and arr.dtype.kind in "OUS":
+        try:
+            sa = arr if arr.dtype.kind == "S" else arr.astype("S")
+            w = sa.dtype.itemsize
+            lens = np.char.str_len(sa).astype(np.int64)
+            if w and int(lens.sum()) == (sum(map(len, v)) if not (isinstance(v, np.ndarray) and arr.dtype.kind in "US") else int(lens.sum())):
+                mat = np.ascontiguousarray(sa).view(np.uint8).reshape(n, w)
+                blob = mat[np.arange(w)[None, :] < lens[:, None]].tobytes()
+                offs = np.zeros(n + 1, np.int64)
+                np.cumsum(lens, out=offs[1:])
+        except (UnicodeEncodeError, ValueError, TypeError):
+            blob = offs = None
+    if blob is None:
+        enc = [x if isinstance(x, bytes) else str(x).encode("utf-8") for x in v]
+        offs = np.zeros(n + 1, np.int64)
+        np.cumsum([len(e) for e in enc], out=offs[1:])
+        blob = b"".join(enc)
+    return blob, offs
+
+
 class HashBucketColumn(_Categorical):
     """categorical_column_with_hash_bucket: Fingerprint64(as_string(v)) mod hash_bucket_size."""
 
@@ -49,29 +80,7 @@ class HashBucketColumn(_Categorical):
             a = np.ascontiguousarray(arr, np.int64)
             _lib.check(lib.mi_hash_bucket_i64(a.ctypes.data, n, self.num_buckets, out.ctypes.data), "mi_hash_bucket_i64")
         else:
-            blob = offs = None
-            # the whole column at once: numpy encodes ASCII strings into a fixed-width byte matrix at C speed; the
-            # padding is cut out with one boolean index.  Anything that path would change takes the per-element path
-            # below (the bytes mean the same in either case: utf-8 of str(value)): non-ASCII text (the encode raises),
-            # values that are neither str nor bytes (len() raises), trailing NULs, which a fixed-width array drops
-            # (the total length then differs from Python's).
-            if n and arr.dtype.kind in "OUS":
-                try:
-                    sa = arr if arr.dtype.kind == "S" else arr.astype("S")
-                    w = sa.dtype.itemsize
-                    lens = np.char.str_len(sa).astype(np.int64)
-                    if w and int(lens.sum()) == (sum(map(len, v)) if not (isinstance(v, np.ndarray) and arr.dtype.kind in "US") else int(lens.sum())):
-                        mat = np.ascontiguousarray(sa).view(np.uint8).reshape(n, w)
-                        blob = mat[np.arange(w)[None, :] < lens[:, None]].tobytes()
-                        offs = np.zeros(n + 1, np.int64)
-                        np.cumsum(lens, out=offs[1:])
-                except (UnicodeEncodeError, ValueError, TypeError):
-                    blob = offs = None
-            if blob is None:
-                enc = [x if isinstance(x, bytes) else str(x).encode("utf-8") for x in v]
-                offs = np.zeros(n + 1, np.int64)
-                np.cumsum([len(e) for e in enc], out=offs[1:])
-                blob = b"".join(enc)
+            blob, offs = encode_strings(v)
             buf = C.create_string_buffer(blob, max(len(blob), 1))
             _lib.check(lib.mi_hash_bucket_bytes(C.addressof(buf), offs.ctypes.data, n, self.num_buckets,
                                                 out.ctypes.data), "mi_hash_bucket_bytes")
@@ -248,6 +257,12 @@ def column_from_json(d):
     raise ValueError("unknown column kind %r" % (kind,))
 
 
+def bad_id_message(c, bad):
+    """What FieldPlan.transform (and the device transform) say of column c's id `bad`, which no table row stands for."""
+    return ("column %r produced id %d outside [0, %d): give the column num_oov_buckets (or a default_value inside the "
+            "vocabulary); the HIP path has no dropped-id row" % (c.name, int(bad), c.num_buckets))
+
+
 class FieldPlan:
     """Lowering of (categorical_columns, numeric_columns) to the fused-table layout.
 
@@ -273,6 +288,8 @@ class FieldPlan:
         if len(set(names)) != len(names):
             raise ValueError("duplicate column names: %s" % names)
         self.vocab_sizes = [c.num_buckets for c in self.categorical]
+        self.device_mode = "off"          # set_device_mode
+        self._on_device = {}
 
     def transform(self, features):
         """features: dict key -> sequence of B raw values.  Returns (ids int32 [B,F], x float32 [B,n_d] or None)."""
@@ -283,16 +300,43 @@ class FieldPlan:
             # value of a vocabulary column without OOV buckets: zero embedding, zero linear term) and fails
             # on ids >= num_buckets; neither may reach the device here.
             if v.size and (v.min() < 0 or v.max() >= c.num_buckets):
-                bad = v[(v < 0) | (v >= c.num_buckets)][0]
-                raise ValueError("column %r produced id %d outside [0, %d): give the column num_oov_buckets (or a "
-                                 "default_value inside the vocabulary); the HIP path has no dropped-id row"
-                                 % (c.name, int(bad), c.num_buckets))
+                raise ValueError(bad_id_message(c, v[(v < 0) | (v >= c.num_buckets)][0]))
             cols.append(v)
         ids = (np.stack(cols, 1) if cols else np.zeros((self._batch_size(features), 0))).astype(np.int32)
         x = None
         if self.numeric:
             x = np.stack([c.values(features) for c in self.numeric], 1).astype(np.float32)
         return np.ascontiguousarray(ids), x
+
+    def device_transform(self, device, kernels=None):
+        """The same transform with the raw columns taken to `device` and turned into ids there, in one launch
+        (mi_ids_transform): a device_transform.DeviceTransform.  Columns it cannot take stay on this host transform; it
+        names them and why (`.refused`)."""
+        from .device_transform import DeviceTransform
+        return DeviceTransform(self, device, kernels)
+
+    def set_device_mode(self, mode):
+        """"on": whoever transforms with this plan (model.run_batch, model.side_inputs, Predictor) takes the raw columns to
+        the device and transforms them there; "off" (the default): the host transform."""
+        if mode not in ("off", "on"):
+            raise ValueError("device_transform must be 'off' or 'on'")
+        self.device_mode = mode
+
+    def on_device(self, device, kernels=None, fields=None, say=None):
+        """The plan's DeviceTransform for `device`, made once — of the whole plan, or (fields: categorical fields 0..F-1,
+        numeric column j as F + j) of one side's columns alone.  say(text) is told once of every column that stays on the
+        host transform."""
+        key = (str(device), None if fields is None else tuple(fields))
+        dt = self._on_device.get(key)
+        if dt is None:
+            plan = self
+            if fields is not None:
+                F = len(self.categorical)
+                plan = FieldPlan([self.categorical[f] for f in fields if f < F], [self.numeric[f - F] for f in fields if f >= F])
+            dt = self._on_device[key] = plan.device_transform(device, kernels)
+            for _, name, why in dt.refused:
+                (say or print)("INFO: device_transform: column %r stays on the host transform: %s" % (name, why))
+        return dt
 
     def _batch_size(self, features):
         for c in self.numeric:

@@ -52,6 +52,8 @@ def split_sides(plan, query_features, candidate_features):
 
 def side_inputs(plan, fields, features, device):
     """ids int32 [n, Fx] and numeric values float32 [n, nx] (or None) of one side's columns, ascending field order."""
+    if plan.device_mode == "on":         # the side's raw columns to the device, its ids made there (device_transform.py)
+        return plan.on_device(device, fields=fields).transform(features)
     F = len(plan.categorical)
     cat = [plan.categorical[f] for f in fields if f < F]
     num = [plan.numeric[f - F] for f in fields if f >= F]
@@ -120,6 +122,7 @@ def run_batch(features, labels, mode, params, make_engine):
     if "engine" not in store:
         plan = FieldPlan(params.get("categorical_columns", []), params.get("numeric_columns", []))
         device = params.get("device", "cuda")
+        plan.set_device_mode(params.get("device_transform", "off"))
         store["plan"] = plan
         shard = params.get("_shard")           # parallel.RowShard of a multi-GPU launch (trainers/_cli.py), else None
         eng = store["engine"] = make_engine(plan, device, shard) if shard is not None else make_engine(plan, device)
@@ -135,30 +138,43 @@ def run_batch(features, labels, mode, params, make_engine):
     plan, eng = store["plan"], store["engine"]
     dev = eng.device
     ahead = params.get("_ahead")
+    # params["device_transform"] = "on": the batch's raw columns go to the device and become ids there in one launch
+    # (mi_ids_transform), bit for bit the host transform's; "off" (the default): the host transform and a copy of its ids
+    on_device = plan.device_mode == "on"
     if ahead is not None and mode == ModeKeys.TRAIN and ahead.get("features") is features:
         # small batches (Estimator.train groups them): the id transforms of a whole group of batches were done in one
         # call and copied to the device once; this batch is rows lo..hi of the group
         g = ahead["group"]
         if "ids" not in g:
-            ids_np, x_np = plan.transform(g["features"])
-            g["ids"] = torch.from_numpy(ids_np).to(dev)
-            g["x"] = torch.from_numpy(x_np).to(dev) if x_np is not None else None
+            if on_device:
+                g["ids"], g["x"] = plan.on_device(dev, eng.k).transform(g["features"])
+            else:
+                ids_np, x_np = plan.transform(g["features"])
+                g["ids"] = torch.from_numpy(ids_np).to(dev)
+                g["x"] = torch.from_numpy(x_np).to(dev) if x_np is not None else None
             g["y"] = torch.from_numpy(np.ascontiguousarray(np.asarray(g["labels"]).reshape(-1)).astype(np.uint8)).to(dev)
         lo, hi = ahead["rows"]
         ids, y = g["ids"][lo:hi], g["y"][lo:hi]
         x = g["x"][lo:hi] if g["x"] is not None else None
     else:
         def stage(f, l):
-            ids_np, x_np = plan.transform(f)
+            """(ids, x, y, status): status is None on the host transform, which has checked its ids; the device transform's
+            is looked at when the batch is used (TransformStatus.raise_if_bad: it waits for its own status copy only)"""
             y_ = None
             if l is not None:
                 y_ = torch.from_numpy(np.ascontiguousarray(np.asarray(l).reshape(-1)).astype(np.uint8)).to(dev)
-            return (torch.from_numpy(ids_np).to(dev), torch.from_numpy(x_np).to(dev) if x_np is not None else None, y_)
+            if on_device:
+                ids_, x_, st = plan.on_device(dev, eng.k).transform(f, check=False)
+                return (ids_, x_, y_), st
+            ids_np, x_np = plan.transform(f)
+            return (torch.from_numpy(ids_np).to(dev), torch.from_numpy(x_np).to(dev) if x_np is not None else None, y_), None
         staged = store.pop("staged", None)          # this batch, transformed and copied a step ago (Estimator._with_lookahead)
         if staged is not None and staged[0] is features and mode == ModeKeys.TRAIN:
-            ids, x, y = staged[1]
+            (ids, x, y), status = staged[1]
         else:
-            ids, x, y = stage(features, labels)
+            (ids, x, y), status = stage(features, labels)
+        if status is not None:
+            status.raise_if_bad()
 
     # multi-GPU: a rank's loss is its SHARE of the global-batch mean (already divided by the global batch); times
     # world = the mean over its own examples — what is logged, and, with every rank evaluating the same batches,
@@ -196,8 +212,8 @@ def run_batch(features, labels, mode, params, make_engine):
             if la is not None and ahead is None and eng.shard is None:
                 nxt = stage(la["features"], la["labels"])
                 store["staged"] = (la["features"], nxt)
-                if nxt[0].shape == ids.shape:
-                    nxt_ids = nxt[0]
+                if nxt[0][0].shape == ids.shape:
+                    nxt_ids = nxt[0][0]
             loss, logits = eng.train_step(ids, y, x, next_ids=nxt_ids) if nxt_ids is not None else eng.train_step(ids, y, x)
         return EstimatorSpec(mode, predictions=None, loss=rescale(loss), train_op=eng.step)
     if mode == ModeKeys.EVAL:

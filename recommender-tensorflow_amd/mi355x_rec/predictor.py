@@ -49,9 +49,12 @@ class Predictor:
     class_ids, classes).  ``features`` maps the receiver names of the export's signature to equally long sequences of
     raw values; a receiver whose spec carries a default may be omitted."""
 
-    def __init__(self, signature, plan, eng, mode="auto"):
+    def __init__(self, signature, plan, eng, mode="auto", device_transform="off"):
         if mode not in ("auto", "fused", "layered"):
             raise ValueError("mode must be 'auto', 'fused' or 'layered'")
+        # device_transform="on": a request's raw columns go to the device and become ids there, written straight into the
+        # per-B ids buffer (mi_ids_transform); recommend / rank_targets transform both sides there too
+        plan.set_device_mode(device_transform)
         self.signature, self.plan, self.engine, self.mode = signature, plan, eng, mode
         self.receivers = {}
         for key, spec in signature["receiver_tensors"].items():
@@ -66,7 +69,7 @@ class Predictor:
             raise ValueError("mode='fused': the model has %s" % eng._fused_limit())
 
     @classmethod
-    def from_export(cls, export_dir, device="cuda", mode="auto"):
+    def from_export(cls, export_dir, device="cuda", mode="auto", device_transform="off"):
         """export_dir: one <timestamp> directory of an export, or the folder that holds them (``<job-dir>/export/exporter``:
         the newest is taken).  The columns and the FieldPlan are rebuilt from the signature's "model" entry, the engine from
         the `layout` table of variables.pt, WEIGHTS ONLY: it is built with the SGD spec, whose table is [R, E] records
@@ -121,7 +124,7 @@ class Predictor:
                     raise ValueError("%s: %r is %s in the export, %s in the model" % (d, key, tuple(sd[key].shape), tuple(dst.shape)))
                 dst.copy_(sd[key].to(eng.device))
         eng.step = eng._final_step = int(sd.get("step", 0))
-        p = cls(sig, plan, eng, mode)
+        p = cls(sig, plan, eng, mode, device_transform)
         p.export_dir = d
         return p
 
@@ -190,16 +193,41 @@ class Predictor:
             b["ids"].copy_(torch.from_numpy(ids))
             if b["x"] is not None:
                 b["x"].copy_(torch.from_numpy(x))
-            pr = eng.predict_fused(b["ids"], b["x"], out=b["out"])
+            return self._predict_device(b["ids"], b["x"])
+        dev = eng.device
+        return self._predict_device(torch.from_numpy(ids).to(dev), torch.from_numpy(x).to(dev) if x is not None else None)
+
+    def _predict_device(self, ids, x):
+        """The PREDICT dict (numpy) of ids / x on the device (the fused path: the per-B buffers themselves)"""
+        eng = self.engine
+        if self.use_fused(ids.shape[0]):
+            pr = eng.predict_fused(ids, x, out=self._buffers(ids.shape[0])["out"])
         else:
-            dev = eng.device
-            logits = eng.predict_logits(torch.from_numpy(ids).to(dev), torch.from_numpy(x).to(dev) if x is not None else None)
-            pr = binary_predictions(logits.clone(), eng.k)
+            pr = binary_predictions(eng.predict_logits(ids, x).clone(), eng.k)
         host = {k: pr[k].to("cpu", copy=True).numpy() for k in OUTPUTS[:4]}     # (copies: the device buffers are reused)
         host["classes"] = host["class_ids"]
         return host
 
+    def _transform_on_device(self, features):
+        """(ids, x) of a request on the device, or None for an empty one: the raw columns copied, the ids made there — into
+        the per-B ids buffer where the fused path will read them"""
+        cols, n = self._columns(features)
+        if n == 0:
+            return None
+        dt = self.plan.on_device(self.engine.device, self.engine.k)
+        if not self.use_fused(n):
+            return dt.transform(cols)
+        b = self._buffers(n)
+        ids, x = dt.transform(cols, out=b["ids"])
+        if b["x"] is not None:
+            b["x"].copy_(x)
+        return b["ids"], b["x"]
+
     def __call__(self, features):
+        if self.plan.device_mode == "on":
+            on_dev = self._transform_on_device(features)
+            if on_dev is not None:
+                return self._predict_device(*on_dev)
         ids, x = self.transform(features)
         return self.predict_ids(ids, x)
 
@@ -325,9 +353,11 @@ class EnsemblePredictor:
           "layered" every member by its own Predictor's path, then a torch fp32 sum in member order, a division and
                     binary_predictions;
           "auto"    fused iff every member's own use_fused(B) says fused (the measured thresholds of profiles/
-                    serve_latency.md; profiles/ensemble_latency.md has the ensemble's own table)."""
+                    serve_latency.md; profiles/ensemble_latency.md has the ensemble's own table).
+    device_transform: None leaves the switch as member 0 was made; "on" / "off" sets it ON MEMBER 0's PLAN, which the
+    ensemble shares — a caller who still holds that Predictor sees it change too."""
 
-    def __init__(self, predictors, mode="auto"):
+    def __init__(self, predictors, mode="auto", device_transform=None):
         if mode not in ("auto", "fused", "layered"):
             raise ValueError("mode must be 'auto', 'fused' or 'layered'")
         self.members = list(predictors)
@@ -361,18 +391,21 @@ class EnsemblePredictor:
                     raise ValueError("mode='fused': member %d: the model has %s" % (
                         i, p.engine._fused_limit() or "row-sharded tables"))
         self.mode, self.signature, self.plan, self.receivers = mode, lead.signature, lead.plan, lead.receivers
+        if device_transform is not None:      # (None: as member 0 was made; "on" / "off": as Predictor takes it)
+            self.plan.set_device_mode(device_transform)
         self.device, self.k = lead.engine.device, lead.engine.k
         self.export_dirs = [getattr(p, "export_dir", None) for p in self.members]
         self._group = None
         self._bufs = {}
 
     @classmethod
-    def from_exports(cls, export_dirs, device="cuda", mode="auto", member_mode="auto"):
+    def from_exports(cls, export_dirs, device="cuda", mode="auto", member_mode="auto", device_transform="off"):
         """One Predictor.from_export per directory (member_mode: the members' own mode, which "layered" and "auto" consult)"""
-        return cls([Predictor.from_export(d, device=device, mode=member_mode) for d in export_dirs], mode=mode)
+        return cls([Predictor.from_export(d, device=device, mode=member_mode) for d in export_dirs], mode=mode,
+                   device_transform=device_transform)
 
     @classmethod
-    def from_sweep(cls, job_dir, top, device="cuda", mode="auto", member_mode="auto"):
+    def from_sweep(cls, job_dir, top, device="cuda", mode="auto", member_mode="auto", device_transform="off"):
         """The first `top` rows of <job_dir>/sweep.json — trainers.sweep ranked them best first — each from its export"""
         path = os.path.join(job_dir, "sweep.json")
         if not os.path.exists(path):
@@ -387,7 +420,7 @@ class EnsemblePredictor:
             if not os.path.isdir(d):                    # (a sweep directory that was moved: the members lie inside it)
                 d = os.path.join(job_dir, "member_%d" % row["member"], "export", "exporter")
             dirs.append(d)
-        ens = cls.from_exports(dirs, device=device, mode=mode, member_mode=member_mode)
+        ens = cls.from_exports(dirs, device=device, mode=mode, member_mode=member_mode, device_transform=device_transform)
         ens.sweep_members = [row["member"] for row in rows[:top]]
         return ens
 
@@ -436,6 +469,11 @@ class EnsemblePredictor:
         b["ids"].copy_(torch.from_numpy(ids))
         if b["x"] is not None:
             b["x"].copy_(torch.from_numpy(x))
+        return self._predict_buffers(b, B, return_members)
+
+    def _predict_buffers(self, b, B, return_members):
+        """The PREDICT dict (numpy) of the ids / x that lie in the per-B buffers b"""
+        M = len(self.members)
         if self.use_fused(B):
             if self._group is None:
                 self._group = FusedGroup([p.engine for p in self.members])
@@ -464,6 +502,15 @@ class EnsemblePredictor:
         return host
 
     def __call__(self, features, return_members=False):
+        if self.plan.device_mode == "on":
+            lead = self.members[0]
+            cols, n = lead._columns(features)
+            if n:
+                b = self._buffers(n)
+                _, x = self.plan.on_device(self.device, self.k).transform(cols, out=b["ids"])
+                if b["x"] is not None:
+                    b["x"].copy_(x)
+                return self._predict_buffers(b, n, return_members)
         ids, x = self.transform(features)
         return self.predict_ids(ids, x, return_members=return_members)
 

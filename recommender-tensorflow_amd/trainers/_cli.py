@@ -38,6 +38,10 @@ _COMMON = [
                             "within 3 ulp + 2e-6 of the movement the replay covers (98.7 %% of them within 1e-7 relative of TensorFlow's "
                             "sweep; logits / loss stay inside 1e-5), a third of the instructions; exact: TensorFlow's fp32 sequence bit "
                             "for bit, ~8 %% slower at large vocabularies (default: %(default)s — the mode bench.py's headline is timed in)")),
+    ("--device-transform", dict(choices=["off", "on"], default="off",
+                                help="on: copy every batch's RAW feature columns to the device and turn them into row ids there "
+                                     "in one launch (hash_bucket, bucketized, vocabulary_list and identity columns, bit for bit "
+                                     "the host transform's ids); off: transform on the host and copy the ids (default: %(default)s)")),
     ("--synthetic", dict(type=int, default=None, metavar="N", help="train on N generated MovieLens-shaped examples (and evaluate on "
                                                                    "N/10) instead of --train-csv / --test-csv")),
     ("--exact-auc", dict(action="store_true", help="every evaluation also sorts its logits on the device and counts the exact AUC — "
@@ -124,6 +128,7 @@ def run(args, make_estimator):
     estimator.params["hip_graph"] = getattr(args, "hip_graph", "auto")
     estimator.params["catchup"] = getattr(args, "catchup", "bounded")
     estimator.params["fused_step"] = getattr(args, "fused_step", "off")
+    estimator.params["device_transform"] = getattr(args, "device_transform", "off")
     gauc_by = getattr(args, "gauc_by", None)
     if getattr(args, "exact_auc", False) or gauc_by:
         estimator.params["exact_auc"] = True

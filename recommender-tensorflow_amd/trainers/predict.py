@@ -27,6 +27,9 @@ def make_parser():
     p.add_argument("--top", type=int, default=None, metavar="N",
                    help="--job-dir is a trainers.sweep directory: score with the mean of its N best members (default: off, one "
                         "export is served)")
+    p.add_argument("--device-transform", choices=["off", "on"], default="off",
+                   help="on: a call's raw columns go to the device and become row ids there in one launch; off: the host "
+                        "transform (default: %(default)s)")
     p.add_argument("--batch-size", type=int, default=4096, help="rows scored per call (default: %(default)s)")
     p.add_argument("--device", default="cuda", help="torch device of the MI355X to run on (default: %(default)s)")
     return p
@@ -38,11 +41,13 @@ def main(argv=None):
         if not os.path.exists(os.path.join(args.job_dir, "sweep.json")):
             raise SystemExit("--top %d: %s has no sweep.json (an ensemble is taken from the job directory of a trainers.sweep run)"
                              % (args.top, args.job_dir))
-        predictor = EnsemblePredictor.from_sweep(args.job_dir, top=args.top, device=args.device, mode=args.mode)
+        predictor = EnsemblePredictor.from_sweep(args.job_dir, top=args.top, device=args.device, mode=args.mode,
+                                                 device_transform=args.device_transform)
         predictor.export_dir = "the %d best members of %s (%s)" % (args.top, args.job_dir, ", ".join(
             "member %d" % m for m in predictor.sweep_members))
     else:
-        predictor = Predictor.from_export(os.path.join(args.job_dir, "export", "exporter"), device=args.device, mode=args.mode)
+        predictor = Predictor.from_export(os.path.join(args.job_dir, "export", "exporter"), device=args.device, mode=args.mode,
+                                          device_transform=args.device_transform)
     cols, n = _read_csv(args.input)
     cols = {k: v for k, v in cols.items() if k in predictor.receivers}
     out = args.output or os.path.join(args.job_dir, "predict", "predictions.csv")

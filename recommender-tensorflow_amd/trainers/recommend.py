@@ -161,7 +161,8 @@ def main(argv=None):
             raise SystemExit("--top %d out of range: the sweep in %s has %d members (1 <= top <= %d)" % (
                 args.top, args.job_dir, n_members, n_members))
         try:
-            ens = EnsemblePredictor.from_sweep(args.job_dir, top=args.top, device=args.device)
+            ens = EnsemblePredictor.from_sweep(args.job_dir, top=args.top, device=args.device,
+                                               device_transform=args.device_transform)
         except ValueError as e:
             raise SystemExit("--top %d: %s" % (args.top, e))
     else:
@@ -169,6 +170,7 @@ def main(argv=None):
         config = get_run_config()
         config.device = args.device
         est = module.make_estimator(args, get_feature_columns(embedding_size=args.embedding_size), config)
+        est.params["device_transform"] = args.device_transform      # (both sides' raw columns to the device, ids made there)
         if est.latest_checkpoint() is None:
             raise SystemExit("no checkpoint in %s: train the model first (python -m trainers.%s --job-dir %s ...)" % (
                 args.job_dir, args.model, args.job_dir))

@@ -62,7 +62,8 @@ from trainers.conf_utils import get_exporter
 from trainers.model_utils import _OPTIMIZERS
 from trainers.ml_100k import _read_csv, get_feature_columns, get_input_fn, serving_input_fn
 
-_KEPT = ("--train-csv", "--test-csv", "--restore", "--batch-size", "--train-steps", "--device", "--catchup", "--synthetic")
+_KEPT = ("--train-csv", "--test-csv", "--restore", "--batch-size", "--train-steps", "--device", "--catchup", "--synthetic",
+         "--device-transform")
 _ASCENDING = ("loss", "average_loss", "mean_rank")
 _EVAL_METRICS = ("auc", "accuracy", "auc_precision_recall", "loss", "average_loss")
 _EXACT_METRICS = ("auc_exact", "gauc")      # of --exact-auc / --gauc-by
@@ -226,7 +227,8 @@ def make_members(args, hps, config):
     for i, hp in enumerate(hps):
         params = {"categorical_columns": get_feature_columns(embedding_size=hp["embedding_size"])["linear"],
                   "use_linear": not args.exclude_linear, "use_mf": not args.exclude_mf, "use_dnn": not args.exclude_dnn,
-                  "catchup": getattr(args, "catchup", "bounded"), "fused_step": "on"}
+                  "catchup": getattr(args, "catchup", "bounded"), "fused_step": "on",
+                  "device_transform": getattr(args, "device_transform", "off")}
         params.update(hp)
         members.append(Estimator(model_fn=deep_fm.model_fn, model_dir=os.path.join(args.job_dir, "member_%d" % i), config=config,
                                  params=params))
@@ -269,7 +271,7 @@ class PopulationEval:
         """the test set, read and transformed ONCE: ids int32 [N, F] and labels uint8 [N] on the device"""
         ids, ys, groups = [], [], []
         for features, labels in get_input_fn(self.test_csv, ModeKeys.EVAL, batch_size=4096)():
-            ids.append(plan.transform(features)[0])
+            ids.append(_ids(plan, features, dev))
             ys.append(np.asarray(labels).reshape(-1).astype(np.uint8))
             if self.gauc_by:
                 if self.gauc_by not in features:
@@ -281,7 +283,7 @@ class PopulationEval:
         if self.exact_auc:
             self.exact = ExactAuc(np.concatenate(ys), np.concatenate(groups) if self.gauc_by else None, device=dev,
                                   method=self.auc_method)
-        self.data = (torch.from_numpy(np.ascontiguousarray(np.concatenate(ids))).to(dev),
+        self.data = (torch.cat(ids),
                      torch.from_numpy(np.ascontiguousarray(np.concatenate(ys))).to(dev))
 
     def run(self, pop, step, lead):
@@ -311,6 +313,13 @@ class PopulationEval:
         return step, ms[i][self.select]
 
 
+def _ids(plan, features, dev):
+    """a batch's ids int32 [B, F] on the device: made there from the raw columns (--device-transform on), or on the host"""
+    if plan.device_mode == "on":
+        return plan.on_device(dev).transform(features)[0]
+    return torch.from_numpy(plan.transform(features)[0]).to(dev)
+
+
 def train(members, input_fn, max_steps, config, job_dir=None, batch_size=None, evaluator=None):
     """The sweep's loop: ONE input pipeline — every batch is read and its ids are transformed once (in groups, as
     Estimator._grouped does for small batches) — and one population step per batch.  evaluator: a PopulationEval whose
@@ -331,12 +340,12 @@ def train(members, input_fn, max_steps, config, job_dir=None, batch_size=None, e
         if ahead is not None and ahead.get("features") is features:
             g = ahead["group"]
             if "ids" not in g:
-                g["ids"] = torch.from_numpy(plan.transform(g["features"])[0]).to(dev)
+                g["ids"] = _ids(plan, g["features"], dev)
                 g["y"] = torch.from_numpy(np.ascontiguousarray(np.asarray(g["labels"]).reshape(-1)).astype(np.uint8)).to(dev)
             lo, hi = ahead["rows"]
             ids, y = g["ids"][lo:hi], g["y"][lo:hi]
         else:
-            ids = torch.from_numpy(plan.transform(features)[0]).to(dev)
+            ids = _ids(plan, features, dev)
             y = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1)).astype(np.uint8)).to(dev)
         loss, _ = pop.train_step(ids, y)
         step += 1
@@ -439,7 +448,8 @@ def train_and_evaluate(args):
     if n_ens:
         if n_ens < 0 or n_ens > len(rows):
             raise ValueError("--ensemble %d: the sweep has %d members" % (n_ens, len(rows)))
-        ens = EnsemblePredictor.from_sweep(args.job_dir, top=n_ens, device=args.device)
+        ens = EnsemblePredictor.from_sweep(args.job_dir, top=n_ens, device=args.device,
+                                           device_transform=getattr(args, "device_transform", "off"))
         if exact_auc and evaluator.data is None:                        # (--restore with nothing left to evaluate)
             evaluator.load(members[0].params["_store"]["plan"], members[0]._engine().device)
         who, metrics = evaluate_ensemble(ens, args.test_csv, exact=evaluator.exact if exact_auc else None)
