@@ -1,6 +1,8 @@
 """CPU: the C-ABI library loads here (no GPU, no compute calls) and exports every symbol that
 include/mi355x_rec.h declares, with the argument counts the ctypes binding assumes."""
+import ctypes
 import inspect
+import os
 import re
 import subprocess
 
@@ -33,6 +35,20 @@ def test_numpy_stand_ins_take_what_the_binding_passes():
         params = list(inspect.signature(f).parameters.values())[1:]               # (self)
         assert all(p.kind == p.POSITIONAL_OR_KEYWORD for p in params), (name, [str(p) for p in params])
         assert len(params) == len(_lib.SIGNATURES[name][1]) - 1, (name, len(params), len(_lib.SIGNATURES[name][1]) - 1)
+
+
+def test_the_fused_model_struct_is_laid_out_as_the_c_compiler_lays_it_out(tmp_path):
+    """host only: the header through the system's C compiler; the ctypes mirror must agree on the size and on the offset of the
+    last field (every field before it then has room for nothing else than its own type)"""
+    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "mi355x_rec.h"\n'
+                   'int main(void) { printf("%zu %zu\\n", sizeof(mi_fused_model_t), offsetof(mi_fused_model_t, wide_fields)); return 0; }\n')
+    exe = tmp_path / "layout"
+    subprocess.run(["cc", "-I", header, str(src), "-o", str(exe)], check=True)
+    size, off = (int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split())
+    assert (size, off) == (ctypes.sizeof(_lib.FusedModel), _lib.FusedModel.wide_fields.offset)
+    assert [n for n, _ in _lib.FusedModel._fields_][-1] == "wide_fields"
 
 
 def test_library_identity(lib):
