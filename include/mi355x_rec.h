@@ -1259,6 +1259,28 @@ int32_t mi_ids_transform(const mi_ids_column_t* columns, int32_t F, int64_t B, i
                          mi_stream_t stream);
 int32_t mi_fingerprint64_device(const uint8_t* bytes, const int64_t* offsets, int64_t n, uint64_t* out, mi_stream_t stream);
 
+/* ---- (a2) one batch out of a dataset that lives on the device, by an index stream, in one launch (csrc/batch.hip) -------
+ * The resident arrays are ids_all int32 [N, ld_ids] (ld_ids >= F), x_all float [N, ld_x] (ld_x >= n_num) and y_all uint8
+ * [N]; order int32 [B] names the rows of the batch (the caller passes the pointer already offset into its pass stream;
+ * an index may repeat).  The outputs are DENSE:
+ *   ids[b, f] = ids_all[order[b] * ld_ids + f]    f < F        int32 [B, F]
+ *   x  [b, j] = x_all  [order[b] * ld_x   + j]    j < n_num    float [B, n_num]   (n_num may be 0: x_all and x NULL)
+ *   y  [b]    = y_all  [order[b]]                              uint8 [B]          (y_all and y both NULL: no labels)
+ * Everything is on the device.  The entry makes no allocation, no copy and no synchronisation, and can be captured in a
+ * graph.  No workgroup reads what another writes and none waits for another.
+ *
+ * A BAD index is order[b] < 0 or order[b] >= N.  The kernel never forms an address from it: it stores a zero row (ids
+ * and x) and label 0, adds 1 to status[0] and takes the maximum of 2^31 - 1 - b into status[1] — mi_ids_transform's
+ * convention: in a status the caller ZEROED, 2^31 - 1 - status[1] is the lowest bad position where status[0] > 0.  status:
+ * int32 [2] (device); integer atomics only, so the result does not depend on order.  Two calls on equal input give equal
+ * bits.
+ * Refused on the host before anything is launched, the outputs and status untouched, the message naming the argument
+ * (MI_ERR_INVALID): NULL ids_all / order / ids / status, N or B outside [1, 2^31 - 1], F outside [1, MI_IDS_MAX_COLUMNS],
+ * ld_ids < F, n_num < 0, n_num > 0 with NULL x_all / x or ld_x < n_num, exactly one of y_all / y NULL. */
+int32_t mi_batch_gather(const int32_t* ids_all, int64_t ld_ids, const float* x_all, int64_t ld_x, const uint8_t* y_all, int64_t N,
+                        const int32_t* order, int64_t B, int32_t F, int32_t n_num, int32_t* ids, float* x, uint8_t* y,
+                        int32_t* status, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

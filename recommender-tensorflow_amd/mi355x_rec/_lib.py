@@ -255,6 +255,7 @@ SIGNATURES = {
     "mi_auc_sorted_counts": (_i32, [_p, _i64, _i32, _p, _p, _i32, _i64, _p, _p, _sz, _p]),
     "mi_ids_transform": (_i32, [_p, _i32, _i64, _p, _i64, _p, _p]),
     "mi_fingerprint64_device": (_i32, [_p, _p, _i64, _p, _p]),
+    "mi_batch_gather": (_i32, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

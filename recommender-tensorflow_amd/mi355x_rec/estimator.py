@@ -22,6 +22,8 @@ import time
 import numpy as np
 import torch
 
+from .dataset import DeviceBatch
+
 
 class ModeKeys:
     TRAIN, EVAL, PREDICT = "train", "eval", "infer"
@@ -304,7 +306,7 @@ class Estimator:
             B = len(cur[1])
         except TypeError:
             B = 0
-        if B < self.LOOKAHEAD_MIN_BATCH or self._shard is not None or not isinstance(cur[0], dict):
+        if B < self.LOOKAHEAD_MIN_BATCH or self._shard is not None or not isinstance(cur[0], (dict, DeviceBatch)):
             self.params.pop("_lookahead", None)
             yield cur
             yield from it
@@ -336,7 +338,7 @@ class Estimator:
             B = 0
         k = self.GROUP_ROWS // B if 0 < B <= self.GROUP_ROWS // 4 else 1
         it = itertools.chain([first], it)
-        if k <= 1 or not isinstance(first[0], dict):
+        if k <= 1 or not isinstance(first[0], (dict, DeviceBatch)):
             self.params.pop("_ahead", None)
             yield from it
             return
@@ -344,8 +346,12 @@ class Estimator:
             grp = list(itertools.islice(it, k))
             if not grp:
                 break
-            feats = {key: np.concatenate([np.asarray(f[key]) for f, _ in grp]) for key in grp[0][0]}
-            group = {"features": feats, "labels": np.concatenate([np.asarray(l).reshape(-1) for _, l in grp])}
+            if isinstance(grp[0][0], DeviceBatch):
+                # a dataset on the device (dataset.py): run_batch forms the whole group's rows there in one launch
+                group = {"handles": [f for f, _ in grp]}
+            else:
+                feats = {key: np.concatenate([np.asarray(f[key]) for f, _ in grp]) for key in grp[0][0]}
+                group = {"features": feats, "labels": np.concatenate([np.asarray(l).reshape(-1) for _, l in grp])}
             lo = 0
             for f, l in grp:
                 n = len(l)

@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .dataset import DeviceBatch, materialise_group
 from .estimator import EstimatorSpec, ModeKeys
 from .feature_column import FieldPlan
 from .metrics import metrics_from_counters
@@ -125,6 +126,11 @@ def run_batch(features, labels, mode, params, make_engine):
         plan.set_device_mode(params.get("device_transform", "off"))
         store["plan"] = plan
         shard = params.get("_shard")           # parallel.RowShard of a multi-GPU launch (trainers/_cli.py), else None
+        dd = params.get("device_dataset", "off")
+        if dd not in ("off", "on"):
+            raise ValueError("device_dataset must be 'off' or 'on'")
+        if shard is not None and (dd == "on" or isinstance(features, DeviceBatch)):
+            raise ValueError("device_dataset=on: one GPU only — a RowShard run takes the plain input pipeline")
         eng = store["engine"] = make_engine(plan, device, shard) if shard is not None else make_engine(plan, device)
         gen = torch.Generator(device=eng.device)
         gen.manual_seed(int(params.get("seed", 0)) + (0 if shard is None else 7919 * shard.rank))
@@ -145,7 +151,10 @@ def run_batch(features, labels, mode, params, make_engine):
         # small batches (Estimator.train groups them): the id transforms of a whole group of batches were done in one
         # call and copied to the device once; this batch is rows lo..hi of the group
         g = ahead["group"]
-        if "ids" not in g:
+        if "ids" not in g and "handles" in g:
+            # a dataset on the device: the group's rows are formed there in one launch, the batches are views of them
+            (g["ids"], g["x"], g["y"]), g["status"] = materialise_group(g["handles"], plan, eng)
+        elif "ids" not in g:
             if on_device:
                 g["ids"], g["x"] = plan.on_device(dev, eng.k).transform(g["features"])
             else:
@@ -153,13 +162,18 @@ def run_batch(features, labels, mode, params, make_engine):
                 g["ids"] = torch.from_numpy(ids_np).to(dev)
                 g["x"] = torch.from_numpy(x_np).to(dev) if x_np is not None else None
             g["y"] = torch.from_numpy(np.ascontiguousarray(np.asarray(g["labels"]).reshape(-1)).astype(np.uint8)).to(dev)
+        if g.get("status") is not None:
+            g.pop("status").raise_if_bad()
         lo, hi = ahead["rows"]
         ids, y = g["ids"][lo:hi], g["y"][lo:hi]
         x = g["x"][lo:hi] if g["x"] is not None else None
     else:
         def stage(f, l):
             """(ids, x, y, status): status is None on the host transform, which has checked its ids; the device transform's
-            is looked at when the batch is used (TransformStatus.raise_if_bad: it waits for its own status copy only)"""
+            is looked at when the batch is used (TransformStatus.raise_if_bad: it waits for its own status copy only).  A
+            handle of a dataset on the device (dataset.py) is materialised there: one launch, or views of the resident arrays"""
+            if isinstance(f, DeviceBatch):
+                return f.materialise(plan, eng)
             y_ = None
             if l is not None:
                 y_ = torch.from_numpy(np.ascontiguousarray(np.asarray(l).reshape(-1)).astype(np.uint8)).to(dev)

@@ -42,6 +42,11 @@ _COMMON = [
                                 help="on: copy every batch's RAW feature columns to the device and turn them into row ids there "
                                      "in one launch (hash_bucket, bucketized, vocabulary_list and identity columns, bit for bit "
                                      "the host transform's ids); off: transform on the host and copy the ids (default: %(default)s)")),
+    ("--device-dataset", dict(choices=["off", "on"], default="off",
+                              help="on (one GPU): transform the WHOLE training and test data once, keep ids, numeric features and "
+                                   "labels on the device and form every training batch there from the shuffle's index stream in "
+                                   "one launch — the same batches, bit for bit; evaluations read the test file once; off: read, "
+                                   "transform and copy every batch on the host (default: %(default)s)")),
     ("--synthetic", dict(type=int, default=None, metavar="N", help="train on N generated MovieLens-shaped examples (and evaluate on "
                                                                    "N/10) instead of --train-csv / --test-csv")),
     ("--exact-auc", dict(action="store_true", help="every evaluation also sorts its logits on the device and counts the exact AUC — "
@@ -112,6 +117,11 @@ def run(args, make_estimator):
     (global batch N x batch size, synchronous), all ranks evaluate the same test batches, and rank r keeps its
     shard in model.ckpt-<step>.rank<r>.pt."""
     rank, world, device, shard = init_distributed(args)
+    device_dataset = getattr(args, "device_dataset", "off")
+    if device_dataset == "on" and shard is not None:
+        raise SystemExit("--device-dataset on: one GPU only (this launch has %d processes, each with a RowShard of the tables)" % world)
+    # (the keyword goes along only when the switch is on: the plain input_fn is called as it always was)
+    dataset_kw = {"device_dataset": True} if device_dataset == "on" else {}
     if getattr(args, "synthetic", None):
         args.train_csv, args.test_csv = "synthetic:%d:1" % args.synthetic, "synthetic:%d:2" % max(args.synthetic // 10, 1)
     if not args.restore and rank == 0:
@@ -129,17 +139,18 @@ def run(args, make_estimator):
     estimator.params["catchup"] = getattr(args, "catchup", "bounded")
     estimator.params["fused_step"] = getattr(args, "fused_step", "off")
     estimator.params["device_transform"] = getattr(args, "device_transform", "off")
+    estimator.params["device_dataset"] = device_dataset
+    eval_input_fn = get_input_fn(args.test_csv, ModeKeys.EVAL, batch_size=args.batch_size, **dataset_kw)
     gauc_by = getattr(args, "gauc_by", None)
     if getattr(args, "exact_auc", False) or gauc_by:
         estimator.params["exact_auc"] = True
     if gauc_by:
         estimator.params["gauc_by"] = gauc_by          # (implies exact_auc, as in trainers.sweep)
-        for features, _ in get_input_fn(args.test_csv, ModeKeys.EVAL, batch_size=args.batch_size)():
+        for features, _ in eval_input_fn():
             if gauc_by not in features:                # refused before the training, not at its first evaluation
                 raise SystemExit("--gauc-by %s: the test file has no such column (it has %s)" % (gauc_by, ", ".join(sorted(features))))
             break
-    train_spec = get_train_spec(get_input_fn(args.train_csv, batch_size=args.batch_size, seed=rank if world > 1 else None),
-                                args.train_steps)
-    eval_spec = get_eval_spec(get_input_fn(args.test_csv, ModeKeys.EVAL, batch_size=args.batch_size),
-                              get_exporter(serving_input_fn))
+    train_spec = get_train_spec(get_input_fn(args.train_csv, batch_size=args.batch_size, seed=rank if world > 1 else None,
+                                             **dataset_kw), args.train_steps)
+    eval_spec = get_eval_spec(eval_input_fn, get_exporter(serving_input_fn))
     return _tae(estimator, train_spec, eval_spec)

@@ -9,6 +9,7 @@ import csv
 import numpy as np
 
 from mi355x_rec import feature_column as fc
+from mi355x_rec.dataset import DeviceDataset, dataset_input_fn, shuffle_passes
 from mi355x_rec.estimator import ModeKeys, ServingInputReceiver
 
 # CSV layout written by the reference's offline ETL (src/data/ml_100k.py): 42 columns.
@@ -87,10 +88,20 @@ def _read_csv(path):
     return cols, len(rows)
 
 
-def get_input_fn(csv_path, mode=ModeKeys.TRAIN, batch_size=32, cutoff=5, seed=None):
+def get_input_fn(csv_path, mode=ModeKeys.TRAIN, batch_size=32, cutoff=5, seed=None, device_dataset=False):
     """input_fn() -> iterator of (features: dict name -> [B] array, labels: [B] bool).
     TRAIN: shuffle with a 16*batch_size buffer, repeat forever; EVAL: one ordered pass, the last
-    batch may be short (no drop_remainder) — the tf.data semantics of the reference pipeline."""
+    batch may be short (no drop_remainder) — the tf.data semantics of the reference pipeline.
+    device_dataset: the same batches out of a dataset that lives on the device (mi355x_rec/dataset.py): the file is
+    read and transformed once, `features` is a lazy handle (a mapping of the batch's raw features) that the model
+    materialises on the device in one launch."""
+    if device_dataset:
+        def load():
+            cols, n = _read_csv(csv_path)
+            label = cols.pop(LABEL_COL) >= cutoff
+            return DeviceDataset(cols, label, n)
+        return dataset_input_fn(load, mode, batch_size, seed)
+
     def input_fn():
         cols, n = _read_csv(csv_path)
         label = cols.pop(LABEL_COL) >= cutoff
@@ -103,35 +114,9 @@ def get_input_fn(csv_path, mode=ModeKeys.TRAIN, batch_size=32, cutoff=5, seed=No
             for s in range(0, n, batch_size):
                 yield emit(np.arange(s, min(n, s + batch_size)))
             return
-        rng = np.random.default_rng(seed)
-        cap = 16 * batch_size
-        pending = np.empty(0, np.int64)
-        while True:                                        # .repeat()
-            # .shuffle(cap): a buffer of cap elements; every further element i draws a slot j uniformly, the slot's
-            # occupant goes out, i takes its place; at the end of the pass the buffer goes out in random order.
-            # The draws of a pass come from the generator in one call, the swap chain — element i's successor is the
-            # next element that draws i's slot — is followed per SLOT in numpy: out[k] = the occupant of slot j[k]
-            # before draw k = the element of the latest earlier draw with the same slot (or the slot's first occupant).
-            m = max(n - cap, 0)
-            j = rng.integers(cap, size=m) if m else np.empty(0, np.int64)
-            order = np.argsort(j, kind="stable")           # draws grouped by slot, in time order inside a group
-            js = j[order]
-            prev = np.empty(m, np.int64)                   # for every draw: who sits in its slot
-            first = np.ones(m, bool)
-            first[1:] = js[1:] != js[:-1]
-            prev[order] = np.where(first, js, np.concatenate([[0], order[:-1]]) + cap)   # slot's first occupant = element js
-            out = prev                                     # (element ids: the first cap elements are 0..cap-1, draw k places element cap + k)
-            buf = np.arange(min(n, cap), dtype=np.int64)
-            if m:
-                last = np.ones(m, bool)
-                last[:-1] = js[1:] != js[:-1]
-                buf[js[last]] = order[last] + cap          # what sits in a drawn slot after the pass
-            rng.shuffle(buf)
-            stream = np.concatenate([pending, out, buf])
-            nb = len(stream) // batch_size
-            for b in range(nb):
+        for stream in shuffle_passes(n, batch_size, seed):     # (.shuffle(16 * batch_size).repeat())
+            for b in range(len(stream) // batch_size):
                 yield emit(stream[b * batch_size:(b + 1) * batch_size])
-            pending = stream[nb * batch_size:]
     return input_fn
 
 
