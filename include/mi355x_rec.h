@@ -244,7 +244,8 @@ int32_t mi_sort_unique_rows_slots(const int32_t* rows, int64_t n, int64_t num_ro
                                   mi_stream_t stream);
 
 /* mi_global_rows + mi_sort_unique_rows in one entry for the single-GPU step: ids [B][F] (local ids, field f's rows are
- * field_off[f] + id: disjoint ranges in ascending field order), max_vocab >= every field's id range.  Same outputs,
+ * field_off[f] + id: disjoint ranges in ascending field order), max_vocab >= every field's id range, 0 < max_vocab <= 2^30
+ * (above it the call is refused, in either form; every admitted max_vocab is sorted by both forms).  Same outputs,
  * bit for bit (equal rows keep ascending example order): sorted_entry [B*F] (entry = b * F + f), uniq_rows (global
  * rows), seg_start, num_uniq.  Every field's ids are sorted on their own, so the radix passes cover the bits of
  * max_vocab, not of the whole table.  B a multiple of 4096, F <= 64 (anything else: the two-entry form).
@@ -264,7 +265,9 @@ int32_t mi_sort_unique_fields(const int32_t* ids, const int64_t* field_off, int6
  * r / world; the reference's own multi-worker mode is TF's parameter-server placement of whole
  * variables, distributed.md:58-82 — see DESIGN.md "Multi-GPU").
  *   mi_shard_keys     : keys[i] = ((i / entries_per_chunk) * world + pos(rows[i] % world)) * rows_per_rank + rows[i] / world
- *                       (chunk-major request key of a pipelined step; entries_per_chunk == 0: one chunk).
+ *                       (chunk-major request key of a pipelined step; entries_per_chunk == 0: one chunk).  n need not be
+ *                       a multiple of entries_per_chunk: the last of the ceil(n / entries_per_chunk) chunks may be short.
+ *                       chunks * world * rows_per_rank <= INT32_MAX (the key is an int32), else the call is refused.
  *                       pos: the owner's place in the send order — the rank itself (self_rank = -1), or, with
  *                       self_rank >= 0, the other ranks in rank order and the asking rank LAST (o -> o below
  *                       self_rank, o - 1 above, world - 1 for self_rank): a rank's requests to itself then end every

@@ -658,7 +658,11 @@ int32_t mi_sort_unique_fields(const int32_t* ids, const int64_t* field_off, int6
   if (tps <= kFusedMaxTps && !beside && mi::env_int("MI_SORT_FUSED", 1) != 0) {
     // one launch per pass + one for the compaction (pass_fused_k / compact_fused_k above).  Digits of 7 bits: 20-bit ids = 3
     // passes, 130 us at config 3 against 149 for 2 passes of 10 bits (1,024 bins per 4,096-key tile scatter 16-byte runs)
-    const Digits D = plan_rows(max_vocab, mi::env_int("MI_SORT_BITS", 7));
+    // Above 28 bits 7-bit digits would take a fifth pass, for which there is neither a bin_total nor a ready word: the digits
+    // widen until kMaxPasses hold the key (max_vocab <= 2^30: 4 passes of 8 bits; pass_fused_k holds kMaxBins bins).
+    int max_bits = mi::env_int("MI_SORT_BITS", 7);
+    Digits D = plan_rows(max_vocab, max_bits);
+    while (D.passes > kMaxPasses && max_bits < kMaxBits) D = plan_rows(max_vocab, ++max_bits);
     MI_REQUIRE(D.passes <= kMaxPasses, "sort_unique_fields: %d passes", D.passes);
     int32_t* ready = W.sync;                                       // [pass][field]
     int32_t* hcf = W.sync + static_cast<int64_t>(kMaxPasses) * F;  // [tile]
