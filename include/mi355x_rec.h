@@ -861,8 +861,13 @@ int32_t mi_pair_target_ranks_mean(const mi_rank_member_t* members, int32_t n_mem
  * Arithmetic: fp32 variables, exact fp32 products (fp32-input MFMA), fp32 accumulation; the FM term rounds each product
  * on its own (a model with one field gives exactly 0).  Within 1e-5 of an fp64 forward, scaled as max_err_scaled.
  * A request's outputs do not depend on the other requests of the call; two calls give the same bits.
- * Limits, checked before anything is launched (MI_ERR_INVALID / MI_ERR_UNSUPPORTED): B >= 1, F <= 64, E a multiple of 4
- * in [4, 256], at most 8 hidden layers, every layer width <= 512.  Enqueues one kernel on the stream; no scratch:
+ * Limits, checked before anything is launched (MI_ERR_INVALID / MI_ERR_UNSUPPORTED): B >= 1, F in [0, 64] with
+ * F + n_numeric >= 1 (F = 0: numeric columns only; table, field_off and ids may be NULL), E a multiple of 4 in [4, 256]
+ * wherever a table row or a numeric embedding is read, at most 8 hidden layers, every layer's OUTPUT width
+ * widths[1 .. n_layers] <= 512 (widths[0], the rows of kernel_0, is bounded by nothing but the arrays: >= the input
+ * columns, rows past them are never multiplied in and must be finite), and 128 (F + the widest output of the layers 0, 2,
+ * .. + the widest of the layers 1, 3, ..) + 4096 <= 160 KiB of LDS: F = 64 with 512 / 512 is the largest launch.
+ * Enqueues one kernel on the stream; no scratch:
  * mi_predict_fused_workspace_bytes is 0 today and workspace may be NULL (kept in the ABI for later shapes). */
 size_t mi_predict_fused_workspace_bytes(int64_t B, int32_t n_layers);
 int32_t mi_predict_fused(const float* table, int64_t table_stride, const float* lin_w, int32_t lin_stride,

@@ -511,10 +511,10 @@ class NumpyKernels:
                 if i + 1 < n_layers:
                     h = _ACT[act](h)
             z += h[:, 0]
+        if logits is not None:                                               # (rounded by the store: an fp64 buffer keeps fp64)
+            logits.numpy().reshape(-1)[:] = z
         z = z.astype(np.float32)
         sig = O.predictions(z)["logistic"]
-        if logits is not None:
-            logits.numpy().reshape(-1)[:] = z
         if logistic is not None:
             logistic.numpy().reshape(-1)[:] = sig
         if probabilities is not None:
