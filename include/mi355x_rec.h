@@ -1067,6 +1067,68 @@ int32_t mi_eval_group(const mi_fused_group_plan_t* plan, int32_t n_members, cons
                       const float* tail_scale, float* logits, float* batch_loss, int64_t* hist, int64_t* counts, double* partials,
                       int32_t blocks, mi_stream_t stream);
 
+/* ---- numeric columns in the one-launch step, the population step and the population evaluation -------------------------
+ * The reference's model_fn takes numeric_columns (trainers/deep_fm.py:59-74, :39): numeric column j owns row j of
+ * numeric_embeddings [nd, E], enters the concat as that row scaled by the column's value, and the wide part holds one weight
+ * per column on the value.  The entries below are mi_train_step_model, mi_train_group_plan_models, mi_train_group_step,
+ * mi_eval_group and mi_train_step_fused_workspace_bytes with that: the same kernels, the same device code, one more input.
+ * (Raw numeric columns — the canned estimators' form, the value itself an MLP input — are not in their scope.)
+ *
+ * mi_fused_numeric_t: n_numeric = nd; num_emb_off: numeric_embeddings [nd, E] in dense; lin_num_off: the numeric linear
+ *   weights [nd] in dense (read with use_linear only) — the engine's offsets, as mi_predict_fused takes them.  Both are
+ *   dense variables: their slots are d_m / d_v at the same offsets, and with two_rules the numeric linear weights belong to
+ *   the WIDE part like the wide bias (hp_wide, dw_m / dw_v).  NULL, or n_numeric = 0: no numeric column — the call is the
+ *   entry without "_numeric", bit for bit, and x_num may be NULL.
+ * x_num [B, nd] fp32 (device): the values, trusted to be finite as ids are trusted to lie inside their field.
+ *
+ * Forward.  The concat is the F gathered rows followed by the nd rows  x[b, j] * V[j, :]  (widths[0] = (F + nd) E):
+ *   sumv and the FM term take the numeric rows after the categorical ones, j ascending, every product rounded on its own;
+ *   layer 1 continues over the nd E further inputs against rows F E .. of kernel_0 (fmaf on the rounded product x V);
+ *   lin[b] = (the categorical wide sum) + x[b, 0] w_num[0] + x[b, 1] w_num[1] + ..., j ascending, each product rounded on
+ *   its own; the wide bias stays with the head.  A numeric row is recomputed wherever it is read and stored nowhere.
+ * Backward, for every j, e:
+ *   g[b, j, :] = d_concat[b, F + j, :] + dlogit[b] * (sumv[b, :] - x[b, j] V[j, :])        (the categorical entry gradient)
+ *   dV[j, e]   = sum_b x[b, j] * g[b, j, e]          dw_num[j] = sum_b dlogit[b] * x[b, j]
+ *   each summed by ONE thread over b ascending, one rounding per operation, into the dense-gradient workspace, and applied
+ *   by dense_rule with the other dense variables.  No atomics to global memory; no workgroup waits for another; the sweep
+ *   workgroups are as before (a numeric column owns no table row).  With x_num all zero, V, w_num and their slots keep
+ *   their bits under every rule whose update of a zero gradient on zero slots is zero (Adam from zero slots, SGD, Adagrad).
+ * Limits, checked on the host before anything is launched: those of mi_train_step_model with 1 <= F <= 32 unchanged, and
+ *   0 <= nd <= 16 and B (F + nd) E <= 16384 — the concat's budget: 26 + 13 columns fit at E = 4, B = 32 — (MI_ERR_UNSUPPORTED);
+ *   with nd > 0: use_fm or use_dnn, x_num not NULL, the offsets inside dense (MI_ERR_INVALID).
+ * workspace: mi_train_step_fused_workspace_bytes_numeric(B, F, nd, E, n_dense) — the dense gradient and d_concat
+ *   [B, (F + nd) E].
+ *
+ * mi_train_group_plan_models_numeric: numerics [n_members] beside models (NULL: none).  All members share n_numeric, as
+ *   they share F (MI_ERR_INVALID, "member i:", otherwise); the offsets are per member.  Writes the same plan struct.
+ * mi_train_group_step_numeric / mi_eval_group_numeric: x_num and its member stride — 0 = one [B, nd] ([N, nd]) array for all
+ *   members, else [M, B, nd] (B nd) / [M, N, nd] (N nd), as with ids.  They take any plan; without numeric columns x_num is
+ *   not read.  mi_train_group_step and mi_eval_group REFUSE a plan that holds numeric columns (MI_ERR_INVALID; nothing is
+ *   launched or written): they have no x_num to give it.  A member's bits are those of mi_train_step_model_numeric on it
+ *   alone; evaluation logits are the step's logits at keep_prob = 1 on the same state. */
+typedef struct mi_fused_numeric {
+  int32_t n_numeric;
+  int64_t num_emb_off;
+  int64_t lin_num_off;
+} mi_fused_numeric_t;
+
+size_t mi_train_step_fused_workspace_bytes_numeric(int64_t B, int32_t F, int32_t n_numeric, int32_t E, int64_t n_dense);
+int32_t mi_train_step_model_numeric(const mi_fused_model_t* model, const mi_fused_numeric_t* numeric, const int64_t* field_off,
+                                    const int32_t* ids, const float* x_num, const uint8_t* labels, int64_t B, int32_t F,
+                                    uint64_t seed, int32_t step, float* logits, float* loss, int32_t sweep_blocks,
+                                    mi_stream_t stream);
+int32_t mi_train_group_plan_models_numeric(const mi_fused_model_t* models, const mi_fused_numeric_t* numerics, int32_t n_members,
+                                           int64_t B, int32_t F, const int64_t* field_off, void* device_table,
+                                           size_t device_table_bytes, mi_fused_group_plan_t* plan, mi_stream_t stream);
+int32_t mi_train_group_step_numeric(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids,
+                                    int64_t ids_member_stride, const float* x_num, int64_t x_num_member_stride,
+                                    const uint8_t* labels, int64_t labels_member_stride, int64_t B, int32_t step, float* logits,
+                                    float* loss, int32_t sweep_blocks, mi_stream_t stream);
+int32_t mi_eval_group_numeric(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids, const float* x_num,
+                              int64_t x_num_member_stride, const uint8_t* labels, int64_t N, const float* tail_scale,
+                              float* logits, float* batch_loss, int64_t* hist, int64_t* counts, double* partials, int32_t blocks,
+                              mi_stream_t stream);
+
 /* ---- serving an ensemble: M models over one request batch, averaged, as one launch (csrc/serve.hip) --------------------
  * The payoff of a sweep (trainers/sweep.py): its best M members scored and averaged as ONE model.  Grid (ceil(B / 32), M):
  * row y of the grid runs the device code of mi_predict_fused on member y (member_logits[y, b] holds the bits of

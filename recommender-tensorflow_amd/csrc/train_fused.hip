@@ -10,14 +10,19 @@
 //       0. rows     field_off[f] + ids[b, f] into LDS
 //       1. forward  sumv and the FM term (products rounded one by one: a one-field model gives exactly 0), the wide sum
 //                   and layer 1 straight from the gathered table rows; then one phase per later layer, outputs
-//                   (after activation and dropout) in LDS
+//                   (after activation and dropout) in LDS.  Numeric column j (deep_fm.py:59-74) is one more row of the
+//                   concat, x[b, j] V[j, :], behind the F gathered ones: recomputed from x_num and numeric_embeddings
+//                   wherever it is read (sumv / FM term, layer 1, the gradients), never stored; the wide sum takes
+//                   x[b, j] w_num[j] after the categorical weights
 //       2. head     logit = ((lin + bias) + fm) + dnn, loss, dlogit
 //       3. backward per layer, top down: the weight and bias gradient into the dense-gradient workspace, then the
 //                   data gradient IN PLACE over the layer's input (the activation's derivative is taken from the
-//                   stored output, the dropout mask from its zeros); layer 1's data gradient is d_concat
+//                   stored output, the dropout mask from its zeros); layer 1's data gradient is d_concat; then the
+//                   numeric columns' gradients, each summed over b ascending by one thread: dV[j, e] and dw_num[j]
 //       4. apply    per DISTINCT touched row (the first entry of a row leads; entries of a row are summed in
 //                   ascending entry order) sparse_rule on the table record and the wide record, stamp = step;
-//                   dense_rule on every dense variable with the gradient of phase 3
+//                   dense_rule on every dense variable with the gradient of phase 3 (numeric_embeddings under hp, the
+//                   numeric linear weights under the wide rule, as the wide bias)
 //     sweep   each workgroup owns a slice of the R rows, builds the batch's touched set itself (a bitmap of R bits in
 //             LDS, from ids) and gives every row of its slice that is NOT touched one step of TF Adam's whole-table
 //             sweep (replay_step of optim_rules.h), table record and wide record, stamp = step.  Only records under
@@ -52,11 +57,12 @@ namespace {
 constexpr int kThreads = 512;
 constexpr int kMaxBatch = 128;
 constexpr int kMaxFields = 32;
+constexpr int kMaxNumeric = 16;
 constexpr int kMaxEmb = 16;
 constexpr int kMaxHidden = 3;
 constexpr int kMaxWidth = 64;
 constexpr int kMaxLayers = kMaxHidden + 1;          // + the logits layer
-constexpr int64_t kMaxConcat = 16384;               // B F E
+constexpr int64_t kMaxConcat = 16384;               // B (F + nd) E
 constexpr int64_t kMaxRows = int64_t(1) << 18;      // a 32 KB bitmap
 constexpr int kMaxSweepBlocks = 1024;
 constexpr size_t kMaxLds = 160 * 1024 - 1024;       // (the static arrays below take the rest)
@@ -83,11 +89,13 @@ struct Args {
   float* dwm; float* dwv;
   uint64_t wide_mask;                   // bit f set: field f has a wide weight (mi_predict_fused's wide_fields)
   float* gdense;                        // workspace: the dense gradient, indexed like dense
-  float* dcat_ws;                       // workspace: d_concat [B][F E] when LDS has no room for it, else NULL
+  float* dcat_ws;                       // workspace: d_concat [B][(F + nd) E] when LDS has no room for it, else NULL
   float* logits; float* loss;
+  const float* x_num;                   // [B][nd], or NULL (nd = 0)
   int64_t ts, R, lin_bias_off;
+  int64_t num_emb_off, lin_num_off;     // in dense: numeric_embeddings [nd][E], the numeric linear weights [nd]
   uint64_t seed;
-  int32_t B, F, E, ls, act, n_layers, use_linear, use_fm, step;
+  int32_t B, F, E, ls, act, n_layers, use_linear, use_fm, step, nd;
   int32_t o_sumv, o_tq, o_lin, o_dl, o_dcat;   // float offsets in LDS (the rows [B F] int32 lead)
   float keep, scale;
   Hp hp, hpw;
@@ -196,8 +204,10 @@ __device__ __forceinline__ float finish(const Args& p, float acc, float bias, bo
 template <bool kTrain>
 __device__ __forceinline__ float forward_block(const Args& p, char* lds, const Layer* layers, float (*red)[kThreads / 64]) {
   const int tid = threadIdx.x;
-  const int B = p.B, F = p.F, E = p.E, L = p.n_layers;
+  const int B = p.B, F = p.F, E = p.E, L = p.n_layers, nd = p.nd;
   const int64_t ts = p.ts;
+  const float* __restrict__ xn = p.x_num;                           // (read only when nd > 0)
+  const float* __restrict__ Vn = p.dense + p.num_emb_off;
   int32_t* rows = reinterpret_cast<int32_t*>(lds);
   float* fl = reinterpret_cast<float*>(lds);
   float* sumv = fl + p.o_sumv;
@@ -223,6 +233,11 @@ __device__ __forceinline__ float forward_block(const Args& p, char* lds, const L
           s = s + v;
           q = q + v * v;
         }
+        for (int j = 0; j < nd; ++j) {                            // the numeric rows, behind the categorical ones
+          const float v = xn[b * nd + j] * Vn[j * E + c];
+          s = s + v;
+          q = q + v * v;
+        }
         sumv[i] = s;
         tq[i] = s * s - q;                                        // deep_fm.py:81-87 (one field: exactly 0)
       } else if (i < nE + nL) {
@@ -230,6 +245,7 @@ __device__ __forceinline__ float forward_block(const Args& p, char* lds, const L
         float acc = 0.f;
         for (int f = 0; f < F; ++f)
           if ((p.wide_mask >> f) & 1u) acc = acc + p.lin_w[static_cast<int64_t>(rows[b * F + f]) * p.ls];
+        for (int j = 0; j < nd; ++j) acc = acc + xn[b * nd + j] * p.dense[p.lin_num_off + j];
         zlin[b] = acc;
       } else {
         const int j = i - nE - nL, b = j / w1, n = j - b * w1;
@@ -245,6 +261,11 @@ __device__ __forceinline__ float forward_block(const Args& p, char* lds, const L
             acc = fmaf(x.z, wk[2 * w1], acc);
             acc = fmaf(x.w, wk[3 * w1], acc);
           }
+        }
+        for (int jn = 0; jn < nd; ++jn) {                          // rows F E .. of kernel_0: the numeric rows x V[jn, :]
+          const float x = xn[b * nd + jn];
+          const float* __restrict__ wk = W + static_cast<int64_t>((F + jn) * E) * w1 + n;
+          for (int c = 0; c < E; ++c) acc = fmaf(x * Vn[jn * E + c], wk[c * w1], acc);
         }
         fl[layers[0].out_off + j] = finish(p, acc, p.dense[layers[0].b_off + n], L == 1, 0, b, n, thresh);
       }
@@ -309,8 +330,10 @@ __device__ __forceinline__ float forward_block(const Args& p, char* lds, const L
 __device__ __forceinline__ void batch_block(const Args& p, char* lds, const Layer* layers, float (*red)[kThreads / 64]) {
   forward_block<true>(p, lds, layers, red);
   const int tid = threadIdx.x;
-  const int B = p.B, F = p.F, E = p.E, L = p.n_layers, D = F * E;
+  const int B = p.B, F = p.F, E = p.E, L = p.n_layers, nd = p.nd, D = (F + nd) * E;
   const int64_t ts = p.ts;
+  const float* __restrict__ xn = p.x_num;
+  const float* Vn = p.dense + p.num_emb_off;                        // (phase 4 writes these: no __restrict__)
   const int32_t* rows = reinterpret_cast<const int32_t*>(lds);
   float* fl = reinterpret_cast<float*>(lds);
   const float* sumv = fl + p.o_sumv;
@@ -334,8 +357,13 @@ __device__ __forceinline__ void batch_block(const Args& p, char* lds, const Laye
           for (int b = 0; b < B; ++b) acc = fmaf(prev[b * K + k], dy[b * N + n], acc);
         } else {
           const int f = k / E, c = k - f * E;
-          for (int b = 0; b < B; ++b)
-            acc = fmaf(p.table[static_cast<int64_t>(rows[b * F + f]) * ts + c], dy[b * N + n], acc);
+          if (f < F) {
+            for (int b = 0; b < B; ++b)
+              acc = fmaf(p.table[static_cast<int64_t>(rows[b * F + f]) * ts + c], dy[b * N + n], acc);
+          } else {                                                  // a numeric row of the concat, as the forward formed it
+            const float v = Vn[(f - F) * E + c];
+            for (int b = 0; b < B; ++b) acc = fmaf(xn[b * nd + (f - F)] * v, dy[b * N + n], acc);
+          }
         }
         p.gdense[ly.w_off + i] = acc;
       } else {
@@ -360,7 +388,7 @@ __device__ __forceinline__ void batch_block(const Args& p, char* lds, const Laye
         prev[i] = g;
       }
     } else {
-      for (int i = tid; i < B * K; i += kThreads) {               // d_concat [B][F E] (K >= F E; rows past it belong to no column)
+      for (int i = tid; i < B * K; i += kThreads) {               // d_concat [B][(F + nd) E] (K >= that; rows past it belong to no column)
         const int b = i / K, k = i - b * K;
         if (k >= D) continue;
         float g = 0.f;
@@ -369,6 +397,27 @@ __device__ __forceinline__ void batch_block(const Args& p, char* lds, const Laye
       }
     }
     __syncthreads();
+  }
+  // the numeric columns: dV[j, c] = sum_b x[b, j] g[b, j, c] with the entry gradient of the categorical rows,
+  // g = d_concat[b, F + j, c] + dlogit[b] (sumv[b, c] - x[b, j] V[j, c]), and dw_num[j] = sum_b dlogit[b] x[b, j]; one thread
+  // per element, b ascending.  The same thread applies its element in phase 4: nothing else reads V or w_num from here on.
+  for (int i = tid; i < nd * E + (p.use_linear ? nd : 0); i += kThreads) {
+    float acc = 0.f;
+    if (i < nd * E) {
+      const int j = i / E, c = i - j * E;
+      const float w = Vn[i];
+      for (int b = 0; b < B; ++b) {
+        const float x = xn[b * nd + j];
+        float g = L ? dcat[b * D + (F + j) * E + c] : 0.f;
+        if (p.use_fm) g = g + dl[b] * (sumv[b * E + c] - x * w);
+        acc = acc + x * g;
+      }
+      p.gdense[p.num_emb_off + i] = acc;
+    } else {
+      const int j = i - nd * E;
+      for (int b = 0; b < B; ++b) acc = acc + dl[b] * xn[b * nd + j];
+      p.gdense[p.lin_num_off + j] = acc;
+    }
   }
 
   // 4. apply.  Sparse: item (entry e, float4 chunk c) — the first entry of a row leads it
@@ -433,6 +482,17 @@ __device__ __forceinline__ void batch_block(const Args& p, char* lds, const Laye
       p.dense[o] = w; st_slot(p.dm, o, m); st_slot(p.dv, o, v);
     }
   }
+  // numeric_embeddings follow hp like the MLP; the numeric linear weights belong to the wide part (hpw, dwm / dwv).  Element i
+  // is applied by the thread that wrote its gradient.
+  for (int i = tid; i < nd * E + (p.use_linear ? nd : 0); i += kThreads) {
+    const bool wide = i >= nd * E;
+    const int64_t o = wide ? p.lin_num_off + (i - nd * E) : p.num_emb_off + i;
+    float* const sm = wide ? p.dwm : p.dm;
+    float* const sv = wide ? p.dwv : p.dv;
+    float w = p.dense[o], m = ld_slot(sm, o), v = ld_slot(sv, o);
+    dense_rule(wide ? p.hpw : p.hp, w, m, v, p.gdense[o]);
+    p.dense[o] = w; st_slot(sm, o, m); st_slot(sv, o, v);
+  }
   if (p.use_linear && tid == 0) {
     float g = red[1][0];
     for (int w = 1; w < nw; ++w) g = g + red[1][w];
@@ -471,7 +531,8 @@ struct Member {
 };
 
 __global__ __launch_bounds__(kThreads) void train_fused_group_k(const Member* __restrict__ members, const int32_t* __restrict__ ids,
-                                                                int64_t ids_stride, const uint8_t* __restrict__ labels,
+                                                                int64_t ids_stride, const float* __restrict__ x_num,
+                                                                int64_t x_stride, const uint8_t* __restrict__ labels,
                                                                 int64_t labels_stride, float* __restrict__ logits,
                                                                 float* __restrict__ loss, int32_t step) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -487,6 +548,7 @@ __global__ __launch_bounds__(kThreads) void train_fused_group_k(const Member* __
     if (me->lr_table) sp.hp.lr_t = me->lr_table[step < me->lr_len ? step : me->lr_len - 1];
     if (me->lr_table_w) sp.hpw.lr_t = me->lr_table_w[step < me->lr_len_w ? step : me->lr_len_w - 1];
     sp.ids = ids + y * ids_stride;
+    sp.x_num = x_num ? x_num + y * x_stride : nullptr;
     sp.labels = labels + y * labels_stride;
     sp.logits = logits + static_cast<int64_t>(y) * sp.B;
     sp.loss = loss + y;
@@ -525,6 +587,7 @@ constexpr size_t kMaxForwardLds = sizeof(float) * static_cast<size_t>(kMaxConcat
 static_assert(kMaxForwardLds + sizeof(EvalShared) + 256 <= 160 * 1024, "the evaluation kernel's LDS");
 
 __global__ __launch_bounds__(kThreads) void eval_fused_group_k(const Member* __restrict__ members, const int32_t* __restrict__ ids,
+                                                               const float* __restrict__ x_num, int64_t x_stride,
                                                                const uint8_t* __restrict__ labels, int64_t N, int64_t T,
                                                                const float* __restrict__ tail_scale, float* __restrict__ logits,
                                                                float* __restrict__ batch_loss, unsigned long long* __restrict__ hist,
@@ -545,6 +608,7 @@ __global__ __launch_bounds__(kThreads) void eval_fused_group_k(const Member* __r
     const int n = static_cast<int>(N - b0 < B ? N - b0 : B);
     if (tid == 0) {
       es.sp.ids = ids + b0 * F;
+      es.sp.x_num = x_num ? x_num + y * x_stride + b0 * es.sp.nd : nullptr;
       es.sp.labels = labels + b0;
       es.sp.logits = logits ? logits + y * N + b0 : nullptr;
       es.sp.loss = batch_loss + y * T + t;
@@ -584,9 +648,10 @@ int64_t batch_lds_floats(int64_t B, int32_t F, int32_t E, const int32_t* widths,
   return n;
 }
 
-size_t workspace_bytes_of(int64_t B, int32_t F, int32_t E, int64_t n_dense) {
-  if (B < 0 || F < 0 || E < 0 || n_dense < 0) return 0;
-  return sizeof(float) * static_cast<size_t>(align4(n_dense) + align4(B * F * E));
+// the dense gradient, then d_concat [B][(F + nd) E]
+size_t workspace_bytes_of(int64_t B, int32_t F, int32_t nd, int32_t E, int64_t n_dense) {
+  if (B < 0 || F < 0 || nd < 0 || E < 0 || n_dense < 0) return 0;
+  return sizeof(float) * static_cast<size_t>(align4(n_dense) + align4(B * (F + nd) * E));
 }
 
 // slots a rule keeps: Adam, Ftrl and RMSProp two, Adagrad slot 0 only, SGD none
@@ -612,10 +677,13 @@ mi_fused_model_t model_of(const mi_fused_member_t& m, int32_t F) {
 // The checks of one model, in mi_train_step_fused's order, and its Args (everything but ids / labels / logits / loss / step /
 // seed / lr_t, which the caller fills in; have_batch / have_outputs: the caller holds those pointers — a plan has none yet),
 // the dynamic LDS of its workgroups and the built-in number of sweep workgroups (0: no part is under Adam, nothing to
-// sweep).  Writes nothing but `a`.  (m's lr_table*, lr_table*_len and seed_base belong to the group plan.)
-int32_t plan_model(const mi_fused_model_t& m, const int64_t* field_off, int64_t B, int32_t F, int32_t step, bool have_batch,
-                   bool have_outputs, int32_t sweep_blocks, Args& a, size_t& lds_out, int& blocks_out) {
+// sweep).  Writes nothing but `a`.  (m's lr_table*, lr_table*_len and seed_base belong to the group plan.)  num: the model's
+// numeric columns, or NULL (none); a.x_num is the caller's to fill in, like ids.
+int32_t plan_model(const mi_fused_model_t& m, const mi_fused_numeric_t* num, const int64_t* field_off, int64_t B, int32_t F,
+                   int32_t step, bool have_batch, bool have_outputs, int32_t sweep_blocks, Args& a, size_t& lds_out,
+                   int& blocks_out) {
   const int64_t R = m.R, n_dense = m.n_dense;
+  const int32_t nd = num ? num->n_numeric : 0;
   const int32_t n_layers = m.n_layers;
   const int32_t* widths = m.widths;
   const bool two = m.two_rules != 0;
@@ -636,8 +704,13 @@ int32_t plan_model(const mi_fused_model_t& m, const int64_t* field_off, int64_t 
   if (emb && (m.E < 4 || m.E > kMaxEmb || (m.E & 3)))
     return unsupported("train_step_fused: embedding size %d (a multiple of 4, at most %d)", m.E, kMaxEmb);
   const int32_t E = emb ? m.E : 4;
-  if (B * F * E > kMaxConcat)
+  if (nd < 0 || nd > kMaxNumeric) return unsupported("train_step_fused: %d numeric columns (0 to %d)", nd, kMaxNumeric);
+  if (nd == 0 && B * F * E > kMaxConcat)
     return unsupported("train_step_fused: B F E = %lld (at most %lld)", (long long)(B * F * E), (long long)kMaxConcat);
+  if (B * (F + nd) * E > kMaxConcat)
+    return unsupported("train_step_fused: B (F + n_numeric) E = %lld (at most %lld)", (long long)(B * (F + nd) * E),
+                       (long long)kMaxConcat);
+  MI_REQUIRE(nd == 0 || emb, "train_step_fused: %d numeric columns without the FM term and the DNN (their embeddings enter nothing)", nd);
   if (R < 1 || R > kMaxRows) return unsupported("train_step_fused: R=%lld table rows (1 to %lld)", (long long)R, (long long)kMaxRows);
   if (sweep_blocks < 0 || sweep_blocks > kMaxSweepBlocks)
     return unsupported("train_step_fused: sweep_blocks=%d (0 = the built-in choice, at most %d)", sweep_blocks, kMaxSweepBlocks);
@@ -659,6 +732,12 @@ int32_t plan_model(const mi_fused_model_t& m, const int64_t* field_off, int64_t 
   MI_REQUIRE(m.dense && (nt < 1 || m.d_m) && (nt < 2 || m.d_v) && n_dense >= 1, "train_step_fused: dense / d_m / d_v / n_dense");
   MI_REQUIRE(!two || ((nw < 1 || m.dw_m) && (nw < 2 || m.dw_v)), "train_step_fused: dw_m / dw_v (the wide rule's dense slots)");
   MI_REQUIRE(!m.use_linear || (m.lin_bias_off >= 0 && m.lin_bias_off < n_dense), "train_step_fused: lin_bias_off");
+  MI_REQUIRE(nd == 0 || (num->num_emb_off >= 0 && num->num_emb_off + static_cast<int64_t>(nd) * E <= n_dense),
+             "train_step_fused: num_emb_off=%lld ([%d, %d] numeric_embeddings inside the %lld dense variables)",
+             (long long)num->num_emb_off, nd, E, (long long)n_dense);
+  MI_REQUIRE(nd == 0 || !m.use_linear || (num->lin_num_off >= 0 && num->lin_num_off + nd <= n_dense),
+             "train_step_fused: lin_num_off=%lld (%d numeric linear weights inside the %lld dense variables)",
+             (long long)num->lin_num_off, nd, (long long)n_dense);
   MI_REQUIRE(m.use_dnn ? n_layers >= 1 : n_layers == 0, "train_step_fused: %d layers (a DNN has at least its logits layer)", n_layers);
   if (n_layers > kMaxLayers)
     return unsupported("train_step_fused: %d hidden layers (at most %d)", n_layers - 1, kMaxHidden);
@@ -674,9 +753,9 @@ int32_t plan_model(const mi_fused_model_t& m, const int64_t* field_off, int64_t 
                "train_step_fused: layer %d lies outside the %lld dense variables", i, (long long)n_dense);
     a.l[i].w_off = wo; a.l[i].b_off = bo; a.l[i].fan_in = fi; a.l[i].fan_out = fo;
   }
-  MI_REQUIRE(n_layers == 0 || widths[0] == F * E, "train_step_fused: widths[0]=%d, the %d input columns expected",
-             n_layers ? widths[0] : 0, F * E);
-  const size_t need = workspace_bytes_of(B, F, E, n_dense);
+  MI_REQUIRE(n_layers == 0 || widths[0] == (F + nd) * E, "train_step_fused: widths[0]=%d, the %d input columns expected",
+             n_layers ? widths[0] : 0, (F + nd) * E);
+  const size_t need = workspace_bytes_of(B, F, nd, E, n_dense);
   if (m.workspace_bytes < need || !m.workspace) {
     mi::set_error("train_step_fused: workspace of %zu bytes, %zu needed", m.workspace_bytes, need);
     return MI_ERR_WORKSPACE;
@@ -691,7 +770,7 @@ int32_t plan_model(const mi_fused_model_t& m, const int64_t* field_off, int64_t 
   a.o_lin = static_cast<int32_t>(o); o += align4(B);
   a.o_dl = static_cast<int32_t>(o); o += align4(B);
   for (int i = 0; i < n_layers; ++i) { a.l[i].out_off = static_cast<int32_t>(o); o += align4(B * widths[i + 1]); }
-  const int64_t dcat = n_layers ? align4(B * F * E) : 0;
+  const int64_t dcat = n_layers ? align4(B * (F + nd) * E) : 0;
   a.gdense = static_cast<float*>(m.workspace);
   a.dcat_ws = nullptr;
   a.o_dcat = static_cast<int32_t>(o);
@@ -711,6 +790,7 @@ int32_t plan_model(const mi_fused_model_t& m, const int64_t* field_off, int64_t 
   a.dwm = nw >= 1 ? (two ? m.dw_m : m.d_m) : nullptr; a.dwv = nw >= 2 ? (two ? m.dw_v : m.d_v) : nullptr;
   a.wide_mask = m.use_linear ? m.wide_fields : 0;
   a.ts = m.table_stride ? m.table_stride : E; a.R = R; a.lin_bias_off = m.lin_bias_off;
+  a.nd = nd; a.num_emb_off = nd ? num->num_emb_off : 0; a.lin_num_off = (nd && m.use_linear) ? num->lin_num_off : 0;
   a.B = iB; a.F = F; a.E = E; a.ls = m.lin_stride; a.act = m.activation; a.n_layers = n_layers;
   a.use_linear = m.use_linear != 0; a.use_fm = m.use_fm != 0;
   a.keep = m.keep_prob; a.scale = m.scale; a.hp = make_hp(&m.hp); a.hpw = make_hp(&hw);
@@ -723,18 +803,29 @@ int32_t plan_model(const mi_fused_model_t& m, const int64_t* field_off, int64_t 
 }
 
 constexpr uint64_t kPlanMagic = 0x6d695f67726f7570ull;   // "mi_group"
+// a plan whose members have nd numeric columns: kPlanMagicNumeric + nd, so that the entries without an x_num know it
+constexpr uint64_t kPlanMagicNumeric = 0x6d695f6e756d0000ull;   // "mi_num", then nd
+int plan_numeric(const mi_fused_group_plan_t* plan) {           // nd of a plan (0: none), -1: not a plan
+  if (!plan || !plan->device_table) return -1;
+  if (plan->magic == kPlanMagic) return 0;
+  const uint64_t nd = plan->magic - kPlanMagicNumeric;
+  return (nd >= 1 && nd <= static_cast<uint64_t>(kMaxNumeric)) ? static_cast<int>(nd) : -1;
+}
 constexpr int kGroupGridBlocks = 1 << 16;                // the built-in sweep_blocks keeps (1 + G) M at or below this
 constexpr int kEvalResident = 4 * 256;                   // workgroups of one evaluation launch (the built-in choice)
 
-// one step of one model: mi_train_step_fused and mi_train_step_model behind their own checks
-int32_t step_one(const mi_fused_model_t& m, const int64_t* field_off, const int32_t* ids, const uint8_t* labels, int64_t B,
-                 int32_t F, uint64_t seed, int32_t step, float* logits, float* loss, int32_t sweep_blocks, mi_stream_t stream) {
+// one step of one model: mi_train_step_fused, mi_train_step_model and mi_train_step_model_numeric behind their own checks
+int32_t step_one(const mi_fused_model_t& m, const mi_fused_numeric_t* num, const int64_t* field_off, const int32_t* ids,
+                 const float* x_num, const uint8_t* labels, int64_t B, int32_t F, uint64_t seed, int32_t step, float* logits,
+                 float* loss, int32_t sweep_blocks, mi_stream_t stream) {
   Args a;
   size_t lds = 0;
   int blocks = 0;
-  const int32_t rc = plan_model(m, field_off, B, F, step, ids && labels, logits && loss, sweep_blocks, a, lds, blocks);
+  const int32_t rc = plan_model(m, num, field_off, B, F, step, ids && labels, logits && loss, sweep_blocks, a, lds, blocks);
   if (rc != MI_OK) return rc;
+  MI_REQUIRE(a.nd == 0 || x_num, "train_step_fused: x_num (the model has %d numeric columns)", a.nd);
   a.ids = ids; a.labels = labels; a.logits = logits; a.loss = loss; a.seed = seed; a.step = step;
+  a.x_num = a.nd ? x_num : nullptr;
   const int32_t rl = mi::raise_lds(&train_fused_k, lds, "train_step_fused");
   if (rl != MI_OK) return rl;
   train_fused_k<<<dim3(1 + blocks), dim3(kThreads), lds, mi::as_stream(stream)>>>(a);       // (no Adam part: the batch workgroup alone)
@@ -742,11 +833,12 @@ int32_t step_one(const mi_fused_model_t& m, const int64_t* field_off, const int3
   return MI_OK;
 }
 
-// mi_train_group_plan (adam_only: its members, behind that entry's refusal) and mi_train_group_plan_models: model(i) is
-// member i's description
+// mi_train_group_plan (adam_only: its members, behind that entry's refusal), mi_train_group_plan_models and
+// mi_train_group_plan_models_numeric: model(i) is member i's description, numerics[i] its numeric columns (NULL: none)
 template <typename Get>
-int32_t plan_group(Get model, bool adam_only, int32_t n_members, int64_t B, int32_t F, const int64_t* field_off, void* device_table,
-                   size_t device_table_bytes, mi_fused_group_plan_t* plan, mi_stream_t stream) {
+int32_t plan_group(Get model, const mi_fused_numeric_t* numerics, bool adam_only, int32_t n_members, int64_t B, int32_t F,
+                   const int64_t* field_off, void* device_table, size_t device_table_bytes, mi_fused_group_plan_t* plan,
+                   mi_stream_t stream) {
   MI_REQUIRE(plan, "train_group_plan: plan");
   MI_REQUIRE(n_members >= 1, "train_group_plan: %d members (at least 1)", n_members);
   if (n_members > MI_FUSED_GROUP_MAX_MEMBERS)
@@ -765,13 +857,19 @@ int32_t plan_group(Get model, bool adam_only, int32_t n_members, int64_t B, int3
   size_t n_owned = 0, lds = 0;
   int blocks = 0;
   int64_t max_step = INT32_MAX;
+  const int32_t nd = numerics ? numerics[0].n_numeric : 0;       // (one set of feature columns: the members share it, like F)
   for (int32_t i = 0; i < n_members; ++i) {
     const mi_fused_model_t m = model(i);
     size_t lds_i = 0;
     int blocks_i = 0;
     int32_t rc = MI_OK;
     if (adam_only && m.hp.kind != MI_OPT_ADAM) rc = unsupported("train_step_fused: optimizer kind %d (Adam only)", m.hp.kind);
-    if (rc == MI_OK) rc = plan_model(m, field_off, B, F, 1, true, true, 0, tab[i].a, lds_i, blocks_i);
+    if (rc == MI_OK && numerics && numerics[i].n_numeric != nd) {
+      mi::set_error("train_step_fused: %d numeric columns, member 0 has %d (the members share one set of feature columns)",
+                    numerics[i].n_numeric, nd);
+      rc = MI_ERR_INVALID;
+    }
+    if (rc == MI_OK) rc = plan_model(m, numerics ? numerics + i : nullptr, field_off, B, F, 1, true, true, 0, tab[i].a, lds_i, blocks_i);
     // a schedule table exactly for a rule that is Adam (with one rule the wide part reads hp's)
     const bool t_adam = m.hp.kind == MI_OPT_ADAM, w_adam = m.two_rules && m.hp_wide.kind == MI_OPT_ADAM;
     if (rc == MI_OK && t_adam && (!m.lr_table || m.lr_table_len < 2)) {
@@ -815,78 +913,14 @@ int32_t plan_group(Get model, bool adam_only, int32_t n_members, int64_t B, int3
   while (blocks > 1 && static_cast<int64_t>(1 + blocks) * n_members > kGroupGridBlocks) --blocks;
   plan->device_table = device_table; plan->n_members = n_members; plan->B = static_cast<int32_t>(B); plan->F = F;
   plan->lds_bytes = static_cast<uint32_t>(lds); plan->sweep_blocks = blocks; plan->max_step = static_cast<int32_t>(max_step);
-  plan->magic = kPlanMagic;
+  plan->magic = nd ? kPlanMagicNumeric + static_cast<uint64_t>(nd) : kPlanMagic;
   return MI_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t mi_train_step_fused_workspace_bytes(int64_t B, int32_t F, int32_t E, int64_t n_dense) {
-  return workspace_bytes_of(B, F, E, n_dense);
-}
-
-int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_stride, float* lin_w, float* l_m, float* l_v,
-                            int32_t lin_stride, int32_t* last_step, const int64_t* field_off, int64_t R, const int32_t* ids,
-                            const uint8_t* labels, int64_t B, int32_t F, int32_t E, float* dense, float* d_m, float* d_v,
-                            int64_t n_dense, const int64_t* layer_off, const int32_t* widths, int32_t n_layers,
-                            int32_t activation, int32_t use_linear, int32_t use_fm, int32_t use_dnn, int64_t lin_bias_off,
-                            float keep_prob, uint64_t seed, float scale, int32_t step, const mi_opt_hparams* hp,
-                            float* logits, float* loss, int32_t sweep_blocks, void* workspace, size_t workspace_bytes,
-                            mi_stream_t stream) {
-  MI_REQUIRE(hp, "train_step_fused: hp");
-  mi_fused_member_t m{};                 // (lr_table, lr_table_len and seed_base stay unused: the call brings lr_t and the seed)
-  m.table = table; m.t_m = t_m; m.t_v = t_v; m.table_stride = table_stride;
-  m.lin_w = lin_w; m.l_m = l_m; m.l_v = l_v; m.lin_stride = lin_stride;
-  m.last_step = last_step; m.R = R; m.E = E;
-  m.dense = dense; m.d_m = d_m; m.d_v = d_v; m.n_dense = n_dense;
-  m.layer_off = layer_off; m.widths = widths; m.n_layers = n_layers; m.activation = activation;
-  m.use_linear = use_linear; m.use_fm = use_fm; m.use_dnn = use_dnn; m.lin_bias_off = lin_bias_off;
-  m.keep_prob = keep_prob; m.scale = scale; m.hp = *hp;
-  m.workspace = workspace; m.workspace_bytes = workspace_bytes;
-  if (hp->kind != MI_OPT_ADAM) return unsupported("train_step_fused: optimizer kind %d (Adam only)", hp->kind);
-  return step_one(model_of(m, F), field_off, ids, labels, B, F, seed, step, logits, loss, sweep_blocks, stream);
-}
-
-int32_t mi_train_step_model(const mi_fused_model_t* model, const int64_t* field_off, const int32_t* ids, const uint8_t* labels,
-                            int64_t B, int32_t F, uint64_t seed, int32_t step, float* logits, float* loss, int32_t sweep_blocks,
-                            mi_stream_t stream) {
-  MI_REQUIRE(model, "train_step_fused: model");
-  return step_one(*model, field_off, ids, labels, B, F, seed, step, logits, loss, sweep_blocks, stream);
-}
-
-size_t mi_train_group_plan_bytes(int32_t n_members) {
-  return n_members < 0 ? 0 : sizeof(Member) * static_cast<size_t>(n_members);
-}
-
-int32_t mi_train_group_plan(const mi_fused_member_t* members, int32_t n_members, int64_t B, int32_t F, const int64_t* field_off,
-                            void* device_table, size_t device_table_bytes, mi_fused_group_plan_t* plan, mi_stream_t stream) {
-  MI_REQUIRE(plan, "train_group_plan: plan");
-  MI_REQUIRE(n_members >= 1, "train_group_plan: %d members (at least 1)", n_members);
-  if (n_members > MI_FUSED_GROUP_MAX_MEMBERS)
-    return unsupported("train_group_plan: %d members (at most %d in one launch)", n_members, MI_FUSED_GROUP_MAX_MEMBERS);
-  MI_REQUIRE(members, "train_group_plan: members");
-  return plan_group([&](int32_t i) { return model_of(members[i], F); }, true, n_members, B, F, field_off, device_table,
-                    device_table_bytes, plan, stream);
-}
-
-int32_t mi_train_group_plan_models(const mi_fused_model_t* models, int32_t n_members, int64_t B, int32_t F,
-                                   const int64_t* field_off, void* device_table, size_t device_table_bytes,
-                                   mi_fused_group_plan_t* plan, mi_stream_t stream) {
-  MI_REQUIRE(plan, "train_group_plan: plan");
-  MI_REQUIRE(n_members >= 1, "train_group_plan: %d members (at least 1)", n_members);
-  if (n_members > MI_FUSED_GROUP_MAX_MEMBERS)
-    return unsupported("train_group_plan: %d members (at most %d in one launch)", n_members, MI_FUSED_GROUP_MAX_MEMBERS);
-  MI_REQUIRE(models, "train_group_plan: models");
-  return plan_group([&](int32_t i) { return models[i]; }, false, n_members, B, F, field_off, device_table, device_table_bytes,
-                    plan, stream);
-}
-
-int32_t mi_train_group_step(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids, int64_t ids_member_stride,
-                            const uint8_t* labels, int64_t labels_member_stride, int64_t B, int32_t step, float* logits,
-                            float* loss, int32_t sweep_blocks, mi_stream_t stream) {
-  MI_REQUIRE(plan && plan->magic == kPlanMagic && plan->device_table, "train_group_step: plan (not written by mi_train_group_plan)");
+// mi_train_group_step and mi_train_group_step_numeric behind their plan checks (nd: the plan's numeric columns)
+int32_t group_step(const mi_fused_group_plan_t* plan, int nd, int32_t n_members, const int32_t* ids, int64_t ids_member_stride,
+                   const float* x_num, int64_t x_member_stride, const uint8_t* labels, int64_t labels_member_stride, int64_t B,
+                   int32_t step, float* logits, float* loss, int32_t sweep_blocks, mi_stream_t stream) {
   MI_REQUIRE(n_members == plan->n_members, "train_group_step: %d members, the plan has %d", n_members, plan->n_members);
   MI_REQUIRE(B == plan->B, "train_group_step: B=%lld, the plan was made for %d", (long long)B, plan->B);
   MI_REQUIRE(step >= 1, "train_group_step: step=%d (the global step after this call, 1-based)", step);
@@ -895,6 +929,10 @@ int32_t mi_train_group_step(const mi_fused_group_plan_t* plan, int32_t n_members
   MI_REQUIRE(ids_member_stride == 0 || ids_member_stride == B * plan->F,
              "train_group_step: ids_member_stride=%lld (0 = one batch for all members, or B F = %lld)",
              (long long)ids_member_stride, (long long)(B * plan->F));
+  MI_REQUIRE(nd == 0 || x_num, "train_group_step: x_num (the plan's members have %d numeric columns)", nd);
+  MI_REQUIRE(nd == 0 || x_member_stride == 0 || x_member_stride == B * nd,
+             "train_group_step: x_num_member_stride=%lld (0 = one batch for all members, or B n_numeric = %lld)",
+             (long long)x_member_stride, (long long)(B * nd));
   MI_REQUIRE(labels_member_stride == 0 || labels_member_stride == B,
              "train_group_step: labels_member_stride=%lld (0 = one batch for all members, or B = %lld)",
              (long long)labels_member_stride, (long long)B);
@@ -906,18 +944,23 @@ int32_t mi_train_group_step(const mi_fused_group_plan_t* plan, int32_t n_members
   const int32_t rl = mi::raise_lds(&train_fused_group_k, plan->lds_bytes, "train_group_step");
   if (rl != MI_OK) return rl;
   train_fused_group_k<<<dim3(1 + blocks, n_members), dim3(kThreads), plan->lds_bytes, mi::as_stream(stream)>>>(
-      static_cast<const Member*>(plan->device_table), ids, ids_member_stride, labels, labels_member_stride, logits, loss, step);
+      static_cast<const Member*>(plan->device_table), ids, ids_member_stride, nd ? x_num : nullptr, nd ? x_member_stride : 0,
+      labels, labels_member_stride, logits, loss, step);
   MI_CHECK_LAUNCH("train_group_step");
   return MI_OK;
 }
 
-int32_t mi_eval_group(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids, const uint8_t* labels, int64_t N,
-                      const float* tail_scale, float* logits, float* batch_loss, int64_t* hist, int64_t* counts, double* partials,
-                      int32_t blocks, mi_stream_t stream) {
-  MI_REQUIRE(plan && plan->magic == kPlanMagic && plan->device_table, "eval_group: plan (not written by mi_train_group_plan)");
+// mi_eval_group and mi_eval_group_numeric behind their plan checks
+int32_t eval_group(const mi_fused_group_plan_t* plan, int nd, int32_t n_members, const int32_t* ids, const float* x_num,
+                   int64_t x_member_stride, const uint8_t* labels, int64_t N, const float* tail_scale, float* logits,
+                   float* batch_loss, int64_t* hist, int64_t* counts, double* partials, int32_t blocks, mi_stream_t stream) {
   MI_REQUIRE(n_members == plan->n_members, "eval_group: %d members, the plan has %d", n_members, plan->n_members);
   MI_REQUIRE(N >= 1 && N <= INT32_MAX, "eval_group: N=%lld examples (1 to %d)", (long long)N, INT32_MAX);
   MI_REQUIRE(ids && labels, "eval_group: ids / labels");
+  MI_REQUIRE(nd == 0 || x_num, "eval_group: x_num (the plan's members have %d numeric columns)", nd);
+  MI_REQUIRE(nd == 0 || x_member_stride == 0 || x_member_stride == N * nd,
+             "eval_group: x_num_member_stride=%lld (0 = one set for all members, or N n_numeric = %lld)",
+             (long long)x_member_stride, (long long)(N * nd));
   MI_REQUIRE(batch_loss && hist && counts && partials, "eval_group: batch_loss / hist / counts / partials");
   MI_REQUIRE(plan->B >= 1 && plan->B <= kMaxBatch && plan->lds_bytes <= kMaxLds, "eval_group: plan (damaged)");
   MI_REQUIRE(N % plan->B == 0 || tail_scale, "eval_group: tail_scale (the last tile has %lld of %d examples)",
@@ -940,10 +983,141 @@ int32_t mi_eval_group(const mi_fused_group_plan_t* plan, int32_t n_members, cons
   const int32_t rl = mi::raise_lds(&eval_fused_group_k, lds, "eval_group");
   if (rl != MI_OK) return rl;
   eval_fused_group_k<<<dim3(static_cast<unsigned>(X), n_members), dim3(kThreads), lds, mi::as_stream(stream)>>>(
-      static_cast<const Member*>(plan->device_table), ids, labels, N, T, tail_scale, logits, batch_loss,
-      reinterpret_cast<unsigned long long*>(hist), reinterpret_cast<unsigned long long*>(counts), partials);
+      static_cast<const Member*>(plan->device_table), ids, nd ? x_num : nullptr, nd ? x_member_stride : 0, labels, N, T,
+      tail_scale, logits, batch_loss, reinterpret_cast<unsigned long long*>(hist),
+      reinterpret_cast<unsigned long long*>(counts), partials);
   MI_CHECK_LAUNCH("eval_group");
   return MI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mi_train_step_fused_workspace_bytes(int64_t B, int32_t F, int32_t E, int64_t n_dense) {
+  return workspace_bytes_of(B, F, 0, E, n_dense);
+}
+
+size_t mi_train_step_fused_workspace_bytes_numeric(int64_t B, int32_t F, int32_t n_numeric, int32_t E, int64_t n_dense) {
+  return workspace_bytes_of(B, F, n_numeric, E, n_dense);
+}
+
+int32_t mi_train_step_fused(float* table, float* t_m, float* t_v, int64_t table_stride, float* lin_w, float* l_m, float* l_v,
+                            int32_t lin_stride, int32_t* last_step, const int64_t* field_off, int64_t R, const int32_t* ids,
+                            const uint8_t* labels, int64_t B, int32_t F, int32_t E, float* dense, float* d_m, float* d_v,
+                            int64_t n_dense, const int64_t* layer_off, const int32_t* widths, int32_t n_layers,
+                            int32_t activation, int32_t use_linear, int32_t use_fm, int32_t use_dnn, int64_t lin_bias_off,
+                            float keep_prob, uint64_t seed, float scale, int32_t step, const mi_opt_hparams* hp,
+                            float* logits, float* loss, int32_t sweep_blocks, void* workspace, size_t workspace_bytes,
+                            mi_stream_t stream) {
+  MI_REQUIRE(hp, "train_step_fused: hp");
+  mi_fused_member_t m{};                 // (lr_table, lr_table_len and seed_base stay unused: the call brings lr_t and the seed)
+  m.table = table; m.t_m = t_m; m.t_v = t_v; m.table_stride = table_stride;
+  m.lin_w = lin_w; m.l_m = l_m; m.l_v = l_v; m.lin_stride = lin_stride;
+  m.last_step = last_step; m.R = R; m.E = E;
+  m.dense = dense; m.d_m = d_m; m.d_v = d_v; m.n_dense = n_dense;
+  m.layer_off = layer_off; m.widths = widths; m.n_layers = n_layers; m.activation = activation;
+  m.use_linear = use_linear; m.use_fm = use_fm; m.use_dnn = use_dnn; m.lin_bias_off = lin_bias_off;
+  m.keep_prob = keep_prob; m.scale = scale; m.hp = *hp;
+  m.workspace = workspace; m.workspace_bytes = workspace_bytes;
+  if (hp->kind != MI_OPT_ADAM) return unsupported("train_step_fused: optimizer kind %d (Adam only)", hp->kind);
+  return step_one(model_of(m, F), nullptr, field_off, ids, nullptr, labels, B, F, seed, step, logits, loss, sweep_blocks, stream);
+}
+
+int32_t mi_train_step_model(const mi_fused_model_t* model, const int64_t* field_off, const int32_t* ids, const uint8_t* labels,
+                            int64_t B, int32_t F, uint64_t seed, int32_t step, float* logits, float* loss, int32_t sweep_blocks,
+                            mi_stream_t stream) {
+  MI_REQUIRE(model, "train_step_fused: model");
+  return step_one(*model, nullptr, field_off, ids, nullptr, labels, B, F, seed, step, logits, loss, sweep_blocks, stream);
+}
+
+int32_t mi_train_step_model_numeric(const mi_fused_model_t* model, const mi_fused_numeric_t* numeric, const int64_t* field_off,
+                                    const int32_t* ids, const float* x_num, const uint8_t* labels, int64_t B, int32_t F,
+                                    uint64_t seed, int32_t step, float* logits, float* loss, int32_t sweep_blocks,
+                                    mi_stream_t stream) {
+  MI_REQUIRE(model, "train_step_fused: model");
+  return step_one(*model, numeric, field_off, ids, x_num, labels, B, F, seed, step, logits, loss, sweep_blocks, stream);
+}
+
+size_t mi_train_group_plan_bytes(int32_t n_members) {
+  return n_members < 0 ? 0 : sizeof(Member) * static_cast<size_t>(n_members);
+}
+
+int32_t mi_train_group_plan(const mi_fused_member_t* members, int32_t n_members, int64_t B, int32_t F, const int64_t* field_off,
+                            void* device_table, size_t device_table_bytes, mi_fused_group_plan_t* plan, mi_stream_t stream) {
+  MI_REQUIRE(plan, "train_group_plan: plan");
+  MI_REQUIRE(n_members >= 1, "train_group_plan: %d members (at least 1)", n_members);
+  if (n_members > MI_FUSED_GROUP_MAX_MEMBERS)
+    return unsupported("train_group_plan: %d members (at most %d in one launch)", n_members, MI_FUSED_GROUP_MAX_MEMBERS);
+  MI_REQUIRE(members, "train_group_plan: members");
+  return plan_group([&](int32_t i) { return model_of(members[i], F); }, nullptr, true, n_members, B, F, field_off, device_table,
+                    device_table_bytes, plan, stream);
+}
+
+int32_t mi_train_group_plan_models(const mi_fused_model_t* models, int32_t n_members, int64_t B, int32_t F,
+                                   const int64_t* field_off, void* device_table, size_t device_table_bytes,
+                                   mi_fused_group_plan_t* plan, mi_stream_t stream) {
+  MI_REQUIRE(plan, "train_group_plan: plan");
+  MI_REQUIRE(n_members >= 1, "train_group_plan: %d members (at least 1)", n_members);
+  if (n_members > MI_FUSED_GROUP_MAX_MEMBERS)
+    return unsupported("train_group_plan: %d members (at most %d in one launch)", n_members, MI_FUSED_GROUP_MAX_MEMBERS);
+  MI_REQUIRE(models, "train_group_plan: models");
+  return plan_group([&](int32_t i) { return models[i]; }, nullptr, false, n_members, B, F, field_off, device_table,
+                    device_table_bytes, plan, stream);
+}
+
+int32_t mi_train_group_plan_models_numeric(const mi_fused_model_t* models, const mi_fused_numeric_t* numerics, int32_t n_members,
+                                           int64_t B, int32_t F, const int64_t* field_off, void* device_table,
+                                           size_t device_table_bytes, mi_fused_group_plan_t* plan, mi_stream_t stream) {
+  MI_REQUIRE(plan, "train_group_plan: plan");
+  MI_REQUIRE(n_members >= 1, "train_group_plan: %d members (at least 1)", n_members);
+  if (n_members > MI_FUSED_GROUP_MAX_MEMBERS)
+    return unsupported("train_group_plan: %d members (at most %d in one launch)", n_members, MI_FUSED_GROUP_MAX_MEMBERS);
+  MI_REQUIRE(models, "train_group_plan: models");
+  return plan_group([&](int32_t i) { return models[i]; }, numerics, false, n_members, B, F, field_off, device_table,
+                    device_table_bytes, plan, stream);
+}
+
+int32_t mi_train_group_step(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids, int64_t ids_member_stride,
+                            const uint8_t* labels, int64_t labels_member_stride, int64_t B, int32_t step, float* logits,
+                            float* loss, int32_t sweep_blocks, mi_stream_t stream) {
+  const int nd = plan_numeric(plan);
+  MI_REQUIRE(nd >= 0, "train_group_step: plan (not written by mi_train_group_plan)");
+  MI_REQUIRE(nd == 0, "train_group_step: the plan's members have %d numeric columns and this entry brings no x_num "
+             "(mi_train_group_step_numeric does)", nd);
+  return group_step(plan, 0, n_members, ids, ids_member_stride, nullptr, 0, labels, labels_member_stride, B, step, logits, loss,
+                    sweep_blocks, stream);
+}
+
+int32_t mi_train_group_step_numeric(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids,
+                                    int64_t ids_member_stride, const float* x_num, int64_t x_num_member_stride,
+                                    const uint8_t* labels, int64_t labels_member_stride, int64_t B, int32_t step, float* logits,
+                                    float* loss, int32_t sweep_blocks, mi_stream_t stream) {
+  const int nd = plan_numeric(plan);
+  MI_REQUIRE(nd >= 0, "train_group_step: plan (not written by mi_train_group_plan)");
+  return group_step(plan, nd, n_members, ids, ids_member_stride, x_num, x_num_member_stride, labels, labels_member_stride, B,
+                    step, logits, loss, sweep_blocks, stream);
+}
+
+int32_t mi_eval_group(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids, const uint8_t* labels, int64_t N,
+                      const float* tail_scale, float* logits, float* batch_loss, int64_t* hist, int64_t* counts, double* partials,
+                      int32_t blocks, mi_stream_t stream) {
+  const int nd = plan_numeric(plan);
+  MI_REQUIRE(nd >= 0, "eval_group: plan (not written by mi_train_group_plan)");
+  MI_REQUIRE(nd == 0, "eval_group: the plan's members have %d numeric columns and this entry brings no x_num "
+             "(mi_eval_group_numeric does)", nd);
+  return eval_group(plan, 0, n_members, ids, nullptr, 0, labels, N, tail_scale, logits, batch_loss, hist, counts, partials, blocks,
+                    stream);
+}
+
+int32_t mi_eval_group_numeric(const mi_fused_group_plan_t* plan, int32_t n_members, const int32_t* ids, const float* x_num,
+                              int64_t x_num_member_stride, const uint8_t* labels, int64_t N, const float* tail_scale,
+                              float* logits, float* batch_loss, int64_t* hist, int64_t* counts, double* partials, int32_t blocks,
+                              mi_stream_t stream) {
+  const int nd = plan_numeric(plan);
+  MI_REQUIRE(nd >= 0, "eval_group: plan (not written by mi_train_group_plan)");
+  return eval_group(plan, nd, n_members, ids, x_num, x_num_member_stride, labels, N, tail_scale, logits, batch_loss, hist, counts,
+                    partials, blocks, stream);
 }
 
 }  // extern "C"

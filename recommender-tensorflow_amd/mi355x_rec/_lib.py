@@ -78,6 +78,12 @@ class FusedModel(C.Structure):
         ("lr_table_wide", C.c_void_p), ("lr_table_wide_len", C.c_int64), ("wide_fields", C.c_uint64)]
 
 
+class FusedNumeric(C.Structure):
+    """mi_fused_numeric_t: a model's numeric columns for the entries that end in _numeric — how many, and where
+    numeric_embeddings [n, E] and the numeric linear weights [n] lie in dense"""
+    _fields_ = [("n_numeric", C.c_int32), ("num_emb_off", C.c_int64), ("lin_num_off", C.c_int64)]
+
+
 class FusedGroupPlan(C.Structure):
     """mi_fused_group_plan_t: what mi_train_group_plan leaves on the host for mi_train_group_step"""
     _fields_ = [("device_table", C.c_void_p), ("magic", C.c_uint64), ("n_members", C.c_int32), ("B", C.c_int32),
@@ -245,6 +251,11 @@ SIGNATURES = {
     "mi_train_group_plan_models": (_i32, [_p, _i32, _i64, _i32, _p, _p, _sz, _p, _p]),
     "mi_train_group_step": (_i32, [_p, _i32, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _i32, _p]),
     "mi_eval_group": (_i32, [_p, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _i32, _p]),
+    "mi_train_step_fused_workspace_bytes_numeric": (_sz, [_i64, _i32, _i32, _i32, _i64]),
+    "mi_train_step_model_numeric": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i32, _u64, _i32, _p, _p, _i32, _p]),
+    "mi_train_group_plan_models_numeric": (_i32, [_p, _p, _i32, _i64, _i32, _p, _p, _sz, _p, _p]),
+    "mi_train_group_step_numeric": (_i32, [_p, _i32, _p, _i64, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _i32, _p]),
+    "mi_eval_group_numeric": (_i32, [_p, _i32, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i32, _p]),
     "mi_predict_group_plan_bytes": (_sz, [_i32]),
     "mi_predict_group_plan": (_i32, [_p, _i32, _i32, _i32, _p, _p, _p, _p]),
     "mi_predict_group": (_i32, [_p, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),

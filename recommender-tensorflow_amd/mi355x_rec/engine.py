@@ -87,6 +87,7 @@ class HipKernels:
 
     supports_planes = True        # the pre-split 16-bit operand path of the MLP (csrc/gemm_pl.hip)
     supports_fused_rules = True   # the one-launch step under any optimizer, two rules, wide_fields (mi_train_step_model)
+    supports_fused_numeric = True  # ... and with numeric embedding columns (the entries that end in _numeric)
 
     def __init__(self):
         self.lib = _lib.load()
@@ -313,7 +314,7 @@ class DeepFM:
                  use_linear=True, use_mf=True, use_dnn=True, dropout=0.0, optimizer=None,
                  linear_optimizer=None, reduction="mean", device="cuda", seed=0, shard=None,
                  gemm="f16x2", numeric="embed", activation="relu", catchup="bounded", field_dims=None, wide_fields=None,
-                 deep_numeric=None, wide_numeric=None, _kernels=None):
+                 deep_numeric=None, wide_numeric=None, fused_numeric=False, _kernels=None):
         if len(vocab_sizes) + n_numeric == 0:
             raise ValueError("At least 1 feature column of categorical_columns or numeric_columns "
                              "must be specified.")            # deep_fm.py:31-32
@@ -352,6 +353,9 @@ class DeepFM:
                 if v is not None and len(v) != int(n_numeric):
                     raise ValueError("deep_numeric / wide_numeric need one entry per numeric column")
         self.catchup = catchup
+        # numeric embedding columns in the one-launch step (fused_train_step with x_num, FusedPopulation): asked for here, so
+        # that an engine built as before keeps answering as before (model_fn asks whenever params["fused_step"] is not "off")
+        self.admit_fused_numeric = bool(fused_numeric)
         self.k = _kernels if _kernels is not None else HipKernels()
         self.device = torch.device(device)
         self.vocab_sizes = [int(v) for v in vocab_sizes]
@@ -1193,7 +1197,8 @@ class DeepFM:
     FUSED_STEP_LIMIT_EMB = 16
     FUSED_STEP_LIMIT_HIDDEN_LAYERS = 3
     FUSED_STEP_LIMIT_WIDTH = 64
-    FUSED_STEP_LIMIT_CONCAT = 16384  # B * F * E
+    FUSED_STEP_LIMIT_NUMERIC = 16    # numeric embedding columns (the entries that end in _numeric)
+    FUSED_STEP_LIMIT_CONCAT = 16384  # B * (F + n_numeric) * E
     FUSED_STEP_LIMIT_ROWS = 1 << 18
     FUSED_STEP_SWEEP_BLOCKS = 0    # workgroups of the all-rows sweep; 0: the library's choice (tests: results do not depend on it)
 
@@ -1206,8 +1211,17 @@ class DeepFM:
         if not rules and (self.opt.name != "Adam" or self.lin_opt is not None):
             return "optimizer %s%s (Adam for every variable, one schedule)" % (
                 self.opt.name, "" if self.lin_opt is None else " with linear_optimizer %s" % self.lin_opt.name)
-        if self.n_numeric:
-            return "%d numeric columns (categorical columns only)" % self.n_numeric
+        nd = self.n_numeric
+        if nd and self.raw_numeric:
+            return "%d raw numeric columns (numeric embeddings only: numeric='embed')" % nd
+        if nd and not getattr(self.k, "supports_fused_numeric", False):
+            return "%d numeric columns (categorical columns only)" % nd
+        if nd and not self.admit_fused_numeric:
+            return "%d numeric columns (fused_numeric=True admits numeric embeddings)" % nd
+        if nd > self.FUSED_STEP_LIMIT_NUMERIC:
+            return "%d numeric columns (at most %d)" % (nd, self.FUSED_STEP_LIMIT_NUMERIC)
+        if self.F == 0:
+            return "no categorical column (1 to %d categorical fields beside the numeric ones)" % self.FUSED_STEP_LIMIT_FIELDS
         if not rules and (self.field_dims is not None or self.wide_fields is not None):
             return "field_dims / wide_fields (the canned estimators' columns)"
         if not 1 <= self.F <= self.FUSED_STEP_LIMIT_FIELDS:
@@ -1225,6 +1239,8 @@ class DeepFM:
         E = self.E if self.use_emb else 4
         if B * self.F * E > self.FUSED_STEP_LIMIT_CONCAT:
             return "B * F * E = %d (at most %d)" % (B * self.F * E, self.FUSED_STEP_LIMIT_CONCAT)
+        if B * (self.F + nd) * E > self.FUSED_STEP_LIMIT_CONCAT:
+            return "B * (F + n_numeric) * E = %d (at most %d)" % (B * (self.F + nd) * E, self.FUSED_STEP_LIMIT_CONCAT)
         return None
 
     def fused_step_ok(self, B):
@@ -1271,16 +1287,34 @@ class DeepFM:
         m.wide_fields = sum(1 << f for f in range(self.F) if self.wide_fields is None or self.wide_fields[f])
         return m, (layer_off, widths, workspace)
 
+    def fused_numeric(self):
+        """This model's numeric columns as a mi_fused_numeric_t (the entries that end in _numeric), or None without any."""
+        if not self.n_numeric:
+            return None
+        n = _lib.FusedNumeric()
+        n.n_numeric = self.n_numeric
+        n.num_emb_off = -1 if self.num_emb_off is None else self.num_emb_off
+        n.lin_num_off = -1 if self.lin_num_off is None else self.lin_num_off
+        return n
+
+    def fused_workspace_bytes(self, B):
+        """Bytes of the one-launch step's workspace for batches of B: the dense gradient and d_concat."""
+        E = self.E if self.use_emb else 4
+        if self.n_numeric:
+            return int(self.k.query("mi_train_step_fused_workspace_bytes_numeric", B, self.F, self.n_numeric, E, self.P))
+        return int(self.k.query("mi_train_step_fused_workspace_bytes", B, self.F, E, self.P))
+
     def fused_step_auto(self, B):
         """Is the fused step the faster choice for this model and batch size (the measured thresholds above)?  (Measured for
         mi_train_step_fused's own scope only: the models mi_train_step_model adds stay with the replay until a table says
-        otherwise — profiles/fused_step_rules.md.)"""
-        return (self._fused_step_plain() and self.fused_step_ok(B) and B <= self.FUSED_STEP_MAX_BATCH and self.state_bytes() <= self.FUSED_STEP_MAX_STATE_BYTES
+        otherwise — profiles/fused_step_rules.md.  Likewise a model with numeric columns: profiles/fused_step_numeric.md.)"""
+        return (self.n_numeric == 0 and self._fused_step_plain() and self.fused_step_ok(B) and B <= self.FUSED_STEP_MAX_BATCH and self.state_bytes() <= self.FUSED_STEP_MAX_STATE_BYTES
                 and 4 * self.dnn_end <= self.FUSED_STEP_MAX_WEIGHT_BYTES)
 
-    def fused_train_step(self, ids, labels):
+    def fused_train_step(self, ids, labels, x_num=None):
         """One optimizer.minimize(loss) as ONE launch (mi_train_step_fused; mi_train_step_model for any other optimizer, a
-        linear_optimizer, field_dims or wide_fields): returns (loss [1], logits [B]) device tensors,
+        linear_optimizer, field_dims or wide_fields; mi_train_step_model_numeric with numeric embedding columns, whose
+        values x_num float32 [B, n_numeric] brings): returns (loss [1], logits [B]) device tensors,
         no host sync.  The same step as train_step — same dropout masks, same Adam schedule(s) — with TF's whole-table Adam
         sweep done literally: after it every row is current (no catch-up is owed).  May follow and be followed by
         train_step / graph_train_step / loss / predict_fused / top_k / state_dict in any order."""
@@ -1290,26 +1324,29 @@ class DeepFM:
             raise ValueError("fused_train_step: the model has %s; use train_step" % why)
         if labels is None:
             raise ValueError("fused_train_step: labels")
-        self._prep(ids, labels, None)
+        self._prep(ids, labels, x_num)
         self.finalize_rows()                      # (a no-op after a fused step)
         k = self.k
         layer_off, widths = self._layer_tabs[0]
         per_b = self._fused_step_tabs
         bufs = per_b.get(B)
         if bufs is None:
-            E = self.E if self.use_emb else 4
-            nbytes = int(k.query("mi_train_step_fused_workspace_bytes", B, self.F, E, self.P))
+            nbytes = self.fused_workspace_bytes(B)
             bufs = per_b[B] = (torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device),
                                torch.empty(1, dtype=torch.float32, device=self.device),
                                torch.empty(B, dtype=torch.float32, device=self.device))
         ws, loss, logits = bufs
         step = self.step + 1
-        if not self._fused_step_plain():
+        if self.n_numeric or not self._fused_step_plain():
             lr_t = self.sched.lr_t(step) if self.sched else 0.0
             lin_lr_t = self.lin_sched.lr_t(step) if self.lin_sched else 0.0
             model, _ = self.fused_model(B, ws, lr_t, lin_lr_t)
-            k.mi_train_step_model(model, self.field_off, ids, labels, B, self.F, self._layer_seed(0), step, logits, loss,
-                                  int(self.FUSED_STEP_SWEEP_BLOCKS))
+            if self.n_numeric:
+                k.mi_train_step_model_numeric(model, self.fused_numeric(), self.field_off, ids, x_num, labels, B, self.F,
+                                              self._layer_seed(0), step, logits, loss, int(self.FUSED_STEP_SWEEP_BLOCKS))
+            else:
+                k.mi_train_step_model(model, self.field_off, ids, labels, B, self.F, self._layer_seed(0), step, logits, loss,
+                                      int(self.FUSED_STEP_SWEEP_BLOCKS))
             self.step = step
             self._final_step = step
             return loss, logits

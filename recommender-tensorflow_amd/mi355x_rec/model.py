@@ -211,7 +211,8 @@ def run_batch(features, labels, mode, params, make_engine):
             if fs == "on" and not ok:
                 raise ValueError("fused_step=on: the model has %s" % eng._fused_step_limit(B))
             if ok and (fs == "on" or eng.fused_step_auto(B)) and not getattr(eng, "summaries_next", False):
-                loss, logits = eng.fused_train_step(ids, y)
+                # (the batch's numeric features, where the model has numeric columns, go with it)
+                loss, logits = eng.fused_train_step(ids, y, x) if x is not None else eng.fused_train_step(ids, y)
                 return EstimatorSpec(mode, predictions=None, loss=rescale(loss), train_op=eng.step)
         hg = params.get("hip_graph", "auto")
         graph = hg in (True, "on") or (hg == "auto" and ids.shape[0] <= GRAPH_AUTO_MAX_BATCH)

@@ -41,11 +41,15 @@ class FusedPopulation:
             if e.vocab_sizes != first.vocab_sizes:
                 raise ValueError("FusedPopulation: member %d has other vocab_sizes than member 0 (%d fields against %d): the "
                                  "members share one set of feature columns" % (i, e.F, first.F))
+            if e.n_numeric != first.n_numeric:
+                raise ValueError("FusedPopulation: member %d has %d numeric columns, member 0 has %d: the members share one "
+                                 "set of feature columns" % (i, e.n_numeric, first.n_numeric))
             if e.device != first.device:
                 raise ValueError("FusedPopulation: member %d lives on %s, member 0 on %s" % (i, e.device, first.device))
         self.engines = engines
         self.M = len(engines)
         self.F = first.F
+        self.nd = first.n_numeric      # numeric embedding columns: x_num float32 [.., nd] beside ids
         self.device = first.device
         self.k = first.k
         self._plans = {}           # B -> (B, struct, device table, the members' schedule generations, what the struct points to)
@@ -67,11 +71,9 @@ class FusedPopulation:
     def _describe(self, e, B, keep_alive):
         """engine e as a mi_fused_member_t for batches of B (keep_alive: the tensors the struct points to and e does not hold)"""
         layer_off, widths = e.layer_tables()
-        E = e.E if e.use_emb else 4
-        nbytes = int(self.k.query("mi_train_step_fused_workspace_bytes", B, e.F, E, e.P))
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=e.device)
-        if not e._fused_step_plain():
-            # any other optimizer, a linear_optimizer, field_dims / wide_fields: the general description
+        ws = torch.empty(max(e.fused_workspace_bytes(B), 16), dtype=torch.uint8, device=e.device)
+        if self.nd or not e._fused_step_plain():
+            # any other optimizer, a linear_optimizer, field_dims / wide_fields, numeric columns: the general description
             m, held = e.fused_model(B, ws)
             keep_alive += list(held)
             for sched, tab, n in ((e.sched, "lr_table", "lr_table_len"),
@@ -113,7 +115,12 @@ class FusedPopulation:
         nbytes = int(self.k.query("mi_train_group_plan_bytes", self.M))
         table = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
         plan = _lib.FusedGroupPlan()
-        if all(e._fused_step_plain() for e in self.engines):
+        if self.nd:
+            members = (_lib.FusedModel * self.M)(*[self._describe(e, B, keep_alive) for e in self.engines])
+            numerics = (_lib.FusedNumeric * self.M)(*[e.fused_numeric() for e in self.engines])
+            self.k.mi_train_group_plan_models_numeric(members, numerics, self.M, B, self.F, self.engines[0].field_off, table,
+                                                      table.numel(), plan)
+        elif all(e._fused_step_plain() for e in self.engines):
             members = (_lib.FusedMember * self.M)(*[self._describe(e, B, keep_alive) for e in self.engines])
             self.k.mi_train_group_plan(members, self.M, B, self.F, self.engines[0].field_off, table, table.numel(), plan)
         else:
@@ -150,6 +157,21 @@ class FusedPopulation:
         return plan
 
     # ------------------------------------------------------------------ the step
+    def _check_x(self, x_num, n, lead):
+        """x_num float32 [n, nd], or [M, n, nd] where `lead` allows one set per member; None exactly without numeric columns"""
+        M, nd = self.M, self.nd
+        if not nd:
+            if x_num is not None:
+                raise ValueError("FusedPopulation: the members have no numeric columns")
+            return
+        shapes = ((n, nd), (M, n, nd)) if lead else ((n, nd),)
+        if not isinstance(x_num, torch.Tensor) or x_num.dtype != torch.float32 or not x_num.is_contiguous() \
+                or tuple(x_num.shape) not in shapes:
+            raise ValueError("FusedPopulation: x_num must be a contiguous float32 %s tensor" % " or ".join(
+                str(list(s)) for s in shapes))
+        if x_num.device.type != self.device.type:
+            raise ValueError("FusedPopulation: x_num must live on %s" % self.device)
+
     def _check_batch(self, ids, labels):
         M, F = self.M, self.F
         if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or not ids.is_contiguous() or ids.dim() not in (2, 3) \
@@ -163,11 +185,13 @@ class FusedPopulation:
             raise ValueError("FusedPopulation: ids and labels must live on %s" % self.device)
         return B
 
-    def train_step(self, ids, labels, out=None):
+    def train_step(self, ids, labels, out=None, x_num=None):
         """One optimizer.minimize(loss) of EVERY member as one launch: returns (loss [M], logits [M, B]) device tensors,
         no host sync.  ids int32 [B, F] (one batch for all members) or [M, B, F] (one per member); labels uint8 [B] or
-        [M, B].  out = (loss, logits): write there instead of into the population's own buffers."""
+        [M, B]; x_num float32 [B, nd] or [M, B, nd] with numeric columns (None without).  out = (loss, logits): write there
+        instead of into the population's own buffers."""
         B = self._check_batch(ids, labels)
+        self._check_x(x_num, B, True)
         engines = self.engines
         step = engines[0].step + 1
         for i, e in enumerate(engines):
@@ -193,20 +217,25 @@ class FusedPopulation:
         if tuple(loss.shape) != (self.M,) or tuple(logits.shape) != (self.M, B) or loss.dtype != torch.float32 \
                 or logits.dtype != torch.float32 or not loss.is_contiguous() or not logits.is_contiguous():
             raise ValueError("FusedPopulation: out = (loss float32 [%d], logits float32 [%d, %d]), contiguous" % (self.M, self.M, B))
-        self.k.mi_train_group_step(plan[1], self.M, ids, B * self.F if ids.dim() == 3 else 0, labels,
-                                   B if labels.dim() == 2 else 0, B, step, logits, loss, int(self.SWEEP_BLOCKS))
+        if self.nd:
+            self.k.mi_train_group_step_numeric(plan[1], self.M, ids, B * self.F if ids.dim() == 3 else 0, x_num,
+                                               B * self.nd if x_num.dim() == 3 else 0, labels, B if labels.dim() == 2 else 0, B,
+                                               step, logits, loss, int(self.SWEEP_BLOCKS))
+        else:
+            self.k.mi_train_group_step(plan[1], self.M, ids, B * self.F if ids.dim() == 3 else 0, labels,
+                                       B if labels.dim() == 2 else 0, B, step, logits, loss, int(self.SWEEP_BLOCKS))
         for e in engines:
             e.step = step
             e._final_step = step
         return loss, logits
 
     # ------------------------------------------------------------------ evaluation
-    def evaluate(self, ids, labels, batch_size=None, return_logits=False, exact=None):
+    def evaluate(self, ids, labels, batch_size=None, return_logits=False, exact=None, x_num=None):
         """Every member's EVAL metrics over a whole evaluation set as ONE launch (mi_eval_group) and one device-to-host copy:
         a list of M dicts with the keys of metrics.metrics_from_counters plus "loss", the fp64 mean over the fp32 losses of
         the batches of batch_size examples (tf.metrics.mean over batch losses; the last batch may be short and is reduced
         with its own 1 / n) — what Estimator.evaluate reports for the member on these batches.  ids int32 [N, F], labels uint8
-        [N], on the population's device, one set for all members.  batch_size None: that of the latest train_step, else
+        [N], x_num float32 [N, nd] with numeric columns, on the population's device, one set for all members.  batch_size None: that of the latest train_step, else
         EVAL_BATCH.  No dropout; no member's variables, slots, step or schedule change.  return_logits: (metrics, logits
         [M, N] device tensor).  exact: an exact_auc.ExactAuc of these labels (and, for GAUC, the examples' groups): the
         logits of this evaluation are kept and every member's dict gains auc_exact, auc_exact_pairs and, with groups, gauc,
@@ -223,6 +252,7 @@ class FusedPopulation:
             raise ValueError("FusedPopulation: labels must be a contiguous uint8 [N] tensor (N = %d)" % N)
         if ids.device.type != self.device.type or labels.device.type != self.device.type:
             raise ValueError("FusedPopulation: ids and labels must live on %s" % self.device)
+        self._check_x(x_num, N, False)
         if exact is not None and (exact.N != N or exact.device.type != self.device.type):
             raise ValueError("FusedPopulation: exact was built for %d examples on %s, the evaluation has %d on %s" % (
                 exact.N, exact.device, N, self.device))
@@ -251,8 +281,12 @@ class FusedPopulation:
             if len(self._eval_buf) > 4:
                 self._eval_buf.pop(next(iter(self._eval_buf)))
         buf["ints"].zero_()
-        self.k.mi_eval_group(plan[1], M, ids, labels, N, buf["tail"], buf["logits"], buf["loss"], buf["hist"], buf["counts"],
-                             buf["partials"], int(self.EVAL_BLOCKS))
+        if self.nd:
+            self.k.mi_eval_group_numeric(plan[1], M, ids, x_num, 0, labels, N, buf["tail"], buf["logits"], buf["loss"],
+                                         buf["hist"], buf["counts"], buf["partials"], int(self.EVAL_BLOCKS))
+        else:
+            self.k.mi_eval_group(plan[1], M, ids, labels, N, buf["tail"], buf["logits"], buf["loss"], buf["hist"], buf["counts"],
+                                 buf["partials"], int(self.EVAL_BLOCKS))
         extra = exact.metrics(buf["logits"]) if exact is not None else None     # (the pair counts of these logits, and their own copy)
         host = buf["raw"].cpu().numpy()
         n_int, n_par = M * 410, M * T * 3

@@ -29,7 +29,7 @@ _COMMON = [
                          help="replay the train step as one hipGraph launch (bit for bit the eager step): auto = for batches of at most "
                               "1,024 examples on one GPU, where a step is launch-bound (default: %(default)s)")),
     ("--fused-step", dict(nargs="?", const="on", default="off", choices=["off", "on", "auto"],
-                          help="small models (categorical columns only, any of the five optimizers and a separate linear optimizer, "
+                          help="small models (categorical columns and DeepFM's numeric embedding columns, any of the five optimizers and a separate linear optimizer, "
                                "at most 128 examples, 3 hidden layers of 64 units; the canned linear / deep / linear_deep models "
                                "too): run the whole train step as ONE kernel launch — on: always (an error if the model is outside the "
                                "kernel's scope), auto: where it was measured ahead of the hipGraph replay (default: %(default)s)")),

@@ -225,10 +225,13 @@ def make_members(args, hps, config):
     """One Estimator of trainers.deep_fm.model_fn per member, model_dir = <job-dir>/member_<i>, with its own params"""
     members = []
     for i, hp in enumerate(hps):
-        params = {"categorical_columns": get_feature_columns(embedding_size=hp["embedding_size"])["linear"],
+        cols = get_feature_columns(embedding_size=hp["embedding_size"])
+        params = {"categorical_columns": cols["linear"],
                   "use_linear": not args.exclude_linear, "use_mf": not args.exclude_mf, "use_dnn": not args.exclude_dnn,
                   "catchup": getattr(args, "catchup", "bounded"), "fused_step": "on",
                   "device_transform": getattr(args, "device_transform", "off")}
+        if cols.get("numeric"):                   # (a feature-column set with numeric columns: DeepFM's numeric embeddings)
+            params["numeric_columns"] = cols["numeric"]
         params.update(hp)
         members.append(Estimator(model_fn=deep_fm.model_fn, model_dir=os.path.join(args.job_dir, "member_%d" % i), config=config,
                                  params=params))
@@ -268,10 +271,13 @@ class PopulationEval:
                 self.curve = [(rec["global_step"], rec["members"]) for rec in map(json.loads, f)]
 
     def load(self, plan, dev):
-        """the test set, read and transformed ONCE: ids int32 [N, F] and labels uint8 [N] on the device"""
-        ids, ys, groups = [], [], []
+        """the test set, read and transformed ONCE: ids int32 [N, F], the numeric columns' values float32 [N, nd] (None
+        without any) and labels uint8 [N] on the device"""
+        ids, xs, ys, groups = [], [], [], []
         for features, labels in get_input_fn(self.test_csv, ModeKeys.EVAL, batch_size=4096)():
-            ids.append(_ids(plan, features, dev))
+            i_, x_ = _ids_x(plan, features, dev)
+            ids.append(i_)
+            xs.append(x_)
             ys.append(np.asarray(labels).reshape(-1).astype(np.uint8))
             if self.gauc_by:
                 if self.gauc_by not in features:
@@ -284,7 +290,8 @@ class PopulationEval:
             self.exact = ExactAuc(np.concatenate(ys), np.concatenate(groups) if self.gauc_by else None, device=dev,
                                   method=self.auc_method)
         self.data = (torch.cat(ids),
-                     torch.from_numpy(np.ascontiguousarray(np.concatenate(ys))).to(dev))
+                     torch.from_numpy(np.ascontiguousarray(np.concatenate(ys))).to(dev),
+                     None if xs[0] is None else torch.cat(xs).contiguous())
 
     def run(self, pop, step, lead):
         """All members on the whole test set at global step `step`; returns their metrics (at most once per step)"""
@@ -294,7 +301,7 @@ class PopulationEval:
         if self.data is None:
             self.load(lead.params["_store"]["plan"], lead._engine().device)
         metrics = [{k: float(v) for k, v in m.items()} for m in pop.evaluate(self.data[0], self.data[1], batch_size=self.batch_size,
-                                                                                     exact=self.exact)]
+                                                                                     exact=self.exact, x_num=self.data[2])]
         self.curve.append((step, metrics))
         os.makedirs(self.job_dir, exist_ok=True)
         with open(self.path, "a") as f:
@@ -313,11 +320,13 @@ class PopulationEval:
         return step, ms[i][self.select]
 
 
-def _ids(plan, features, dev):
-    """a batch's ids int32 [B, F] on the device: made there from the raw columns (--device-transform on), or on the host"""
+def _ids_x(plan, features, dev):
+    """a batch's ids int32 [B, F] and its numeric columns' values float32 [B, nd] (None when the feature-column set has no
+    numeric column) on the device: made there from the raw columns (--device-transform on), or on the host"""
     if plan.device_mode == "on":
-        return plan.on_device(dev).transform(features)[0]
-    return torch.from_numpy(plan.transform(features)[0]).to(dev)
+        return tuple(plan.on_device(dev).transform(features)[:2])
+    ids, x = plan.transform(features)
+    return torch.from_numpy(ids).to(dev), None if x is None else torch.from_numpy(x).to(dev)
 
 
 def train(members, input_fn, max_steps, config, job_dir=None, batch_size=None, evaluator=None):
@@ -340,14 +349,15 @@ def train(members, input_fn, max_steps, config, job_dir=None, batch_size=None, e
         if ahead is not None and ahead.get("features") is features:
             g = ahead["group"]
             if "ids" not in g:
-                g["ids"] = _ids(plan, g["features"], dev)
+                g["ids"], g["x"] = _ids_x(plan, g["features"], dev)
                 g["y"] = torch.from_numpy(np.ascontiguousarray(np.asarray(g["labels"]).reshape(-1)).astype(np.uint8)).to(dev)
             lo, hi = ahead["rows"]
             ids, y = g["ids"][lo:hi], g["y"][lo:hi]
+            x = None if g["x"] is None else g["x"][lo:hi]
         else:
-            ids = _ids(plan, features, dev)
+            ids, x = _ids_x(plan, features, dev)
             y = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1)).astype(np.uint8)).to(dev)
-        loss, _ = pop.train_step(ids, y)
+        loss, _ = pop.train_step(ids, y, x_num=x)
         step += 1
         n_log += 1
         if step % config.log_step_count_steps == 0:

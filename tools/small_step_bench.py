@@ -16,6 +16,9 @@ alternate; per path the median and the 10th / 90th percentile over BLOCKS blocks
     python tools/small_step_bench.py [--json FILE] [--blocks N] [--steps N]
     python tools/small_step_bench.py --rules ...     the legs of profiles/fused_step_rules.md instead: B = 32, the three canned
                                                      CLIs' default models and the default DeepFM under Adagrad, Ftrl, RMSProp, SGD
+    python tools/small_step_bench.py --numeric N [N ...]   the legs of profiles/fused_step_numeric.md instead: B = 32, the
+                                                     default DeepFM with N numeric embedding columns beside the 26 categorical
+                                                     ones (x_num standard normal), one case per N
 """
 import argparse
 import json
@@ -61,6 +64,10 @@ RULE_CASES = [
      for name, lr in (("Adagrad", 0.05), ("Ftrl", 0.05), ("RMSProp", 0.001), ("SGD", 0.05))]
 
 
+def numeric_cases(counts):
+    return [("default + %d numeric" % n, vocab(), 4, [16, 16], (32,), dict(n_numeric=n, fused_numeric=True)) for n in counts]
+
+
 def engines(voc, E, hidden, n, **kw):
     out = []
     kw = dict(dict(dropout=0.1, optimizer=OptimizerSpec("Adam", 0.001)), **kw)
@@ -79,17 +86,21 @@ def main():
     ap.add_argument("--blocks", type=int, default=7)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--rules", action="store_true", help="the legs of profiles/fused_step_rules.md instead of the Adam cases")
+    ap.add_argument("--numeric", type=int, nargs="+", default=None, metavar="N",
+                    help="the legs of profiles/fused_step_numeric.md instead: the default DeepFM with N numeric embedding columns")
     args = ap.parse_args()
     cells = []
-    for name, voc, E, hidden, batches, *kw in (RULE_CASES if args.rules else CASES):
+    for name, voc, E, hidden, batches, *kw in (numeric_cases(args.numeric) if args.numeric else RULE_CASES if args.rules else CASES):
         for B in batches:
             eager, graph, fused = engines(voc, E, hidden, 3, **(kw[0] if kw else {}))
+            nd = fused.n_numeric
             g = torch.Generator(device="cuda")
             g.manual_seed(1)
             ring = []
             for _ in range(ROTATE):
                 ids = torch.stack([torch.randint(0, v, (B,), device="cuda", generator=g) for v in voc], 1).to(torch.int32).contiguous()
-                ring.append((ids, (torch.rand(B, device="cuda", generator=g) < 0.3).to(torch.uint8)))
+                ring.append((ids, (torch.rand(B, device="cuda", generator=g) < 0.3).to(torch.uint8)) +
+                            ((torch.randn(B, nd, device="cuda", generator=g),) if nd else ()))
             paths = [("eager (one launch per kernel)", eager.train_step), ("hipGraph replay", graph.graph_train_step)]
             if fused.fused_step_ok(B):
                 paths.append(("fused (one launch)", fused.fused_train_step))
@@ -111,7 +122,7 @@ def main():
             state = fused.state_bytes()
             for p, _ in paths:
                 t = np.asarray(times[p])
-                cell = {"case": name, "E": E, "hidden": hidden, "B": B, "rows": fused.R, "state_bytes": state, "path": p,
+                cell = {"case": name, "E": E, "hidden": hidden, "B": B, "n_numeric": nd, "rows": fused.R, "state_bytes": state, "path": p,
                         "us_median": float(np.median(t)), "us_p10": float(np.percentile(t, 10)),
                         "us_p90": float(np.percentile(t, 90)), "blocks": args.blocks, "steps_per_block": args.steps}
                 cells.append(cell)
